@@ -46,6 +46,7 @@ HP = dict(lr=1e-3, train_steps=100000, warmup_steps=3000, gradient_clipping=1.0)
 PER_GPU_BATCH = 32
 PEAK_BF16_TFLOPS = 2500.0
 ROUND_TAG = "r06"      # profiles/<ROUND_TAG>_traffic_*.json must come from this round's kernels
+DUMP_SAMPLE = 1 << 20  # --dump-outputs: elements kept of a larger array (4 MB in float32; six arrays stay under 64 MB)
 
 
 def fwd_flops_per_token(d, L, S, V):
@@ -158,6 +159,26 @@ def dp_schedule_summary(schedule, lay):
             "dp_exposed_tail_MB": sum(b - a for a, b in schedule if a >= tail0) * 4 / 2 ** 20}
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32.  An array of more than DUMP_SAMPLE elements is flattened
+    and cut to the elements at DUMP_SAMPLE sorted indices drawn from a fixed seed, so that two builds are compared at the same
+    elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def train_state(model):
+    """parameters, gradients and Adam moments after a train step, in the reference's variable layout (no padding) and flattened
+    in its variable order: independent of how a build lays its buffers out"""
+    flat = lambda buf: np.concatenate([a.reshape(-1) for a in model.export_reference(buf).values()])  # noqa: E731
+    return {"params": flat(model.p), "grads": flat(model.g), "adam_m": flat(model.m), "adam_v": flat(model.v)}
+
+
 def load_traffic(name, kernel_substr):
     """bytes/launch from this round's PMC passes, or None when absent / measured on another kernel"""
     path = os.path.join(ROOT, "profiles", f"{ROUND_TAG}_traffic_{name}.json")
@@ -239,6 +260,9 @@ def bench_vae(args, world, rank, pg, comm):
         step(i)
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:      # before the event-timing steps below move the state on
+        dump_outputs(args.dump_outputs, {"loss": vae.loss.cpu().numpy(), "reconstruction": vae.reconstruction().cpu().numpy(),
+                                         **train_state(vae)})
     if graphed and heavy is not None:
         vae.event_hook = (heavy.name, evs)
         for i in range(22):
@@ -308,7 +332,12 @@ def main():
     ap.add_argument("--reserve-cus", type=int, default=None,
                     help="N > 1: CUs the persistent kernels of the BACKWARD leave to the exchange's RCCL channels (engine option "
                          "dp_reserve_cus; default: DALLE_DP_RESERVE_CUS or 0).  For the first multi-GPU A/B: one call per value.")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, per-position loss or reconstruction, and "
+                         "fixed seeded samples of the parameters, gradients and Adam moments) as DIR/<name>.npy in float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     world, rank, pg, comm = setup_dist(args)
     if args.model in VAE_MODELS:
         bench_vae(args, world, rank, pg, comm)
@@ -351,6 +380,9 @@ def main():
         eng.train_step(batches[i % 4])
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": eng.loss.cpu().numpy(), "loss_rows": eng.loss_rows.view(B, S).cpu().numpy(),
+                                         "grad_norm": np.sqrt(eng.gnorm_sq.cpu().numpy()), **train_state(eng)})
     loss = float(eng.loss.item())
     schedule = list(eng.reducer.last_log)
     if world > 1:
