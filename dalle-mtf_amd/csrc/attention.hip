@@ -1596,3 +1596,669 @@ extern "C" int dmi_attention_decode(uint16_t* qkv, const uint16_t* fresh, uint16
   DMI_CHECK_LAUNCH("attention_decode");
   return DMI_OK;
 }
+
+// =====================================================================================
+// head dim 64 (n_embd / n_heads = 64): the same four operations, semantics and buffer layouts as the kernels above
+// =====================================================================================
+// The operand roles are those of the 128 kernels (softmax row = lane, reduction index in the accumulator registers, P / dS straight
+// from registers into the next MFMA, every transposed fragment a ds_read_b64_tr_b16 of a natural tile); what changes is the width:
+//   * a score tile takes half the matrix work (4 + 4 MFMAs per 32 x 32 instead of 8 + 8) while the softmax work per score stays, so
+//     these kernels are bound by vector issue, not by the matrix pipe.  They spend the registers the narrower head frees on more
+//     waves per SIMD -- three in the forward and the dQ kernel, two in the dK/dV kernel (the 128 ones: two, two, one) -- so that one wave's
+//     softmax issues while another wave's MFMAs run, instead of hand-interleaving the two inside one wave;
+//   * tile rows are 128 B.  LDS image: off(row, chunk) = 128 row + 16 (chunk ^ swz64(row)), chunk = 16-byte piece 0..7.  Over the
+//     16-lane groups of a ds_read_b128 row read (32 rows, one chunk) the (row parity, swizzled chunk) pairs are all distinct, and
+//     the 32 lanes of a half of a transposed read (4 rows x 64 B) cover the 64 banks once: both reads conflict-free.
+//   * the forward is the program-order form (exact online softmax: the running maximum and the O / l rescale whenever some row's
+//     maximum grows), the backward the two-kernel split of the 128 path (dQ + delta + (lse, delta) pairs, then dK / dV).
+// 32-bit offsets: every LDS-DMA source offset is (row * 3 d + column) * 2 bytes with row < S + 64 (a tile may start at the last
+// row); the host refuses (S + 64) * 3 H * 64 * 2 >= 2^31.  Everything indexed by (batch, head, position) is 64-bit.
+#define HD64 64
+#define A64_STAGE 16384      // forward / dQ stage: K 8192 | V 8192 (64 keys x 128 B)
+#define A64_DKV_STAGE 8448   // dK/dV stage: Q 4096 | dO 4096 (32 queries x 128 B) | (lse * log2 e, delta) pairs 256
+#define A64_PITCH 144        // epilogue strip pitch: 32 rows x 128 B (+16: 16-byte aligned rows for the ds_read_b128 read-back)
+#define A64_FWD_WAVES 3      // waves per SIMD (= blocks per CU of 256 threads) the kernels are built for: 168 registers (at four, 128
+#define A64_DQ_WAVES 3       // registers, both spilled: 10 and 32 VGPRs)
+#define A64_DKV_WAVES 2
+__device__ __forceinline__ int swz64(int row) { return (((row >> 1) & 1) << 2) | ((row >> 2) & 3); }
+
+// Epilogue of a wave's 32 x 64 result (two 32x32 accumulators, lane (r, h) owns row r, acc[dt][e] is column 32 dt + (e & 3) + 8 (e >> 2)
+// + 4 h) through a wave-private LDS strip: whole 128-byte rows, eight rows per store instruction.  Nobody else may use the strip.
+__device__ __forceinline__ void a64_store_rows(char* strip, const f32x16 (&acc)[2], float scale, bf16_t* gbase, int64_t pitch,
+                                               int rows_valid, int lane) {
+  const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+      const int dd = dt * 32 + 8 * q4 + 4 * h;
+      *(u32x2*)(strip + r * A64_PITCH + dd * 2) = u32x2{pack2bf(acc[dt][4 * q4] * scale, acc[dt][4 * q4 + 1] * scale),
+                                                        pack2bf(acc[dt][4 * q4 + 2] * scale, acc[dt][4 * q4 + 3] * scale)};
+    }
+  __builtin_amdgcn_wave_barrier();
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // wave-private strip: in-order LDS, no block barrier needed
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int row = 8 * it + (lane >> 3);
+    const u32x4 v = *(const u32x4*)(strip + row * A64_PITCH + (lane & 7) * 16);
+    if (row < rows_valid) *(u32x4*)(gbase + (int64_t)row * pitch + (lane & 7) * 8) = v;
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+// transposed-fragment offsets in a natural [rows][64] image: {rows 4h + (l16 >> 2) + 8 w2} x {columns 4 (l16 & 3) + 16 (g4 & 1)} of
+// d-tile 0 (T10 lane map); d-tile 1 is the same offset XOR 64 (its chunks are 4..7: bit 2 of the chunk, bit 6 of the byte offset), the
+// next 16 rows are + 2048 (swz64 depends on row bits 1..3 only)
+__device__ __forceinline__ unsigned a64_tr_off(int lane, int w2) {
+  const int h = lane >> 5, g4 = lane >> 4, l16 = lane & 15;
+  const int row = 4 * h + (l16 >> 2) + 8 * w2;
+  const int chunk = 2 * (g4 & 1) + ((l16 & 3) >> 1);
+  return row * 128 + ((chunk ^ swz64(row)) << 4) + 8 * (l16 & 1);
+}
+
+// ---- forward: block = 128 queries (4 waves x 32), 64-key tiles double-buffered by LDS-DMA
+//   S^T = K Q^T (8 MFMAs per tile and wave) ; O^T += V^T P^T (8 MFMAs)
+__global__ __launch_bounds__(256, A64_FWD_WAVES) void attn64_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o,
+                                                                        float* __restrict__ lse, int B, int H, int S, int perxcd) {
+  extern __shared__ __attribute__((aligned(16))) char sm[];  // 2 x A64_STAGE
+  const int d = H * HD64, ld3 = 3 * d;
+  const int T = (S + 127) / 128;
+  const AttnSched sched = attn_sched(T, B * H, perxcd);
+  int tile_, bh;
+  for (int round = 0; attn_item(sched, round, tile_, bh); ++round) {
+  const int qt = T - 1 - tile_;  // heaviest (latest) query tiles first
+  const int b = bh / H, hh = bh % H;
+  const int q0 = qt * 128;
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));   // opaque per item (see attn_bwd_dkv_kernel)
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, h = lane >> 5;
+  const int qrow = q0 + wid * 32 + r;
+  const int qrow_c = qrow < S ? qrow : S - 1;
+  const bf16_t* qb = qkv + (int64_t)b * S * ld3 + hh * HD64;
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
+  const int nbytes = (int)(((int64_t)(S - 1) * ld3 + HD64) * 2);
+  const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)(qb + d), 0, nbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)(qb + 2 * d), 0, nbytes, 0x00020000);
+
+  bf16x8 qf[4];
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) qf[kk] = *(const bf16x8*)(qb + (int64_t)qrow_c * ld3 + 16 * kk + 8 * h);
+
+  int vo[2];   // source offset of this thread's chunks of a tile; + key0 * ld3 * 2 < (S + 64) * ld3 * 2 < 2^31 (host bound)
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int c = tid + 256 * i, row = c >> 3, pc = c & 7;
+    vo[i] = (row * ld3 + 8 * (pc ^ swz64(row))) * 2;
+  }
+  auto stage = [&](int st, int key0) {
+    char* base = sm + st * A64_STAGE;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      dma16(rk, base + (wid * 64 + 256 * i) * 16, vo[i] + key0 * ld3 * 2);
+      dma16(rv, base + 8192 + (wid * 64 + 256 * i) * 16, vo[i] + key0 * ld3 * 2);
+    }
+  };
+  int ofa[4];
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) ofa[kk] = r * 128 + (((2 * kk + h) ^ swz64(r)) << 4);
+  const unsigned ot0 = a64_tr_off(lane, 0), ot1 = a64_tr_off(lane, 1);
+
+  f32x16 oacc[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) oacc[i][e] = 0.f;
+  float m = -1e30f, l = 0.f;
+
+  const int qlast = (q0 + 127 < S - 1) ? q0 + 127 : S - 1;
+  const int nsteps = qlast / 64 + 1;
+  const int wave_qmin = q0 + wid * 32, wave_qmax = wave_qmin + 31;
+
+  auto compute = [&](int st, int j) {
+    if (64 * j > wave_qmax) return;  // wave-uniform: tile entirely above the diagonal for this wave
+    const char* base = sm + st * A64_STAGE;
+    const unsigned vb = lds0 + st * A64_STAGE + 8192;
+    f32x16 s0, s1;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) s0[e] = s1[e] = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const bf16x8 a0 = *(const bf16x8*)(base + ofa[kk]);
+      const bf16x8 a1 = *(const bf16x8*)(base + 4096 + ofa[kk]);
+      s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, qf[kk], s0, 0, 0, 0);  // S^T[key][q], keys 0..31 of the tile
+      s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, qf[kk], s1, 0, 0, 0);  // keys 32..63
+    }
+    Tr2 tv[2];   // V^T fragments of d-tiles 0, 1 for one 16-key step
+    tr2_issue(tv[0], vb + ot0, vb + ot1, vb + (ot0 ^ 64u), vb + (ot1 ^ 64u));
+    if (64 * j + 63 > wave_qmin) {  // diagonal tile: additive -1e10 mask == probability exactly 0
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int key = 64 * j + (e & 3) + 8 * (e >> 2) + 4 * h;
+        s0[e] = (key > qrow) ? -1e30f : s0[e];
+        s1[e] = (key + 32 > qrow) ? -1e30f : s1[e];
+      }
+    }
+    float mx = -1e30f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) mx = fmaxf(mx, fmaxf(s0[e], s1[e]));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    if (__any(mx > m)) {   // exact online softmax: rescale whenever some row's maximum grew (wave-uniform branch)
+      const float mn = fmaxf(m, mx);
+      const float alpha = __builtin_amdgcn_exp2f((m - mn) * LOG2E_F);
+      m = mn;
+      l *= alpha;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) oacc[i][e] *= alpha;
+    }
+    const float m2 = m * LOG2E_F;
+    float rs = 0.f;
+    bf16x8 pb[4];
+    {
+      float pe[16];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        pe[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[e], LOG2E_F, -m2));
+        rs += pe[e];
+      }
+      pb[0] = pack_bf8(pe);
+      pb[1] = pack_bf8(pe + 8);
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        pe[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[e], LOG2E_F, -m2));
+        rs += pe[e];
+      }
+      pb[2] = pack_bf8(pe);
+      pb[3] = pack_bf8(pe + 8);
+    }
+    l += rs;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {  // 16-key step: keys 16 ks + {4h..4h+3, 8+4h..8+4h+3}
+      Tr2& c = tv[ks & 1];
+      tr2_wait(c);
+      if (ks < 3) {
+        const unsigned v2 = vb + (ks + 1) * 2048;
+        tr2_issue(tv[(ks + 1) & 1], v2 + ot0, v2 + ot1, v2 + (ot0 ^ 64u), v2 + (ot1 ^ 64u));
+      }
+      oacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.a0, c.a1), pb[ks], oacc[0], 0, 0, 0);  // O^T[d][q]
+      oacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.b0, c.b1), pb[ks], oacc[1], 0, 0, 0);
+    }
+  };
+
+  stage(0, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  int j = 0;
+  for (; j + 2 <= nsteps; j += 2) {
+    stage(1, 64 * (j + 1));
+    compute(0, j);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (j + 2 < nsteps) stage(0, 64 * (j + 2));
+    compute(1, j + 1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+  if (j < nsteps) compute(0, j);
+
+  l += __shfl_xor(l, 32, 64);
+  if (h == 0 && qrow < S) lse[(int64_t)bh * S + qrow] = m + __logf(l);
+  __syncthreads();   // every wave's last LDS reads are done: the strips may overwrite the stages
+  a64_store_rows(sm + wid * (32 * A64_PITCH), oacc, 1.f / l, o + ((int64_t)b * S + q0 + wid * 32) * d + hh * HD64, d, S - (q0 + wid * 32), lane);
+  __syncthreads();   // the strips are read before the next item's first DMA
+  }   // items
+}
+
+// ---- backward dQ: block = 128 queries, the forward's K / V tile ring.  S^T = K Q^T, dP^T = V dO^T (row reads), dQ^T += K^T dS^T (K^T
+// by transpose reads of the same K tile).  Also produces delta[q] = dO[q] . O[q] and the (lse * log2 e, delta) pairs of the dK/dV kernel.
+__global__ __launch_bounds__(256, A64_DQ_WAVES) void attn64_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
+                                                                          const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
+                                                                          float* __restrict__ delta, float* __restrict__ stats,
+                                                                          bf16_t* __restrict__ dqkv, int B, int H, int S, int perxcd) {
+  extern __shared__ __attribute__((aligned(16))) char sm[];  // 2 x A64_STAGE
+  const int d = H * HD64, ld3 = 3 * d;
+  const int T = (S + 127) / 128;
+  const AttnSched sched = attn_sched(T, B * H, perxcd);
+  int tile_, bh;
+  for (int round = 0; attn_item(sched, round, tile_, bh); ++round) {
+  const int qt = T - 1 - tile_;
+  const int b = bh / H, hh = bh % H;
+  const int q0 = qt * 128;
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));   // opaque per item (see attn_bwd_dkv_kernel)
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, h = lane >> 5;
+  const int qrow = q0 + wid * 32 + r;
+  const int qrow_c = qrow < S ? qrow : S - 1;
+  const bf16_t* qb = qkv + (int64_t)b * S * ld3 + hh * HD64;
+  const bf16_t* dob = d_o + (int64_t)b * S * d + hh * HD64;
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
+  const int nbytes = (int)(((int64_t)(S - 1) * ld3 + HD64) * 2);
+  const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)(qb + d), 0, nbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)(qb + 2 * d), 0, nbytes, 0x00020000);
+
+  bf16x8 qf[4], dof[4];
+  float delta_q = 0.f;
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    qf[kk] = *(const bf16x8*)(qb + (int64_t)qrow_c * ld3 + 16 * kk + 8 * h);
+    dof[kk] = *(const bf16x8*)(dob + (int64_t)qrow_c * d + 16 * kk + 8 * h);
+    float fo[8], fd[8];
+    unpack8(*(const u32x4*)(o + ((int64_t)b * S + qrow_c) * d + hh * HD64 + 16 * kk + 8 * h), fo);
+    unpack8(__builtin_bit_cast(u32x4, dof[kk]), fd);
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) delta_q += fo[jj] * fd[jj];
+  }
+  delta_q += __shfl_xor(delta_q, 32, 64);   // the other half of the row lives in lane ^ 32
+  const float lse2_q = lse[(int64_t)bh * S + qrow_c] * LOG2E_F;   // p = exp2(s * log2(e) - lse * log2(e))
+  if (h == 0 && qrow < S) {
+    const int64_t idx = (int64_t)bh * S + qrow;
+    delta[idx] = delta_q;
+    stats[2 * idx] = lse2_q;   // base-2 units: the dK/dV kernel computes exp2(s * log2(e) - this)
+    stats[2 * idx + 1] = delta_q;
+  }
+
+  int vo[2];   // as in the forward: + key0 * ld3 * 2 < 2^31
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int c = tid + 256 * i, row = c >> 3, pc = c & 7;
+    vo[i] = (row * ld3 + 8 * (pc ^ swz64(row))) * 2;
+  }
+  auto stage = [&](int st, int key0) {
+    char* base = sm + st * A64_STAGE;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      dma16(rk, base + (wid * 64 + 256 * i) * 16, vo[i] + key0 * ld3 * 2);
+      dma16(rv, base + 8192 + (wid * 64 + 256 * i) * 16, vo[i] + key0 * ld3 * 2);
+    }
+  };
+  int ofa[4];
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) ofa[kk] = r * 128 + (((2 * kk + h) ^ swz64(r)) << 4);
+  const unsigned ot0 = a64_tr_off(lane, 0), ot1 = a64_tr_off(lane, 1);
+
+  f32x16 dq[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dq[i][e] = 0.f;
+
+  const int qlast = (q0 + 127 < S - 1) ? q0 + 127 : S - 1;
+  const int nsteps = qlast / 64 + 1;
+  const int wave_qmax = q0 + wid * 32 + 31;
+
+  auto compute = [&](int st, int j) {
+    if (64 * j > wave_qmax) return;
+    const char* base = sm + st * A64_STAGE;
+#pragma unroll
+    for (int kt2 = 0; kt2 < 2; ++kt2) {   // 32-key halves of the tile
+      f32x16 s, dp;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) s[e] = dp[e] = 0.f;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const bf16x8 ka = *(const bf16x8*)(base + kt2 * 4096 + ofa[kk]);
+        const bf16x8 va = *(const bf16x8*)(base + 8192 + kt2 * 4096 + ofa[kk]);
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qf[kk], s, 0, 0, 0);     // S^T[key][q]
+        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, dof[kk], dp, 0, 0, 0);  // dP^T[key][q]
+      }
+      // K^T fragments of d-tiles 0, 1, one 16-key step per set, two sets
+      Tr2 tk[2];
+      const unsigned t0 = lds0 + st * A64_STAGE + kt2 * 4096;
+      tr2_issue(tk[0], t0 + ot0, t0 + ot1, t0 + (ot0 ^ 64u), t0 + (ot1 ^ 64u));
+      float ds[16];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int key = 64 * j + kt2 * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const float pe = __builtin_amdgcn_exp2f((key > qrow) ? -INFINITY : __builtin_fmaf(s[e], LOG2E_F, -lse2_q));
+        ds[e] = pe * (dp[e] - delta_q);
+      }
+      bf16x8 dsb[2];
+      dsb[0] = pack_bf8(ds);
+      dsb[1] = pack_bf8(ds + 8);
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        Tr2& c = tk[s2];
+        tr2_wait(c);
+        if (s2 == 0) tr2_issue(tk[1], t0 + 2048 + ot0, t0 + 2048 + ot1, t0 + 2048 + (ot0 ^ 64u), t0 + 2048 + (ot1 ^ 64u));
+        dq[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.a0, c.a1), dsb[s2], dq[0], 0, 0, 0);   // dQ^T[d][q]
+        dq[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.b0, c.b1), dsb[s2], dq[1], 0, 0, 0);
+      }
+    }
+  };
+
+  stage(0, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  int j = 0;
+  for (; j + 2 <= nsteps; j += 2) {
+    stage(1, 64 * (j + 1));
+    compute(0, j);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (j + 2 < nsteps) stage(0, 64 * (j + 2));
+    compute(1, j + 1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+  if (j < nsteps) compute(0, j);
+
+  __syncthreads();   // every wave's last LDS reads are done: the strips may overwrite the stages
+  a64_store_rows(sm + wid * (32 * A64_PITCH), dq, 1.0f, dqkv + ((int64_t)b * S + q0 + wid * 32) * ld3 + hh * HD64, ld3, S - (q0 + wid * 32), lane);
+  __syncthreads();   // the strips are read before the next item's first DMA
+  }   // items
+}
+
+// ---- backward dK / dV: block = 128 keys (4 waves x 32), 32-query tiles from the diagonal down, double-buffered by LDS-DMA.
+//   S = Q K^T, dP = dO V^T        : A = Q / dO rows (ds_read_b128), B = this lane's K / V row (registers: 4 + 4 fragments)
+//   dV^T += dO^T P, dK^T += Q^T dS : A = transpose reads of the same Q / dO tiles, B = P / dS packed from the accumulators
+// Rows past S need no mask: their Q / dO rows and stats read as zeros (buffer bounds), so dS = 0 and P multiplies a zero dO row.
+__global__ __launch_bounds__(256, A64_DKV_WAVES) void attn64_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ d_o,
+                                                                            const float* __restrict__ stats /* [B,H,S,2] */,
+                                                                            bf16_t* __restrict__ dqkv, int B, int H, int S, int perxcd) {
+  extern __shared__ __attribute__((aligned(16))) char sm[];  // 2 x A64_DKV_STAGE (the epilogue strips: 4 x 32 x A64_PITCH)
+  const int d = H * HD64, ld3 = 3 * d;
+  const AttnSched sched = attn_sched((S + 127) / 128, B * H, perxcd);
+  int ktile, bh;
+  for (int round = 0; attn_item(sched, round, ktile, bh); ++round) {
+  const int b = bh / H, hh = bh % H;
+  const int key0 = ktile * 128;
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));   // opaque per item (see attn_bwd_dkv_kernel)
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, h = lane >> 5;
+  const int krow = key0 + wid * 32 + r;
+  const int krow_c = krow < S ? krow : S - 1;
+  const bf16_t* qb = qkv + (int64_t)b * S * ld3 + hh * HD64;
+  const bf16_t* dob = d_o + (int64_t)b * S * d + hh * HD64;
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
+
+  const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)qb, 0, (int)(((int64_t)(S - 1) * ld3 + HD64) * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rdo = __builtin_amdgcn_make_buffer_rsrc((void*)dob, 0, (int)(((int64_t)(S - 1) * d + HD64) * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rst = __builtin_amdgcn_make_buffer_rsrc((void*)(stats + (int64_t)bh * S * 2), 0, S * 8, 0x00020000);
+
+  bf16x8 kf[4], vf[4];
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    kf[kk] = *(const bf16x8*)(qb + d + (int64_t)krow_c * ld3 + 16 * kk + 8 * h);
+    vf[kk] = *(const bf16x8*)(qb + 2 * d + (int64_t)krow_c * ld3 + 16 * kk + 8 * h);
+  }
+  // one chunk of Q and of dO per thread and tile: row tid >> 3 of the 32, chunk tid & 7; + q0 * ld3 * 2 < (S + 64) * ld3 * 2 < 2^31
+  const int srow = tid >> 3, spc = tid & 7;
+  const int voq = (srow * ld3 + 8 * (spc ^ swz64(srow))) * 2, vod = (srow * d + 8 * (spc ^ swz64(srow))) * 2;
+  auto stage = [&](int st, int q0) {
+    char* base = sm + st * A64_DKV_STAGE;
+    dma16(rq, base + wid * 64 * 16, voq + q0 * ld3 * 2);
+    dma16(rdo, base + 4096 + wid * 64 * 16, vod + q0 * d * 2);
+    dma4(rst, base + 8192, (q0 * 2 + lane) * 4);   // (every wave writes the same 256 B)
+  };
+  int ofa[4];
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) ofa[kk] = r * 128 + (((2 * kk + h) ^ swz64(r)) << 4);
+  const unsigned ot0 = a64_tr_off(lane, 0), ot1 = a64_tr_off(lane, 1);
+
+  f32x16 dv[2], dk[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dv[i][e] = dk[i][e] = 0.f;
+
+  const int nqi = (S + 31) / 32;
+  const int qi0 = key0 / 32;
+  const int nsteps = nqi - qi0;
+  const int wave_kmin = key0 + wid * 32;
+
+  auto compute = [&](int st, int qi) {
+    const int qbase = 32 * qi;
+    if (qbase + 31 < wave_kmin) return;   // every query of the tile precedes every key of this wave: P = 0 (wave-uniform)
+    const char* base = sm + st * A64_DKV_STAGE;
+    const unsigned lb = lds0 + st * A64_DKV_STAGE;
+    f32x16 s, dp;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) s[e] = dp[e] = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const bf16x8 qa = *(const bf16x8*)(base + ofa[kk]);
+      const bf16x8 da = *(const bf16x8*)(base + 4096 + ofa[kk]);
+      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[kk], s, 0, 0, 0);    // S[q][key]
+      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vf[kk], dp, 0, 0, 0);  // dP[q][key]
+    }
+    // transposed dO / Q fragments of the two 16-query steps (d-tiles 0, 1 each), in flight under the softmax
+    Tr2 tdo0, tdo1, tq0, tq1;
+    tr2_issue(tdo0, lb + 4096 + ot0, lb + 4096 + ot1, lb + 4096 + (ot0 ^ 64u), lb + 4096 + (ot1 ^ 64u));
+    tr2_issue(tdo1, lb + 6144 + ot0, lb + 6144 + ot1, lb + 6144 + (ot0 ^ 64u), lb + 6144 + (ot1 ^ 64u));
+    tr2_issue(tq0, lb + ot0, lb + ot1, lb + (ot0 ^ 64u), lb + (ot1 ^ 64u));
+    tr2_issue(tq1, lb + 2048 + ot0, lb + 2048 + ot1, lb + 2048 + (ot0 ^ 64u), lb + 2048 + (ot1 ^ 64u));
+    St8 stt;   // (lse * log2 e, delta) of this lane's 16 query rows
+    st8_issue(stt, lb + 8192 + 32 * h);
+    st8_wait<0>(stt);
+    asm volatile("" : "+v"(tdo0.a0), "+v"(tdo0.a1), "+v"(tdo0.b0), "+v"(tdo0.b1), "+v"(tdo1.a0), "+v"(tdo1.a1), "+v"(tdo1.b0), "+v"(tdo1.b1),
+                      "+v"(tq0.a0), "+v"(tq0.a1), "+v"(tq0.b0), "+v"(tq0.b1), "+v"(tq1.a0), "+v"(tq1.a1), "+v"(tq1.b0), "+v"(tq1.b1));   // (all landed: lgkmcnt(0) above)
+    const int kd = krow - qbase - 4 * h;   // key - (first query row of this lane in the tile)
+    const bool diag = qbase < wave_kmin + 32;
+    unsigned pw[8], dw[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {   // accumulator elements (2i, 2i+1) = query rows 8 (i >> 1) + 4h + 2 (i & 1) + {0, 1}
+      const int g = i >> 1;
+      const f32x4 sv = stt.v[i];
+      float x0 = __builtin_fmaf(s[2 * i], LOG2E_F, -sv[0]);
+      float x1 = __builtin_fmaf(s[2 * i + 1], LOG2E_F, -sv[2]);
+      if (diag) {   // key > query (wave-uniform branch)
+        x0 = (kd > 8 * g + 2 * (i & 1)) ? -INFINITY : x0;
+        x1 = (kd > 8 * g + 2 * (i & 1) + 1) ? -INFINITY : x1;
+      }
+      const float p0 = __builtin_amdgcn_exp2f(x0), p1 = __builtin_amdgcn_exp2f(x1);
+      pw[i] = pack2bf(p0, p1);
+      dw[i] = pack2bf(p0 * (dp[2 * i] - sv[1]), p1 * (dp[2 * i + 1] - sv[3]));
+    }
+    const bf16x8 pb0 = __builtin_bit_cast(bf16x8, u32x4{pw[0], pw[1], pw[2], pw[3]});
+    const bf16x8 pb1 = __builtin_bit_cast(bf16x8, u32x4{pw[4], pw[5], pw[6], pw[7]});
+    const bf16x8 dsb0 = __builtin_bit_cast(bf16x8, u32x4{dw[0], dw[1], dw[2], dw[3]});
+    const bf16x8 dsb1 = __builtin_bit_cast(bf16x8, u32x4{dw[4], dw[5], dw[6], dw[7]});
+    dv[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo0.a0, tdo0.a1), pb0, dv[0], 0, 0, 0);   // dV^T[d][key]
+    dv[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo0.b0, tdo0.b1), pb0, dv[1], 0, 0, 0);
+    dk[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tq0.a0, tq0.a1), dsb0, dk[0], 0, 0, 0);     // dK^T[d][key]
+    dk[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tq0.b0, tq0.b1), dsb0, dk[1], 0, 0, 0);
+    dv[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo1.a0, tdo1.a1), pb1, dv[0], 0, 0, 0);
+    dv[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo1.b0, tdo1.b1), pb1, dv[1], 0, 0, 0);
+    dk[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tq1.a0, tq1.a1), dsb1, dk[0], 0, 0, 0);
+    dk[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tq1.b0, tq1.b1), dsb1, dk[1], 0, 0, 0);
+  };
+
+  if (nsteps > 0) stage(0, 32 * qi0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int t = 0; t < nsteps; ++t) {
+    if (t + 1 < nsteps) stage((t + 1) & 1, 32 * (qi0 + t + 1));   // its slot's last readers are behind the previous step's barrier
+    compute(t & 1, qi0 + t);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+
+  // every step ended with a barrier: the stages have no readers left
+  bf16_t* gk = dqkv + ((int64_t)b * S + wave_kmin) * ld3 + d + hh * HD64;
+  char* strip = sm + wid * (32 * A64_PITCH);
+  a64_store_rows(strip, dk, 1.0f, gk, ld3, S - wave_kmin, lane);
+  a64_store_rows(strip, dv, 1.0f, gk + d, ld3, S - wave_kmin, lane);
+  __syncthreads();   // the strips are read before the next item's DMA overwrites them
+  }   // items
+}
+
+// ---- decode: one query position against the K/V cache, the contract of attn_decode_kernel.  Lane (c = lane & 7, g = lane >> 3) owns
+// head dims [8c, 8c + 8) and, per 64-key chunk, keys 8i + g (i = 0..7): a load instruction fetches eight whole 128-B rows; the eight partial
+// dot products per lane are combined over the 8 lanes of a group by a reduce-scatter (7 exchanges): lane (c, g) ends with key 8c + g.
+__global__ __launch_bounds__(64 * DEC_WAVES) void attn64_decode_kernel(bf16_t* qkv, const bf16_t* __restrict__ fresh, bf16_t* __restrict__ o,
+                                                                       int H, int S, int pos_arg, const int* __restrict__ pos_dev) {
+  __shared__ float ps[DEC_WAVES][64];
+  __shared__ float red_m[DEC_WAVES], red_l[DEC_WAVES];
+  __shared__ float oacc[DEC_WAVES][HD64];
+  const int bh = blockIdx.x, b = bh / H, hh = bh % H;
+  const int d = H * HD64;
+  const int64_t ld3 = 3 * (int64_t)d;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int c = lane & 7, g = lane >> 3;
+  const int pos = pos_dev ? *pos_dev : pos_arg;
+  if (pos < 0 || pos >= S) return;                     // (block-uniform; the host checks the by-value form)
+  bf16_t* base = qkv + (int64_t)b * S * ld3 + hh * HD64;
+  const bf16_t* fr = fresh ? fresh + (int64_t)b * ld3 + hh * HD64 : nullptr;
+  float q[8];
+  unpack8(*(const u32x4*)((fr ? fr : base + (int64_t)pos * ld3) + 8 * c), q);
+  if (fr && threadIdx.x < 3 * HD64 / 8) {   // q | k | v of this head: 3 x 128 B -> cache row pos (read back by no one in this launch)
+    const int part = threadIdx.x / (HD64 / 8), ch = threadIdx.x % (HD64 / 8);
+    *(u32x4*)(base + (int64_t)pos * ld3 + part * d + ch * 8) = *(const u32x4*)(fr + part * d + ch * 8);
+  }
+  float m = -1e30f, l = 0.f;
+  float oa[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int ch0 = wid; ch0 * 64 <= pos; ch0 += DEC_WAVES) {
+    const int k0 = ch0 * 64;
+    auto row_ptr = [&](int i, int which) -> const u32x4* {   // key k0 + 8i + g, clamped to pos; row pos comes from the staging buffer
+      int key = k0 + 8 * i + g;
+      key = key < pos ? key : pos;
+      return (const u32x4*)((fr && key == pos) ? fr + which * d + 8 * c : base + which * d + (int64_t)key * ld3 + 8 * c);
+    };
+    u32x4 raw[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) raw[i] = *row_ptr(i, 1);
+    float p[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      float f[8];
+      unpack8(raw[i], f);
+      float t = 0.f;
+#pragma unroll
+      for (int jj = 0; jj < 8; ++jj) t = __builtin_fmaf(f[jj], q[jj], t);
+      p[i] = t;
+    }
+    // reduce-scatter over the 8 lanes of a group: after the stage with mask w, a lane keeps the half of its values whose index has
+    // bit w equal to its own bit w of c
+#pragma unroll
+    for (int w = 4; w >= 1; w >>= 1) {
+      const bool up = (c & w) != 0;
+#pragma unroll
+      for (int jj = 0; jj < w; ++jj) {
+        const float send = up ? p[jj] : p[jj + w];
+        const float keep = up ? p[jj + w] : p[jj];
+        p[jj] = keep + __shfl_xor(send, w, 64);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) raw[i] = *row_ptr(i, 2);     // value rows requested before the softmax' wave reductions
+    const int key = k0 + 8 * c + g;
+    const bool valid = key <= pos;
+    const float sc = valid ? p[0] : -1e30f;
+    const float mn = fmaxf(m, wave_max(sc));
+    const float alpha = __expf(m - mn);
+    const float pe = valid ? __expf(sc - mn) : 0.f;
+    l = l * alpha + wave_sum(pe);
+    m = mn;
+    ps[wid][8 * c + g] = bf2f(f2bf(pe));
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // wave-private strip: in-order LDS, no block barrier needed
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) oa[jj] *= alpha;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      float f[8];
+      unpack8(raw[i], f);
+      const float pj = ps[wid][8 * i + g];               // 0 for keys past pos (their rows were clamped to row pos)
+#pragma unroll
+      for (int jj = 0; jj < 8; ++jj) oa[jj] = __builtin_fmaf(pj, f[jj], oa[jj]);
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+#pragma unroll
+  for (int jj = 0; jj < 8; ++jj) {                        // the eight lane groups hold disjoint key subsets of the same dims
+    oa[jj] += __shfl_xor(oa[jj], 8, 64);
+    oa[jj] += __shfl_xor(oa[jj], 16, 64);
+    oa[jj] += __shfl_xor(oa[jj], 32, 64);
+  }
+  if (lane == 0) { red_m[wid] = m; red_l[wid] = l; }
+  if (g == 0) {
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) oacc[wid][8 * c + jj] = oa[jj];
+  }
+  __syncthreads();
+  if (wid == 0) {
+    float M = red_m[0];
+#pragma unroll
+    for (int w = 1; w < DEC_WAVES; ++w) M = fmaxf(M, red_m[w]);
+    float L = 0.f, a = 0.f;
+#pragma unroll
+    for (int w = 0; w < DEC_WAVES; ++w) {      // fixed order: deterministic
+      const float sc = __expf(red_m[w] - M);
+      L += red_l[w] * sc;
+      a += oacc[w][lane] * sc;
+    }
+    o[(int64_t)b * d + hh * HD64 + lane] = f2bf(a / L);
+  }
+}
+
+// ---- C ABI with a head-dim argument: 128 -> the calls above, 64 -> the kernels of this section
+#define A64_HEAD_DIM_CHECK(name)                                                                             \
+  do {                                                                                                       \
+    if (head_dim != 64 && head_dim != 128) {                                                                 \
+      dmi_set_error(name ": head_dim must be 64 or 128 (head_dim=%d)", head_dim);                             \
+      return DMI_ERR_UNSUPPORTED;                                                                            \
+    }                                                                                                        \
+  } while (0)
+static int a64_grid(int items, int blocks_per_cu) {   // persistent grid: blocks_per_cu per CU left to these kernels, at most one per item
+  const int g = blocks_per_cu * attn_num_cus();
+  return items < g ? items : g;
+}
+
+extern "C" int dmi_attention_fwd_hd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int H, int S, int head_dim, void* stream) {
+  A64_HEAD_DIM_CHECK("attention_fwd");
+  if (head_dim == 128) return dmi_attention_fwd(qkv, o, lse, B, H, S, stream);
+  DMI_REQUIRE(qkv && o && lse, "attention_fwd: null pointer");
+  DMI_REQUIRE(B > 0 && H > 0 && S > 0 && S % 8 == 0, "attention_fwd: S must be a multiple of 8 (S=%d)", S);
+  DMI_REQUIRE(((int64_t)S + 64) * 3 * H * HD64 * 2 < 0x7fffffff, "attention_fwd: sequence too long for 32-bit buffer offsets");
+  const int grid = a64_grid(((S + 127) / 128) * B * H, A64_FWD_WAVES);
+  const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
+  attn64_fwd_kernel<<<dim3(grid), dim3(256), 2 * A64_STAGE, (hipStream_t)stream>>>((const bf16_t*)qkv, (bf16_t*)o, lse, B, H, S, perxcd);
+  DMI_CHECK_LAUNCH("attention_fwd");
+  return DMI_OK;
+}
+
+extern "C" int dmi_attention_bwd_hd(const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, float* delta,
+                                    uint16_t* dqkv, int B, int H, int S, int head_dim, void* stream) {
+  A64_HEAD_DIM_CHECK("attention_bwd");
+  if (head_dim == 128) return dmi_attention_bwd(qkv, o, d_o, lse, delta, dqkv, B, H, S, stream);
+  DMI_REQUIRE(qkv && o && d_o && lse && delta && dqkv, "attention_bwd: null pointer");
+  DMI_REQUIRE(B > 0 && H > 0 && S > 0 && S % 8 == 0, "attention_bwd: S must be a multiple of 8 (S=%d)", S);
+  DMI_REQUIRE(((int64_t)S + 64) * 3 * H * HD64 * 2 < 0x7fffffff, "attention_bwd: sequence too long for 32-bit buffer offsets");
+  hipStream_t st = (hipStream_t)stream;
+  float* stats = delta + (int64_t)B * H * S;  // delta scratch is [3][B,H,S]: delta | (lse, delta) pairs
+  const int items = ((S + 127) / 128) * B * H;
+  {
+    const int grid = a64_grid(items, A64_DQ_WAVES);
+    const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
+    attn64_bwd_dq_kernel<<<dim3(grid), dim3(256), 2 * A64_STAGE, st>>>((const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o, lse, delta,
+                                                                     stats, (bf16_t*)dqkv, B, H, S, perxcd);
+  }
+  DMI_CHECK_LAUNCH("attention_bwd_dq");
+  {
+    const int grid = a64_grid(items, A64_DKV_WAVES);
+    const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
+    const int shm = 4 * 32 * A64_PITCH > 2 * A64_DKV_STAGE ? 4 * 32 * A64_PITCH : 2 * A64_DKV_STAGE;
+    attn64_bwd_dkv_kernel<<<dim3(grid), dim3(256), shm, st>>>((const bf16_t*)qkv, (const bf16_t*)d_o, stats, (bf16_t*)dqkv, B, H, S, perxcd);
+  }
+  DMI_CHECK_LAUNCH("attention_bwd_dkv");
+  return DMI_OK;
+}
+
+extern "C" int dmi_attention_decode_hd(uint16_t* qkv, const uint16_t* fresh, uint16_t* o, int B, int H, int S, int pos, const int* pos_dev,
+                                       int head_dim, void* stream) {
+  A64_HEAD_DIM_CHECK("attention_decode");
+  if (head_dim == 128) return dmi_attention_decode(qkv, fresh, o, B, H, S, pos, pos_dev, stream);
+  DMI_REQUIRE(qkv && o, "attention_decode: null pointer");
+  DMI_REQUIRE(B > 0 && H > 0 && S > 0, "attention_decode: bad shape");
+  DMI_REQUIRE(pos_dev || (pos >= 0 && pos < S), "attention_decode: need 0 <= pos < S (pos=%d, S=%d)", pos, S);
+  attn64_decode_kernel<<<dim3((unsigned)(B * H)), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream>>>((bf16_t*)qkv, (const bf16_t*)fresh,
+                                                                                                   (bf16_t*)o, H, S, pos, pos_dev);
+  DMI_CHECK_LAUNCH("attention_decode");
+  return DMI_OK;
+}

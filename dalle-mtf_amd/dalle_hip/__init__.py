@@ -79,6 +79,9 @@ def _declare(L):
         "dmi_attention_fwd": (I, [P, P, P, I, I, I, P]),
         "dmi_attention_bwd": (I, [P, P, P, P, P, P, I, I, I, P]),
         "dmi_attention_decode": (I, [P, P, P, I, I, I, I, P, P]),
+        "dmi_attention_fwd_hd": (I, [P, P, P, I, I, I, I, P]),
+        "dmi_attention_bwd_hd": (I, [P, P, P, P, P, P, I, I, I, I, P]),
+        "dmi_attention_decode_hd": (I, [P, P, P, I, I, I, I, P, I, P]),
         "dmi_label_logit": (I, [P, I, P, I, P, P, P, P, L64, I, I, P]),
         "dmi_gemm_nt_softmax_partials": (L64, [I]),
         "dmi_gemm_nt_softmax": (I, [P, I, P, I, P, P, P, I, P, I, I, I, P]),
@@ -287,17 +290,18 @@ def ln_gemm_nt(X, ldx, gamma, beta, Bt, ldb, C, ldc, M, N, K, flags=0, bias=None
            "ln_gemm_nt")
 
 
-def attention_decode(qkv, o, B, H, S, pos, fresh=None, pos_dev=None):
+def attention_decode(qkv, o, B, H, S, pos, fresh=None, pos_dev=None, head_dim=128):
     """one query position against the K/V cache held in the [B*S, 3d] projection buffer.  fresh=None: row pos already
     written; fresh = [B, 3d] staging buffer: the kernel moves it into row pos.  pos_dev (int32 [1] on the device) overrides
-    pos -- the graph-replayable form."""
+    pos -- the graph-replayable form.  head_dim: 64 or 128 (d = H * head_dim)."""
     _dev(qkv, o)
     if fresh is not None:
         _dev(fresh)
     if pos_dev is not None:
         _dev(pos_dev)
         assert pos_dev.dtype == torch.int32
-    _check(lib().dmi_attention_decode(_p(qkv), _p(fresh), _p(o), B, H, S, int(pos), _p(pos_dev), _stream()), "attention_decode")
+    _check(lib().dmi_attention_decode_hd(_p(qkv), _p(fresh), _p(o), B, H, S, int(pos), _p(pos_dev), int(head_dim), _stream()),
+           "attention_decode")
 
 
 def gemm_nt_splitk_workspace_bytes(M, N, nsplit):
@@ -408,14 +412,16 @@ def transpose_batch(in_base, out_base, table, n, total_tiles):
     _check(lib().dmi_transpose_bf16_batch(_p(in_base), _p(out_base), _p(table), n, total_tiles, _stream()), "transpose_batch")
 
 
-def attention_fwd(qkv, o, lse, B, H, S):
+def attention_fwd(qkv, o, lse, B, H, S, head_dim=128):
+    """causal attention over qkv [B*S, 3*H*head_dim]; head_dim: 64 or 128"""
     _dev(qkv, o, lse)
-    _check(lib().dmi_attention_fwd(_p(qkv), _p(o), _p(lse), B, H, S, _stream()), "attention_fwd")
+    _check(lib().dmi_attention_fwd_hd(_p(qkv), _p(o), _p(lse), B, H, S, int(head_dim), _stream()), "attention_fwd")
 
 
-def attention_bwd(qkv, o, d_o, lse, scratch, dqkv, B, H, S):
+def attention_bwd(qkv, o, d_o, lse, scratch, dqkv, B, H, S, head_dim=128):
     _dev(qkv, o, d_o, lse, scratch, dqkv)
-    _check(lib().dmi_attention_bwd(_p(qkv), _p(o), _p(d_o), _p(lse), _p(scratch), _p(dqkv), B, H, S, _stream()), "attention_bwd")
+    _check(lib().dmi_attention_bwd_hd(_p(qkv), _p(o), _p(d_o), _p(lse), _p(scratch), _p(dqkv), B, H, S, int(head_dim), _stream()),
+           "attention_bwd")
 
 
 def shift_labels(tokens, labels, B, S, eos):

@@ -29,7 +29,7 @@ import torch
 import dalle_hip as dh
 from ..dp import GradReducer
 
-HEAD_DIM = 128
+HEAD_DIMS = (64, 128)   # n_embd / n_heads values the attention kernels are built for
 ALIGN = 128  # elements
 
 
@@ -99,10 +99,11 @@ class DalleEngine:
             raise dh.DalleHipError("DalleEngine needs a HIP device (MI355X); there is no CPU fallback")
         dh.lib()
         assert n_embd % n_heads == 0, "n_state must be divisible by n_heads"
-        if n_embd // n_heads != HEAD_DIM:
-            raise dh.DalleHipError(f"attention kernels are built for head dim {HEAD_DIM} (n_embd/n_heads = {n_embd // n_heads}); "
-                                   "the reference README recommends exactly this ratio")
+        if n_embd // n_heads not in HEAD_DIMS:
+            raise dh.DalleHipError(f"attention kernels are built for head dims 64 and 128 (n_embd/n_heads = {n_embd // n_heads}); "
+                                   "the reference README recommends 128")
         self.d, self.L, self.H = n_embd, n_layers, n_heads
+        self.hd = n_embd // n_heads   # selects the attention kernels
         self.text_vocab_size, self.image_vocab_size = text_vocab_size, image_vocab_size
         self.T, self.S = text_seq_len, text_seq_len + image_seq_len
         assert self.S % 8 == 0, "total sequence length must be a multiple of 8"
@@ -398,7 +399,7 @@ class DalleEngine:
         if not (self.fuse_ln1 and l > 0):   # (fused: written by block l-1's FFN-2)
             dh.layernorm_fwd(x, self._w(p + "norm_1/g"), self._w(p + "norm_1/b"), self.xn1[l], st[0], st[1], M, d)
         dh.gemm_nt(self.xn1[l], d, self.tview(p + "attn/qkv"), d, self.qkv[l], 3 * d, M, 3 * d, d)
-        dh.attention_fwd(self.qkv[l], self.o[l], self.lse[l], B, H, S)   # no transposed copies: hardware transpose reads
+        dh.attention_fwd(self.qkv[l], self.o[l], self.lse[l], B, H, S, head_dim=self.hd)   # no transposed copies: hardware transpose reads
         if self.fuse_ln:
             dh.gemm_nt_ln(self.o[l], d, self.tview(p + "attn/o"), d, self.x1[l], d, M, d, d,
                           self._w(p + "norm_2/g"), self._w(p + "norm_2/b"), self.xn2[l], d, st[2], st[3],
@@ -577,7 +578,7 @@ class DalleEngine:
             p = f"layer_{l}/"
             cache = self.qkv[l]                                        # [B*S, 3d]; row b*S + pos <- q | k | v of this step
             ln_dense(x, p + "norm_1", self.tview(p + "attn/qkv"), fresh, 3 * d)
-            dh.attention_decode(cache, o, B, H, S, 0, fresh=fresh, pos_dev=D["pos_i"])
+            dh.attention_decode(cache, o, B, H, S, 0, fresh=fresh, pos_dev=D["pos_i"], head_dim=self.hd)
             dh.gemm_nt(o, d, self.tview(p + "attn/o"), d, x1, d, B, d, d, dh.GEMM_BIAS | dh.GEMM_RESIDUAL,
                        bias=self._w(p + "attn/compute_output_bias/o_b"), residual=x)
             ln_dense(x1, p + "norm_2", self.tview(p + "mlp/mlp_linear_1/kernel"), h, 4 * d, dh.GEMM_BIAS | dh.GEMM_RELU,
@@ -728,7 +729,7 @@ class DalleEngine:
                             dbias=self._gv(p + "attn/compute_output_bias/o_b"), slot=2)
             if not chain:
                 dh.gemm_nt(dxb, d, self._w(p + "attn/o"), d, self.d_o, d, M, d, d)
-            dh.attention_bwd(self.qkv[l], self.o[l], self.d_o, self.lse[l], self.delta, self.dqkv, B, H, S)
+            dh.attention_bwd(self.qkv[l], self.o[l], self.d_o, self.lse[l], self.delta, self.dqkv, B, H, S, head_dim=self.hd)
             if pair:   # [r05] the out-projection and QKV kernels' gradients in ONE launch: 16 + 48 tiles fill the chip together
                 probs = [dict(X=self.o[l], ldx=d, dY=dxb, ldy=d, dW=self._gv(p + "attn/o"), I=d, J=d, ws=self.ws_blk[2],
                               dbias=self._gv(p + "attn/compute_output_bias/o_b")),

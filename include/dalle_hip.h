@@ -141,7 +141,8 @@ int dmi_transpose_bf16(const uint16_t* in, uint16_t* out, int batch, int R, int 
 
 /* ---- K4  causal attention, UNSCALED logits, fp32 softmax   models.py:221-227,292-299 (Appendix A.2/A.3)
  * qkv [B*S, 3*H*128] bf16 = the QKV projection output, row = [q | k | v] x [H, 128] (heads-major, A.1);
- * o [B*S, H*128] bf16;  lse [B,H,S] fp32.  head dim is fixed at 128 (README.md:164); S % 8 == 0.
+ * o [B*S, H*128] bf16;  lse [B,H,S] fp32.  These three calls take head dim 128 (README.md:164); the _hd forms below take
+ * head dim 64 or 128; S % 8 == 0.
  * Every transposed MFMA operand is a hardware transpose read of the natural tile: no transposed copies. */
 int dmi_attention_fwd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int H, int S, void* stream);
 /* backward.  d_o [B*S, H*128] bf16; scratch: 3*B*H*S floats (delta | interleaved (lse, delta) pairs);
@@ -159,6 +160,14 @@ int dmi_attention_bwd(const uint16_t* qkv, const uint16_t* o, const uint16_t* d_
  * no-op), so ONE captured HIP graph serves every step of the sampling loop. */
 int dmi_attention_decode(uint16_t* qkv, const uint16_t* fresh, uint16_t* o, int B, int H, int S, int pos, const int* pos_dev,
                          void* stream);
+/* The same three operations for head_dim = 64 or 128 (any other value: DMI_ERR_UNSUPPORTED): every 128 above becomes head_dim
+ * (qkv [B*S, 3*H*head_dim], o / d_o [B*S, H*head_dim]; lse, scratch and the decode contract unchanged).  head_dim = 128 is the
+ * call above; head_dim = 64 runs kernels of its own and needs (S + 64) * 3 * H * 64 * 2 < 2^31 (32-bit buffer offsets). */
+int dmi_attention_fwd_hd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int H, int S, int head_dim, void* stream);
+int dmi_attention_bwd_hd(const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, float* scratch,
+                         uint16_t* dqkv, int B, int H, int S, int head_dim, void* stream);
+int dmi_attention_decode_hd(uint16_t* qkv, const uint16_t* fresh, uint16_t* o, int B, int H, int S, int pos, const int* pos_dev,
+                            int head_dim, void* stream);
 
 /* ---- K7/K8  to_logits + cross entropy, labels = shift(tokens)   models.py:391-395,348-359,407-410
  * labels[t] = tokens[t+1], last = eos (bit-exact int path). */
