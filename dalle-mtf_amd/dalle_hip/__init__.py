@@ -105,6 +105,8 @@ def _declare(L):
         "dmi_sumsq_workspace_bytes": (L64, [L64]),
         "dmi_sumsq": (I, [P, L64, P, P, P]),
         "dmi_adam_step": (I, [P, P, P, P, P, L64, P, F, F, F, F, F, F, F, P, P]),
+        "dmi_adafactor_plan": (I, [P, I, P]),
+        "dmi_adafactor_step": (I, [P, I, P, P, P, P, P, P, P, F, F, P, F, F, F, F, P, L64, P]),
         "dmi_cast_f32_bf16": (I, [P, P, L64, P]),
         "dmi_transpose_bf16_padded": (I, [P, P, I, I, I, P]),
         "dmi_transpose_bf16_batch": (I, [P, P, P, I, L64, P]),
@@ -512,6 +514,28 @@ def adam_step(p, g, m, v, p_bf16, n, gnorm_sq, clip, lr, beta1, beta2, eps, wd, 
     _dev(p, g, m, v)
     _check(lib().dmi_adam_step(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), n, _p(gnorm_sq), clip, lr, beta1, beta2, eps,
                                wd, grad_scale, _p(lr_dev), _stream()), "adam_step")
+
+
+AF_FIELDS = 17   # DMI_AF_FIELDS: int64 per variable in an Adafactor descriptor table
+
+
+def adafactor_plan(table):
+    """table: int64 CPU tensor [nvars, AF_FIELDS] with fields 0..8 filled (include/dalle_hip.h K9b); fills fields 9..16 in place
+    and returns (tiles, segments, workspace bytes)"""
+    assert table.dtype == torch.int64 and not table.is_cuda and table.is_contiguous() and table.shape[1] == AF_FIELDS
+    totals = torch.zeros(3, dtype=torch.int64)
+    _check(lib().dmi_adafactor_plan(_p(table), table.shape[0], _p(totals)), "adafactor_plan")
+    return tuple(int(x) for x in totals)
+
+
+def adafactor_step(table_dev, nvars, totals, p, g, m, slots, p_bf16, gnorm_sq, clip, lr, decay, beta1, eps1, eps2, ws,
+                   lr_dev=None):
+    """one Adafactor step over every variable of the planned table (six launches); totals: the tuple adafactor_plan returned"""
+    _dev(table_dev, p, g, m, slots, gnorm_sq, ws)
+    tot = (ctypes.c_int64 * 3)(*totals)
+    _check(lib().dmi_adafactor_step(_p(table_dev), nvars, ctypes.addressof(tot), _p(p), _p(g), _p(m), _p(slots), _p(p_bf16),
+                                    _p(gnorm_sq), clip, lr, _p(lr_dev), decay, beta1, eps1, eps2, _p(ws), ws.numel() * ws.element_size(),
+                                    _stream()), "adafactor_step")
 
 
 def cast_f32_bf16(inp, out, n):

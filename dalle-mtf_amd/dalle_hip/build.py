@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "csrc")
 LIB = os.path.join(HERE, "libdalle_hip.so")
-SOURCES = ["elementwise.hip", "gemm.hip", "attention.hip", "vae.hip", "comm.hip", "host.hip"]
+SOURCES = ["elementwise.hip", "gemm.hip", "attention.hip", "vae.hip", "comm.hip", "host.hip", "optim.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 
 

@@ -10,7 +10,8 @@ torch.distributed, bucketed and overlapped with backward on the collective's own
 PyTorch is plumbing only (device memory, streams, torch.distributed); all arithmetic runs in the
 hand-written kernels behind the C ABI.  There is no CPU fallback.
 
-Memory plan (HBM, per GPU): parameters live in ONE flat fp32 buffer (+ flat grads, Adam m, v) laid out in
+Memory plan (HBM, per GPU): parameters live in ONE flat fp32 buffer (+ flat grads, Adam m, v -- or Adafactor's m and
+factored second moments, DESIGN.md §4 "Adafactor") laid out in
 reverse-usage order [to_logits | layer_{L-1} .. layer_0 | wpe | wte] so finished gradients always form
 a contiguous prefix (= all-reduce buckets).  bf16 compute copies: `pb` (same offsets, natural [in,out]
 layout, written by the Adam kernel) and `pbt` ([out,in] copies of the GEMM weights for the forward).
@@ -35,6 +36,40 @@ ALIGN = 128  # elements
 
 def _round_up(x, m):
     return (x + m - 1) // m * m
+
+
+def adafactor_factored_dims(shape, min_dim_size_to_factor=128):
+    """mtf AdafactorOptimizer._factored_dims (mesh-tensorflow 0.1.18 optimize.py, restated from memory: no mesh-tensorflow was
+    available to check it against): None below rank 2; otherwise the axes sorted by size, descending and stable (ties keep axis
+    order), d0 = the largest, d1 = the second -- None when d1 is smaller than min_dim_size_to_factor.  Returns (d0, d1) axes."""
+    if len(shape) < 2:
+        return None
+    order = sorted(range(len(shape)), key=lambda i: -shape[i])
+    if shape[order[1]] < min_dim_size_to_factor:
+        return None
+    return order[0], order[1]
+
+
+def adafactor_table(lay):
+    """the Adafactor descriptor table of a ParamLayout (fields 0..8 of include/dalle_hip.h K9b; dmi_adafactor_plan fills the
+    rest), one row per reference variable, the per-variable slot records and the slot buffer's length.  Slots: the row vector [R]
+    and the column vector [C] of a factored variable, the dense v [R, C] otherwise, in 16-byte aligned pieces."""
+    rows, recs, so = [], [], 0
+    for name, shp, off, ld in lay.reference_variables():
+        R, C = (1, shp[0]) if len(shp) == 1 else shp
+        fd = adafactor_factored_dims(shp)
+        rec = dict(name=name, shape=shp, factored=fd is not None)
+        if fd is not None:
+            rec["row"], rec["col"] = so, so + _round_up(R, 4)
+            so += _round_up(R, 4) + _round_up(C, 4)
+            rec["vr_row"] = fd[0] == 1       # vr is indexed along d1: the rows when d0 is the column axis
+            rows.append([off, R, C, ld, 1, int(rec["vr_row"]), rec["row"], rec["col"], 0] + [0] * 8)
+        else:
+            rec["v"] = so
+            so += _round_up(R * C, 4)
+            rows.append([off, R, C, ld, 0, 0, 0, 0, rec["v"]] + [0] * 8)
+        recs.append(rec)
+    return torch.tensor(rows, dtype=torch.int64), recs, so
 
 
 class ParamLayout:
@@ -90,6 +125,23 @@ class ParamLayout:
     def numel(self, name):
         return int(np.prod(self.shape[name]))
 
+    def reference_variables(self):
+        """the reference's variables in flat-buffer order as (name, shape, offset, leading dimension):
+        q / k / v are column blocks of the fused [d, 3d] matrix; the head's kernel and bias keep V of their Vp columns"""
+        out = []
+        for name, shp in self.entries:
+            o = self.offset[name]
+            if name.endswith("attn/qkv"):
+                base = name[:-3]
+                out += [(base + t, (self.d, self.d), o + i * self.d, 3 * self.d) for i, t in enumerate("qkv")]
+            elif name == "to_logits/linear_out/kernel":
+                out.append((name, (self.d, self.V), o, self.Vp))
+            elif name == "to_logits/linear_out/bias":
+                out.append((name, (self.V,), o, self.V))
+            else:
+                out.append((name, shp, o, shp[-1]))
+        return out
+
 
 class DalleEngine:
     def __init__(self, n_embd, n_layers, n_heads, text_vocab_size, image_vocab_size, text_seq_len, image_seq_len,
@@ -122,8 +174,7 @@ class DalleEngine:
         b16 = dict(dtype=torch.bfloat16, device=self.dev)
         self.p = torch.zeros(n, **f32)
         self.g = torch.zeros(n, **f32)
-        self.m = torch.zeros(n, **f32)
-        self.v = torch.zeros(n, **f32)
+        self.set_optimizer(self.hp.get("optimizer") or "adam")
         self.pb = torch.zeros(n, **b16)
         self.pbt = torch.zeros(self.lay.t_total, **b16)
         self.global_step = 0
@@ -137,6 +188,62 @@ class DalleEngine:
         self._alloc_activations()
         # gradient exchange: RCCL behind the C ABI when `comm` (dp.init_comm) is given, torch.distributed otherwise
         self.reducer = GradReducer(self.g, world_size, comm=comm, pg=process_group)
+
+    # ------------------------------------------------------------------ optimizer state
+    OPTIMIZERS = ("adam", "adafactor")
+
+    def set_optimizer(self, name):
+        """allocates the state of the optimizer src/optimizers.py:78-99 selects ("optimizer", case-insensitive): Adam keeps m and v
+        over the whole flat buffer; Adafactor keeps m (only when beta_1 != 0), a row and a column vector per factored variable and
+        a full v only for the variables that do not factor (DESIGN.md §4 "Adafactor").  Re-selecting the current optimizer
+        keeps its state; switching starts from zero state."""
+        name = (name or "adam").lower()
+        if name not in self.OPTIMIZERS:
+            raise ValueError(f"{name} not recognized")
+        if getattr(self, "optimizer", None) == name:
+            return
+        self.optimizer = name
+        n = self.lay.total
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self.m = self.v = self.af_slots = None
+        if name == "adam":
+            self.m = torch.zeros(n, **f32)
+            self.v = torch.zeros(n, **f32)
+            return
+        table, self.af_vars, so = adafactor_table(self.lay)
+        self.af_totals = dh.adafactor_plan(table)
+        self.af_table = table.to(self.dev)
+        self.af_ws = torch.empty(self.af_totals[2], dtype=torch.uint8, device=self.dev)
+        self.af_slots = torch.zeros(max(so, 4), **f32)
+        if self._af_beta1() != 0.0:
+            self.m = torch.zeros(n, **f32)
+
+    def _af_beta1(self):
+        b1 = self.hp.get("beta_1")
+        return 0.9 if b1 is None else float(b1)
+
+    def export_adafactor_slots(self) -> "OrderedDict[str, np.ndarray]":
+        """the Adafactor slots under mtf's names ([MTF-RECALL]): <var>_slot_vr (indexed along d1), <var>_slot_vc (along d0) for a
+        factored variable, <var>_slot_v otherwise, and <var>_slot_m when beta_1 != 0"""
+        assert self.optimizer == "adafactor"
+        sl = self.af_slots.detach().cpu().numpy()
+        mm = self.export_reference(self.m) if self.m is not None else None
+        out: "OrderedDict[str, np.ndarray]" = OrderedDict()
+        for r in self.af_vars:
+            shp = r["shape"]
+            if r["factored"]:
+                R, C = shp
+                vrow, vcol = sl[r["row"]:r["row"] + R].copy(), sl[r["col"]:r["col"] + C].copy()
+                out[r["name"] + "_slot_vr"], out[r["name"] + "_slot_vc"] = (vrow, vcol) if r["vr_row"] else (vcol, vrow)
+            else:
+                out[r["name"] + "_slot_v"] = sl[r["v"]:r["v"] + int(np.prod(shp))].reshape(shp).copy()
+            if mm is not None:
+                out[r["name"] + "_slot_m"] = mm[r["name"]]
+        return out
+
+    def optimizer_buffers(self):
+        """every device buffer of the optimizer state (the data-parallel start broadcasts them from rank 0)"""
+        return [b for b in (self.m, self.v, self.af_slots) if b is not None]
 
     # ------------------------------------------------------------------ parameter access
     def view(self, buf, name):
@@ -787,9 +894,31 @@ class DalleEngine:
         return float(v)
 
     def optimizer_step(self):
+        """the optimizer src/optimizers.py:78-99 selects, on the all-reduced gradients; refreshes the bf16 compute copies"""
+        self.wait_grads()
+        if self.optimizer == "adafactor":
+            return self._adafactor_step()
+        return self._adam_step()
+
+    def _adafactor_step(self):
+        """clip_by_global_norm (src/optimizers.py:11-16, applied first, :100-103) + mtf.optimize.AdafactorOptimizer
+        (src/optimizers.py:91-97) over every variable in six launches (dmi_adafactor_step); refreshes the bf16 compute copies."""
+        hp = self.hp
+        clip = hp.get("gradient_clipping", 1.0)
+        lr = self.learning_rate()
+        get = lambda k, dflt: dflt if hp.get(k) is None else float(hp[k])   # noqa: E731  (0.0 is a value, not "unset")
+        if self._af_beta1() != 0.0 and self.m is None:   # beta_1 set after the state was allocated
+            self.m = torch.zeros(self.lay.total, dtype=torch.float32, device=self.dev)
+        dh.adafactor_step(self.af_table, len(self.af_vars), self.af_totals, self.p, self.g, self.m, self.af_slots, self.pb,
+                          self.gnorm_sq, 0.0 if clip is None else float(clip), lr, get("weight_decay", 0.0), self._af_beta1(),
+                          get("epsilon_1", 1e-30), get("epsilon_2", 1e-3), self.af_ws)
+        self.refresh_compute_copies(cast=False)
+        self.global_step += 1
+        return lr
+
+    def _adam_step(self):
         """clip_by_global_norm (src/optimizers.py:11-16) + AdamWeightDecayOptimizer without bias correction
         (src/optimizers.py:82-89,154-177) on the all-reduced gradients; refreshes the bf16 compute copies."""
-        self.wait_grads()
         hp = self.hp
         n = self.lay.total
         clip = hp.get("gradient_clipping", 1.0)
@@ -849,10 +978,22 @@ class DalleEngine:
 
     # ------------------------------------------------------------------ checkpoint
     def state_dict(self):
-        return {"p": self.p.detach().cpu(), "m": self.m.detach().cpu(), "v": self.v.detach().cpu(),
-                "global_step": self.global_step}
+        sd = {"p": self.p.detach().cpu(), "global_step": self.global_step, "optimizer": self.optimizer}
+        for k in ("m", "v", "af_slots"):
+            if getattr(self, k) is not None:
+                sd[k] = getattr(self, k).detach().cpu()
+        return sd
 
     def load_state_dict(self, sd):
-        self.p.copy_(sd["p"]); self.m.copy_(sd["m"]); self.v.copy_(sd["v"])
+        written = sd.get("optimizer", "adam")   # checkpoints from before the optimizer was recorded are Adam's
+        if written != self.optimizer:
+            raise ValueError(f"checkpoint was written by the {written} optimizer; this run uses {self.optimizer}: "
+                             "the optimizer state of one cannot continue the other")
+        self.p.copy_(sd["p"])
+        for k in ("m", "v", "af_slots"):
+            if getattr(self, k) is not None:
+                if k not in sd:
+                    raise ValueError(f"checkpoint has no {k!r} state for {self.optimizer} (beta_1 differs from the run's?)")
+                getattr(self, k).copy_(sd[k])
         self.global_step = int(sd["global_step"])
         self.refresh_compute_copies(cast=True)

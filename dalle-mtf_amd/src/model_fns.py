@@ -126,9 +126,9 @@ def _build(params, mode_str):
     else:
         eng.init_params(seed=params.get("seed") or 1234)
     if world > 1:
-        # every rank starts from rank 0's weights, Adam state AND step (the LR schedule and the loop length depend on it)
+        # every rank starts from rank 0's weights, optimizer state AND step (the LR schedule and the loop length depend on it)
         import torch.distributed as dist
-        for buf in (eng.p, eng.m, eng.v):
+        for buf in [eng.p] + eng.optimizer_buffers():
             eng.reducer.broadcast(buf, root=0)
         box = [eng.global_step]
         dist.broadcast_object_list(box, src=0, group=pg)

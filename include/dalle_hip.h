@@ -281,6 +281,28 @@ int dmi_adam_step(float* p, const float* g, float* m, float* v, uint16_t* p_bf16
                   const float* gnorm_sq, float clip, float lr, float beta1, float beta2, float eps,
                   float weight_decay, float grad_scale, const float* lr_dev, void* stream);
 
+/* ---- K9b  mtf.optimize.AdafactorOptimizer   src/optimizers.py:91-97 (get_optimizer, "optimizer": "adafactor"), clip :100-103
+ * Per variable, with gc = mult * g the clipped gradient (mult as for dmi_adam_step) and w the variable before the step:
+ *   g2 = gc^2 + eps1;  scale = lr * max(rms(w), eps2)   (rms over the variable's real elements)
+ *   factored:   vr = decay vr + (1-decay) mean_over_d0(g2);  vc = decay vc + (1-decay) mean_over_d1(g2)
+ *               x = gc * rsqrt(vr / mean(vr)) * rsqrt(vc)
+ *   otherwise:  v = decay v + (1-decay) g2;  x = gc * rsqrt(v)
+ *   x /= max(1, rms(x));  u = scale * x;  beta1 != 0: m = beta1 m + (1-beta1) u, u = m;  w -= u;  p_bf16 (optional) = bf16(w)
+ * (restated from mesh-tensorflow 0.1.18 optimize.py from memory: no mesh-tensorflow was available to check it against.)
+ * The table holds DMI_AF_FIELDS int64 per variable; the caller fills fields 0..8, dmi_adafactor_plan fills 9..16 and writes
+ * totals[3] = {tiles, segments, workspace bytes}; copy the planned table to device memory for the step.
+ *   0 offset of element [0, 0] in p / g / m    1 rows R (1 for a 1-D variable)   2 cols C   3 leading dimension (>= C)
+ *   4 factored (0/1)   5 1: vr is indexed by rows (d0 = the column axis), 0: vr is indexed by columns (d0 = the row axis)
+ *   6 / 7 float offsets in `slots` of the row vector [R] / column vector [C] (factored)   8 offset of the dense v [R, C] (otherwise)
+ * Elements past C in a row (pad columns) and everything outside the variables are neither read nor written.
+ * gnorm_sq (out): sum of g^2 over all variables, computed by the step.  clip <= 0: no clipping.  lr_dev as for dmi_adam_step.
+ * m may be NULL when beta1 == 0.  Six launches per step, deterministic (fixed reduction order, no atomics). */
+#define DMI_AF_FIELDS 17
+int dmi_adafactor_plan(int64_t* table, int nvars, int64_t* totals);
+int dmi_adafactor_step(const int64_t* table_dev, int nvars, const int64_t* totals, float* p, const float* g, float* m,
+                       float* slots, uint16_t* p_bf16, float* gnorm_sq, float clip, float lr, const float* lr_dev,
+                       float decay, float beta1, float eps1, float eps2, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- data-parallel exchange: the all-reduce mtf inserts for `layout: batch_dim:data`   src/model_fns.py:81-82,189,
  * VAE src/model_fns_tf.py:61 (CrossShardOptimizer).  One process per GPU, RCCL over xGMI, bound at run time
  * (dmi_comm_load(path or NULL) -- call it first when the process already maps a specific librccl, e.g. PyTorch's).
