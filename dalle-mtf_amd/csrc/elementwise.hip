@@ -1465,6 +1465,208 @@ extern "C" int dmi_sample_tokens(const uint16_t* z, int ldz, const uint16_t* bia
   return DMI_OK;
 }
 
+// Nucleus (top-p) draw with the row's log-likelihood, beside sample_tokens_kernel (which stays as it is).  One block per row:
+//   v = (z + bias) * (1/temperature); top-k filter as above (ties of the k-th value kept);
+//   q = softmax(v) over the top-k survivors, quantised: u[i] = floor(exp(v[i] - max v) * 2^31) (the maximum has u = 2^31), the
+//   mass of a set is the 64-bit integer sum of its u, the whole survivor set has mass Z, and the target is
+//   ceil(double(top_p) * double(Z)) (one IEEE double product: a numpy restatement reproduces it bit for bit);
+//   nucleus: tau = the largest u-candidate with mass(u >= tau) >= target, found by the same 32-step bitwise search as the k-th
+//   value (the predicate "mass of entries with u >= candidate >= target") -- tau is the u of the last entry of the shortest
+//   descending prefix that reaches top_p, and EVERY survivor with u >= tau is kept (ties at tau kept, as for top-k).  No sort;
+//   the kept set does not depend on summation order.  Entries with u = 0 (q < 2^-31) are never in a nucleus with top_p < 1;
+//   the draw is Gumbel-max over the kept set with the noise of sample_tokens_kernel, hash(seed, position, b, i);
+//   top_p >= 1 (or not in (0, 1), or a row whose maximum is not finite) skips the nucleus step: the kept set is the top-k set
+//   and the choice is sample_tokens_kernel's, bit for bit.  temperature <= 0: first maximum, top_k and top_p ignored.
+//   logp (nullable): logp[b] += (z + bias)[c] - logsumexp_i (z + bias)[i] (fp32, temperature 1, unfiltered; c the choice).
+// LDS: keys and u, 2 x 32 KB at nv = 8192 -- at most two blocks per CU, so a B <= 128 launch is resident at once.
+__device__ __forceinline__ float block_max_f32(float x, float* red, int lane, int wid) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
+  if (lane == 0) red[wid] = x;
+  __syncthreads();
+  x = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  return x;
+}
+__device__ __forceinline__ float block_sum_f32(float x, float* red, int lane, int wid) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  if (lane == 0) red[wid] = x;
+  __syncthreads();
+  x = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return x;
+}
+__device__ __forceinline__ uint64_t block_sum_u64(uint64_t x, uint64_t* red, int lane, int wid) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  if (lane == 0) red[wid] = x;
+  __syncthreads();
+  x = red[0] + red[1] + red[2] + red[3];
+  __syncthreads();
+  return x;
+}
+__global__ __launch_bounds__(256) void sample_tokens_p_kernel(const bf16_t* __restrict__ z, int ldz, const bf16_t* __restrict__ bias, int nv,
+                                                              float inv_temp, int top_k, uint64_t seed, float top_p,
+                                                              const unsigned* __restrict__ params_dev, int pos_arg, int* pos_dev, int advance,
+                                                              int token_offset, int* __restrict__ next_tok, int* __restrict__ out, int out_ld,
+                                                              int out_col0, float* __restrict__ logp) {
+  __shared__ unsigned keys[SAMPLE_MAX_VOCAB];
+  __shared__ unsigned qu[SAMPLE_MAX_VOCAB];
+  __shared__ int cnt[4];
+  __shared__ uint64_t red64[4];
+  __shared__ float redf[4];
+  __shared__ float bval[4];
+  __shared__ int bidx[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (params_dev) {
+    inv_temp = __uint_as_float(params_dev[0]);
+    top_k = (int)params_dev[1];
+    seed = (uint64_t)params_dev[2] | ((uint64_t)params_dev[3] << 32);
+    top_p = __uint_as_float(params_dev[4]);
+  }
+  const int counter = pos_dev ? *pos_dev : pos_arg;
+  const bool greedy = !(inv_temp > 0.f);
+  unsigned kmax = 0u;
+  for (int i = tid; i < nv; i += 256) {
+    float v = bf2f(z[(int64_t)b * ldz + i]);
+    if (bias) v += bf2f(bias[i]);
+    if (!greedy) v *= inv_temp;
+    const unsigned k = order_key(v);
+    keys[i] = k;
+    kmax = max(kmax, k);
+  }
+  __syncthreads();
+  unsigned thr = 0u;
+  if (!greedy && top_k > 0 && top_k < nv) {
+    for (int bit = 31; bit >= 0; --bit) {
+      const unsigned cand = thr | (1u << bit);
+      int c = 0;
+      for (int i = tid; i < nv; i += 256) c += keys[i] >= cand;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+      if (lane == 0) cnt[wid] = c;
+      __syncthreads();
+      const int total = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+      __syncthreads();
+      if (total >= top_k) thr = cand;   // block-uniform
+    }
+  }
+  // nucleus threshold on the quantised probabilities (block-uniform; 0 = no nucleus step)
+  unsigned qthr = 0u;
+  if (!greedy && top_p > 0.f && top_p < 1.f) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o, 64));
+    if (lane == 0) cnt[wid] = (int)kmax;
+    __syncthreads();
+    kmax = max(max((unsigned)cnt[0], (unsigned)cnt[1]), max((unsigned)cnt[2], (unsigned)cnt[3]));
+    __syncthreads();
+    const float vmax = key_value(kmax);
+    if (isfinite(vmax)) {
+      uint64_t part = 0;
+      for (int i = tid; i < nv; i += 256) {
+        const unsigned k = keys[i];
+        unsigned u = 0u;
+        if (k >= thr) {
+          const float e = expf(key_value(k) - vmax);     // in [0, 1]; NaN entries compare false and weigh nothing
+          u = e >= 0.f ? (unsigned)(e * 2147483648.0f) : 0u;
+        }
+        qu[i] = u;
+        part += u;
+      }
+      const uint64_t mass = block_sum_u64(part, red64, lane, wid);   // __syncthreads inside: qu is complete
+      const uint64_t target = (uint64_t)ceil((double)top_p * (double)mass);
+      for (int bit = 31; bit >= 0; --bit) {
+        const unsigned cand = qthr | (1u << bit);
+        uint64_t s = 0;
+        for (int i = tid; i < nv; i += 256) {
+          const unsigned u = qu[i];
+          s += u >= cand ? u : 0u;
+        }
+        if (block_sum_u64(s, red64, lane, wid) >= target) qthr = cand;   // block-uniform
+      }
+    }
+  }
+  const uint64_t stream_key = splitmix64(seed ^ ((uint64_t)(unsigned)counter * 0xD2B74407B1CE6E93ull));
+  float best = -INFINITY;
+  int besti = nv;
+  for (int i = tid; i < nv; i += 256) {   // ascending i per thread: strict > keeps the first maximum
+    const unsigned k = keys[i];
+    if (k < thr) continue;
+    if (qthr && qu[i] < qthr) continue;
+    float s = key_value(k);
+    if (!greedy) {
+      const uint64_t h = splitmix64(stream_key + (((uint64_t)(unsigned)b << 32) | (unsigned)i));
+      const float u = ((float)(unsigned)(h >> 41) + 0.5f) * (1.0f / 8388608.0f);   // as sample_tokens_kernel: u strictly in (0, 1)
+      s -= __logf(-__logf(u));
+    }
+    if (s > best) { best = s; besti = i; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(besti, o, 64);
+    if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+  }
+  if (lane == 0) { bval[wid] = best; bidx[wid] = besti; }
+  __syncthreads();
+  if (logp) {   // log-softmax of the unscaled row at the choice (every thread takes the choice from the wave winners)
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+      if (bval[w] > best || (bval[w] == best && bidx[w] < besti)) { best = bval[w]; besti = bidx[w]; }
+    float m = -INFINITY;
+    for (int i = tid; i < nv; i += 256) {
+      float v = bf2f(z[(int64_t)b * ldz + i]);
+      if (bias) v += bf2f(bias[i]);
+      m = fmaxf(m, v);
+    }
+    m = block_max_f32(m, redf, lane, wid);
+    float se = 0.f;
+    for (int i = tid; i < nv; i += 256) {
+      float v = bf2f(z[(int64_t)b * ldz + i]);
+      if (bias) v += bf2f(bias[i]);
+      se += expf(v - m);
+    }
+    se = block_sum_f32(se, redf, lane, wid);
+    if (tid == 0) {
+      const int c = besti >= nv ? 0 : besti;
+      float vc = bf2f(z[(int64_t)b * ldz + c]);
+      if (bias) vc += bf2f(bias[c]);
+      logp[b] += (vc - m) - logf(se);
+    }
+  }
+  if (tid == 0) {
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+      if (bval[w] > best || (bval[w] == best && bidx[w] < besti)) { best = bval[w]; besti = bidx[w]; }
+    if (besti >= nv) besti = 0;          // all-NaN row: defined output
+    if (next_tok) next_tok[b] = token_offset + besti;
+    const int col = counter - out_col0;
+    if (out && col >= 0 && col < out_ld) out[(int64_t)b * out_ld + col] = besti;
+    if (advance && pos_dev) {            // the last block to finish moves the position on (every block has read it by then)
+      __threadfence();
+      if (atomicAdd(pos_dev + 1, 1) == (int)gridDim.x - 1) {
+        pos_dev[1] = 0;
+        pos_dev[0] = counter + 1;
+      }
+    }
+  }
+}
+extern "C" int dmi_sample_tokens_p(const uint16_t* z, int ldz, const uint16_t* bias, int B, int nv, float temperature, int top_k,
+                                   uint64_t seed, float top_p, const uint32_t* params_dev, int pos, int32_t* pos_dev, int advance,
+                                   int token_offset, int32_t* next_tok, int32_t* out, int out_ld, int out_col0, float* logp, void* stream) {
+  DMI_REQUIRE(z && (next_tok || out), "sample_tokens_p: null pointer");
+  DMI_REQUIRE(B > 0 && nv > 0 && nv <= SAMPLE_MAX_VOCAB && ldz >= nv, "sample_tokens_p: need 0 < nv <= %d (nv=%d)", SAMPLE_MAX_VOCAB, nv);
+  DMI_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_tokens_p: top_p must lie in (0, 1] (top_p=%g)", (double)top_p);
+  DMI_REQUIRE(!out || out_ld > 0, "sample_tokens_p: out_ld");
+  DMI_REQUIRE(!advance || pos_dev, "sample_tokens_p: advance needs pos_dev");
+  const float inv_temp = temperature > 0.f ? 1.f / temperature : 0.f;
+  sample_tokens_p_kernel<<<dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream>>>(z, ldz, bias, nv, inv_temp, top_k, seed, top_p, params_dev, pos,
+                                                                                  pos_dev, advance, token_offset, next_tok, out, out_ld, out_col0, logp);
+  DMI_CHECK_LAUNCH("sample_tokens_p");
+  return DMI_OK;
+}
+
 // fp32 logits of a head-output slice: out[b, i] = float(z[b, i]) + float(bias[i])  (src/dalle_mtf/models.py:394-395)
 __global__ void logits_f32_kernel(const bf16_t* __restrict__ z, int ldz, const bf16_t* __restrict__ bias, float* __restrict__ out, int nv) {
   const int b = blockIdx.y;

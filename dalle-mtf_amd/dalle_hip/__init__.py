@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
+import struct
 from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
 
 import torch
@@ -91,6 +92,7 @@ def _declare(L):
         "dmi_sum_f32": (I, [P, L64, F, P, P]),
         "dmi_assemble_tokens": (I, [P, P, P, I, I, I, I, I, P]),
         "dmi_sample_tokens": (I, [P, I, P, I, I, F, I, ctypes.c_uint64, P, I, P, I, I, P, P, I, I, P]),
+        "dmi_sample_tokens_p": (I, [P, I, P, I, I, F, I, ctypes.c_uint64, F, P, I, P, I, I, P, P, I, I, P, P]),
         "dmi_ln_gemm_nt": (I, [P, I, P, P, F, P, I, P, I, I, I, I, I, P, P]),
         "dmi_logits_f32": (I, [P, I, P, P, I, I, P]),
         "dmi_gemm_nt_ln": (I, [P, I, P, I, P, I, I, I, I, P, P, P, P, F, P, I, P, P, P]),
@@ -488,6 +490,41 @@ def sample_tokens(z, ldz, bias, B, nv, temperature=1.0, top_k=0, seed=0, pos=0, 
     _check(lib().dmi_sample_tokens(_p(z), ldz, _p(bias), B, nv, float(temperature), int(top_k), int(seed) & (2 ** 64 - 1),
                                    _p(params_dev), int(pos), _p(pos_dev), int(bool(advance)), int(token_offset), _p(next_tok), _p(out), out_ld,
                                    int(out_col0), _stream()), "sample_tokens")
+
+
+def sample_tokens_p(z, ldz, bias, B, nv, temperature=1.0, top_k=0, seed=0, top_p=1.0, pos=0, token_offset=0, next_tok=None,
+                    out=None, out_col0=0, params_dev=None, pos_dev=None, advance=False, logp=None):
+    """sample_tokens with a nucleus (top-p) filter after the top-k one, and optionally the row's log-likelihood of the choice:
+    logp fp32 [B] (zeroed by the caller) += log_softmax(z + bias)[choice] at temperature 1, unfiltered.  params_dev is uint32 [6]:
+    {bits of 1/temperature (0: greedy), top_k, seed lo, seed hi, bits of top_p, 0}.  At top_p = 1 the tokens are sample_tokens'
+    bit for bit (include/dalle_hip.h)."""
+    _dev(z)
+    assert z.dtype == torch.bfloat16 and (bias is None or bias.dtype == torch.bfloat16)
+    if pos_dev is not None:
+        assert pos_dev.dtype == torch.int32 and pos_dev.numel() >= (2 if advance else 1), \
+            "sample_tokens_p: pos_dev must be int32 [2] ([position, zeroed counter]) when advance=True, int32 [1] otherwise"
+    if params_dev is not None:
+        assert params_dev.numel() >= 6 and params_dev.element_size() == 4, "sample_tokens_p: params_dev must be 32-bit [6]"
+    if logp is not None:
+        assert logp.dtype == torch.float32 and logp.numel() >= B, "sample_tokens_p: logp must be fp32 [B]"
+    for t in (bias, next_tok, out, params_dev, pos_dev, logp):
+        if t is not None:
+            _dev(t)
+    out_ld = int(out.shape[1]) if out is not None else 0
+    _check(lib().dmi_sample_tokens_p(_p(z), ldz, _p(bias), B, nv, float(temperature), int(top_k), int(seed) & (2 ** 64 - 1),
+                                     float(top_p), _p(params_dev), int(pos), _p(pos_dev), int(bool(advance)), int(token_offset),
+                                     _p(next_tok), _p(out), out_ld, int(out_col0), _p(logp), _stream()), "sample_tokens_p")
+
+
+def sample_params(temperature=1.0, top_k=0, seed=0, top_p=None):
+    """the device parameter block of the draw kernels as int32 (bit pattern of the uint32 words): [4] for sample_tokens,
+    [6] for sample_tokens_p when top_p is given"""
+    def bits(x):
+        return struct.unpack("<I", struct.pack("<f", x))[0]
+    words = [bits(1.0 / temperature if temperature > 0 else 0.0), int(top_k), int(seed) & 0xffffffff, (int(seed) >> 32) & 0xffffffff]
+    if top_p is not None:
+        words += [bits(top_p), 0]
+    return torch.tensor([w - (1 << 32) if w >= (1 << 31) else w for w in words], dtype=torch.int32)
 
 
 def logits_f32(z, ldz, bias, out, B, nv):

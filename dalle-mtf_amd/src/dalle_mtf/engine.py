@@ -543,72 +543,149 @@ class DalleEngine:
 
     # ------------------------------------------------------------------ sampling
     def sample_image_tokens(self, text: torch.Tensor, temperature: float = 1.0, top_k: int = 0, seed: int = 0,
-                            kv_cache: bool = True, decode_graph: bool = True, fused_sampling: bool = True) -> torch.Tensor:
+                            top_p: float = 1.0, image_prefix: Optional[torch.Tensor] = None, return_logprobs: bool = False,
+                            kv_cache: bool = True, decode_graph: bool = True, fused_sampling: bool = True):
         """Autoregressive image-token sampling: text int32 [B, T] -> image-token ids [B, P] in [0, image_vocab_size).
         The reference scaffolds this (is_incremental_inference, models.py:246-254,281-285) but its predict path raises
         NotImplementedError (model_fns.py:135-136).  Logits are restricted to the image vocabulary; temperature / top-k /
-        greedy (temperature 0).
+        greedy (temperature 0) / nucleus (top_p < 1).
 
         kv_cache=True (default): ONE full forward over the text prefix fills the per-layer key/value cache (the [B*S, 3d]
         projection buffers of the forward pass), then every further token is one incremental step over B rows --
         decode_step(): QKV GEMM writing row `pos` of the cache in place, dmi_attention_decode (one query against keys
         0..pos), out-projection, MLP -- ~90 launches of a few microseconds instead of a 1280-position forward, replayed as
         one HIP graph (decode_graph; see decode_step).
+        Under recompute_grad the forward keeps ONE shared set of projection buffers, so the sampler allocates its own
+        per-layer caches on the first cached call and keeps them for later calls: L * B * S * 3d * 2 bytes (dalle_coco at
+        B = 128: 12 GB); the prefill forward writes into them.  Training buffers are not touched.
         fused_sampling (with kv_cache and decode_graph): the draw itself is a kernel at the end of the replayed graph
         (dmi_sample_tokens: temperature / top-k / Gumbel-max categorical draw, noise a pure function of (seed, position, row))
         that writes the chosen token where the next step's embedding reads it -- P graph replays back to back, no host round
         trip per position.  fused_sampling=False launches the same draw kernel from the host after each decode step (same
         tokens for the same seed: the noise is a pure function of (seed, position, row, index)).
         kv_cache=False: the plain form, one full evaluation forward per generated position (the causal mask makes the
-        not-yet-generated tail irrelevant); kept as the cross-check the cached path is tested against."""
+        not-yet-generated tail irrelevant); kept as the cross-check the cached path is tested against.
+
+        top_p < 1 or return_logprobs=True draw with dmi_sample_tokens_p (nucleus filter after top-k; same noise, so top_p = 1
+        gives the same tokens); otherwise the launches are exactly those above.  return_logprobs=True returns (tokens,
+        logp fp32 [B]): the sum over the drawn positions of log softmax(logits over the image vocabulary)[token] at
+        temperature 1, unfiltered -- the model's own score of each sample.
+        image_prefix (int [B, k], ids in [0, image_vocab_size), 0 <= k < P): image completion.  The returned tokens start with
+        the prefix; positions T-1 .. T+k-2 go through the same decode steps as sampled positions, teacher-forced (the
+        decode_step body), and drawing starts at position T+k-1 -- so sampling s and then completing s[:, :k] returns s
+        bit for bit.  Prefix tokens are not drawn and add nothing to logp."""
         B, T, S, P = self.B, self.T, self.S, self.S - self.T
         assert text.shape == (B, T)
+        top_p = float(top_p)
+        if not (0.0 < top_p <= 1.0):
+            raise ValueError(f"sample_image_tokens: top_p must lie in (0, 1] (got {top_p})")
         lo, hi = self.text_vocab_size, self.text_vocab_size + self.image_vocab_size
+        nv = hi - lo
+        k = 0
+        if image_prefix is not None:
+            image_prefix = torch.as_tensor(image_prefix)
+            if image_prefix.dim() != 2 or image_prefix.shape[0] != B or not (0 <= image_prefix.shape[1] < P):
+                raise ValueError(f"sample_image_tokens: image_prefix must be [B={B}, k] with 0 <= k < {P} (got {tuple(image_prefix.shape)})")
+            if image_prefix.dtype.is_floating_point or image_prefix.dtype == torch.bool:
+                raise ValueError("sample_image_tokens: image_prefix must hold integer token ids")
+            k = int(image_prefix.shape[1])
+            if k and (int(image_prefix.min()) < 0 or int(image_prefix.max()) >= nv):
+                raise ValueError(f"sample_image_tokens: image_prefix ids must lie in [0, {nv})")
+        nucleus = top_p < 1.0 or return_logprobs
         toks = torch.full((B, S), lo, dtype=torch.int32, device=self.dev)
         toks[:, :T] = text.to(device=self.dev, dtype=torch.int32)
-        if kv_cache and self.recompute:
-            kv_cache = False     # recompute_grad keeps ONE shared set of projection buffers: there is no per-layer cache to decode from
-        if kv_cache and decode_graph and fused_sampling and self.image_vocab_size <= 8192:
-            self.forward(toks, need_grad=False)          # prefill: k, v of the text positions are in the cache
-            D = self._decode_state()
-            D["tok"].copy_(toks[:, T - 1])
-            D["pos_i"][0:1].fill_(T - 1)
-            inv_t = np.array([1.0 / temperature if temperature > 0 else 0.0], dtype=np.float32).view(np.uint32)[0]
-            prm = np.array([inv_t, int(top_k), seed & 0xffffffff, (seed >> 32) & 0xffffffff], dtype=np.uint32).view(np.int32)
-            D["params"].copy_(torch.from_numpy(prm))
-            for _ in range(P):                           # position T-1+i predicts image token i; the graph advances the position itself
-                self._run_decode(sample=True, graph=True)
-            return D["out"].clone()
+        if k:
+            toks[:, T:T + k] = image_prefix.to(device=self.dev, dtype=torch.int32) + lo
+        logp = torch.zeros(B, dtype=torch.float32, device=self.dev) if return_logprobs else None
 
-        nv = hi - lo
+        def result(img):
+            return (img, logp) if return_logprobs else img
+
+        if kv_cache and decode_graph and fused_sampling and nv <= 8192:
+            self._prefill(toks)                          # k, v of the text positions are in the cache
+            D = self._decode_state()
+            for pos in range(T - 1, T - 1 + k):          # the prefix, teacher-forced through the decode step
+                self.decode_step(toks[:, pos].contiguous(), pos, graph=True)
+            D["tok"].copy_(toks[:, T - 1 + k])
+            D["pos_i"][0:1].fill_(T - 1 + k)
+            if nucleus:
+                D["params"].copy_(dh.sample_params(temperature, top_k, seed, top_p))
+                variant = "p+logp" if return_logprobs else "p"
+                if return_logprobs:
+                    D["logp"].zero_()
+            else:
+                inv_t = np.array([1.0 / temperature if temperature > 0 else 0.0], dtype=np.float32).view(np.uint32)[0]
+                prm = np.array([inv_t, int(top_k), seed & 0xffffffff, (seed >> 32) & 0xffffffff], dtype=np.uint32).view(np.int32)
+                D["params"][:4].copy_(torch.from_numpy(prm))
+                variant = True
+            for _ in range(P - k):                       # position T-1+i predicts image token i; the graph advances the position itself
+                self._run_decode(sample=variant, graph=True)
+            img = D["out"].clone()
+            if k:
+                img[:, :k] = toks[:, T:T + k] - lo
+            if return_logprobs:
+                logp.copy_(D["logp"])
+            return result(img)
+
         if nv > 8192:
             raise dh.DalleHipError(f"sample_image_tokens: the draw kernel (dmi_sample_tokens) handles image vocabularies up to 8192 (got {nv})")
         bias = self._w("to_logits/linear_out/bias")[lo:hi]
         nxt = torch.empty(B, dtype=torch.int32, device=self.dev)
 
         def pick(z, ldz, zbias, position):
-            """the draw itself is dmi_sample_tokens on every path (temperature / top-k / Gumbel-max with counter-based noise
-            hash(seed, position, row, index), first maximum when temperature <= 0): host-launched here, the last node of the
-            replayed graph on the fused path -- the same (seed, position) gives the same draw on both."""
-            dh.sample_tokens(z, ldz, zbias, B, nv, temperature=temperature, top_k=top_k, seed=seed, pos=position,
-                             token_offset=lo, next_tok=nxt)
+            """the draw itself is dmi_sample_tokens (dmi_sample_tokens_p for top_p / logp) on every path (temperature / top-k /
+            Gumbel-max with counter-based noise hash(seed, position, row, index), first maximum when temperature <= 0):
+            host-launched here, the last node of the replayed graph on the fused path -- the same (seed, position) gives the
+            same draw on both."""
+            if nucleus:
+                dh.sample_tokens_p(z, ldz, zbias, B, nv, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p, pos=position,
+                                   token_offset=lo, next_tok=nxt, logp=logp)
+            else:
+                dh.sample_tokens(z, ldz, zbias, B, nv, temperature=temperature, top_k=top_k, seed=seed, pos=position,
+                                 token_offset=lo, next_tok=nxt)
             return nxt
 
         for pos in range(P):
             if not kv_cache:
+                if pos < k:
+                    continue                             # the causal mask: a full forward needs no steps over the prefix
                 self.forward(toks, need_grad=False)
                 # the position before predicts token T + pos; the evaluation head already carries the bias (GEMM epilogue)
                 z = self.z.view(B, S, self.Vp)[:, T + pos - 1, lo:hi]
                 tok = pick(z, S * self.Vp, None, T + pos - 1)
             else:
                 if pos == 0:
-                    self.forward(toks, need_grad=False)    # prefill: leaves k, v of the text positions in the cache
+                    self._prefill(toks)                  # leaves k, v of the text positions in the cache
                 # (position T - 1 is decoded again rather than read from the prefill's logits: every cached path then takes
                 # every token through the same arithmetic)
                 self.decode_step(toks[:, T + pos - 1].contiguous(), T + pos - 1, graph=decode_graph)
+                if pos < k:
+                    continue                             # teacher-forced: the prefix token is already in toks
                 tok = pick(self._dec["z"], nv, bias, T + pos - 1)      # bf16 head output + bias, as the fused path draws
             toks[:, T + pos] = tok
-        return (toks[:, T:] - lo).contiguous()
+        return result((toks[:, T:] - lo).contiguous())
+
+    def _kv_caches(self):
+        """the per-layer [B*S, 3d] key/value caches the decode step reads: the forward's own projection buffers, or under
+        recompute_grad (one shared buffer) the sampler's, allocated once: L * B * S * 3d * 2 bytes"""
+        if not self.recompute:
+            return self.qkv
+        if getattr(self, "_kv", None) is None:
+            self._kv = [torch.empty(self.M, 3 * self.d, dtype=torch.bfloat16, device=self.dev) for _ in range(self.L)]
+        return self._kv
+
+    def _prefill(self, toks):
+        """evaluation forward over toks that leaves every layer's q | k | v in the decode caches"""
+        caches = self._kv_caches()
+        if caches is self.qkv:
+            self.forward(toks, need_grad=False)
+            return
+        shared = self.qkv
+        self.qkv = caches
+        try:
+            self.forward(toks, need_grad=False)
+        finally:
+            self.qkv = shared
 
     def _decode_state(self):
         if getattr(self, "_dec", None) is None:
@@ -621,14 +698,14 @@ class DalleEngine:
                              z=torch.empty(B, self.image_vocab_size, **b16), fresh=torch.empty(B, 3 * d, **b16),
                              tok=torch.empty(B, **i32), pos_i=torch.zeros(2, **i32),    # [position, scratch counter of the sampler]
                              logits=torch.empty(B, self.image_vocab_size, **f32),
-                             params=torch.zeros(4, **i32), out=torch.zeros(B, self.S - self.T, **i32),
+                             params=torch.zeros(6, **i32), out=torch.zeros(B, self.S - self.T, **i32), logp=torch.zeros(B, **f32),
                              graphs={}, warm=set())
         return self._dec
 
     def decode_step(self, tokens_at_pos: torch.Tensor, pos: int, graph: bool = True) -> torch.Tensor:
         """Incremental inference (reference hooks src/dalle_mtf/models.py:246-254,281-285): the hidden state of sequence
         position `pos` alone, given the tokens int32 [B] at that position and the key/value cache of positions < pos left by
-        forward() / earlier decode steps in self.qkv[l].  Returns fp32 logits over the IMAGE vocabulary [B, image_vocab_size]
+        forward() / earlier decode steps in self.qkv[l] (under recompute_grad: in the sampler's caches, filled by its prefill).  Returns fp32 logits over the IMAGE vocabulary [B, image_vocab_size]
         (what predicts the token at pos + 1; the buffer is reused by the next call).
 
         graph=True: the ~90 launches of a step are a few microseconds of GPU work each, so the step is launch-bound when
@@ -644,7 +721,9 @@ class DalleEngine:
         self._run_decode(sample=False, graph=graph)
         return D["logits"]
 
-    def _run_decode(self, sample: bool, graph: bool):
+    def _run_decode(self, sample, graph: bool):
+        """sample: False (the decode_step body) or the draw variant (True: dmi_sample_tokens, "p" / "p+logp":
+        dmi_sample_tokens_p without / with logp) -- one captured graph per variant, the draw node differs"""
         D = self._dec
         if not graph:
             self._decode_body(sample)
@@ -660,10 +739,11 @@ class DalleEngine:
                 D["graphs"][sample] = g    # (capture records, it does not execute: the replay below is the step)
             D["graphs"][sample].replay()
 
-    def _decode_body(self, sample: bool = False):
+    def _decode_body(self, sample=False):
         """the launches of one decode step; reads D[tok] and the position D[pos_i][0] from device memory.  sample=False: writes
-        D[logits].  sample=True: draws the next token (settings in D[params]) into D[tok] and column pos - (T - 1) of
-        D[out], then advances the position (inside the sampling kernel).
+        D[logits].  sample=True / "p" / "p+logp": draws the next token (settings in D[params]) into D[tok] and
+        column pos - (T - 1) of D[out], then advances the position (inside the sampling kernel); "p" draws with the nucleus
+        kernel, "p+logp" also adds the choice's log-probability to D[logp].
         B <= 32: LayerNorm rides in the prologue of the product that consumes it (dmi_ln_gemm_nt) -- 5 dependent launches per
         block instead of 7; a dependent launch costs ~7 us on this part, more than any of these kernels' work."""
         B, d, L, H, S = self.B, self.d, self.L, self.H, self.S
@@ -679,11 +759,12 @@ class DalleEngine:
                 dh.layernorm_fwd(inp, g, b, xn, st[0], st[1], B, d)
                 dh.gemm_nt(xn, d, W, d, out, N, B, N, d, flags, bias=bias)
 
+        caches = self._kv_caches()
         dh.embed_fwd(D["tok"], self._w("embedding/wte"), self._w("positional_embedding/wpe"), x, S, d, self.V,
                      pos_dev=D["pos_i"])                                  # every row takes wpe[pos]
         for l in range(L):
             p = f"layer_{l}/"
-            cache = self.qkv[l]                                        # [B*S, 3d]; row b*S + pos <- q | k | v of this step
+            cache = caches[l]                                          # [B*S, 3d]; row b*S + pos <- q | k | v of this step
             ln_dense(x, p + "norm_1", self.tview(p + "attn/qkv"), fresh, 3 * d)
             dh.attention_decode(cache, o, B, H, S, 0, fresh=fresh, pos_dev=D["pos_i"], head_dim=self.hd)
             dh.gemm_nt(o, d, self.tview(p + "attn/o"), d, x1, d, B, d, d, dh.GEMM_BIAS | dh.GEMM_RESIDUAL,
@@ -696,7 +777,10 @@ class DalleEngine:
         Wt = self.tview("to_logits/linear_out/kernel")                 # [Vp, d]: rows lo .. lo + nv are the image vocabulary
         ln_dense(x, "to_logits/layer_norm", Wt[lo:lo + nv], z, nv)
         bias = self._w("to_logits/linear_out/bias")[lo:lo + nv]
-        if sample:
+        if sample in ("p", "p+logp"):
+            dh.sample_tokens_p(z, nv, bias, B, nv, params_dev=D["params"], pos_dev=D["pos_i"], advance=True, token_offset=lo,
+                               next_tok=D["tok"], out=D["out"], out_col0=self.T - 1, logp=D["logp"] if sample == "p+logp" else None)
+        elif sample:
             dh.sample_tokens(z, nv, bias, B, nv, params_dev=D["params"], pos_dev=D["pos_i"], advance=True, token_offset=lo,
                              next_tok=D["tok"], out=D["out"], out_col0=self.T - 1)
         else:

@@ -70,11 +70,19 @@ class DALLE:
                     "to_logits/linear_out/kernel": (d, V), "to_logits/linear_out/bias": (V,)})
         return out
 
-    def sample(self, text_tokens, vae=None, temperature=1.0, top_k=0, seed=0):
+    def sample(self, text_tokens, vae=None, temperature=1.0, top_k=0, seed=0, top_p=1.0, image_prefix=None, return_logprobs=False):
         """text ids [B, text_seq_len] -> image-token ids [B, image_seq_len] (and the decoded images when a DiscreteVAE is
-        given): the generation path the reference leaves unfinished (model_fns.py:135-136)."""
-        toks = self.engine.sample_image_tokens(text_tokens, temperature=temperature, top_k=top_k, seed=seed)
-        return (toks, vae.decode_tokens(toks)) if vae is not None else toks
+        given): the generation path the reference leaves unfinished (model_fns.py:135-136).  top_p < 1: nucleus filter after
+        top-k; image_prefix int [B, k]: complete images from their first k tokens; return_logprobs: also the model's
+        log-likelihood of each sample, fp32 [B] (DalleEngine.sample_image_tokens).  Returns toks, (toks, images),
+        (toks, logp) or (toks, images, logp)."""
+        res = self.engine.sample_image_tokens(text_tokens, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p,
+                                              image_prefix=image_prefix, return_logprobs=return_logprobs)
+        toks, logp = res if return_logprobs else (res, None)
+        out = (toks, vae.decode_tokens(toks)) if vae is not None else (toks,)
+        if return_logprobs:
+            out = out + (logp,)
+        return out if len(out) > 1 else out[0]
 
     def forward(self, features, return_loss=True, return_logits=False):
         """features["tokens"]: int32 [B, S] device tensor.  Returns (loss, loss_batch[, logits]) like the

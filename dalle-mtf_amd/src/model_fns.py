@@ -77,6 +77,49 @@ def serialize_num_microbatches(batch_per_replica, sequence_length, tokens_per_mi
     return max(1, batch_per_replica // microbatch_size)
 
 
+def image_seq_len_of(params):
+    """image tokens per sequence: params["synthetic_image_tokens"], or the VAE's grid (reference model_fns.py:68)"""
+    if params.get("synthetic_image_tokens"):
+        return int(params["synthetic_image_tokens"])
+    vp = params["vae_params"]
+    cb = vp.get("convblocks") or [(3, 64), (3, 128), (3, 256)]
+    return (params["dataset"]["image_size"] // (2 ** len(cb))) ** 2 // ((vp.get("stack_factor") or 1) ** 2)
+
+
+def restore_dalle_weights(eng, params, checkpoint=None):
+    """the DALL-E weights of a run: `checkpoint` when given (a model.ckpt-<step>.pt of this build, a run directory, or the
+    `<prefix>` of a checkpoint of the reference), else the newest checkpoint under params["model_path"], else
+    params["tf_checkpoint"], else a fresh initialisation.  Returns the path restored from, or None."""
+    ck = None
+    if checkpoint is not None:
+        if os.path.isdir(checkpoint):
+            ck = latest_checkpoint(checkpoint)
+            if ck is None:
+                raise FileNotFoundError(f"no model.ckpt-<step>.pt under {checkpoint}")
+        elif os.path.exists(str(checkpoint) + ".index"):
+            from .data.tf_checkpoint import global_step_of, load_model_variables
+            eng.load_reference_params(load_model_variables(str(checkpoint)))
+            eng.global_step = global_step_of(str(checkpoint))
+            return str(checkpoint)
+        elif os.path.isfile(checkpoint):
+            ck = checkpoint
+        else:
+            raise FileNotFoundError(f"checkpoint {checkpoint} not found")
+    elif params.get("model_path"):
+        ck = latest_checkpoint(params["model_path"])
+    if ck is not None:
+        eng.load_state_dict(torch.load(ck, map_location="cpu")["dalle"])
+        return ck
+    if params.get("tf_checkpoint"):
+        # warm start from a checkpoint of the reference (`<prefix>.index` + `.data-*`, variable names of SURVEY Appendix B)
+        from .data.tf_checkpoint import global_step_of, load_model_variables
+        eng.load_reference_params(load_model_variables(params["tf_checkpoint"]))
+        eng.global_step = global_step_of(params["tf_checkpoint"])
+        return params["tf_checkpoint"]
+    eng.init_params(seed=params.get("seed") or 1234)
+    return None
+
+
 def _build(params, mode_str):
     world, rank, pg, comm = _dist_info()
     mesh = parse_mesh_shape(params.get("mesh_shape"))
@@ -84,13 +127,8 @@ def _build(params, mode_str):
     assert gbs % world == 0, f"{mode_str}_batch_size {gbs} must divide over {world} data-parallel ranks"
     local_bs = gbs // world
     state = {"world": world, "rank": rank}
-    if params.get("synthetic_image_tokens"):
-        image_seq_len = int(params["synthetic_image_tokens"])
-    else:
-        vp = params["vae_params"]
-        cb = vp.get("convblocks") or [(3, 64), (3, 128), (3, 256)]
-        # reference model_fns.py:68 (from the VAE's configuration: the micro-batch count below sizes the tokenizer)
-        image_seq_len = (params["dataset"]["image_size"] // (2 ** len(cb))) ** 2 // ((vp.get("stack_factor") or 1) ** 2)
+    # reference model_fns.py:68 (from the VAE's configuration: the micro-batch count below sizes the tokenizer)
+    image_seq_len = image_seq_len_of(params)
     nmb = 1
     if mode_str == "train":
         nmb = serialize_num_microbatches(local_bs, params["text_seq_len"] + image_seq_len,
@@ -115,16 +153,7 @@ def _build(params, mode_str):
     eng.hp["num_microbatches"] = nmb   # reference model_fns.py:141-154 (1 when tokens_per_mb_per_replica is unset)
     params["num_microbatches"] = nmb
     state["local_bs"] = local_bs
-    ck = latest_checkpoint(params["model_path"]) if params.get("model_path") else None
-    if ck is not None:
-        eng.load_state_dict(torch.load(ck, map_location="cpu")["dalle"])
-    elif params.get("tf_checkpoint"):
-        # warm start from a checkpoint of the reference (`<prefix>.index` + `.data-*`, variable names of SURVEY Appendix B)
-        from .data.tf_checkpoint import global_step_of, load_model_variables
-        eng.load_reference_params(load_model_variables(params["tf_checkpoint"]))
-        eng.global_step = global_step_of(params["tf_checkpoint"])
-    else:
-        eng.init_params(seed=params.get("seed") or 1234)
+    state["restored_from"] = restore_dalle_weights(eng, params, params.get("_dalle_checkpoint"))
     if world > 1:
         # every rank starts from rank 0's weights, optimizer state AND step (the LR schedule and the loop length depend on it)
         import torch.distributed as dist

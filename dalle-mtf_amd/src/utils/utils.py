@@ -119,6 +119,16 @@ def scalar_summary(name, x):
     return x
 
 
+def pil_images(x):
+    """NHWC images in [0, 1] (tensor or array) -> [(uint8 HWC array, PIL image)]: the PNG path of SummaryWriter.images, also
+    what src/generate.py writes its samples with"""
+    import numpy as np
+    from PIL import Image
+    a = x.detach().float().cpu().numpy() if hasattr(x, "detach") else np.asarray(x, np.float32)
+    a = (np.clip(a, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+    return [(im, Image.fromarray(im[..., 0] if im.shape[-1] == 1 else im[..., :3])) for im in a]
+
+
 class SummaryWriter:
     """tf2.summary.create_file_writer stand-in (reference src/utils/utils.py:103-161, src/model_fns_tf.py:68-96): scalars and
     images go to a TensorBoard event file `events.out.tfevents.<time>.<host>` under model_dir -- TFRecord framing of
@@ -164,16 +174,11 @@ class SummaryWriter:
         """tf2.summary.image (reference src/model_fns_tf.py:74-75,89-90; TF writes max_outputs = 3 images):
         x NHWC in [0, 1] -> event-file Image values tagged <name>/image/<i> and model_dir/images/<name>_<step>_<i>.png"""
         import io
-        import numpy as np
-        from PIL import Image
         from ..data.tfrecord import _ld, _varint
         d = os.path.join(os.path.dirname(self.path), "images")
         os.makedirs(d, exist_ok=True)
-        a = x[:max_images].detach().float().cpu().numpy() if hasattr(x, "detach") else np.asarray(x[:max_images], np.float32)
-        a = (np.clip(a, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
         summary = b""
-        for i, im in enumerate(a):
-            pil = Image.fromarray(im[..., 0] if im.shape[-1] == 1 else im[..., :3])
+        for i, (im, pil) in enumerate(pil_images(x[:max_images])):
             pil.save(os.path.join(d, f"{name.replace('/', '_')}_{int(step)}_{i}.png"))
             buf = io.BytesIO()
             pil.save(buf, format="PNG")

@@ -263,6 +263,24 @@ int dmi_sample_tokens(const uint16_t* z, int ldz, const uint16_t* bias, int B, i
                       uint64_t seed, const uint32_t* params_dev, int pos, int32_t* pos_dev, int advance, int token_offset,
                       int32_t* next_tok, int32_t* out, int out_ld, int out_col0, void* stream);
 
+/* Nucleus (top-p) draw with the log-likelihood of the choice: dmi_sample_tokens's arguments plus top_p and logp.
+ * v and the top-k filter as above; then q = softmax(v) over the top-k survivors, in fixed point: u[i] = floor(exp(v[i] - max v) * 2^31),
+ * the mass of a set is the 64-bit integer sum of its u, Z the mass of all survivors, target = ceil(double(top_p) * double(Z)).
+ * Nucleus: the shortest prefix of the survivors sorted by q (descending) whose mass reaches top_p; tau = the u of its last entry;
+ * EVERY survivor with u >= tau is kept (ties at tau kept, the top-k rule).  Found without a sort: a 32-step bitwise search for the
+ * largest tau with mass(u >= tau) >= target.  The draw is Gumbel-max over the kept set with dmi_sample_tokens's noise
+ * hash(seed, position, b, i).  top_p = 1: no nucleus step, the tokens equal dmi_sample_tokens's bit for bit.  temperature <= 0:
+ * first maximum (top_k and top_p ignored).  0 < top_p <= 1, else DMI_ERR_INVALID (NaN included).
+ * logp (nullable, device fp32 [B], zeroed by the caller): logp[b] += (z + bias)[c] - logsumexp_i (z + bias)[i], c the choice --
+ * the log-probability of the drawn token at temperature 1, unfiltered, over the nv columns; one call per position accumulates a
+ * sample's score.
+ * params_dev (optional, device uint32[6] = {bits of 1/temperature (0: greedy), top_k, seed low, seed high, bits of top_p, 0})
+ * overrides temperature / top_k / seed / top_p (a device top_p outside (0, 1) skips the nucleus step); pos_dev / advance /
+ * next_tok / out as for dmi_sample_tokens.  One 256-thread block per row, nv <= 8192, 64 KB of LDS per block. */
+int dmi_sample_tokens_p(const uint16_t* z, int ldz, const uint16_t* bias, int B, int nv, float temperature, int top_k,
+                        uint64_t seed, float top_p, const uint32_t* params_dev, int pos, int32_t* pos_dev, int advance,
+                        int token_offset, int32_t* next_tok, int32_t* out, int out_ld, int out_col0, float* logp, void* stream);
+
 /* "Go to full precision for the logits" (src/dalle_mtf/models.py:394-395) for a slice of the head's output:
  * out[b, i] = float(z[b, i]) + float(bias[i]), z bf16 [B, ldz] (first nv columns), bias bf16 [nv] (nullable), out fp32 [B, nv]. */
 int dmi_logits_f32(const uint16_t* z, int ldz, const uint16_t* bias, float* out, int B, int nv, void* stream);

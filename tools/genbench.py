@@ -1,0 +1,103 @@
+"""Generation throughput in one process (random weights): the KV-cached graph sampler against the plain sampler (one full
+forward per position), and the per-position cost of the draw variants (top-k, top-k + top-p, + log-likelihood).
+    python tools/genbench.py --shape example|coco --batch B [--out FILE.json]
+    python tools/genbench.py --kernels        # the two draw kernels alone (time them under rocprofv3 --kernel-trace --stats)
+The plain sampler is timed over its last --plain-positions positions (an image prefix teacher-forces the rest; each of its
+positions is one full forward, so the rate does not depend on which positions are timed)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "dalle-mtf_amd"))
+import torch  # noqa: E402
+
+SHAPES = {"example": dict(d=512, L=6, H=4, iv=512, hp={}),                        # configs/dalle_example.json
+          "coco": dict(d=1024, L=12, H=8, iv=2048, hp=dict(recompute_grad=True))}  # configs/dalle_coco.json (recompute on)
+
+
+def timed(fn, reps=1):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        r = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps, r
+
+
+def engine_bench(shape, B, plain_positions):
+    from src.dalle_mtf.engine import DalleEngine
+    c = SHAPES[shape]
+    T, P, tv = 256, 1024, 50258
+    eng = DalleEngine(c["d"], c["L"], c["H"], tv, c["iv"], T, P, batch_size=B, hparams=dict(lr=1e-3, train_steps=10, **c["hp"]))
+    eng.init_params(seed=1)
+    text = torch.randint(0, tv - 1, (B, T), dtype=torch.int32, device="cuda")
+    res = dict(shape=shape, batch=B, n_embd=c["d"], n_layers=c["L"], n_heads=c["H"], seq=T + P, image_vocab=c["iv"],
+               recompute_grad=bool(eng.recompute))
+    variants = (("top_k", dict(temperature=1.0, top_k=32)), ("top_k+top_p", dict(temperature=1.0, top_k=32, top_p=0.9)),
+                ("top_k+top_p+logp", dict(temperature=1.0, top_k=32, top_p=0.9, return_logprobs=True)),
+                ("top_p", dict(temperature=1.0, top_p=0.9)))
+    for _, kw in variants:
+        eng.sample_image_tokens(text, seed=0, **kw)        # warm-up: caches, graph capture per variant
+        eng.sample_image_tokens(text, seed=0, **kw)
+    for name, kw in variants:
+        dt, _ = timed(lambda: eng.sample_image_tokens(text, seed=1, **kw))
+        res[f"cached_graph_{name}_tokens_per_s"] = round(B * P / dt, 1)
+        res[f"cached_graph_{name}_ms_per_position"] = round(dt / P * 1e3, 4)
+    k = P - plain_positions
+    prefix = torch.zeros(B, k, dtype=torch.int32)
+    eng.sample_image_tokens(text, seed=0, temperature=1.0, top_k=32, kv_cache=False, image_prefix=prefix[:, :P - 1])   # warm-up
+    dt, _ = timed(lambda: eng.sample_image_tokens(text, seed=1, temperature=1.0, top_k=32, kv_cache=False, image_prefix=prefix))
+    res["plain_top_k_tokens_per_s"] = round(B * plain_positions / dt, 1)
+    res["plain_top_k_ms_per_position"] = round(dt / plain_positions * 1e3, 3)
+    res["plain_positions_timed"] = plain_positions
+    res["cached_over_plain"] = round(res["cached_graph_top_k_tokens_per_s"] / res["plain_top_k_tokens_per_s"], 1)
+    if eng.recompute:
+        res["sampler_kv_cache_bytes"] = int(sum(t.numel() * t.element_size() for t in eng._kv))
+    return res
+
+
+def kernel_bench(reps):
+    import dalle_hip as dh
+    res = {}
+    for nv in (2048, 8192):
+        for B in (32, 128):
+            z = (torch.randn(B, nv, device="cuda") * 2).to(torch.bfloat16)
+            bias = (torch.randn(nv, device="cuda") * 0.5).to(torch.bfloat16)
+            nxt = torch.empty(B, dtype=torch.int32, device="cuda")
+            lp = torch.zeros(B, dtype=torch.float32, device="cuda")
+            runs = (("sample_tokens top_k=32", lambda p: dh.sample_tokens(z, nv, bias, B, nv, temperature=1.0, top_k=32, seed=1, pos=p, next_tok=nxt)),
+                    ("sample_tokens_p top_k=32 top_p=0.9", lambda p: dh.sample_tokens_p(z, nv, bias, B, nv, temperature=1.0, top_k=32, seed=1, top_p=0.9, pos=p, next_tok=nxt)),
+                    ("sample_tokens_p top_p=0.9", lambda p: dh.sample_tokens_p(z, nv, bias, B, nv, temperature=1.0, seed=1, top_p=0.9, pos=p, next_tok=nxt)),
+                    ("sample_tokens_p top_p=0.9 logp", lambda p: dh.sample_tokens_p(z, nv, bias, B, nv, temperature=1.0, seed=1, top_p=0.9, pos=p, next_tok=nxt, logp=lp)))
+            for name, fn in runs:
+                for p in range(reps):
+                    fn(p)
+                torch.cuda.synchronize()
+                dt, _ = timed(lambda: [fn(p) for p in range(reps)])
+                res[f"nv{nv} B{B} {name} host_us_per_launch"] = round(dt / reps * 1e6, 2)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shape", choices=sorted(SHAPES), default="example")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--plain-positions", type=int, default=16)
+    ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    res = kernel_bench(a.reps) if a.kernels else engine_bench(a.shape, a.batch, a.plain_positions)
+    res["device"] = torch.cuda.get_device_name(0)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
