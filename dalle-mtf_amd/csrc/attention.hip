@@ -16,6 +16,9 @@
 // source side) and every transposed fragment (V^T, K^T, Q^T, dO^T) is a hardware transpose read (ds_read_b64_tr_b16).
 #include "common.h"
 #include <type_traits>
+#include <algorithm>
+#include <string.h>
+#include <vector>
 
 #define HD 128
 #define LOG2E_F 1.4426950408889634f
@@ -2260,5 +2263,983 @@ extern "C" int dmi_attention_decode_hd(uint16_t* qkv, const uint16_t* fresh, uin
   attn64_decode_kernel<<<dim3((unsigned)(B * H)), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream>>>((bf16_t*)qkv, (const bf16_t*)fresh,
                                                                                                    (bf16_t*)o, H, S, pos, pos_dev);
   DMI_CHECK_LAUNCH("attention_decode");
+  return DMI_OK;
+}
+
+// =====================================================================================
+// custom attention masks, head dim 128: block-sparse forms of the forward, dQ, dK/dV and decode kernels
+// =====================================================================================
+// A mask is a boolean [S, S] matrix M (M[i][j]: query i may attend to key j), causal and with no empty row; where M is false the
+// probability is exactly 0.  dmi_attn_mask_plan compiles it on the host into a plan of int32 words (DESIGN.md §4 "Attention masks"):
+//   header (AMP_HDR words)  magic, S, NB = ceil(S/128), W = ceil(S/32), causal flag, word offsets of the sections below, tile counts;
+//   forward / dQ lists      per 128-query block (CSR: NB + 1 pointers, then entries): its live 64-key tiles in key order, entry =
+//                           tile | (class of each wave's 32 x 64 sub-tile << 16 + 2 wave), class 0 empty (the wave skips the tile),
+//                           1 full (no predicate), 2 partial (the row bitmap is applied with a select: masked scores are -inf);
+//   dK/dV lists             per 128-key block: its live 32-query tiles in query order, entry = tile | (partial << 16);
+//   two work orders         the blocks of each kind sorted by their number of live tiles, heaviest first -- the persistent kernels
+//                           deal (order position, batch * head) items in the serpentine of attn_sched / attn_item, as the causal
+//                           kernels deal their 40, 36, ..., 4-step tiles;
+//   row bitmap [S][W]       bit b of word w of row i = M[i][32 w + b] (partial forward / dQ tiles, the decode row of `pos`);
+//   column bitmap [S][W]    bit b of word w of row j = M[32 w + b][j] (partial dK/dV tiles).
+// A tile no query of a block attends to is never loaded.  Bits of keys >= S are 0, so a tile that reaches past S is partial.
+// The kernels below keep the buffer layouts, the unscaled fp32 softmax, the tile shapes and the persistent schedule of the causal
+// kernels; the causal kernels themselves are unchanged (a causal plan is routed to them unless the option attn_mask_force is set).
+#define AMP_MAGIC 0x504d4144
+#define AMP_HDR 32
+enum {
+  AMP_S = 1, AMP_NB, AMP_W, AMP_CAUSAL, AMP_FPTR, AMP_FLIST, AMP_KPTR, AMP_KLIST, AMP_FORDER, AMP_KORDER, AMP_ROWBITS, AMP_COLBITS,
+  AMP_WORDS, AMP_LIVE_F, AMP_CAUSAL_F, AMP_LIVE_K, AMP_CAUSAL_K
+};
+extern int g_opt_attn_mask_force;   // 1: a causal plan runs the masked kernels too (tests, tools/attn_mask_bench.py)
+
+// ---- forward: attn_fwd_kernel (the round-2 program-order form, not the default software-pipelined attn_fwd2_kernel) walking a
+// block's live key tiles.  Built for two waves per SIMD.
+__global__ __launch_bounds__(256, 2) void attn_fwd_masked_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o,
+                                                                 float* __restrict__ lse, const int* __restrict__ plan, int B, int H,
+                                                                 int S, int perxcd) {
+  extern __shared__ __attribute__((aligned(16))) char sm[];  // 2 x QK_STAGE
+  const int d = H * HD, ld3 = 3 * d;
+  const int T = plan[AMP_NB], W = plan[AMP_W];
+  const int* __restrict__ fptr = plan + plan[AMP_FPTR];
+  const int* __restrict__ flist = plan + plan[AMP_FLIST];
+  const int* __restrict__ forder = plan + plan[AMP_FORDER];
+  const unsigned* __restrict__ rowbits = (const unsigned*)(plan + plan[AMP_ROWBITS]);
+  const AttnSched sched = attn_sched(T, B * H, perxcd);
+  int tile_, bh;
+  for (int round = 0; attn_item(sched, round, tile_, bh); ++round) {
+  const int qt = forder[tile_];   // heaviest query blocks first
+  const int* __restrict__ list = flist + fptr[qt];
+  const int nsteps = fptr[qt + 1] - fptr[qt];
+  const int b = bh / H, hh = bh % H;
+  const int q0 = qt * 128;
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, h = lane >> 5, g4 = lane >> 4, l16 = lane & 15;
+  const int qrow = q0 + wid * 32 + r;
+  const int qrow_c = qrow < S ? qrow : S - 1;
+  const unsigned* __restrict__ mrow = rowbits + (int64_t)qrow_c * W;
+  const bf16_t* qb = qkv + (int64_t)b * S * ld3 + hh * HD;
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
+  const int nbytes = (int)(((int64_t)(S - 1) * ld3 + HD) * 2);
+  const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)(qb + d), 0, nbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)(qb + 2 * d), 0, nbytes, 0x00020000);
+
+  bf16x8 qf[8];
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk) qf[kk] = *(const bf16x8*)(qb + (int64_t)qrow_c * ld3 + 16 * kk + 8 * h);
+
+  int vo[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = tid + 256 * i, row = c >> 4, pc = c & 15;
+    vo[i] = (row * ld3 + 8 * (pc ^ swz(row))) * 2;
+  }
+  auto stage = [&](int st, int key0) {
+    char* base = sm + st * QK_STAGE;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      dma16(rk, base + (wid * 64 + 256 * i) * 16, vo[i] + key0 * ld3 * 2);
+      dma16(rv, base + 16384 + (wid * 64 + 256 * i) * 16, vo[i] + key0 * ld3 * 2);
+    }
+  };
+  int ofa[8];
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk) ofa[kk] = r * 256 + (((2 * kk + h) ^ swz(r)) << 4);
+  const int rr = l16 >> 2;
+  unsigned oft[4][2];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+    for (int w2 = 0; w2 < 2; ++w2) {
+      const int row = 4 * h + rr + 8 * w2;
+      const int chunk = dt * 4 + 2 * (g4 & 1) + ((l16 & 3) >> 1);
+      oft[dt][w2] = row * 256 + ((chunk ^ swz(row)) << 4) + 8 * (l16 & 1);
+    }
+
+  f32x16 oacc[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) oacc[i][e] = 0.f;
+  float m = -1e30f, l = 0.f;
+
+  // row bits of a partial tile: keys 64 j + 0..31 and + 32..63 of this lane's query row (words past the row read as 0)
+  auto bits = [&](int ent, unsigned& b0, unsigned& b1) {
+    const int j = ent & 0xffff;
+    b0 = b1 = 0xffffffffu;
+    if (((ent >> (16 + 2 * wid)) & 3) == 2) {
+      b0 = mrow[2 * j];
+      b1 = 2 * j + 1 < W ? mrow[2 * j + 1] : 0u;
+    }
+  };
+  auto compute = [&](int st, int ent, unsigned b0, unsigned b1) {
+    const int cls = (ent >> (16 + 2 * wid)) & 3;
+    if (cls == 0) return;  // wave-uniform: no query row of this wave attends to the tile
+    const char* base = sm + st * QK_STAGE;
+    const unsigned vb = lds0 + st * QK_STAGE + 16384;
+    f32x16 s0, s1;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) s0[e] = s1[e] = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) {
+      const bf16x8 a0 = *(const bf16x8*)(base + ofa[kk]);
+      const bf16x8 a1 = *(const bf16x8*)(base + 8192 + ofa[kk]);
+      s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, qf[kk], s0, 0, 0, 0);  // S^T[key][q]
+      s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, qf[kk], s1, 0, 0, 0);
+    }
+    Tr4 tv[2];
+    tr4_issue(tv[0], vb + oft[0][0], vb + oft[0][1], vb + oft[1][0], vb + oft[1][1], vb + oft[2][0], vb + oft[2][1], vb + oft[3][0], vb + oft[3][1]);
+    if (cls == 2) {  // partial tile: select, so masked scores are -inf (probability exactly 0, never NaN)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int kb = (e & 3) + 8 * (e >> 2) + 4 * h;
+        s0[e] = ((b0 >> kb) & 1u) ? s0[e] : -INFINITY;
+        s1[e] = ((b1 >> kb) & 1u) ? s1[e] : -INFINITY;
+      }
+    }
+    float mx = -1e30f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) mx = fmaxf(mx, fmaxf(s0[e], s1[e]));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    if (__any(mx > m)) {
+      const float mn = fmaxf(m, mx);
+      const float alpha = __builtin_amdgcn_exp2f((m - mn) * LOG2E_F);
+      m = mn;
+      l *= alpha;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) oacc[i][e] *= alpha;
+    }
+    const float m2 = m * LOG2E_F;
+    float rs = 0.f;
+    bf16x8 pb[4];
+    {
+      float pe[16];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        pe[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[e], LOG2E_F, -m2));
+        rs += pe[e];
+      }
+      pb[0] = pack_bf8(pe);
+      pb[1] = pack_bf8(pe + 8);
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        pe[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[e], LOG2E_F, -m2));
+        rs += pe[e];
+      }
+      pb[2] = pack_bf8(pe);
+      pb[3] = pack_bf8(pe + 8);
+    }
+    l += rs;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      Tr4& c = tv[ks & 1];
+      tr4_wait(c);
+      if (ks < 3) {
+        const unsigned o2 = vb + (ks + 1) * 4096;
+        tr4_issue(tv[(ks + 1) & 1], o2 + oft[0][0], o2 + oft[0][1], o2 + oft[1][0], o2 + oft[1][1], o2 + oft[2][0], o2 + oft[2][1], o2 + oft[3][0], o2 + oft[3][1]);
+      }
+      oacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.a0, c.a1), pb[ks], oacc[0], 0, 0, 0);  // O^T[d][q]
+      oacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.b0, c.b1), pb[ks], oacc[1], 0, 0, 0);
+      oacc[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.c0, c.c1), pb[ks], oacc[2], 0, 0, 0);
+      oacc[3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.d0, c.d1), pb[ks], oacc[3], 0, 0, 0);
+    }
+  };
+
+  // The row-bit loads of step i are issued ahead of the DMA of step i + 1, but hipcc's wait for them is a vmcnt(0): on a partial
+  // tile the select, softmax and P.V wait for the next tile's DMA too (measured cost: DESIGN.md §4 "Attention masks").
+  if (nsteps > 0) stage(0, 64 * (list[0] & 0xffff));
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int i = 0; i < nsteps; ++i) {
+    const int ent = list[i];
+    unsigned b0, b1;
+    bits(ent, b0, b1);
+    if (i + 1 < nsteps) stage((i + 1) & 1, 64 * (list[i + 1] & 0xffff));
+    compute(i & 1, ent, b0, b1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+
+  l += __shfl_xor(l, 32, 64);
+  if (qrow < S) {
+    const float inv = 1.f / l;
+    bf16_t* op = o + ((int64_t)b * S + qrow) * d + hh * HD;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) {
+        const int dd = dt * 32 + 8 * q4 + 4 * h;
+        *(u32x2*)(op + dd) = u32x2{pack2bf(oacc[dt][4 * q4] * inv, oacc[dt][4 * q4 + 1] * inv),
+                                   pack2bf(oacc[dt][4 * q4 + 2] * inv, oacc[dt][4 * q4 + 3] * inv)};
+      }
+    if (h == 0) lse[(int64_t)bh * S + qrow] = m + __logf(l);
+  }
+  __syncthreads();
+  }   // items
+}
+
+// ---- dQ (+ delta and the (lse, delta) pairs): attn_bwd_dq_kernel<1> walking a block's live key tiles.  Two waves per SIMD.
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_masked_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
+                                                                    const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
+                                                                    float* __restrict__ delta, float* __restrict__ stats,
+                                                                    bf16_t* __restrict__ dqkv, const int* __restrict__ plan, int B, int H,
+                                                                    int S, int perxcd) {
+  extern __shared__ __attribute__((aligned(16))) char sm[];  // 2 x QK_STAGE
+  const int d = H * HD, ld3 = 3 * d;
+  const int T = plan[AMP_NB], W = plan[AMP_W];
+  const int* __restrict__ fptr = plan + plan[AMP_FPTR];
+  const int* __restrict__ flist = plan + plan[AMP_FLIST];
+  const int* __restrict__ forder = plan + plan[AMP_FORDER];
+  const unsigned* __restrict__ rowbits = (const unsigned*)(plan + plan[AMP_ROWBITS]);
+  const AttnSched sched = attn_sched(T, B * H, perxcd);
+  int tile_, bh;
+  for (int round = 0; attn_item(sched, round, tile_, bh); ++round) {
+  const int qt = forder[tile_];
+  const int* __restrict__ list = flist + fptr[qt];
+  const int nsteps = fptr[qt + 1] - fptr[qt];
+  const int b = bh / H, hh = bh % H;
+  const int q0 = qt * 128;
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, h = lane >> 5, g4 = lane >> 4, l16 = lane & 15;
+  const int qrow = q0 + wid * 32 + r;
+  const int qrow_c = qrow < S ? qrow : S - 1;
+  const unsigned* __restrict__ mrow = rowbits + (int64_t)qrow_c * W;
+  const bf16_t* qb = qkv + (int64_t)b * S * ld3 + hh * HD;
+  const bf16_t* dob = d_o + (int64_t)b * S * d + hh * HD;
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
+  const int nbytes = (int)(((int64_t)(S - 1) * ld3 + HD) * 2);
+  const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)(qb + d), 0, nbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)(qb + 2 * d), 0, nbytes, 0x00020000);
+
+  bf16x8 qf[8], dof[8], of_[8];
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk) {
+    qf[kk] = *(const bf16x8*)(qb + (int64_t)qrow_c * ld3 + 16 * kk + 8 * h);
+    dof[kk] = *(const bf16x8*)(dob + (int64_t)qrow_c * d + 16 * kk + 8 * h);
+    of_[kk] = *(const bf16x8*)(o + ((int64_t)b * S + qrow_c) * d + hh * HD + 16 * kk + 8 * h);
+  }
+  const float lse_q = lse[(int64_t)bh * S + qrow_c];
+  const float lse2_q = lse_q * LOG2E_F;
+  float delta_q = 0.f;
+  {
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) {
+      float fo[8], fd[8];
+      unpack8(__builtin_bit_cast(u32x4, of_[kk]), fo);
+      unpack8(__builtin_bit_cast(u32x4, dof[kk]), fd);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) delta_q += fo[j] * fd[j];
+    }
+    delta_q += __shfl_xor(delta_q, 32, 64);
+    if (h == 0 && qrow < S) {
+      const int64_t idx = (int64_t)bh * S + qrow;
+      delta[idx] = delta_q;
+      stats[2 * idx] = lse2_q;
+      stats[2 * idx + 1] = delta_q;
+    }
+  }
+
+  int vo[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = tid + 256 * i, row = c >> 4, pc = c & 15;
+    vo[i] = (row * ld3 + 8 * (pc ^ swz(row))) * 2;
+  }
+  auto stage = [&](int st, int key0) {
+    char* base = sm + st * QK_STAGE;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      dma16(rk, base + (wid * 64 + 256 * i) * 16, vo[i] + key0 * ld3 * 2);
+      dma16(rv, base + 16384 + (wid * 64 + 256 * i) * 16, vo[i] + key0 * ld3 * 2);
+    }
+  };
+  int ofa[8];
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk) ofa[kk] = r * 256 + (((2 * kk + h) ^ swz(r)) << 4);
+  const int rr = l16 >> 2;
+  unsigned oft0[2];
+#pragma unroll
+  for (int w2 = 0; w2 < 2; ++w2) {
+    const int row = 4 * h + rr + 8 * w2;
+    const int chunk = 2 * (g4 & 1) + ((l16 & 3) >> 1);
+    oft0[w2] = row * 256 + ((chunk ^ swz(row)) << 4) + 8 * (l16 & 1);
+  }
+
+  f32x16 dq[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dq[i][e] = 0.f;
+
+  auto bits = [&](int ent, unsigned& b0, unsigned& b1) {
+    const int j = ent & 0xffff;
+    b0 = b1 = 0xffffffffu;
+    if (((ent >> (16 + 2 * wid)) & 3) == 2) {
+      b0 = mrow[2 * j];
+      b1 = 2 * j + 1 < W ? mrow[2 * j + 1] : 0u;
+    }
+  };
+  auto compute = [&](int st, int ent, unsigned b0, unsigned b1) {
+    const int cls = (ent >> (16 + 2 * wid)) & 3;
+    if (cls == 0) return;
+    const char* base = sm + st * QK_STAGE;
+#pragma unroll
+    for (int kt2 = 0; kt2 < 2; ++kt2) {
+      f32x16 s, dp;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) s[e] = dp[e] = 0.f;
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk) {
+        const bf16x8 ka = *(const bf16x8*)(base + kt2 * 8192 + ofa[kk]);
+        const bf16x8 va = *(const bf16x8*)(base + 16384 + kt2 * 8192 + ofa[kk]);
+        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qf[kk], s, 0, 0, 0);     // S^T[key][q]
+        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, dof[kk], dp, 0, 0, 0);  // dP^T[key][q]
+      }
+      Tr2 tk[2];
+      unsigned ob = st * QK_STAGE + kt2 * 8192;
+      asm volatile("" : "+v"(ob));
+      const unsigned t0 = ob + oft0[0], t1 = ob + oft0[1];
+      tr2_issue(tk[0], lds0 + t0, lds0 + t1, lds0 + (t0 ^ 64u), lds0 + (t1 ^ 64u));
+      float ds[16];
+      if (cls == 2) {   // partial tile: masked scores -> exp2(-inf) = 0 by a select
+        const unsigned mb = kt2 ? b1 : b0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int kb = (e & 3) + 8 * (e >> 2) + 4 * h;
+          const float pe = __builtin_amdgcn_exp2f(((mb >> kb) & 1u) ? __builtin_fmaf(s[e], LOG2E_F, -lse2_q) : -INFINITY);
+          ds[e] = pe * (dp[e] - delta_q);
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const float pe = __builtin_amdgcn_exp2f(__builtin_fmaf(s[e], LOG2E_F, -lse2_q));
+          ds[e] = pe * (dp[e] - delta_q);
+        }
+      }
+      bf16x8 dsb[2];
+      dsb[0] = pack_bf8(ds);
+      dsb[1] = pack_bf8(ds + 8);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int s2 = q >> 1, dp2 = (q & 1) * 2;
+        Tr2& c = tk[q & 1];
+        tr2_wait(c);
+        if (q < 3) {
+          const int s2n = (q + 1) >> 1, dn = ((q + 1) & 1) * 2;
+          const unsigned u0 = t0 + s2n * 4096, u1 = t1 + s2n * 4096;
+          tr2_issue(tk[(q + 1) & 1], lds0 + (u0 ^ (dn << 6)), lds0 + (u1 ^ (dn << 6)), lds0 + (u0 ^ ((dn + 1) << 6)), lds0 + (u1 ^ ((dn + 1) << 6)));
+        }
+        dq[dp2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.a0, c.a1), dsb[s2], dq[dp2], 0, 0, 0);          // dQ^T[d][q]
+        dq[dp2 + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.b0, c.b1), dsb[s2], dq[dp2 + 1], 0, 0, 0);
+      }
+    }
+  };
+
+  if (nsteps > 0) stage(0, 64 * (list[0] & 0xffff));
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int i = 0; i < nsteps; ++i) {
+    const int ent = list[i];
+    unsigned b0, b1;
+    bits(ent, b0, b1);
+    if (i + 1 < nsteps) stage((i + 1) & 1, 64 * (list[i + 1] & 0xffff));
+    compute(i & 1, ent, b0, b1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+  // whole-row stores through a wave-private LDS strip (the loop ended with a barrier: the last tile's readers are done)
+  store_rows_via_lds(sm + wid * (32 * ROWS_PITCH), dq, 1.0f, dqkv + ((int64_t)b * S + q0 + wid * 32) * ld3 + hh * HD, ld3, S - (q0 + wid * 32), lane);
+  __syncthreads();
+  }   // items
+}
+
+// ---- dK/dV: attn_bwd_dkv_kernel<1> (the software-pipelined 4-slot ring) walking a key block's live 32-query tiles.  Every tile
+// applies the column bitmap word of this lane's key (bit = query row within the tile) with a select; a full tile takes an all-ones
+// word without a load.  A key block no query attends to writes zero dK / dV.  One wave per SIMD.
+__global__ __launch_bounds__(256, 1) void attn_bwd_dkv_masked_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ d_o,
+                                                                     const float* __restrict__ stats, bf16_t* __restrict__ dqkv,
+                                                                     const int* __restrict__ plan, int B, int H, int S, int perxcd) {
+  extern __shared__ __attribute__((aligned(16))) char sm[];  // V 32768 | 4 x DKV_STAGE
+  const int d = H * HD, ld3 = 3 * d;
+  const int W = plan[AMP_W];
+  const int* __restrict__ kptr = plan + plan[AMP_KPTR];
+  const int* __restrict__ klist = plan + plan[AMP_KLIST];
+  const int* __restrict__ korder = plan + plan[AMP_KORDER];
+  const unsigned* __restrict__ colbits = (const unsigned*)(plan + plan[AMP_COLBITS]);
+  const AttnSched sched = attn_sched(plan[AMP_NB], B * H, perxcd);
+  int tile_, bh;
+  for (int round = 0; attn_item(sched, round, tile_, bh); ++round) {
+  const int ktile = korder[tile_];
+  const int* __restrict__ list = klist + kptr[ktile];
+  const int nsteps = kptr[ktile + 1] - kptr[ktile];
+  const int b = bh / H, hh = bh % H;
+  const int key0 = ktile * 128;
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, h = lane >> 5, g4 = lane >> 4, l16 = lane & 15;
+  const int krow = key0 + wid * 32 + r;
+  const int krow_c = krow < S ? krow : S - 1;
+  const bf16_t* qb = qkv + (int64_t)b * S * ld3 + hh * HD;
+  const bf16_t* kb = qb + d;
+  const bf16_t* vb = qb + 2 * d;
+  const bf16_t* dob = d_o + (int64_t)b * S * d + hh * HD;
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
+
+  const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)qb, 0, (int)(((int64_t)(S - 1) * ld3 + HD) * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rdo = __builtin_amdgcn_make_buffer_rsrc((void*)dob, 0, (int)(((int64_t)(S - 1) * d + HD) * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)vb, 0, (int)(((int64_t)(S - 1) * ld3 + HD) * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rcol = __builtin_amdgcn_make_buffer_rsrc((void*)colbits, 0, S * W * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rst = __builtin_amdgcn_make_buffer_rsrc((void*)(stats + (int64_t)bh * S * 2), 0, S * 8, 0x00020000);
+
+  bf16x8 kf[8];
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk) kf[kk] = *(const bf16x8*)(kb + (int64_t)krow_c * ld3 + 16 * kk + 8 * h);
+
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {   // resident V tile
+    const int c = tid + 256 * i, row = c >> 4, pc = c & 15;
+    int gr = key0 + row;
+    gr = gr < S ? gr : S - 1;
+    dma16(rv, sm + (wid * 64 + 256 * i) * 16, (gr * ld3 + 8 * (pc ^ swz(row))) * 2);
+  }
+  int voq[2], vod[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int c = tid + 256 * i, row = c >> 4, pc = c & 15;
+    voq[i] = (row * ld3 + 8 * (pc ^ swz(row))) * 2;
+    vod[i] = (row * d + 8 * (pc ^ swz(row))) * 2;
+  }
+  auto stage = [&](int st, int q0) {
+    char* base = sm + 32768 + st * DKV_STAGE;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      dma16(rq, base + (wid * 64 + 256 * i) * 16, voq[i] + q0 * ld3 * 2);
+      dma16(rdo, base + 8192 + (wid * 64 + 256 * i) * 16, vod[i] + q0 * d * 2);
+    }
+    dma4(rst, base + 16384, (q0 * 2 + lane) * 4);
+  };
+  auto stage_q = [&](int st, int q0, int i) {
+    char* base = sm + 32768 + st * DKV_STAGE;
+    dma16(rq, base + (wid * 64 + 256 * i) * 16, voq[i] + q0 * ld3 * 2);
+    dma16(rdo, base + 8192 + (wid * 64 + 256 * i) * 16, vod[i] + q0 * d * 2);
+  };
+  auto stage_st = [&](int st, int q0) {
+    dma4(rst, sm + 32768 + st * DKV_STAGE + 16384, (q0 * 2 + lane) * 4);
+  };
+  int ofa[8];
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk) ofa[kk] = r * 256 + (((2 * kk + h) ^ swz(r)) << 4);
+  const int rr = l16 >> 2;
+  unsigned oft[4][2];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+    for (int w2 = 0; w2 < 2; ++w2) {
+      const int row = 4 * h + rr + 8 * w2;
+      const int chunk = dt * 4 + 2 * (g4 & 1) + ((l16 & 3) >> 1);
+      oft[dt][w2] = row * 256 + ((chunk ^ swz(row)) << 4) + 8 * (l16 & 1);
+    }
+
+  f32x16 dv[4], dk[4];   // (a key block nobody attends to, nsteps = 0, writes these zeros)
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dv[i][e] = dk[i][e] = 0.f;
+  f32x16 sA, dpA, sB, dpB;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) sA[e] = dpA[e] = sB[e] = dpB[e] = 0.f;
+
+  unsigned aq[8];
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk) aq[kk] = lds0 + 32768 + ofa[kk];
+  const unsigned vrel = (unsigned)(wid * 8192 - 32768);
+  auto sdp_only = [&](int st, f32x16& s, f32x16& dp) {
+    const unsigned so = st * DKV_STAGE;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) s[e] = dp[e] = 0.f;
+    Fr3 F[3];
+    fr3_issue<0>(F[0], aq[0] + so, aq[0] + vrel);
+    fr3_issue<0>(F[1], aq[1] + so, aq[1] + vrel);
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) {
+      Fr3& c = F[kk % 3];
+      if (kk == 0) fr3_wait<3>(c);
+      else if (kk < 7) fr3_wait<3>(c, F[(kk + 2) % 3]);
+      else fr3_wait<0>(c, F[(kk + 2) % 3]);
+      if (kk + 2 < 8) fr3_issue<0>(F[(kk + 2) % 3], aq[kk + 2] + so, aq[kk + 2] + vrel);
+      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, c.q), kf[kk], s, 0, 0, 0);
+      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, c.d), __builtin_bit_cast(bf16x8, c.v), dp, 0, 0, 0);
+    }
+  };
+  // softmax + dS of the accumulator-element pair (2i, 2i+1) = query rows 8g + 4h + 2(i&1) + {0, 1} of the tile (g = i >> 1).
+  // (The phase-A interleave takes 6 + 8 VALU per MFMA pair instead of the causal kernel's 4 + 6: the select adds two per element.)
+  // MASK: bit (query row in the tile) of the lane's column word selects the score or -inf
+  auto softmax_pair = [&](auto mask_c, int i, const St8& stt, const f32x16& s, const f32x16& dp, unsigned mw, unsigned* pw, unsigned* dw) {
+    constexpr bool MASK = decltype(mask_c)::value;
+    const int g = i >> 1;
+    const f32x4 sv = stt.v[i];
+    float x0 = __builtin_fmaf(s[2 * i], LOG2E_F, -sv[0]);
+    float x1 = __builtin_fmaf(s[2 * i + 1], LOG2E_F, -sv[2]);
+    if constexpr (MASK) {   // mw is pre-shifted by 4h: the bit positions are immediates (lane-dependent shifts were hoisted, 16 registers)
+      const int qb0 = 8 * g + 2 * (i & 1);
+      x0 = (mw & (1u << qb0)) ? x0 : -INFINITY;
+      x1 = (mw & (2u << qb0)) ? x1 : -INFINITY;
+    }
+    const float p0 = __builtin_amdgcn_exp2f(x0), p1 = __builtin_amdgcn_exp2f(x1);
+    const float q0 = p0 * (dp[2 * i] - sv[1]), q1 = p1 * (dp[2 * i + 1] - sv[3]);
+    pw[i] = pack2bf(p0, p1);
+    dw[i] = pack2bf(q0, q1);
+    asm volatile("" : "+v"(pw[i]), "+v"(dw[i]));
+  };
+  St8 stt;
+  Tr4 tdo, tq;
+  auto body = [&](int st, int t, f32x16& s, f32x16& dp, f32x16& sn, f32x16& dpn, auto has_next_c, auto mask_c, int qi) {
+    constexpr bool has_next = decltype(has_next_c)::value;
+    const unsigned lb = lds0 + 32768 + st * DKV_STAGE;
+    const unsigned so = ((st + 1) & 3) * DKV_STAGE;
+    const unsigned ta[8] = {lb + oft[0][0], lb + oft[0][1], lb + oft[1][0], lb + oft[1][1], lb + oft[2][0], lb + oft[2][1], lb + oft[3][0], lb + oft[3][1]};
+    tr4_issue_off<8192>(tdo, ta);
+    tr4_issue_off<0>(tq, ta);
+    unsigned pw[8], dw[8];
+    // the column word of this lane's key for this tile (~0 for a full tile), pre-shifted by 4h, by a buffer load with the tile in
+    // the scalar offset.  Loaded here: a word prefetched a step ahead, a 64-bit address kept across the loop, or a second,
+    // unpredicated body for full tiles each pushed this 512-register kernel into spills.  The cost: hipcc waits for the word with
+    // a vmcnt(0), which on a partial tile also drains the DMA of tile t + 2 (issued a step earlier) before the softmax.
+    unsigned mw = 0u;
+    if constexpr (decltype(mask_c)::value) {
+      const int kr = key0 + wid * 32 + (tid & 31);
+      mw = ((list[t] >> 16) & 1) ? __builtin_amdgcn_raw_buffer_load_b32(rcol, (kr < S ? kr : S - 1) * (4 * W), 4 * qi, 0) >> (4 * h) : 0xffffffffu;
+    }
+    if constexpr (has_next) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) sn[e] = dpn[e] = 0.f;
+      Fr3 F[2];
+      fr3_issue<0>(F[0], aq[0] + so, aq[0] + vrel);
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk) {
+        Fr3& c = F[kk & 1];
+        if (kk == 0) fr3_wait<0>(c); else fr3_wait<0>(c, F[(kk + 1) & 1]);
+        if (kk + 1 < 8) fr3_issue<0>(F[(kk + 1) & 1], aq[kk + 1] + so, aq[kk + 1] + vrel);
+        sn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, c.q), kf[kk], sn, 0, 0, 0);
+        dpn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, c.d), __builtin_bit_cast(bf16x8, c.v), dpn, 0, 0, 0);
+        softmax_pair(mask_c, kk, stt, s, dp, mw, pw, dw);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) softmax_pair(mask_c, i, stt, s, dp, mw, pw, dw);
+    }
+    bf16x8 pb[2], dsb[2];
+    pb[0] = __builtin_bit_cast(bf16x8, u32x4{pw[0], pw[1], pw[2], pw[3]});
+    pb[1] = __builtin_bit_cast(bf16x8, u32x4{pw[4], pw[5], pw[6], pw[7]});
+    dsb[0] = __builtin_bit_cast(bf16x8, u32x4{dw[0], dw[1], dw[2], dw[3]});
+    dsb[1] = __builtin_bit_cast(bf16x8, u32x4{dw[4], dw[5], dw[6], dw[7]});
+    const bool do_dma = t + 3 < nsteps;
+    const int st3 = (st + 3) & 3, q3 = do_dma ? 32 * (list[t + 3] & 0xffff) : 0;
+    Tr4 t2;
+    {
+      tr4_wait(tq);
+      tr4_issue_off<8192 + 4096>(t2, ta);
+      dv[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.a0, tdo.a1), pb[0], dv[0], 0, 0, 0);   // dV^T[d][key]
+      dv[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.b0, tdo.b1), pb[0], dv[1], 0, 0, 0);
+      if (do_dma) stage_q(st3, q3, 0);
+      dv[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.c0, tdo.c1), pb[0], dv[2], 0, 0, 0);
+      dv[3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.d0, tdo.d1), pb[0], dv[3], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      tr4_issue_off<4096>(tdo, ta);
+      dk[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tq.a0, tq.a1), dsb[0], dk[0], 0, 0, 0);    // dK^T[d][key]
+      dk[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tq.b0, tq.b1), dsb[0], dk[1], 0, 0, 0);
+      if (do_dma) stage_q(st3, q3, 1);
+      dk[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tq.c0, tq.c1), dsb[0], dk[2], 0, 0, 0);
+      dk[3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tq.d0, tq.d1), dsb[0], dk[3], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      tr4_wait8(t2, tq);
+      if constexpr (has_next) st8_issue(stt, lds0 + 32768 + so + 16384 + 32 * h);
+      dv[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(t2.a0, t2.a1), pb[1], dv[0], 0, 0, 0);
+      dv[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(t2.b0, t2.b1), pb[1], dv[1], 0, 0, 0);
+      if (do_dma) stage_st(st3, q3);
+      dv[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(t2.c0, t2.c1), pb[1], dv[2], 0, 0, 0);
+      dv[3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(t2.d0, t2.d1), pb[1], dv[3], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (has_next) tr4_wait8(tdo, t2); else tr4_wait(tdo);
+      dk[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.a0, tdo.a1), dsb[1], dk[0], 0, 0, 0);
+      dk[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.b0, tdo.b1), dsb[1], dk[1], 0, 0, 0);
+      dk[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.c0, tdo.c1), dsb[1], dk[2], 0, 0, 0);
+      dk[3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.d0, tdo.d1), dsb[1], dk[3], 0, 0, 0);
+      if constexpr (has_next) st8_wait<0>(stt);
+    }
+  };
+
+#define DKV_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
+#define DKV_BARRIER()                                  \
+  do {                                                 \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
+    __builtin_amdgcn_s_barrier();                      \
+  } while (0)
+  if (nsteps > 0) stage(0, 32 * (list[0] & 0xffff));
+  if (nsteps > 1) stage(1, 32 * (list[1] & 0xffff));
+  if (nsteps > 2) stage(2, 32 * (list[2] & 0xffff));
+  if (nsteps > 2) DKV_WAIT(5); else DKV_WAIT(0);
+  DKV_BARRIER();
+  if (nsteps > 0) {
+    st8_issue(stt, lds0 + 32768 + 16384 + 32 * h);
+    sdp_only(0, sA, dpA);
+  }
+  int t = 0;
+#define DKVM_STEP(CS, CD, NS, ND, NEXT)                                                                          \
+  {                                                                                                             \
+    const int ent = list[t];                                                                                    \
+    body(t & 3, t, CS, CD, NS, ND, std::integral_constant<bool, NEXT>{}, std::true_type{}, ent & 0xffff); \
+    if (nsteps - 1 - t >= 3) DKV_WAIT(5); else DKV_WAIT(0);                                                     \
+    DKV_BARRIER();                                                                                              \
+    ++t;                                                                                                        \
+  }
+  while (t + 3 <= nsteps) {
+    DKVM_STEP(sA, dpA, sB, dpB, true) DKVM_STEP(sB, dpB, sA, dpA, true)
+  }
+  if (nsteps - t == 2) {
+    DKVM_STEP(sA, dpA, sB, dpB, true) DKVM_STEP(sB, dpB, sA, dpA, false)
+  } else if (nsteps - t == 1) {
+    DKVM_STEP(sA, dpA, sB, dpB, false)
+  }
+#undef DKVM_STEP
+#undef DKV_WAIT
+#undef DKV_BARRIER
+
+  bf16_t* gk = dqkv + ((int64_t)b * S + key0 + wid * 32) * ld3 + d + hh * HD;
+  char* strip = sm + wid * (2 * 32 * ROWS_PITCH);
+  store_rows_via_lds(strip, dk, 1.0f, gk, ld3, S - (key0 + wid * 32), lane);
+  store_rows_via_lds(strip + 32 * ROWS_PITCH, dv, 1.0f, gk + d, ld3, S - (key0 + wid * 32), lane);
+  __syncthreads();
+  }   // items
+}
+
+// ---- decode: attn_decode_kernel reading row `pos` of the row bitmap (pos from pos_dev on the graph-replayable path, so one
+// captured graph serves every position).  A 64-key chunk whose two mask words are 0 is skipped (no loads); masked keys of a
+// chunk get probability exactly 0.
+__global__ __launch_bounds__(64 * DEC_WAVES) void attn_decode_masked_kernel(bf16_t* qkv, const bf16_t* __restrict__ fresh, bf16_t* __restrict__ o,
+                                                                            const int* __restrict__ plan, int H, int S, int pos_arg,
+                                                                            const int* __restrict__ pos_dev) {
+  __shared__ float ps[DEC_WAVES][64];
+  __shared__ float red_m[DEC_WAVES], red_l[DEC_WAVES];
+  __shared__ float oacc[DEC_WAVES][HD];
+  const int bh = blockIdx.x, b = bh / H, hh = bh % H;
+  const int d = H * HD;
+  const int64_t ld3 = 3 * (int64_t)d;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int pos = pos_dev ? *pos_dev : pos_arg;
+  if (pos < 0 || pos >= S) return;
+  const int W = plan[AMP_W];
+  const unsigned* __restrict__ mrow = (const unsigned*)(plan + plan[AMP_ROWBITS]) + (int64_t)pos * W;
+  bf16_t* base = qkv + (int64_t)b * S * ld3 + hh * HD;
+  const bf16_t* fr = fresh ? fresh + (int64_t)b * ld3 + hh * HD : nullptr;
+  float q[8];
+  unpack8(*(const u32x4*)((fr ? fr : base + (int64_t)pos * ld3) + 8 * c), q);
+  if (fr && threadIdx.x < 3 * HD / 8) {
+    const int part = threadIdx.x / (HD / 8), ch = threadIdx.x % (HD / 8);
+    *(u32x4*)(base + (int64_t)pos * ld3 + part * d + ch * 8) = *(const u32x4*)(fr + part * d + ch * 8);
+  }
+  float m = -1e30f, l = 0.f;
+  float oa[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int ch0 = wid; ch0 * 64 <= pos; ch0 += DEC_WAVES) {
+    const unsigned w0 = mrow[2 * ch0], w1 = 2 * ch0 + 1 < W ? mrow[2 * ch0 + 1] : 0u;
+    if ((w0 | w1) == 0u) continue;                       // (wave-uniform) nothing of this chunk is attended to
+    const int k0 = ch0 * 64;
+    auto row_ptr = [&](int i, int which) -> const u32x4* {
+      int key = k0 + 4 * i + g;
+      key = key < pos ? key : pos;
+      return (const u32x4*)((fr && key == pos) ? fr + which * d + 8 * c : base + which * d + (int64_t)key * ld3 + 8 * c);
+    };
+    u32x4 raw[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) raw[i] = *row_ptr(i, 1);
+    float p[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      float f[8];
+      unpack8(raw[i], f);
+      float t = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) t = __builtin_fmaf(f[j], q[j], t);
+      p[i] = t;
+    }
+#pragma unroll
+    for (int w = 8; w >= 1; w >>= 1) {
+      const bool up = (c & w) != 0;
+#pragma unroll
+      for (int j = 0; j < w; ++j) {
+        const float send = up ? p[j] : p[j + w];
+        const float keep = up ? p[j + w] : p[j];
+        p[j] = keep + __shfl_xor(send, w, 64);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) raw[i] = *row_ptr(i, 2);
+    const int kb = 4 * c + g;                              // this lane's key k0 + kb
+    const bool valid = k0 + kb <= pos && (((kb < 32 ? w0 : w1) >> (kb & 31)) & 1u);
+    const float sc = valid ? p[0] : -1e30f;
+    const float mn = fmaxf(m, wave_max(sc));
+    const float alpha = __expf(m - mn);
+    const float pe = valid ? __expf(sc - mn) : 0.f;
+    l = l * alpha + wave_sum(pe);
+    m = mn;
+    ps[wid][4 * c + g] = bf2f(f2bf(pe));
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int j = 0; j < 8; ++j) oa[j] *= alpha;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      float f[8];
+      unpack8(raw[i], f);
+      const float pj = ps[wid][4 * i + g];               // 0 for masked keys and keys past pos
+#pragma unroll
+      for (int j = 0; j < 8; ++j) oa[j] = __builtin_fmaf(pj, f[j], oa[j]);
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    oa[j] += __shfl_xor(oa[j], 16, 64);
+    oa[j] += __shfl_xor(oa[j], 32, 64);
+  }
+  if (lane == 0) { red_m[wid] = m; red_l[wid] = l; }
+  if (g == 0) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) oacc[wid][8 * c + j] = oa[j];
+  }
+  __syncthreads();
+  if (wid == 0) {
+    float M = red_m[0];
+#pragma unroll
+    for (int w = 1; w < DEC_WAVES; ++w) M = fmaxf(M, red_m[w]);
+    float L = 0.f, a0 = 0.f, a1 = 0.f;
+#pragma unroll
+    for (int w = 0; w < DEC_WAVES; ++w) {
+      const float sc = __expf(red_m[w] - M);
+      L += red_l[w] * sc;
+      a0 += oacc[w][2 * lane] * sc;
+      a1 += oacc[w][2 * lane + 1] * sc;
+    }
+    const float inv = 1.f / L;
+    *(unsigned*)(o + (int64_t)b * d + hh * HD + 2 * lane) = pack2bf(a0 * inv, a1 * inv);
+  }
+}
+
+// ---- host: the plan builder and the C ABI of the masked kernels
+extern "C" int64_t dmi_attn_mask_plan(const uint8_t* mask, int S, int32_t* plan, int64_t plan_bytes) {
+  DMI_REQUIRE(mask, "attn_mask_plan: null mask");
+  DMI_REQUIRE(S > 0 && S % 8 == 0 && S <= 65536, "attn_mask_plan: S must be a positive multiple of 8, at most 65536 (S=%d)", S);
+  const int NB = (S + 127) / 128, W = (S + 31) / 32, N64 = (S + 63) / 64;
+  std::vector<uint32_t> rowb((size_t)S * W, 0u), colb((size_t)S * W, 0u);
+  bool causal = true;
+  for (int i = 0; i < S; ++i) {
+    const uint8_t* mr = mask + (size_t)i * S;
+    bool any = false;
+    for (int j = 0; j < S; ++j) {
+      if (!mr[j]) {
+        if (j <= i) causal = false;
+        continue;
+      }
+      if (j > i) {
+        dmi_set_error("attn_mask_plan: the mask is not causal: query %d may attend to key %d", i, j);
+        return DMI_ERR_INVALID;
+      }
+      any = true;
+      rowb[(size_t)i * W + (j >> 5)] |= 1u << (j & 31);
+      colb[(size_t)j * W + (i >> 5)] |= 1u << (i & 31);
+    }
+    if (!any) {
+      dmi_set_error("attn_mask_plan: query %d attends to no key (every row needs at least one allowed key)", i);
+      return DMI_ERR_INVALID;
+    }
+  }
+  // allowed entries of rows [r0, r1) x keys [c0, c0 + 32 nw) (c0 a multiple of 32; bits past S are 0)
+  auto count = [&](int r0, int r1, int c0, int nw) {
+    int64_t n = 0;
+    for (int i = r0; i < r1; ++i)
+      for (int w = 0; w < nw && (c0 >> 5) + w < W; ++w) n += __builtin_popcount(rowb[(size_t)i * W + (c0 >> 5) + w]);
+    return n;
+  };
+  std::vector<int> fptr(NB + 1, 0), flist, kptr(NB + 1, 0), klist;
+  int64_t live_f = 0, causal_f = 0, live_k = 0, causal_k = 0;
+  for (int qb = 0; qb < NB; ++qb) {
+    for (int j = 0; j < N64; ++j) {
+      int cls = 0;
+      for (int w = 0; w < 4; ++w) {
+        const int r0 = qb * 128 + 32 * w, r1 = r0 + 32 < S ? r0 + 32 : S;
+        if (r0 >= S) continue;
+        const int64_t n = count(r0, r1, 64 * j, 2);
+        const int c = n == 0 ? 0 : (n == (int64_t)(r1 - r0) * 64 ? 1 : 2);   // keys >= S are never set: such a tile is partial
+        cls |= c << (2 * w);
+        live_f += c != 0;
+        causal_f += 64 * j <= r1 - 1;
+      }
+      if (cls) flist.push_back(j | (cls << 16));
+    }
+    fptr[qb + 1] = (int)flist.size();
+  }
+  for (int kb = 0; kb < NB; ++kb) {
+    const int c0 = kb * 128, c1 = c0 + 128 < S ? c0 + 128 : S;
+    for (int qi = 0; qi < W; ++qi) {
+      const int r0 = 32 * qi, r1 = r0 + 32 < S ? r0 + 32 : S;
+      const int64_t n = count(r0, r1, c0, 4);
+      causal_k += r1 - 1 >= c0;
+      if (n == 0) continue;
+      ++live_k;
+      klist.push_back(qi | ((n == (int64_t)(r1 - r0) * (c1 - c0) ? 0 : 1) << 16));   // rows and keys >= S: zero contribution / discarded
+    }
+    kptr[kb + 1] = (int)klist.size();
+  }
+  auto order = [&](const std::vector<int>& ptr) {   // heaviest first; equal counts: later blocks first (the causal kernels' order)
+    std::vector<int> o(NB);
+    for (int i = 0; i < NB; ++i) o[i] = NB - 1 - i;
+    std::stable_sort(o.begin(), o.end(), [&](int a, int b) { return ptr[a + 1] - ptr[a] > ptr[b + 1] - ptr[b]; });
+    return o;
+  };
+  const std::vector<int> forder = order(fptr), korder = order(kptr);
+  int64_t off = AMP_HDR;
+  int32_t hdr[AMP_HDR] = {0};
+  hdr[0] = AMP_MAGIC;
+  hdr[AMP_S] = S;
+  hdr[AMP_NB] = NB;
+  hdr[AMP_W] = W;
+  hdr[AMP_CAUSAL] = causal ? 1 : 0;
+  hdr[AMP_FPTR] = (int32_t)off; off += NB + 1;
+  hdr[AMP_FLIST] = (int32_t)off; off += (int64_t)flist.size();
+  hdr[AMP_KPTR] = (int32_t)off; off += NB + 1;
+  hdr[AMP_KLIST] = (int32_t)off; off += (int64_t)klist.size();
+  hdr[AMP_FORDER] = (int32_t)off; off += NB;
+  hdr[AMP_KORDER] = (int32_t)off; off += NB;
+  off = (off + 3) & ~(int64_t)3;
+  hdr[AMP_ROWBITS] = (int32_t)off; off += (int64_t)S * W;
+  hdr[AMP_COLBITS] = (int32_t)off; off += (int64_t)S * W;
+  hdr[AMP_WORDS] = (int32_t)off;
+  hdr[AMP_LIVE_F] = (int32_t)live_f;
+  hdr[AMP_CAUSAL_F] = (int32_t)causal_f;
+  hdr[AMP_LIVE_K] = (int32_t)live_k;
+  hdr[AMP_CAUSAL_K] = (int32_t)causal_k;
+  const int64_t bytes = off * 4;
+  if (!plan || plan_bytes < bytes) return bytes;   // size query
+  memset(plan, 0, (size_t)bytes);
+  memcpy(plan, hdr, sizeof(hdr));
+  auto put = [&](int sec, const void* src, size_t n) { if (n) memcpy(plan + hdr[sec], src, n); };
+  put(AMP_FPTR, fptr.data(), fptr.size() * 4);
+  put(AMP_FLIST, flist.data(), flist.size() * 4);
+  put(AMP_KPTR, kptr.data(), kptr.size() * 4);
+  put(AMP_KLIST, klist.data(), klist.size() * 4);
+  put(AMP_FORDER, forder.data(), forder.size() * 4);
+  put(AMP_KORDER, korder.data(), korder.size() * 4);
+  put(AMP_ROWBITS, rowb.data(), rowb.size() * 4);
+  put(AMP_COLBITS, colb.data(), colb.size() * 4);
+  return bytes;
+}
+
+// the host copy of the plan (its header) decides the route: a causal plan runs the causal kernels unless attn_mask_force is set
+static int amp_route(const int32_t* plan, const int32_t* plan_host, int S, int head_dim, const char* name) {
+  if (!plan || !plan_host) {
+    dmi_set_error("%s: null plan pointer", name);
+    return DMI_ERR_INVALID;
+  }
+  if (plan_host[0] != AMP_MAGIC) {
+    dmi_set_error("%s: plan_host is not a mask plan (build it with dmi_attn_mask_plan)", name);
+    return DMI_ERR_INVALID;
+  }
+  if (plan_host[AMP_S] != S) {
+    dmi_set_error("%s: the plan was built for S=%d, called with S=%d", name, plan_host[AMP_S], S);
+    return DMI_ERR_INVALID;
+  }
+  if (plan_host[AMP_CAUSAL] && !g_opt_attn_mask_force) return 1;
+  if (head_dim != 128) {
+    dmi_set_error("%s: the masked attention kernels are built for head dim 128 (head_dim=%d); head dim 64 takes the causal mask only",
+                  name, head_dim);
+    return DMI_ERR_UNSUPPORTED;
+  }
+  return 0;
+}
+
+extern "C" int dmi_attention_fwd_masked(const uint16_t* qkv, uint16_t* o, float* lse, const int32_t* plan, const int32_t* plan_host,
+                                        int B, int H, int S, int head_dim, void* stream) {
+  DMI_REQUIRE(qkv && o && lse, "attention_fwd_masked: null pointer");
+  const int rt = amp_route(plan, plan_host, S, head_dim, "attention_fwd_masked");
+  if (rt < 0) return rt;
+  if (rt == 1) return dmi_attention_fwd_hd(qkv, o, lse, B, H, S, head_dim, stream);
+  DMI_REQUIRE(B > 0 && H > 0 && S > 0 && S % 8 == 0, "attention_fwd_masked: S must be a multiple of 8 (S=%d)", S);
+  DMI_REQUIRE((int64_t)S * 3 * H * HD * 2 < 0x7fffffff, "attention_fwd_masked: sequence too long for 32-bit buffer offsets");
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute((const void*)attn_fwd_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
+    attr_done = true;
+  }
+  const int items = ((S + 127) / 128) * B * H;
+  const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();   // two persistent blocks per CU
+  const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
+  attn_fwd_masked_kernel<<<dim3(grid), dim3(256), 2 * QK_STAGE, (hipStream_t)stream>>>((const bf16_t*)qkv, (bf16_t*)o, lse, (const int*)plan,
+                                                                                      B, H, S, perxcd);
+  DMI_CHECK_LAUNCH("attention_fwd_masked");
+  return DMI_OK;
+}
+
+extern "C" int dmi_attention_bwd_masked(const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, float* delta,
+                                        uint16_t* dqkv, const int32_t* plan, const int32_t* plan_host, int B, int H, int S, int head_dim,
+                                        void* stream) {
+  DMI_REQUIRE(qkv && o && d_o && lse && delta && dqkv, "attention_bwd_masked: null pointer");
+  const int rt = amp_route(plan, plan_host, S, head_dim, "attention_bwd_masked");
+  if (rt < 0) return rt;
+  if (rt == 1) return dmi_attention_bwd_hd(qkv, o, d_o, lse, delta, dqkv, B, H, S, head_dim, stream);
+  DMI_REQUIRE(B > 0 && H > 0 && S > 0 && S % 8 == 0, "attention_bwd_masked: S must be a multiple of 8 (S=%d)", S);
+  DMI_REQUIRE((int64_t)S * 3 * H * HD * 2 < 0x7fffffff, "attention_bwd_masked: sequence too long for 32-bit buffer offsets");
+  hipStream_t st = (hipStream_t)stream;
+  float* stats = delta + (int64_t)B * H * S;
+  const int shm = 32768 + DKV_NSTAGE * DKV_STAGE;
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
+    attr_done = true;
+  }
+  const int items = ((S + 127) / 128) * B * H;
+  {
+    const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();
+    const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
+    attn_bwd_dq_masked_kernel<<<dim3(grid), dim3(256), 2 * QK_STAGE, st>>>((const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o, lse, delta,
+                                                                         stats, (bf16_t*)dqkv, (const int*)plan, B, H, S, perxcd);
+  }
+  DMI_CHECK_LAUNCH("attention_bwd_dq_masked");
+  {
+    const int grid = items < attn_num_cus() ? items : attn_num_cus();
+    const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
+    attn_bwd_dkv_masked_kernel<<<dim3(grid), dim3(256), shm, st>>>((const bf16_t*)qkv, (const bf16_t*)d_o, stats, (bf16_t*)dqkv,
+                                                                   (const int*)plan, B, H, S, perxcd);
+  }
+  DMI_CHECK_LAUNCH("attention_bwd_dkv_masked");
+  return DMI_OK;
+}
+
+extern "C" int dmi_attention_decode_masked(uint16_t* qkv, const uint16_t* fresh, uint16_t* o, const int32_t* plan, const int32_t* plan_host,
+                                           int B, int H, int S, int pos, const int* pos_dev, int head_dim, void* stream) {
+  DMI_REQUIRE(qkv && o, "attention_decode_masked: null pointer");
+  const int rt = amp_route(plan, plan_host, S, head_dim, "attention_decode_masked");
+  if (rt < 0) return rt;
+  if (rt == 1) return dmi_attention_decode_hd(qkv, fresh, o, B, H, S, pos, pos_dev, head_dim, stream);
+  DMI_REQUIRE(B > 0 && H > 0 && S > 0, "attention_decode_masked: bad shape");
+  DMI_REQUIRE(pos_dev || (pos >= 0 && pos < S), "attention_decode_masked: need 0 <= pos < S (pos=%d, S=%d)", pos, S);
+  attn_decode_masked_kernel<<<dim3((unsigned)(B * H)), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream>>>((bf16_t*)qkv, (const bf16_t*)fresh,
+                                                                                                      (bf16_t*)o, (const int*)plan, H, S, pos, pos_dev);
+  DMI_CHECK_LAUNCH("attention_decode_masked");
   return DMI_OK;
 }

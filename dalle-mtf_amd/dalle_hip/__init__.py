@@ -10,6 +10,8 @@ import ctypes
 import os
 import re
 import struct
+
+import numpy as np
 from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
 
 import torch
@@ -83,6 +85,10 @@ def _declare(L):
         "dmi_attention_fwd_hd": (I, [P, P, P, I, I, I, I, P]),
         "dmi_attention_bwd_hd": (I, [P, P, P, P, P, P, I, I, I, I, P]),
         "dmi_attention_decode_hd": (I, [P, P, P, I, I, I, I, P, I, P]),
+        "dmi_attn_mask_plan": (L64, [P, I, P, L64]),
+        "dmi_attention_fwd_masked": (I, [P, P, P, P, P, I, I, I, I, P]),
+        "dmi_attention_bwd_masked": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P]),
+        "dmi_attention_decode_masked": (I, [P, P, P, P, P, I, I, I, I, P, I, P]),
         "dmi_label_logit": (I, [P, I, P, I, P, P, P, P, L64, I, I, P]),
         "dmi_gemm_nt_softmax_partials": (L64, [I]),
         "dmi_gemm_nt_softmax": (I, [P, I, P, I, P, P, P, I, P, I, I, I, P]),
@@ -426,6 +432,64 @@ def attention_bwd(qkv, o, d_o, lse, scratch, dqkv, B, H, S, head_dim=128):
     _dev(qkv, o, d_o, lse, scratch, dqkv)
     _check(lib().dmi_attention_bwd_hd(_p(qkv), _p(o), _p(d_o), _p(lse), _p(scratch), _p(dqkv), B, H, S, int(head_dim), _stream()),
            "attention_bwd")
+
+
+# header words of a mask plan (the AMP_* enum of csrc/attention.hip; word 0 is the magic)
+PLAN_MAGIC = 0x504D4144
+PLAN_HDR = dict(S=1, NB=2, W=3, CAUSAL=4, FPTR=5, FLIST=6, KPTR=7, KLIST=8, FORDER=9, KORDER=10, ROWBITS=11, COLBITS=12, WORDS=13,
+                LIVE_F=14, CAUSAL_F=15, LIVE_K=16, CAUSAL_K=17)
+
+
+class AttnMaskPlan:
+    """a compiled attention mask (dmi_attn_mask_plan): `host` int32 numpy words, `dev` the same words on the device.
+    mask: bool / uint8 [S, S] (True = query i may attend to key j); it must be causal with no empty row."""
+
+    def __init__(self, mask, device="cuda"):
+        m = np.ascontiguousarray(np.asarray(mask.cpu() if hasattr(mask, "cpu") else mask).astype(np.uint8))
+        if m.ndim != 2 or m.shape[0] != m.shape[1]:
+            raise DalleHipError(f"attn_mask_plan: the mask must be [S, S] (got {m.shape})")
+        self.S = int(m.shape[0])
+        fn = lib().dmi_attn_mask_plan
+        nbytes = fn(m.ctypes.data, self.S, None, 0)
+        if nbytes < 0:
+            _check(int(nbytes), "attn_mask_plan")
+        self.host = np.zeros(nbytes // 4, dtype=np.int32)
+        _check(0 if fn(m.ctypes.data, self.S, self.host.ctypes.data, nbytes) == nbytes else -1, "attn_mask_plan")
+        assert self.host[0] == PLAN_MAGIC and self.host[PLAN_HDR["S"]] == self.S
+        self.causal = bool(self.host[PLAN_HDR["CAUSAL"]])
+        self.dev = torch.from_numpy(self.host).to(device) if device is not None else None
+
+    def live_fraction(self):
+        """live 32-query x 64-key tiles of the forward / dQ kernels, as a fraction of the causal mask's"""
+        return float(self.host[PLAN_HDR["LIVE_F"]]) / float(self.host[PLAN_HDR["CAUSAL_F"]])
+
+    def live_fraction_dkv(self):
+        """live 32-query x 128-key tiles of the dK/dV kernel, as a fraction of the causal mask's"""
+        return float(self.host[PLAN_HDR["LIVE_K"]]) / float(self.host[PLAN_HDR["CAUSAL_K"]])
+
+
+def attn_mask_plan_bytes(mask_u8, S):
+    """size query of dmi_attn_mask_plan (status < 0 on a refused mask)"""
+    m = np.ascontiguousarray(mask_u8, dtype=np.uint8)
+    return int(lib().dmi_attn_mask_plan(m.ctypes.data, int(S), None, 0))
+
+
+def attention_fwd_masked(qkv, o, lse, plan, B, H, S, head_dim=128):
+    """attention over qkv under a compiled mask (AttnMaskPlan); a causal plan runs attention_fwd's kernels"""
+    _dev(qkv, o, lse)
+    _check(lib().dmi_attention_fwd_masked(_p(qkv), _p(o), _p(lse), _p(plan.dev), plan.host.ctypes.data, B, H, S, int(head_dim),
+                                          _stream()), "attention_fwd_masked")
+
+
+def attention_bwd_masked(qkv, o, d_o, lse, scratch, dqkv, plan, B, H, S, head_dim=128):
+    _dev(qkv, o, d_o, lse, scratch, dqkv)
+    _check(lib().dmi_attention_bwd_masked(_p(qkv), _p(o), _p(d_o), _p(lse), _p(scratch), _p(dqkv), _p(plan.dev), plan.host.ctypes.data,
+                                          B, H, S, int(head_dim), _stream()), "attention_bwd_masked")
+
+
+def attention_decode_masked(qkv, o, plan, B, H, S, pos, fresh=None, pos_dev=None, head_dim=128):
+    _check(lib().dmi_attention_decode_masked(_p(qkv), _p(fresh), _p(o), _p(plan.dev), plan.host.ctypes.data, B, H, S, int(pos),
+                                             _p(pos_dev), int(head_dim), _stream()), "attention_decode_masked")
 
 
 def shift_labels(tokens, labels, B, S, eos):

@@ -19,6 +19,7 @@ Activations needed by backward are kept in bf16 per layer (no recompute; 288 GB 
 """
 from __future__ import annotations
 
+import hashlib
 import math
 import os
 from collections import OrderedDict
@@ -146,7 +147,7 @@ class ParamLayout:
 class DalleEngine:
     def __init__(self, n_embd, n_layers, n_heads, text_vocab_size, image_vocab_size, text_seq_len, image_seq_len,
                  batch_size, global_batch_size=None, eos_token_id=None, hparams: Optional[dict] = None,
-                 device="cuda", process_group=None, world_size=1, comm=None):
+                 device="cuda", process_group=None, world_size=1, comm=None, attn_masks=None):
         if not torch.cuda.is_available():
             raise dh.DalleHipError("DalleEngine needs a HIP device (MI355X); there is no CPU fallback")
         dh.lib()
@@ -185,9 +186,39 @@ class DalleEngine:
         # default (it also hands the full-row products back to the 128x128 kernel and turns the fused LayerNorm forms off):
         # hparams["dp_reserve_cus"], DALLE_DP_RESERVE_CUS or bench.py --reserve-cus select it for the first multi-GPU A/B.
         self.dp_reserve_cus = int(self.hp.get("dp_reserve_cus", os.environ.get("DALLE_DP_RESERVE_CUS", "0"))) if world_size > 1 else 0
+        self._build_attn_plans(attn_masks)
         self._alloc_activations()
         # gradient exchange: RCCL behind the C ABI when `comm` (dp.init_comm) is given, torch.distributed otherwise
         self.reducer = GradReducer(self.g, world_size, comm=comm, pg=process_group)
+
+    # ------------------------------------------------------------------ attention masks
+    def _build_attn_plans(self, attn_masks):
+        """attn_masks: None (every layer causal) or one bool [S, S] mask per layer (dalle_mtf.masks).  One device plan
+        (dmi_attn_mask_plan) per distinct mask; causal layers keep plan None and call the causal entry points unchanged."""
+        self.attn_plan = [None] * self.L
+        if attn_masks is None:
+            return
+        if len(attn_masks) != self.L:
+            raise ValueError(f"attn_masks: expected {self.L} per-layer masks, got {len(attn_masks)}")
+        plans = {}
+        for l, m in enumerate(attn_masks):
+            m = np.ascontiguousarray(np.asarray(m, dtype=bool))
+            key = (m.shape, hashlib.sha1(np.packbits(m)).hexdigest())
+            if key not in plans:
+                plans[key] = dh.AttnMaskPlan(m, device=self.dev)
+            plan = plans[key]
+            if plan.causal:
+                continue
+            if self.hd != 128:
+                raise dh.DalleHipError(f"custom attention masks need head dim 128 (n_embd/n_heads = {self.hd}); "
+                                       "the head-dim-64 kernels implement the causal mask only")
+            self.attn_plan[l] = plan
+
+    def _attn_fwd(self, l, qkv, o, lse):
+        if self.attn_plan[l] is None:
+            dh.attention_fwd(qkv, o, lse, self.B, self.H, self.S, head_dim=self.hd)
+        else:
+            dh.attention_fwd_masked(qkv, o, lse, self.attn_plan[l], self.B, self.H, self.S, head_dim=self.hd)
 
     # ------------------------------------------------------------------ optimizer state
     OPTIMIZERS = ("adam", "adafactor")
@@ -506,7 +537,7 @@ class DalleEngine:
         if not (self.fuse_ln1 and l > 0):   # (fused: written by block l-1's FFN-2)
             dh.layernorm_fwd(x, self._w(p + "norm_1/g"), self._w(p + "norm_1/b"), self.xn1[l], st[0], st[1], M, d)
         dh.gemm_nt(self.xn1[l], d, self.tview(p + "attn/qkv"), d, self.qkv[l], 3 * d, M, 3 * d, d)
-        dh.attention_fwd(self.qkv[l], self.o[l], self.lse[l], B, H, S, head_dim=self.hd)   # no transposed copies: hardware transpose reads
+        self._attn_fwd(l, self.qkv[l], self.o[l], self.lse[l])   # no transposed copies: hardware transpose reads
         if self.fuse_ln:
             dh.gemm_nt_ln(self.o[l], d, self.tview(p + "attn/o"), d, self.x1[l], d, M, d, d,
                           self._w(p + "norm_2/g"), self._w(p + "norm_2/b"), self.xn2[l], d, st[2], st[3],
@@ -766,7 +797,10 @@ class DalleEngine:
             p = f"layer_{l}/"
             cache = caches[l]                                          # [B*S, 3d]; row b*S + pos <- q | k | v of this step
             ln_dense(x, p + "norm_1", self.tview(p + "attn/qkv"), fresh, 3 * d)
-            dh.attention_decode(cache, o, B, H, S, 0, fresh=fresh, pos_dev=D["pos_i"], head_dim=self.hd)
+            if self.attn_plan[l] is None:
+                dh.attention_decode(cache, o, B, H, S, 0, fresh=fresh, pos_dev=D["pos_i"], head_dim=self.hd)
+            else:                                                      # mask row of pos from the plan, pos from D[pos_i]
+                dh.attention_decode_masked(cache, o, self.attn_plan[l], B, H, S, 0, fresh=fresh, pos_dev=D["pos_i"], head_dim=self.hd)
             dh.gemm_nt(o, d, self.tview(p + "attn/o"), d, x1, d, B, d, d, dh.GEMM_BIAS | dh.GEMM_RESIDUAL,
                        bias=self._w(p + "attn/compute_output_bias/o_b"), residual=x)
             ln_dense(x1, p + "norm_2", self.tview(p + "mlp/mlp_linear_1/kernel"), h, 4 * d, dh.GEMM_BIAS | dh.GEMM_RELU,
@@ -920,7 +954,11 @@ class DalleEngine:
                             dbias=self._gv(p + "attn/compute_output_bias/o_b"), slot=2)
             if not chain:
                 dh.gemm_nt(dxb, d, self._w(p + "attn/o"), d, self.d_o, d, M, d, d)
-            dh.attention_bwd(self.qkv[l], self.o[l], self.d_o, self.lse[l], self.delta, self.dqkv, B, H, S, head_dim=self.hd)
+            if self.attn_plan[l] is None:
+                dh.attention_bwd(self.qkv[l], self.o[l], self.d_o, self.lse[l], self.delta, self.dqkv, B, H, S, head_dim=self.hd)
+            else:
+                dh.attention_bwd_masked(self.qkv[l], self.o[l], self.d_o, self.lse[l], self.delta, self.dqkv, self.attn_plan[l],
+                                        B, H, S, head_dim=self.hd)
             if pair:   # [r05] the out-projection and QKV kernels' gradients in ONE launch: 16 + 48 tiles fill the chip together
                 probs = [dict(X=self.o[l], ldx=d, dY=dxb, ldy=d, dW=self._gv(p + "attn/o"), I=d, J=d, ws=self.ws_blk[2],
                               dbias=self._gv(p + "attn/compute_output_bias/o_b")),

@@ -4,8 +4,15 @@ from collections import defaultdict
 
 import torch
 
+import numpy as np
+
 from .engine import DalleEngine
+from .masks import layer_masks
 from .ops import get_variable_dtype
+
+
+def _causal(S):
+    return np.tril(np.ones((S, S), dtype=bool))
 
 
 class DALLE:
@@ -35,8 +42,6 @@ class DALLE:
                           "setting (loss agrees to ~1e-5 relative, gradients to a few percent per tensor; DESIGN.md §2)", stacklevel=2)
         self.mode = mode
         self.batch_size = batch_size
-        if attn_mask is not None:
-            raise NotImplementedError("custom attn_mask: the kernels implement the reference's causal mask (models.py:221-227)")
         if is_incremental_inference or context is not None:
             raise NotImplementedError("incremental inference is unfinished upstream (predict raises NotImplementedError, model_fns.py:135)")
         if loss_fn is not None or activation_fn is not None:
@@ -48,10 +53,24 @@ class DALLE:
                 raise NotImplementedError(f"{k} > 0 is not supported (all shipped configs use 0)")
         if (self.params.get("scale_type") or "scale_by_depth") != "scale_by_depth":
             raise NotImplementedError("scale_type other than scale_by_depth")
+        # attn_mask (reference models.py:221-227, the attention bias at :292-299): a bool [S, S] mask, an additive float mask (0 or
+        # <= -1e9), a pattern name (dalle_mtf.masks), or a list of n_layers of these; else the config key "attention_pattern" (a
+        # name or a list of n_layers names).  Both absent: the causal kernels, unchanged.
+        spec = attn_mask
+        if spec is None and self.params.get("attention_pattern") is not None:
+            spec = self.params["attention_pattern"]
+            if not (isinstance(spec, str) or (isinstance(spec, (list, tuple)) and all(isinstance(x, str) for x in spec))):
+                raise ValueError(f"config key attention_pattern: expected a pattern name or a list of {n_layers} names (got {spec!r})")
+        attn_masks = None
+        if spec is not None:
+            attn_masks = layer_masks(spec, n_layers, text_seq_len, image_seq_len)
+            causal = _causal(self.total_seq_dim)
+            if all(np.array_equal(m, causal) for m in attn_masks):
+                attn_masks = None
         self.engine = DalleEngine(n_embd, n_layers, n_heads, text_vocab_size, image_vocab_size, text_seq_len,
                                   image_seq_len, batch_size, global_batch_size=global_batch_size,
                                   eos_token_id=eos_token_id, hparams=dict(self.params), device=device,
-                                  process_group=process_group, world_size=world_size, comm=comm)
+                                  process_group=process_group, world_size=world_size, comm=comm, attn_masks=attn_masks)
         self.dimensions = {"embed_dim": n_embd, "final_vocab_dim": self.total_tokens, "total_seq_dim": self.total_seq_dim,
                            "heads_dim": n_heads, "kv_dim": n_embd // n_heads, "batch_dim": batch_size}
 

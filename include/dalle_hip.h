@@ -33,7 +33,8 @@ int dmi_version(void);
  * "nt8" / "tn8" 0/1/2 = the 256x256 8-wave NT / weight-gradient tiles, "tn_tail" 0/1 = row-split the ragged last residency of
  * unsplit weight gradients, "nt8_min_k" = smallest K at which the auto mode picks the 256x256 NT tile, "skinny" 0/1 = products with M <= 32 rows (the decode step) on the weight-streaming kernel,
  * "attn_xcd" = schedule of the persistent attention blocks (0: one serpentine over all blocks,
- * != 0: per-XCD item lists when the (batch, head) count divides by 8).  Unknown name -> -1. */
+ * != 0: per-XCD item lists when the (batch, head) count divides by 8), "attn_mask_force" 0/1 = a causal mask plan runs the masked
+ * attention kernels too.  Unknown name -> -1. */
 int dmi_get_option(const char* name);
 int dmi_set_option(const char* name, int value);
 /* Diagnostics (tools/phases.py): u64 device buffer [blocks][5 or 8] that the 256x128 NT kernel and the weight-gradient
@@ -168,6 +169,23 @@ int dmi_attention_bwd_hd(const uint16_t* qkv, const uint16_t* o, const uint16_t*
                          uint16_t* dqkv, int B, int H, int S, int head_dim, void* stream);
 int dmi_attention_decode_hd(uint16_t* qkv, const uint16_t* fresh, uint16_t* o, int B, int H, int S, int pos, const int* pos_dev,
                             int head_dim, void* stream);
+
+/* Custom attention masks (the reference's DALLE(attn_mask=...), models.py:221-227,292-299; DESIGN.md §4 "Attention masks").
+ * dmi_attn_mask_plan (host only, no GPU): mask = uint8 [S, S] row-major, nonzero = query i may attend to key j.  It must be causal
+ * and every row must allow a key (otherwise DMI_ERR_INVALID with a message).  Returns the plan's size in bytes (> 0); fills `plan`
+ * (int32 words) when plan != NULL and plan_bytes >= that size.  Copy the filled plan to the device unchanged.
+ * dmi_attention_*_masked: the calls above under the mask; `plan` = the device copy, `plan_host` = the host copy (its header is read to
+ * route the call).  A causal plan runs the causal kernels above (unless the test option "attn_mask_force" is 1); any other plan runs
+ * block-sparse head-dim-128 kernels (head_dim 64: DMI_ERR_UNSUPPORTED).  A plan built for another S is refused.  Decode reads the mask
+ * row of the position (pos_dev on the graph-replayable path). */
+int64_t dmi_attn_mask_plan(const uint8_t* mask, int S, int32_t* plan, int64_t plan_bytes);
+int dmi_attention_fwd_masked(const uint16_t* qkv, uint16_t* o, float* lse, const int32_t* plan, const int32_t* plan_host, int B, int H,
+                             int S, int head_dim, void* stream);
+int dmi_attention_bwd_masked(const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, float* scratch,
+                             uint16_t* dqkv, const int32_t* plan, const int32_t* plan_host, int B, int H, int S, int head_dim,
+                             void* stream);
+int dmi_attention_decode_masked(uint16_t* qkv, const uint16_t* fresh, uint16_t* o, const int32_t* plan, const int32_t* plan_host,
+                                int B, int H, int S, int pos, const int* pos_dev, int head_dim, void* stream);
 
 /* ---- K7/K8  to_logits + cross entropy, labels = shift(tokens)   models.py:391-395,348-359,407-410
  * labels[t] = tokens[t+1], last = eos (bit-exact int path). */
