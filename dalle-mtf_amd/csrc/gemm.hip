@@ -3469,32 +3469,44 @@ extern "C" int dmi_conv_gemm_nt(const uint16_t* x, int B, int H, int W, int C, i
   DMI_REQUIRE(C % 64 == 0 && ntaps >= 1 && ntaps <= CONV_MAX_TAPS && N % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && ldw >= ntaps * C && ldc >= N,
               "conv_gemm_nt: need C%%64==0, 1..16 taps, N/ldw/ldc multiples of 8 (C=%d ntaps=%d N=%d)", C, ntaps, N);
   DMI_REQUIRE(B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && stride >= 1, "conv_gemm_nt: bad geometry");
-  const int64_t xbytes = (int64_t)B * H * W * C * 2, Ml = (int64_t)B * Ho * Wo;
-  DMI_REQUIRE(xbytes < 0x7ffffff0 && Ml < 0x7fffffff, "conv_gemm_nt: activation tensor too large for 32-bit buffer offsets");
+  // The kernel addresses x through one buffer descriptor (< 2 GiB).  An implicit convolution never reads across images, so a
+  // larger batch runs as launches over whole-image chunks that each fit (vae_coco's 256x256x128 decoder stage is 2 GiB at B = 128).
+  const int64_t img_bytes = (int64_t)H * W * C * 2, img_rows = (int64_t)Ho * Wo;
+  DMI_REQUIRE(img_bytes < 0x7ffffff0 && img_rows < 0x7fffffff, "conv_gemm_nt: activation tensor too large for 32-bit buffer offsets");
+  DMI_REQUIRE((int64_t)B * img_rows < 0x7fffffff, "conv_gemm_nt: too many output rows");
   DMI_REQUIRE((((uintptr_t)x | (uintptr_t)Wt | (uintptr_t)out) & 15) == 0, "conv_gemm_nt: operands must be 16-byte aligned");
   DMI_REQUIRE(!(flags & DMI_GEMM_BIAS) || bias, "conv_gemm_nt: bias flag without pointer");
   DMI_REQUIRE(!(flags & DMI_GEMM_RESIDUAL) || residual, "conv_gemm_nt: residual flag without pointer");
   DMI_REQUIRE(!(flags & DMI_GEMM_RELU_MASK) || relu_src, "conv_gemm_nt: relu-mask flag without pointer");
-  GemmArgs a;
-  a.A = x; a.B = Wt; a.C = out; a.bias = bias; a.residual = residual; a.relu_src = relu_src;
-  a.M = (int)Ml; a.N = N; a.K = ntaps * C; a.lda = (int)xbytes /* descriptor size */; a.ldb = ldw; a.ldc = ldc;
-  a.tiles_m = (a.M + BM - 1) / BM; a.tiles_n = (N + BN - 1) / BN;
-  a.rowscale = nullptr; a.rowshift = nullptr; a.rowsum_part = nullptr; a.relu_bits = nullptr;
-  a.k_per_split = a.K; a.slab_stride = 0; a.dbg = nullptr; a.cpol = 0;
-  a.ln_gamma = nullptr; a.ln_beta = nullptr; a.ln_y = nullptr; a.ln_mean = nullptr; a.ln_rstd = nullptr; a.ln_eps = 0.f; a.ln_ldy = 0;
-  a.ln_x = nullptr; a.ln_part = nullptr; a.B2 = nullptr; a.C2 = nullptr; a.ldb2 = 0;
+  DMI_REQUIRE(flags == 0 || flags == DMI_GEMM_BIAS || flags == (DMI_GEMM_BIAS | DMI_GEMM_RELU) || flags == (DMI_GEMM_BIAS | DMI_GEMM_RESIDUAL) ||
+              flags == DMI_GEMM_RESIDUAL || flags == DMI_GEMM_RELU_MASK, "conv_gemm_nt: unsupported epilogue flags %d", flags);
+  const int per = (int)((B < (0x7ffffff0 - 1) / img_bytes) ? B : (0x7ffffff0 - 1) / img_bytes);   // images per launch
   ConvGeom g;
   g.H = H; g.W = W; g.C = C; g.Ho = Ho; g.Wo = Wo; g.stride = stride; g.ntaps = ntaps; g.lw = 0; g.lh = 0;
   for (int i = 0; i < CONV_MAX_TAPS; ++i) { g.dy[i] = i < ntaps ? dy[i] : 0; g.dx[i] = i < ntaps ? dx[i] : 0; }
   hipStream_t st = (hipStream_t)stream;
-  switch (flags) {
-    case 0: return launch_conv<0>(a, g, st);
-    case DMI_GEMM_BIAS: return launch_conv<DMI_GEMM_BIAS>(a, g, st);
-    case DMI_GEMM_BIAS | DMI_GEMM_RELU: return launch_conv<DMI_GEMM_BIAS | DMI_GEMM_RELU>(a, g, st);
-    case DMI_GEMM_BIAS | DMI_GEMM_RESIDUAL: return launch_conv<DMI_GEMM_BIAS | DMI_GEMM_RESIDUAL>(a, g, st);
-    case DMI_GEMM_RESIDUAL: return launch_conv<DMI_GEMM_RESIDUAL>(a, g, st);
-    case DMI_GEMM_RELU_MASK: return launch_conv<DMI_GEMM_RELU_MASK>(a, g, st);
-    default: DMI_REQUIRE(false, "conv_gemm_nt: unsupported epilogue flags %d", flags);
+  for (int b0 = 0; b0 < B; b0 += per) {
+    const int nb = (B - b0 < per) ? B - b0 : per;
+    const int64_t xo = (int64_t)b0 * H * W * C, oo = (int64_t)b0 * img_rows * ldc;   // whole-image offsets (elements)
+    GemmArgs a;
+    a.A = x + xo; a.B = Wt; a.C = out + oo; a.bias = bias; a.residual = residual ? residual + oo : nullptr;
+    a.relu_src = relu_src ? relu_src + oo : nullptr;
+    a.M = (int)(nb * img_rows); a.N = N; a.K = ntaps * C; a.lda = (int)(nb * img_bytes) /* descriptor size */; a.ldb = ldw; a.ldc = ldc;
+    a.tiles_m = (a.M + BM - 1) / BM; a.tiles_n = (N + BN - 1) / BN;
+    a.rowscale = nullptr; a.rowshift = nullptr; a.rowsum_part = nullptr; a.relu_bits = nullptr;
+    a.k_per_split = a.K; a.slab_stride = 0; a.dbg = nullptr; a.cpol = 0;
+    a.ln_gamma = nullptr; a.ln_beta = nullptr; a.ln_y = nullptr; a.ln_mean = nullptr; a.ln_rstd = nullptr; a.ln_eps = 0.f; a.ln_ldy = 0;
+    a.ln_x = nullptr; a.ln_part = nullptr; a.B2 = nullptr; a.C2 = nullptr; a.ldb2 = 0;
+    int rc = DMI_OK;
+    switch (flags) {
+      case 0: rc = launch_conv<0>(a, g, st); break;
+      case DMI_GEMM_BIAS: rc = launch_conv<DMI_GEMM_BIAS>(a, g, st); break;
+      case DMI_GEMM_BIAS | DMI_GEMM_RELU: rc = launch_conv<DMI_GEMM_BIAS | DMI_GEMM_RELU>(a, g, st); break;
+      case DMI_GEMM_BIAS | DMI_GEMM_RESIDUAL: rc = launch_conv<DMI_GEMM_BIAS | DMI_GEMM_RESIDUAL>(a, g, st); break;
+      case DMI_GEMM_RESIDUAL: rc = launch_conv<DMI_GEMM_RESIDUAL>(a, g, st); break;
+      default: rc = launch_conv<DMI_GEMM_RELU_MASK>(a, g, st); break;
+    }
+    if (rc != DMI_OK) return rc;
   }
   return DMI_OK;
 }
@@ -3528,31 +3540,45 @@ extern "C" int dmi_conv_wgrad_tn(const uint16_t* x, int B, int H, int W, int C, 
               "conv_wgrad_tn: need C%%64==0, 1..16 taps, N/ldy multiples of 8 (C=%d ntaps=%d N=%d)", C, ntaps, N);
   const int lw = ilog2_exact(Wo), lh = ilog2_exact(Ho);
   DMI_REQUIRE(lw >= 0 && lh >= 0 && B > 0 && H > 0 && W > 0 && stride >= 1, "conv_wgrad_tn: output dims must be powers of two (Ho=%d Wo=%d)", Ho, Wo);
-  const int64_t xbytes = (int64_t)B * H * W * C * 2, Ml = (int64_t)B * Ho * Wo;
-  DMI_REQUIRE(xbytes < 0x7ffffff0 && Ml < 0x7fffffff, "conv_wgrad_tn: activation tensor too large for 32-bit buffer offsets");
+  // x is addressed through one buffer descriptor (< 2 GiB): a larger batch runs as launches over whole-image chunks
+  // (conv_gemm_nt does the same), each writing its own fp32 slabs; the slab reduce then adds them in a fixed order.
+  const int64_t img_bytes = (int64_t)H * W * C * 2, img_rows = (int64_t)Ho * Wo, Ml = (int64_t)B * img_rows;
+  DMI_REQUIRE(img_bytes < 0x7ffffff0 && Ml < 0x7fffffff, "conv_wgrad_tn: activation tensor too large for 32-bit buffer offsets");
   DMI_REQUIRE((((uintptr_t)x | (uintptr_t)dY | (uintptr_t)dW | (uintptr_t)workspace) & 15) == 0, "conv_wgrad_tn: 16-byte alignment required");
   DMI_REQUIRE((int64_t)TN_BKM * ldy * 2 < 0x7fffffff, "conv_wgrad_tn: leading dimension too large");
   hipStream_t st = (hipStream_t)stream;
   const int M = (int)Ml, I = ntaps * C, J = N;
-  const int nsplit = tn_splits(M, I, J);
+  const int per = (int)((B < (0x7ffffff0 - 1) / img_bytes) ? B : (0x7ffffff0 - 1) / img_bytes);   // images per launch
+  const int nchunk = (B + per - 1) / per;
+  // row splits per launch: the single launch's plan, shared out among the chunks (the workspace holds that many slabs); a
+  // product with fewer splits than chunks (more than 512 / nchunk tiles) would need more workspace and is refused
+  const int splits_all = tn_splits(M, I, J);
+  const int sc = (nchunk == 1) ? splits_all : splits_all / nchunk;
+  DMI_REQUIRE(sc >= 1, "conv_wgrad_tn: %d image chunks but a workspace of %d slabs (I=%d J=%d)", nchunk, splits_all, I, J);
+  const int nsplit = sc * nchunk;
   float* slabs = (float*)workspace;
   const int64_t slab_bytes = (nsplit > 1) ? round_up64((int64_t)nsplit * I * J * 4, 256) : 0;
-  TnArgs a;
-  a.X = x; a.Y = dY; a.M = M; a.I = I; a.J = J; a.ldx = (int)xbytes /* descriptor size */; a.ldy = ldy;
-  a.tiles_i = (I + 127) / 128; a.tiles_j = (J + 127) / 128;
-  a.m_per_split = (int)round_up64((M + nsplit - 1) / nsplit, TN_BKM);
-  a.C = (nsplit > 1) ? slabs : dW;
-  a.slab_stride = (nsplit > 1) ? (int64_t)I * J : 0;
-  a.dbg = nullptr; a.bias_w = nullptr;
   float* bpart = (float*)((char*)workspace + slab_bytes);
-  a.bias_part = dbias ? ((nsplit > 1) ? bpart : dbias) : nullptr;
   ConvGeom g;
   g.H = H; g.W = W; g.C = C; g.Ho = Ho; g.Wo = Wo; g.stride = stride; g.ntaps = ntaps; g.lw = lw; g.lh = lh;
   for (int i = 0; i < CONV_MAX_TAPS; ++i) { g.dy[i] = i < ntaps ? dy[i] : 0; g.dx[i] = i < ntaps ? dx[i] : 0; }
   static bool attr_done = false;
   if (!attr_done) { (void)hipFuncSetAttribute((const void*)conv_wgrad_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES); attr_done = true; }
-  conv_wgrad_tn_kernel<<<dim3(a.tiles_i * a.tiles_j * nsplit), dim3(256), TN_LDS_BYTES, st>>>(a, g);
-  DMI_CHECK_LAUNCH("conv_wgrad_tn");
+  for (int c = 0; c < nchunk; ++c) {
+    const int b0 = c * per, nb = (B - b0 < per) ? B - b0 : per;
+    const int Mc = (int)(nb * img_rows);
+    TnArgs a;
+    a.X = x + (int64_t)b0 * H * W * C; a.Y = dY + (int64_t)b0 * img_rows * ldy; a.M = Mc; a.I = I; a.J = J;
+    a.ldx = (int)(nb * img_bytes) /* descriptor size */; a.ldy = ldy;
+    a.tiles_i = (I + 127) / 128; a.tiles_j = (J + 127) / 128;
+    a.m_per_split = (int)round_up64((Mc + sc - 1) / sc, TN_BKM);
+    a.C = (nsplit > 1) ? slabs + (int64_t)c * sc * I * J : dW;
+    a.slab_stride = (nsplit > 1) ? (int64_t)I * J : 0;
+    a.dbg = nullptr; a.bias_w = nullptr;
+    a.bias_part = dbias ? ((nsplit > 1) ? bpart + (int64_t)c * sc * J : dbias) : nullptr;
+    conv_wgrad_tn_kernel<<<dim3(a.tiles_i * a.tiles_j * sc), dim3(256), TN_LDS_BYTES, st>>>(a, g);
+    DMI_CHECK_LAUNCH("conv_wgrad_tn");
+  }
   if (nsplit > 1) {
     const int64_t n4 = (int64_t)I * J / 4;
     if (deferred && n_deferred) {   // the caller reduces later (dmi_reduce_slabs_batch); the workspace must stay untouched until then

@@ -374,7 +374,8 @@ int dmi_transpose_bf16_padded(const uint16_t* in, uint16_t* out, int R_valid, in
 /* Implicit-im2col convolution: dmi_im2col + dmi_gemm_nt in one kernel, no column matrix in HBM, bit-identical results.
  *   out[(b,oy,ox)][n] = sum_t sum_c x[b, oy*stride + dy[t], ox*stride + dx[t], c] * Wt[n][t*C + c]  (+ epilogue flags)
  * x NHWC bf16 [B,H,W,C] with C % 64 == 0 (zero outside the image = TF SAME padding, src/vae_tf/models.py:67-68);
- * Wt [N, ldw] (ldw >= ntaps*C), out [B*Ho*Wo, ldc]; flags/bias/residual/relu_src as dmi_gemm_nt. */
+ * Wt [N, ldw] (ldw >= ntaps*C), out [B*Ho*Wo, ldc]; flags/bias/residual/relu_src as dmi_gemm_nt.  A batch whose x reaches
+ * 2 GiB runs as launches over whole-image chunks (x is addressed through one buffer descriptor); one image must stay below. */
 int dmi_conv_gemm_nt(const uint16_t* x, int B, int H, int W, int C, int Ho, int Wo, int stride, int ntaps,
                      const int* dy, const int* dx, const uint16_t* Wt, int ldw, uint16_t* out, int ldc, int N,
                      int flags, const uint16_t* bias, const uint16_t* residual, const uint16_t* relu_src, void* stream);
@@ -383,7 +384,11 @@ int dmi_conv_gemm_nt(const uint16_t* x, int B, int H, int W, int C, int Ho, int 
  * (+ dbias[n] = column sums of dY, nullable) = dmi_im2col + dmi_gemm_tn without the column matrix; lands in the TF kernel
  * layout [kh*kw*Cin, Cout] of tf.layers.conv2d (src/vae_tf/models.py:67).  C % 64 == 0, Ho and Wo powers of two.
  * workspace >= dmi_conv_wgrad_tn_workspace_bytes(B*Ho*Wo, ntaps*C, N).  deferred / n_deferred as dmi_gemm_tn: the final slab
- * reduces are handed back for one dmi_reduce_slabs_batch launch (the workspace then belongs to this call until that launch). */
+ * reduces are handed back for one dmi_reduce_slabs_batch launch (the workspace then belongs to this call until that launch).
+ * A batch whose x reaches 2 GiB runs in whole-image chunks as dmi_conv_gemm_nt does; the chunks share the single launch's row
+ * splits, so each writes its own slabs and the one slab reduce adds them in a fixed order.  That needs at least one split per
+ * chunk.  The single launch splits 512 / tiles ways (128x128 output tiles of ntaps*C x N; one split from 257 tiles up), so a
+ * batch in n chunks is refused above 512 / n tiles (the vae_coco layers that reach 2 GiB at B = 128 have 9 and 32 tiles). */
 int64_t dmi_conv_wgrad_tn_workspace_bytes(int M, int K, int N);
 int dmi_conv_wgrad_tn(const uint16_t* x, int B, int H, int W, int C, int Ho, int Wo, int stride, int ntaps,
                       const int* dy, const int* dx, const uint16_t* dY, int ldy, int N, float* dW, float* dbias,
