@@ -28,6 +28,7 @@ from ..dp import GradReducer
 
 IMG_CP = 8     # padded image channels
 OUT_CP = 64    # padded reconstruction channels
+GUMBEL_MAX_TOKENS = 4096    # largest codebook of dmi_gumbel_softmax_fwd (eight 8-column chunks per lane)
 ALIGN = 128
 WS_POOL = 7    # weight gradients in flight before their slab reduces are flushed (2 reduce items each, 16 per batched launch)
 
@@ -69,6 +70,9 @@ class DiscreteVAE:
     def __init__(self, num_tokens, dimensions, convblocks, dim=512, hidden_dim=64, input_channels=3, recompute_grad=False,
                  use_bf16=False, stack_factor=1, batch_size=32, mode="train", device="cuda", process_group=None, world_size=1,
                  comm=None):
+        if num_tokens > GUMBEL_MAX_TOKENS:
+            raise ValueError(f"num_tokens = {num_tokens}: the Gumbel-softmax kernel (dmi_gumbel_softmax_fwd, one wave per row) "
+                             f"handles codebooks of at most {GUMBEL_MAX_TOKENS} tokens")
         if not torch.cuda.is_available():
             raise dh.DalleHipError("DiscreteVAE needs a HIP device (MI355X); there is no CPU fallback")
         dh.lib()
