@@ -135,11 +135,11 @@ struct GemmArgs {
   // fused LayerNorm of the output rows (dmi_gemm_nt_ln, full-row tiles only): Y = LN(C) * gamma + beta, row statistics
   const bf16_t* ln_gamma;
   const bf16_t* ln_beta;
-  bf16_t* ln_y;
-  float* ln_mean;
-  float* ln_rstd;
-  float ln_eps;
-  int ln_ldy;
+  union { bf16_t* ln_y; bf16_t* gelu_pre; };   // GELU (dmi_gemm_nt_gelu / _gelu_grad): the pre-activation bf16 [M, ldpre] -- written
+  float* ln_mean;                              // with GEMM_GELU_PRE, read with GEMM_GELU_GRAD.  No kernel has both epilogues: sharing
+  float* ln_rstd;                              // the LayerNorm's fields keeps GemmArgs, and so the code of every other instantiation,
+  float ln_eps;                                // as it was
+  union { int ln_ldy; int ldpre; };
   // fused LayerNorm BACKWARD of the product (dmi_gemm_nt_lnbwd, full-row tiles only): the product is dy; ln_x = the LayerNorm's input,
   // ln_gamma / ln_mean / ln_rstd as above, residual = the gradient arriving over the residual connection (nullable), ln_y = dx,
   // ln_part = [2 * blocks][2 * N] fp32 partial gain | bias gradients (one row per 80-row half tile)
@@ -154,6 +154,28 @@ struct GemmArgs {
 #define GEMM_SOFTMAX 64   // internal epilogue flag of dmi_gemm_nt_softmax (not part of the public flag set)
 #define GEMM_RELU_BITS 128   // internal: with DMI_GEMM_RELU, also emit one bit per output (> 0) -- dmi_gemm_nt_relu_bits
 #define GEMM_MASK_BITS 256   // internal: C *= bit, the bits written by GEMM_RELU_BITS -- dmi_gemm_nt_mask_bits
+// (DMI_GEMM_GELU = 512 is public: C = bf16(gelu(acc + bias)))
+#define GEMM_GELU_PRE 1024   // internal: with DMI_GEMM_GELU, also store pre = bf16(acc + bias) -- dmi_gemm_nt_gelu
+#define GEMM_GELU_GRAD 2048  // internal: C = bf16(acc * gelu'(pre)) -- dmi_gemm_nt_gelu_grad
+
+// ---- GELU, the tanh form of mtf.gelu [MTF-RECALL: mesh-tensorflow 0.1.18, not checked against its source here] ------------------
+//   gelu(x) = 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3)  =  x * s,  s = sigmoid(2u)   (exact identity)
+//   gelu'(x) = s + x s (1 - s) 2u',  2u' = 2 sqrt(2/pi) (1 + 3 * 0.044715 x^2)
+// s = 1 / (1 + exp2(-2u log2 e)): one v_exp_f32 + one v_rcp_f32 per element, and both saturate correctly (x -> +inf: exp2 -> 0,
+// s = 1; x -> -inf: exp2 -> inf, s = 0).  No tanhf / erf.
+__device__ __forceinline__ float gelu_sig(float x) {
+  constexpr float C0 = 2.302208198144325f;     // 2 sqrt(2/pi) log2 e
+  constexpr float C1 = 0.1029432395800235f;    // 2 sqrt(2/pi) 0.044715 log2 e
+  const float t = x * __builtin_fmaf(C1, x * x, C0);    // 2u log2 e
+  return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-t));
+}
+__device__ __forceinline__ float gelu_f(float x) { return x * gelu_sig(x); }
+__device__ __forceinline__ float gelu_grad_f(float x) {
+  constexpr float D0 = 1.5957691216057308f;    // 2 sqrt(2/pi)
+  constexpr float D1 = 0.21406444881780076f;   // 6 sqrt(2/pi) 0.044715
+  const float s = gelu_sig(x);
+  return __builtin_fmaf(x * s * (1.f - s), __builtin_fmaf(D1, x * x, D0), s);
+}
 
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int xcd = bid & 7, idx = bid >> 3, q = nwg >> 3, r = nwg & 7;
@@ -339,6 +361,11 @@ __device__ __forceinline__ void epilogue_regs(const GemmArgs& a, const f32x4 (&a
     if (m < a.M && ok0) nsrc0 = *(const u32x4*)(a.relu_src + (int64_t)m * a.ldc + nst);
     if (m < a.M && ok1) nsrc1 = *(const u32x4*)(a.relu_src + (int64_t)m * a.ldc + nst + 32);
   }
+  if constexpr (FLAGS & GEMM_GELU_GRAD) {   // pre of the first row tile, in the STORE layout (two 16-B pieces), like the ReLU source
+    const int m = mrow0 + c16;
+    if (m < a.M && ok0) nsrc0 = *(const u32x4*)(a.gelu_pre + (int64_t)m * a.ldpre + nst);
+    if (m < a.M && ok1) nsrc1 = *(const u32x4*)(a.gelu_pre + (int64_t)m * a.ldpre + nst + 32);
+  }
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const int m = mrow0 + 16 * t + c16;
@@ -376,6 +403,21 @@ __device__ __forceinline__ void epilogue_regs(const GemmArgs& a, const f32x4 (&a
         if (ok1) nsrc1 = *(const u32x4*)(a.relu_src + off + (int64_t)16 * a.ldc + 32);
       }
     }
+    unsigned G[4][2];   // GEMM_GELU_GRAD: pre of this row tile in the accumulator layout (the 4 bf16 of chunk 16 j + 4 g)
+    if constexpr (FLAGS & GEMM_GELU_GRAD) {   // requested one row tile ahead, as the ReLU source; the row swap is its own inverse
+      G[0][0] = nsrc0[0]; G[0][1] = nsrc0[1]; G[1][0] = nsrc0[2]; G[1][1] = nsrc0[3];
+      G[2][0] = nsrc1[0]; G[2][1] = nsrc1[1]; G[3][0] = nsrc1[2]; G[3][1] = nsrc1[3];
+#pragma unroll
+      for (int d = 0; d < 2; ++d) { swap16(G[0][d], G[1][d]); swap16(G[2][d], G[3][d]); }
+      const int m2 = m + 16;
+      const int64_t poff = (int64_t)m2 * a.ldpre + nst;
+      nsrc0 = u32x4{0u, 0u, 0u, 0u}; nsrc1 = u32x4{0u, 0u, 0u, 0u};
+      if (t + 1 < NT && m2 < a.M) {
+        if (ok0) nsrc0 = *(const u32x4*)(a.gelu_pre + poff);
+        if (ok1) nsrc1 = *(const u32x4*)(a.gelu_pre + poff + 32);
+      }
+    }
+    unsigned Q[4][2];   // GEMM_GELU_PRE: bf16(acc + bias), packed like P
     unsigned P[4][2];
     float ps = 0.f;
 #pragma unroll
@@ -388,6 +430,17 @@ __device__ __forceinline__ void epilogue_regs(const GemmArgs& a, const f32x4 (&a
       if constexpr (FLAGS & DMI_GEMM_RELU) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+      }
+      if constexpr (FLAGS & DMI_GEMM_GELU) {
+        if constexpr (FLAGS & GEMM_GELU_PRE) { Q[j][0] = pack2bf(v[0], v[1]); Q[j][1] = pack2bf(v[2], v[3]); }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = gelu_f(v[e]);
+      }
+      if constexpr (FLAGS & GEMM_GELU_GRAD) {
+        v[0] *= gelu_grad_f(__uint_as_float(G[j][0] << 16));
+        v[1] *= gelu_grad_f(__uint_as_float(G[j][0] & 0xffff0000u));
+        v[2] *= gelu_grad_f(__uint_as_float(G[j][1] << 16));
+        v[3] *= gelu_grad_f(__uint_as_float(G[j][1] & 0xffff0000u));
       }
       if constexpr (FLAGS & DMI_GEMM_RESIDUAL) {
         v[0] += __uint_as_float(rres[j][0] << 16);
@@ -430,6 +483,13 @@ __device__ __forceinline__ void epilogue_regs(const GemmArgs& a, const f32x4 (&a
     }
     if (mok && ok0) store_c16(a, rc, off, lo);
     if (mok && ok1) store_c16(a, rc, off + 32, hi);
+    if constexpr (FLAGS & GEMM_GELU_PRE) {   // the same row swap brings pre into the store layout
+#pragma unroll
+      for (int d = 0; d < 2; ++d) { swap16(Q[0][d], Q[1][d]); swap16(Q[2][d], Q[3][d]); }
+      const int64_t poff = (int64_t)m * a.ldpre + nst;
+      if (mok && ok0) *(u32x4*)(a.gelu_pre + poff) = u32x4{Q[0][0], Q[0][1], Q[1][0], Q[1][1]};
+      if (mok && ok1) *(u32x4*)(a.gelu_pre + poff + 32) = u32x4{Q[2][0], Q[2][1], Q[3][0], Q[3][1]};
+    }
     if constexpr (FLAGS & GEMM_RELU_BITS) {
       if (mok && ok0) a.relu_bits[((int64_t)(ncol0 >> 6) * a.M + m) * 4 + g16] = (unsigned short)(relu_bits8(lo) | (relu_bits8(hi) << 8));
     }
@@ -463,7 +523,7 @@ __device__ __forceinline__ void epilogue_bf16(const GemmArgs& a, ACC& acc, float
   const __amdgpu_buffer_rsrc_t rc = c_rsrc(a);
 #pragma unroll
   for (int i = 0; i < MI; ++i) {
-    u32x4 rres[4], rsrc[4];
+    u32x4 rres[4], rsrc[4], rpre[4];
     float rsc[4];   // per-row fp32 scalars (row scale / softmax shift) of the 4 store iterations
     float psum[4];  // softmax: fp32 sum of this lane's 8 exponentials per store iteration
 #pragma unroll
@@ -473,6 +533,7 @@ __device__ __forceinline__ void epilogue_bf16(const GemmArgs& a, ACC& acc, float
       const bool ok = nok && m < a.M;
       if constexpr (FLAGS & DMI_GEMM_RESIDUAL) rres[it] = ok ? *(const u32x4*)(a.residual + off) : u32x4{0, 0, 0, 0};
       if constexpr (FLAGS & DMI_GEMM_RELU_MASK) rsrc[it] = ok ? *(const u32x4*)(a.relu_src + off) : u32x4{0, 0, 0, 0};
+      if constexpr (FLAGS & GEMM_GELU_GRAD) rpre[it] = ok ? *(const u32x4*)(a.gelu_pre + (int64_t)m * a.ldpre + n) : u32x4{0, 0, 0, 0};
       if constexpr (FLAGS & DMI_GEMM_ROWSCALE) rsc[it] = (m < a.M) ? a.rowscale[m] : 0.f;
       if constexpr (FLAGS & GEMM_SOFTMAX) rsc[it] = (shifted && m < a.M) ? a.rowshift[m] * LOG2E : 0.f;
     }
@@ -492,6 +553,19 @@ __device__ __forceinline__ void epilogue_bf16(const GemmArgs& a, ACC& acc, float
       if constexpr (FLAGS & DMI_GEMM_RELU) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+      }
+      if constexpr (FLAGS & DMI_GEMM_GELU) {
+        if constexpr (FLAGS & GEMM_GELU_PRE) {
+          if (nok && m < a.M) *(u32x4*)(a.gelu_pre + (int64_t)m * a.ldpre + n) = pack8(v);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = gelu_f(v[e]);
+      }
+      if constexpr (FLAGS & GEMM_GELU_GRAD) {
+        float b[8];
+        unpack8(rpre[it], b);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] *= gelu_grad_f(b[e]);
       }
       if constexpr (FLAGS & DMI_GEMM_RESIDUAL) {
         float b[8];
@@ -1637,6 +1711,11 @@ __global__ __launch_bounds__(64 * SK_WAVES) void gemm_nt_skinny_kernel(const Gem
     if (m >= a.M) continue;
     float x = v[e] + bias;
     if constexpr (FLAGS & DMI_GEMM_RELU) x = fmaxf(x, 0.f);
+    if constexpr (FLAGS & DMI_GEMM_GELU) {
+      if constexpr (FLAGS & GEMM_GELU_PRE) a.gelu_pre[(int64_t)m * a.ldpre + n] = f2bf(x);
+      x = gelu_f(x);
+    }
+    if constexpr (FLAGS & GEMM_GELU_GRAD) x *= gelu_grad_f(bf2f(a.gelu_pre[(int64_t)m * a.ldpre + n]));
     if constexpr (FLAGS & DMI_GEMM_RESIDUAL) x += bf2f(a.residual[(int64_t)m * a.ldc + n]);
     ((bf16_t*)a.C)[(int64_t)m * a.ldc + n] = f2bf(x);
   }
@@ -1743,6 +1822,7 @@ __global__ __launch_bounds__(64 * SK_WAVES) void gemm_ln_nt_skinny_kernel(const 
     if (m >= a.M) continue;
     float y = v[e] + bias;
     if constexpr (FLAGS & DMI_GEMM_RELU) y = fmaxf(y, 0.f);
+    if constexpr (FLAGS & DMI_GEMM_GELU) y = gelu_f(y);
     ((bf16_t*)a.C)[(int64_t)m * a.ldc + n] = f2bf(y);
   }
 }
@@ -1785,14 +1865,16 @@ static int launch_nt8p(const GemmArgs& a, hipStream_t st) {
 template <int FLAGS>
 static int launch_nt(const GemmArgs& a, int nsplit, hipStream_t st) {
   const dim3 grid(a.tiles_m * a.tiles_n, nsplit), blk(256);
-  if constexpr (FLAGS == 0 || FLAGS == DMI_GEMM_BIAS || FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_RELU) || FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_RESIDUAL)) {
+  if constexpr (FLAGS == 0 || FLAGS == DMI_GEMM_BIAS || FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_RELU) || FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_RESIDUAL) ||
+                FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_GELU) || FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_GELU | GEMM_GELU_PRE) || FLAGS == GEMM_GELU_GRAD) {
     if (g_opt_skinny && a.M <= 32 && nsplit == 1 && a.N % 16 == 0) {
       gemm_nt_skinny_kernel<FLAGS><<<dim3(a.N / 16), dim3(64 * SK_WAVES), 0, st>>>(a);
       DMI_CHECK_LAUNCH("gemm_nt_skinny");
       return DMI_OK;
     }
   }
-  if constexpr (epi_regs_ok<FLAGS> && !(FLAGS & GEMM_SOFTMAX)) {
+  // (the GELU epilogues are not compiled into the full-row kernel: with 4 d = 512 those products run on the tiles below)
+  if constexpr (epi_regs_ok<FLAGS> && !(FLAGS & (GEMM_SOFTMAX | DMI_GEMM_GELU | GEMM_GELU_GRAD))) {
     // full-row tiles: N = 512 exactly, one 160-row tile per block
     if (g_opt_ntr && a.N == 512 && nsplit == 1 && a.k_per_split == a.K && a.K % 32 == 0 && (int64_t)a.N * a.ldb < (1 << 30) &&
         (g_opt_ntr == 2 || (a.M >= 160 * (num_cus() / 2) && a.K <= 4096 && g_opt_reserve_cus == 0))) {   // (the head's input gradient, K = 50816: 1.83 ms here vs 1.32 ms on 256x256 tiles)
@@ -1893,6 +1975,7 @@ extern "C" int dmi_gemm_nt(const uint16_t* A, int lda, const uint16_t* Bt, int l
     case 0: return launch_nt<0>(a, 1, st);
     case DMI_GEMM_BIAS: return launch_nt<DMI_GEMM_BIAS>(a, 1, st);
     case DMI_GEMM_BIAS | DMI_GEMM_RELU: return launch_nt<DMI_GEMM_BIAS | DMI_GEMM_RELU>(a, 1, st);
+    case DMI_GEMM_BIAS | DMI_GEMM_GELU: return launch_nt<DMI_GEMM_BIAS | DMI_GEMM_GELU>(a, 1, st);
     case DMI_GEMM_BIAS | DMI_GEMM_RESIDUAL: return launch_nt<DMI_GEMM_BIAS | DMI_GEMM_RESIDUAL>(a, 1, st);
     case DMI_GEMM_RELU_MASK: return launch_nt<DMI_GEMM_RELU_MASK>(a, 1, st);
     case DMI_GEMM_RESIDUAL: return launch_nt<DMI_GEMM_RESIDUAL>(a, 1, st);
@@ -1940,6 +2023,37 @@ extern "C" int dmi_gemm_nt_mask_bits(const uint16_t* A, int lda, const uint16_t*
   a.relu_bits = (unsigned short*)bits; a.dbg = g_dbg_buf;
   if ((rc = check_bits("gemm_nt_mask_bits", a, bits))) return rc;
   return launch_nt8p<GEMM_MASK_BITS>(a, (hipStream_t)stream);
+}
+
+// ---- the GELU FFN (DALLE activation_fn "gelu", see gelu_sig above): FFN-1 forward keeps the pre-activation for the FFN-2 input
+// gradient.  Reference: h = mtf.gelu(dense(x)) (src/dalle_mtf/models.py:317-324 with activation_fn = mtf.gelu), dh = dh * gelu'(a).
+// Every tile kernel launch_nt chooses has both epilogues, except the full-row one (gemm_ntr_kernel is compiled without them).
+static int check_pre(const char* who, const void* pre, int ldpre, int N) {
+  DMI_REQUIRE(pre, "%s: null pre", who);
+  DMI_REQUIRE(((uintptr_t)pre & 15) == 0, "%s: pre must be 16-byte aligned", who);
+  DMI_REQUIRE(ldpre % 8 == 0 && ldpre >= N, "%s: need ldpre %% 8 == 0 and ldpre >= N (ldpre=%d N=%d)", who, ldpre, N);
+  return DMI_OK;
+}
+extern "C" int dmi_gemm_nt_gelu(const uint16_t* A, int lda, const uint16_t* Bt, int ldb, uint16_t* C, int ldc, int M, int N, int K,
+                                const uint16_t* bias, uint16_t* pre, int ldpre, void* stream) {
+  int rc = check_nt(A, lda, Bt, ldb, C, ldc, M, N, K);
+  if (rc) return rc;
+  DMI_REQUIRE(bias, "gemm_nt_gelu: null bias");
+  if ((rc = check_pre("gemm_nt_gelu", pre, ldpre, N))) return rc;
+  GemmArgs a;
+  fill_nt_args(a, A, lda, Bt, ldb, C, ldc, M, N, K);
+  a.bias = bias; a.gelu_pre = pre; a.ldpre = ldpre; a.dbg = g_dbg_buf;
+  return launch_nt<DMI_GEMM_BIAS | DMI_GEMM_GELU | GEMM_GELU_PRE>(a, 1, (hipStream_t)stream);
+}
+extern "C" int dmi_gemm_nt_gelu_grad(const uint16_t* A, int lda, const uint16_t* Bt, int ldb, uint16_t* C, int ldc, int M, int N, int K,
+                                     const uint16_t* pre, int ldpre, void* stream) {
+  int rc = check_nt(A, lda, Bt, ldb, C, ldc, M, N, K);
+  if (rc) return rc;
+  if ((rc = check_pre("gemm_nt_gelu_grad", pre, ldpre, N))) return rc;
+  GemmArgs a;
+  fill_nt_args(a, A, lda, Bt, ldb, C, ldc, M, N, K);
+  a.gelu_pre = (bf16_t*)pre; a.ldpre = ldpre; a.dbg = g_dbg_buf;
+  return launch_nt<GEMM_GELU_GRAD>(a, 1, (hipStream_t)stream);
 }
 
 // 1 where dmi_gemm_nt_ln / dmi_gemm_nt_lnbwd accept a product [M, K] x [N, K]^T with K-contiguous operands (lda = ldb = K) AND the
@@ -2036,6 +2150,7 @@ extern "C" int dmi_ln_gemm_nt(const uint16_t* X, int ldx, const uint16_t* gamma,
     case 0: gemm_ln_nt_skinny_kernel<0><<<grid, blk, 0, st>>>(a, gamma, beta, eps); break;
     case DMI_GEMM_BIAS: gemm_ln_nt_skinny_kernel<DMI_GEMM_BIAS><<<grid, blk, 0, st>>>(a, gamma, beta, eps); break;
     case DMI_GEMM_BIAS | DMI_GEMM_RELU: gemm_ln_nt_skinny_kernel<DMI_GEMM_BIAS | DMI_GEMM_RELU><<<grid, blk, 0, st>>>(a, gamma, beta, eps); break;
+    case DMI_GEMM_BIAS | DMI_GEMM_GELU: gemm_ln_nt_skinny_kernel<DMI_GEMM_BIAS | DMI_GEMM_GELU><<<grid, blk, 0, st>>>(a, gamma, beta, eps); break;
     default:
       dmi_set_error("ln_gemm_nt: unsupported flag combination %d", flags);
       return DMI_ERR_UNSUPPORTED;

@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("DALLE_HIP_LIB") or os.path.join(_HERE, "libdalle_hip.
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "dalle_hip.h")
 
 GEMM_BIAS, GEMM_RELU, GEMM_RESIDUAL, GEMM_RELU_MASK, GEMM_OUT_F32, GEMM_ROWSCALE = 1, 2, 4, 8, 16, 32
+GEMM_GELU = 512
 
 _lib = None
 
@@ -110,6 +111,8 @@ def _declare(L):
         "dmi_gemm_nt_ln_auto": (I, [I, I, I]),
         "dmi_gemm_nt_relu_bits": (I, [P, I, P, I, P, I, I, I, I, P, P, P]),
         "dmi_gemm_nt_mask_bits": (I, [P, I, P, I, P, I, I, I, I, P, P]),
+        "dmi_gemm_nt_gelu": (I, [P, I, P, I, P, I, I, I, I, P, P, I, P]),
+        "dmi_gemm_nt_gelu_grad": (I, [P, I, P, I, P, I, I, I, I, P, I, P]),
         "dmi_sumsq_workspace_bytes": (L64, [L64]),
         "dmi_sumsq": (I, [P, L64, P, P, P]),
         "dmi_adam_step": (I, [P, P, P, P, P, L64, P, F, F, F, F, F, F, F, P, P]),
@@ -293,8 +296,20 @@ def gemm_nt_mask_bits(A, lda, Bt, ldb, C, ldc, M, N, K, bits):
     _check(lib().dmi_gemm_nt_mask_bits(_p(A), lda, _p(Bt), ldb, _p(C), ldc, M, N, K, _p(bits), _stream()), "gemm_nt_mask_bits")
 
 
+def gemm_nt_gelu(A, lda, Bt, ldb, C, ldc, M, N, K, bias, pre, ldpre):
+    """a = A . Bt^T + bias (fp32): C = bf16(gelu(a)) (tanh form) and pre = bf16(a) [M, ldpre], the input of gemm_nt_gelu_grad"""
+    _dev(A, Bt, C, bias, pre)
+    _check(lib().dmi_gemm_nt_gelu(_p(A), lda, _p(Bt), ldb, _p(C), ldc, M, N, K, _p(bias), _p(pre), ldpre, _stream()), "gemm_nt_gelu")
+
+
+def gemm_nt_gelu_grad(A, lda, Bt, ldb, C, ldc, M, N, K, pre, ldpre):
+    """C = bf16((A . Bt^T) * gelu'(pre)), pre as gemm_nt_gelu wrote it"""
+    _dev(A, Bt, C, pre)
+    _check(lib().dmi_gemm_nt_gelu_grad(_p(A), lda, _p(Bt), ldb, _p(C), ldc, M, N, K, _p(pre), ldpre, _stream()), "gemm_nt_gelu_grad")
+
+
 def ln_gemm_nt(X, ldx, gamma, beta, Bt, ldb, C, ldc, M, N, K, flags=0, bias=None, eps=1e-5):
-    """C = LayerNorm(X) . Bt^T (+ bias)(ReLU) for the decode step (M <= 32)"""
+    """C = LayerNorm(X) . Bt^T (+ bias)(ReLU / GELU) for the decode step (M <= 32)"""
     _dev(X, gamma, beta, Bt, C)
     _check(lib().dmi_ln_gemm_nt(_p(X), ldx, _p(gamma), _p(beta), eps, _p(Bt), ldb, _p(C), ldc, M, N, K, flags, _p(bias), _stream()),
            "ln_gemm_nt")

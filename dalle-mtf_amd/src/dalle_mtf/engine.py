@@ -30,6 +30,7 @@ import torch
 
 import dalle_hip as dh
 from ..dp import GradReducer
+from .activations import check_activation
 
 HEAD_DIMS = (64, 128)   # n_embd / n_heads values the attention kernels are built for
 ALIGN = 128  # elements
@@ -168,6 +169,8 @@ class DalleEngine:
         self.dev = torch.device(device)
         self.pg, self.world = process_group, world_size
         self.hp = dict(hparams or {})
+        # the FFN activation (reference src/dalle_mtf/models.py:317-324): "relu" (default) or "gelu" (dalle_mtf.activations)
+        self.activation = check_activation(self.hp.get("activation_fn") or "relu")
         self.lay = ParamLayout(n_embd, n_layers, n_heads, self.V, self.S)
         self.Vp = self.lay.Vp
         n = self.lay.total
@@ -392,8 +395,12 @@ class DalleEngine:
         # [r05] the ReLU mask of the FFN as bits: FFN-1's epilogue emits them, the FFN-2 input gradient reads M * 4d / 8 bytes instead
         # of the whole h (168 MB per layer at dalle_example) -- where the library runs both products on the kernel that has the bit
         # forms (dmi_relu_bits_auto); bit-identical to the relu_src form (tested)
-        self.use_relu_bits = bool(self.hp.get("relu_bits", True)) and dh.relu_bits_auto(M, 4 * d, d)
+        gelu = self.activation == "gelu"
+        self.use_relu_bits = not gelu and bool(self.hp.get("relu_bits", True)) and dh.relu_bits_auto(M, 4 * d, d)
         self.hbits = per_layer(lambda: torch.empty(dh.relu_bits_bytes(M, 4 * d), dtype=torch.uint8, device=self.dev)) if self.use_relu_bits else None
+        # GELU: FFN-1 also keeps its pre-activation a = xn2 . W1 + b1 (bf16, what the FFN-2 input gradient's gelu'(a) reads; GELU
+        # cannot be inverted from h) -- 2 bytes per hidden element, 168 MB per layer at dalle_example B = 32
+        self.hpre = per_layer(lambda: torch.empty(M, 4 * d, **b16)) if gelu else None
         self.stats = per_layer(lambda: [torch.empty(M, **f32) for _ in range(4)])  # mean1, rstd1, mean2, rstd2
         self.xnf = torch.empty(M, d, **b16)
         self.statf = [torch.empty(M, **f32) for _ in range(2)]
@@ -546,7 +553,10 @@ class DalleEngine:
             dh.gemm_nt(self.o[l], d, self.tview(p + "attn/o"), d, self.x1[l], d, M, d, d, dh.GEMM_BIAS | dh.GEMM_RESIDUAL,
                        bias=self._w(p + "attn/compute_output_bias/o_b"), residual=x)
             dh.layernorm_fwd(self.x1[l], self._w(p + "norm_2/g"), self._w(p + "norm_2/b"), self.xn2[l], st[2], st[3], M, d)
-        if self.use_relu_bits:
+        if self.hpre is not None:
+            dh.gemm_nt_gelu(self.xn2[l], d, self.tview(p + "mlp/mlp_linear_1/kernel"), d, self.h[l], 4 * d, M, 4 * d, d,
+                            self._w(p + "mlp/mlp_linear_1/bias"), self.hpre[l], 4 * d)
+        elif self.use_relu_bits:
             dh.gemm_nt_relu_bits(self.xn2[l], d, self.tview(p + "mlp/mlp_linear_1/kernel"), d, self.h[l], 4 * d, M, 4 * d, d,
                                  self._w(p + "mlp/mlp_linear_1/bias"), self.hbits[l])
         else:
@@ -782,7 +792,7 @@ class DalleEngine:
         x, x1, xn, o, h, st, z, fresh = D["x"][0], D["x"][1], D["xn"], D["o"], D["h"], D["st"], D["z"], D["fresh"]
         fuse_ln = B <= 32 and d <= 2048 and self.image_vocab_size % 16 == 0 and self.hp.get("decode_fuse_ln", True)
 
-        def ln_dense(inp, ln, W, out, N, flags=0, bias=None):       # out = LN(inp) . W^T (+ bias)(ReLU)
+        def ln_dense(inp, ln, W, out, N, flags=0, bias=None):       # out = LN(inp) . W^T (+ bias)(ReLU / GELU)
             g, b = self._w(ln + "/g"), self._w(ln + "/b")
             if fuse_ln:
                 dh.ln_gemm_nt(inp, d, g, b, W, d, out, N, B, N, d, flags, bias=bias)
@@ -790,6 +800,7 @@ class DalleEngine:
                 dh.layernorm_fwd(inp, g, b, xn, st[0], st[1], B, d)
                 dh.gemm_nt(xn, d, W, d, out, N, B, N, d, flags, bias=bias)
 
+        act = dh.GEMM_GELU if self.activation == "gelu" else dh.GEMM_RELU
         caches = self._kv_caches()
         dh.embed_fwd(D["tok"], self._w("embedding/wte"), self._w("positional_embedding/wpe"), x, S, d, self.V,
                      pos_dev=D["pos_i"])                                  # every row takes wpe[pos]
@@ -803,7 +814,7 @@ class DalleEngine:
                 dh.attention_decode_masked(cache, o, self.attn_plan[l], B, H, S, 0, fresh=fresh, pos_dev=D["pos_i"], head_dim=self.hd)
             dh.gemm_nt(o, d, self.tview(p + "attn/o"), d, x1, d, B, d, d, dh.GEMM_BIAS | dh.GEMM_RESIDUAL,
                        bias=self._w(p + "attn/compute_output_bias/o_b"), residual=x)
-            ln_dense(x1, p + "norm_2", self.tview(p + "mlp/mlp_linear_1/kernel"), h, 4 * d, dh.GEMM_BIAS | dh.GEMM_RELU,
+            ln_dense(x1, p + "norm_2", self.tview(p + "mlp/mlp_linear_1/kernel"), h, 4 * d, dh.GEMM_BIAS | act,
                      bias=self._w(p + "mlp/mlp_linear_1/bias"))
             dh.gemm_nt(h, 4 * d, self.tview(p + "mlp/mlp_linear_2/kernel"), 4 * d, x, d, B, d, 4 * d,
                        dh.GEMM_BIAS | dh.GEMM_RESIDUAL, bias=self._w(p + "mlp/mlp_linear_2/bias"), residual=x1)
@@ -931,7 +942,9 @@ class DalleEngine:
             if not group4:
                 self._wgrad(self.h[l], 4 * d, dxa, d, self._gv(p + "mlp/mlp_linear_2/kernel"), M, 4 * d, d,
                             dbias=self._gv(p + "mlp/mlp_linear_2/bias"), slot=0)
-            if self.use_relu_bits:
+            if self.hpre is not None:
+                dh.gemm_nt_gelu_grad(dxa, d, self._w(p + "mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d, self.hpre[l], 4 * d)
+            elif self.use_relu_bits:
                 dh.gemm_nt_mask_bits(dxa, d, self._w(p + "mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d, self.hbits[l])
             else:
                 dh.gemm_nt(dxa, d, self._w(p + "mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d, dh.GEMM_RELU_MASK,
@@ -1100,7 +1113,7 @@ class DalleEngine:
 
     # ------------------------------------------------------------------ checkpoint
     def state_dict(self):
-        sd = {"p": self.p.detach().cpu(), "global_step": self.global_step, "optimizer": self.optimizer}
+        sd = {"p": self.p.detach().cpu(), "global_step": self.global_step, "optimizer": self.optimizer, "activation_fn": self.activation}
         for k in ("m", "v", "af_slots"):
             if getattr(self, k) is not None:
                 sd[k] = getattr(self, k).detach().cpu()
@@ -1111,6 +1124,10 @@ class DalleEngine:
         if written != self.optimizer:
             raise ValueError(f"checkpoint was written by the {written} optimizer; this run uses {self.optimizer}: "
                              "the optimizer state of one cannot continue the other")
+        act = sd.get("activation_fn", "relu")   # checkpoints from before the activation was recorded are ReLU models
+        if act != self.activation:
+            raise ValueError(f"checkpoint was written by a {act} model; this run uses activation_fn {self.activation!r}: "
+                             "the weights of one do not compute the other")
         self.p.copy_(sd["p"])
         for k in ("m", "v", "af_slots"):
             if getattr(self, k) is not None:

@@ -6,6 +6,7 @@ import torch
 
 import numpy as np
 
+from .activations import resolve_activation
 from .engine import DalleEngine
 from .masks import layer_masks
 from .ops import get_variable_dtype
@@ -44,10 +45,13 @@ class DALLE:
         self.batch_size = batch_size
         if is_incremental_inference or context is not None:
             raise NotImplementedError("incremental inference is unfinished upstream (predict raises NotImplementedError, model_fns.py:135)")
-        if loss_fn is not None or activation_fn is not None:
-            raise NotImplementedError("custom loss_fn / activation_fn: kernels implement softmax-CE and ReLU (reference defaults)")
+        if loss_fn is not None:
+            raise NotImplementedError("custom loss_fn: the kernels implement softmax cross-entropy (the reference default)")
         params = {} if params is None else params
         self.params = defaultdict(lambda: None, params)
+        # activation_fn (reference models.py:317-324, the FFN's hidden layer): "relu" | "gelu" | None -> config key "activation_fn"
+        # -> "relu" (dalle_mtf.activations)
+        self.activation_fn = resolve_activation(activation_fn, params)
         for k in ("embed_dropout", "attention_dropout", "residual_dropout"):
             if self.params.get(k):
                 raise NotImplementedError(f"{k} > 0 is not supported (all shipped configs use 0)")
@@ -69,7 +73,7 @@ class DALLE:
                 attn_masks = None
         self.engine = DalleEngine(n_embd, n_layers, n_heads, text_vocab_size, image_vocab_size, text_seq_len,
                                   image_seq_len, batch_size, global_batch_size=global_batch_size,
-                                  eos_token_id=eos_token_id, hparams=dict(self.params), device=device,
+                                  eos_token_id=eos_token_id, hparams=dict(self.params, activation_fn=self.activation_fn), device=device,
                                   process_group=process_group, world_size=world_size, comm=comm, attn_masks=attn_masks)
         self.dimensions = {"embed_dim": n_embd, "final_vocab_dim": self.total_tokens, "total_seq_dim": self.total_seq_dim,
                            "heads_dim": n_heads, "kv_dim": n_embd // n_heads, "batch_dim": batch_size}

@@ -79,19 +79,21 @@ int dmi_layernorm_bwd_finish_batch(const void* const* workspaces, float* const* 
  * C[M,N] = A[M,K] . Bt[N,K]^T  (both operands K-contiguous), bf16 in, fp32 accumulate on MFMA.
  * flags: DMI_GEMM_*;  bias bf16 [N];  residual bf16 [M,ldc] added;  relu_src bf16 [M,ldc]: C *= (relu_src>0);
  * rowscale fp32 [M]: C[m,:] *= rowscale[m].  K % 64 == 0, N % 8 == 0.  Output bf16 (or fp32 with DMI_GEMM_OUT_F32).
- * Supported flag sets: 0, BIAS, BIAS|RELU, BIAS|RESIDUAL, RESIDUAL, RELU_MASK, ROWSCALE, OUT_F32. */
+ * GELU: C = bf16(gelu(acc + bias)), the tanh form of mtf.gelu (see dmi_gemm_nt_gelu).
+ * Supported flag sets: 0, BIAS, BIAS|RELU, BIAS|GELU, BIAS|RESIDUAL, RESIDUAL, RELU_MASK, ROWSCALE, OUT_F32. */
 #define DMI_GEMM_BIAS 1
 #define DMI_GEMM_RELU 2
 #define DMI_GEMM_RESIDUAL 4
 #define DMI_GEMM_RELU_MASK 8
 #define DMI_GEMM_OUT_F32 16
 #define DMI_GEMM_ROWSCALE 32
+#define DMI_GEMM_GELU 512
 int dmi_gemm_nt(const uint16_t* A, int lda, const uint16_t* Bt, int ldb, void* C, int ldc,
                 int M, int N, int K, int flags, const uint16_t* bias, const uint16_t* residual,
                 const uint16_t* relu_src, const float* rowscale, void* stream);
 /* LayerNorm (eps, biased variance: K2) fused into the product, for the incremental decode step only (M <= 32 rows, N % 16 == 0,
- * K = the normalised width <= 2048; anything else -> DMI_ERR_UNSUPPORTED): C = LN(X; gamma, beta) . Bt^T (+ bias bf16 [N])(ReLU).
- * flags: 0, BIAS, BIAS|RELU.  LN(X) is rounded to bf16 before the product, as dmi_layernorm_fwd + dmi_gemm_nt would. */
+ * K = the normalised width <= 2048; anything else -> DMI_ERR_UNSUPPORTED): C = LN(X; gamma, beta) . Bt^T (+ bias bf16 [N])(ReLU / GELU).
+ * flags: 0, BIAS, BIAS|RELU, BIAS|GELU.  LN(X) is rounded to bf16 before the product, as dmi_layernorm_fwd + dmi_gemm_nt would. */
 int dmi_ln_gemm_nt(const uint16_t* X, int ldx, const uint16_t* gamma, const uint16_t* beta, float eps, const uint16_t* Bt, int ldb,
                    uint16_t* C, int ldc, int M, int N, int K, int flags, const uint16_t* bias, void* stream);
 /* same product with the K range split over nsplit block groups (fp32 slabs in workspace, deterministic reduction to
@@ -231,6 +233,16 @@ int dmi_gemm_nt_relu_bits(const uint16_t* A, int lda, const uint16_t* Bt, int ld
                           const uint16_t* bias, void* bits, void* stream);
 int dmi_gemm_nt_mask_bits(const uint16_t* A, int lda, const uint16_t* Bt, int ldb, uint16_t* C, int ldc, int M, int N, int K,
                           const void* bits, void* stream);
+/* The FFN's GELU (the DALLE activation_fn "gelu"; reference src/dalle_mtf/models.py:317-324 with mtf.gelu, the tanh form
+ * gelu(x) = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) = x * sigmoid(2u), evaluated in fp32):
+ *   dmi_gemm_nt_gelu:      a = A . Bt^T + bias (fp32);  C = bf16(gelu(a)),  pre[M, ldpre] = bf16(a)   (the backward's input: GELU
+ *                          cannot be inverted from C);
+ *   dmi_gemm_nt_gelu_grad: C = bf16((A . Bt^T) * gelu'(pre)), gelu' in fp32 from the bf16 pre.
+ * Same shapes as dmi_gemm_nt; pre 16-byte aligned, ldpre % 8 == 0, ldpre >= N. */
+int dmi_gemm_nt_gelu(const uint16_t* A, int lda, const uint16_t* Bt, int ldb, uint16_t* C, int ldc, int M, int N, int K,
+                     const uint16_t* bias, uint16_t* pre, int ldpre, void* stream);
+int dmi_gemm_nt_gelu_grad(const uint16_t* A, int lda, const uint16_t* Bt, int ldb, uint16_t* C, int ldc, int M, int N, int K,
+                          const uint16_t* pre, int ldpre, void* stream);
 /* An input-gradient product whose result arrives at a LayerNorm, with that LayerNorm's BACKWARD fused into the epilogue (reference:
  * the backward of src/dalle_mtf/layers.py:30-33 + models.py:387-388 behind models.py:330 / :333 -- norm_1 <- QKV, norm_2 <- FFN-1):
  *   dy = bf16(A . Bt^T) [M, N];  xh = (x - mean) * rstd;  dx[M, N] = bf16(rstd * (dy*gamma - mean_n(dy*gamma) - xh * mean_n(dy*gamma*xh)) + dres)
