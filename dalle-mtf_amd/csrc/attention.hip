@@ -253,19 +253,85 @@ __device__ __forceinline__ void store_rows_via_lds(char* strip, const f32x16 (&a
   }
   __builtin_amdgcn_wave_barrier();
 }
+// ---- attention-mask plans (custom masks, head dim 128; DESIGN.md §4 "Attention masks") ----------------------------------------------
+// A mask is a boolean [S, S] matrix M (M[i][j]: query i may attend to key j), causal and with no empty row; where M is false the
+// probability is exactly 0.  dmi_attn_mask_plan (below, with the masked entry points) compiles it on the host into a plan of int32 words:
+//   header (AMP_HDR words)  magic, S, NB = ceil(S/128), W = ceil(S/32), causal flag, word offsets of the sections below, tile counts;
+//   forward / dQ lists      per 128-query block (CSR: NB + 1 pointers, then entries): its live 64-key tiles in key order, entry =
+//                           tile | (class of each wave's 32 x 64 sub-tile << 16 + 2 wave), class 0 empty (the wave skips the tile),
+//                           1 full (no predicate), 2 partial (the row bitmap is applied with a select: masked scores are -inf);
+//   dK/dV lists             per 128-key block: its live 32-query tiles in query order, entry = tile | (partial << 16);
+//   two work orders         the blocks of each kind sorted by their number of live tiles, heaviest first -- the persistent kernels
+//                           deal (order position, batch * head) items in the serpentine of attn_sched / attn_item, as the causal
+//                           kernels deal their 40, 36, ..., 4-step tiles;
+//   row bitmap [S][W]       bit b of word w of row i = M[i][32 w + b] (partial forward / dQ tiles, the decode row of `pos`);
+//   column bitmap [S][W]    bit b of word w of row j = M[32 w + b][j] (partial dK/dV tiles).
+// A tile no query of a block attends to is never loaded.  Bits of keys >= S are 0, so a tile that reaches past S is partial.
+//
+// The round-2 forward, the dQ and the decode kernel are templates on MASKED: one source per operation, which differs between
+// the instances only in which key tiles an item walks, what a wave does with a tile, and the predicate.  Instances:
+//   attn_fwd_kernel<false | true>, attn_bwd_dq_kernel<0 | 1, false> and <1, true>, attn_decode_kernel<128 | 64, false> and <128, true>.
+// MASKED = false compiles to the code the causal kernels compiled to before they were templates (profiles/attn_merge_isa.txt); the
+// masked instances keep the buffer layouts, the unscaled fp32 softmax, the tile shapes and the persistent schedule.  The plan
+// pointer is a kernel argument of the masked instances only (a kernel's argument offsets are part of its code): PLAN is one
+// `const int*` there and an empty pack otherwise.  The masked dK/dV kernel is still a kernel of its own (attn_bwd_dkv_masked_kernel).
+#define AMP_MAGIC 0x504d4144
+#define AMP_HDR 32
+enum {
+  AMP_S = 1, AMP_NB, AMP_W, AMP_CAUSAL, AMP_FPTR, AMP_FLIST, AMP_KPTR, AMP_KLIST, AMP_FORDER, AMP_KORDER, AMP_ROWBITS, AMP_COLBITS,
+  AMP_WORDS, AMP_LIVE_F, AMP_CAUSAL_F, AMP_LIVE_K, AMP_CAUSAL_K
+};
+
+// row bits of a plan entry's tile for one wave: keys 64 j + 0..31 and + 32..63 of this lane's query row `mrow` if the wave's
+// sub-tile is partial (words past the row read as 0), all ones otherwise
+__device__ __forceinline__ void amp_row_bits(int ent, int wid, const unsigned* __restrict__ mrow, int W, unsigned& b0, unsigned& b1) {
+  const int j = ent & 0xffff;
+  b0 = b1 = 0xffffffffu;
+  if (((ent >> (16 + 2 * wid)) & 3) == 2) {
+    b0 = mrow[2 * j];
+    b1 = 2 * j + 1 < W ? mrow[2 * j + 1] : 0u;
+  }
+}
+
 // (A coalesced form of the prologue fetches -- Q / dO / O / K as 128-byte half rows, 8 rows per load instruction, turned into fragments
 // through wave-private 4-KB LDS strips -- was built, bit-identical and measured NEUTRAL in all three kernels (backward 242.2 vs 242.3 us,
 // profiles/r06_attn_ab.log): the fragments' 32-byte pieces of 32 rows per instruction are absorbed by the vector L1.  Removed.)
 #define QK_STAGE 32768  // K 16384 | V 16384
+// ---- forward, the round-2 program-order form (A/B arm attn_fwd = 0, and the forward of a custom mask; the default is the
+// software-pipelined attn_fwd2_kernel below).  Built for two waves per SIMD.
+template <bool MASKED, typename... PLAN>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o,
-                                                          float* __restrict__ lse, int B, int H, int S, int perxcd) {
+                                                          float* __restrict__ lse, PLAN __restrict__... plan_, int B, int H, int S, int perxcd) {
+  static_assert(sizeof...(PLAN) == (MASKED ? 1 : 0), "the plan pointer is an argument of the masked instance only");
   extern __shared__ __attribute__((aligned(16))) char sm[];  // 2 x QK_STAGE
   const int d = H * HD, ld3 = 3 * d;
-  const int T = (S + 127) / 128;
+  int T = (S + 127) / 128, W = 0;
+  const int* __restrict__ fptr = nullptr;
+  const int* __restrict__ flist = nullptr;
+  const int* __restrict__ forder = nullptr;
+  const unsigned* __restrict__ rowbits = nullptr;
+  if constexpr (MASKED) {
+    const int* __restrict__ plan = (plan_, ...);
+    T = plan[AMP_NB], W = plan[AMP_W];
+    fptr = plan + plan[AMP_FPTR];
+    flist = plan + plan[AMP_FLIST];
+    forder = plan + plan[AMP_FORDER];
+    rowbits = (const unsigned*)(plan + plan[AMP_ROWBITS]);
+  }
   const AttnSched sched = attn_sched(T, B * H, perxcd);
   int tile_, bh;
   for (int round = 0; attn_item(sched, round, tile_, bh); ++round) {   // persistent: two blocks per CU walk their item lists
-  const int qt = T - 1 - tile_;  // heaviest (latest) query tiles first
+  // which key tiles the item walks.  Causal: tiles 0 .. qlast / 64 of query block T - 1 - tile_ (heaviest = latest first);
+  // plan: the live tiles (CSR list) of query block forder[tile_] (heaviest first)
+  int qt, nsteps;
+  const int* __restrict__ list = nullptr;
+  if constexpr (MASKED) {
+    qt = forder[tile_];
+    list = flist + fptr[qt];
+    nsteps = fptr[qt + 1] - fptr[qt];
+  } else {
+    qt = T - 1 - tile_;
+  }
   const int b = bh / H, hh = bh % H;
   const int q0 = qt * 128;
   int tid = threadIdx.x;
@@ -275,6 +341,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restri
   const int r = lane & 31, h = lane >> 5, g4 = lane >> 4, l16 = lane & 15;
   const int qrow = q0 + wid * 32 + r;
   const int qrow_c = qrow < S ? qrow : S - 1;
+  const unsigned* __restrict__ mrow = nullptr;
+  if constexpr (MASKED) mrow = rowbits + (int64_t)qrow_c * W;
   const bf16_t* qb = qkv + (int64_t)b * S * ld3 + hh * HD;
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
   const int nbytes = (int)(((int64_t)(S - 1) * ld3 + HD) * 2);
@@ -320,12 +388,27 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restri
     for (int e = 0; e < 16; ++e) oacc[i][e] = 0.f;
   float m = -1e30f, l = 0.f;
 
-  const int qlast = (q0 + 127 < S - 1) ? q0 + 127 : S - 1;
-  const int nsteps = qlast / 64 + 1;
-  const int wave_qmin = q0 + wid * 32, wave_qmax = wave_qmin + 31;
+  int wave_qmin = 0, wave_qmax = 0;
+  if constexpr (!MASKED) {
+    const int qlast = (q0 + 127 < S - 1) ? q0 + 127 : S - 1;
+    nsteps = qlast / 64 + 1;
+    wave_qmin = q0 + wid * 32, wave_qmax = wave_qmin + 31;
+  }
 
-  auto compute = [&](int st, int j) {
-    if (64 * j > wave_qmax) return;  // wave-uniform: tile entirely above the diagonal for this wave
+  // A tile is named by t: its key tile index (causal) or its plan entry (masked).  What a wave does with it is wave-uniform:
+  // skip it (causal: entirely above the wave's diagonal; plan: class 0, no query row of the wave attends to it), take it whole,
+  // or apply the predicate (causal: the diagonal tile; plan: class 2)
+  auto tile_skipped = [&](int t) {
+    if constexpr (MASKED) return ((t >> (16 + 2 * wid)) & 3) == 0;
+    else return 64 * t > wave_qmax;
+  };
+  auto tile_partial = [&](int t) {
+    if constexpr (MASKED) return ((t >> (16 + 2 * wid)) & 3) == 2;
+    else return 64 * t + 63 > wave_qmin;
+  };
+  // one 64-key tile in stage st; (b0, b1) = amp_row_bits of the entry (masked only)
+  auto compute = [&](int st, int t, unsigned b0 = 0u, unsigned b1 = 0u) {
+    if (tile_skipped(t)) return;
     const char* base = sm + st * QK_STAGE;
     const unsigned vb = lds0 + st * QK_STAGE + 16384;
     f32x16 s0, s1;
@@ -340,12 +423,18 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restri
     }
     Tr4 tv[2];
     tr4_issue(tv[0], vb + oft[0][0], vb + oft[0][1], vb + oft[1][0], vb + oft[1][1], vb + oft[2][0], vb + oft[2][1], vb + oft[3][0], vb + oft[3][1]);
-    if (64 * j + 63 > wave_qmin) {  // diagonal tile: additive -1e10 mask == probability exactly 0
+    if (tile_partial(t)) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int key = 64 * j + (e & 3) + 8 * (e >> 2) + 4 * h;
-        s0[e] = (key > qrow) ? -1e30f : s0[e];
-        s1[e] = (key + 32 > qrow) ? -1e30f : s1[e];
+        const int kb = (e & 3) + 8 * (e >> 2) + 4 * h;   // s0[e]: key kb of the tile, s1[e]: key kb + 32
+        if constexpr (MASKED) {   // select, so masked scores are -inf (probability exactly 0, never NaN)
+          s0[e] = ((b0 >> kb) & 1u) ? s0[e] : -INFINITY;
+          s1[e] = ((b1 >> kb) & 1u) ? s1[e] : -INFINITY;
+        } else {                  // additive -1e10 mask == probability exactly 0
+          const int key = 64 * t + kb;
+          s0[e] = (key > qrow) ? -1e30f : s0[e];
+          s1[e] = (key + 32 > qrow) ? -1e30f : s1[e];
+        }
       }
     }
     float mx = -1e30f;
@@ -402,21 +491,39 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restri
     }
   };
 
-  stage(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  int j = 0;
-  for (; j + 2 <= nsteps; j += 2) {
-    stage(1, 64 * (j + 1));
-    compute(0, j);
+  // the two-stage ring: the DMA of the next tile runs under the compute of this one.  Each instance keeps its own loop form.
+  if constexpr (MASKED) {
+    // The row-bit loads of step i are issued ahead of the DMA of step i + 1, but hipcc's wait for them is a vmcnt(0): on a partial
+    // tile the select, softmax and P.V wait for the next tile's DMA too (measured cost: DESIGN.md §4 "Attention masks").
+    if (nsteps > 0) stage(0, 64 * (list[0] & 0xffff));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (j + 2 < nsteps) stage(0, 64 * (j + 2));
-    compute(1, j + 1);
+    for (int i = 0; i < nsteps; ++i) {
+      const int ent = list[i];
+      unsigned b0, b1;
+      amp_row_bits(ent, wid, mrow, W, b0, b1);
+      if (i + 1 < nsteps) stage((i + 1) & 1, 64 * (list[i + 1] & 0xffff));
+      compute(i & 1, ent, b0, b1);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+  } else {
+    stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    int j = 0;
+    for (; j + 2 <= nsteps; j += 2) {   // unrolled by two: literal stage indices
+      stage(1, 64 * (j + 1));
+      compute(0, j);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (j + 2 < nsteps) stage(0, 64 * (j + 2));
+      compute(1, j + 1);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+    if (j < nsteps) compute(0, j);
   }
-  if (j < nsteps) compute(0, j);
 
   l += __shfl_xor(l, 32, 64);
   if (qrow < S) {
@@ -884,7 +991,7 @@ extern "C" int dmi_attention_fwd(const uint16_t* qkv, uint16_t* o, float* lse, i
   DMI_REQUIRE((int64_t)S * 3 * H * HD * 2 < 0x7fffffff, "attention_fwd: sequence too long for 32-bit buffer offsets");
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
     (void)hipFuncSetAttribute((const void*)attn_fwd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
     attr_done = true;
   }
@@ -892,7 +999,7 @@ extern "C" int dmi_attention_fwd(const uint16_t* qkv, uint16_t* o, float* lse, i
     const int items = ((S + 127) / 128) * B * H;
     const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();   // two persistent blocks per CU
     const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
-    if (g_opt_attn_fwd == 0) attn_fwd_kernel<<<dim3(grid), dim3(256), 2 * QK_STAGE, (hipStream_t)stream>>>(qkv, o, lse, B, H, S, perxcd);
+    if (g_opt_attn_fwd == 0) attn_fwd_kernel<false><<<dim3(grid), dim3(256), 2 * QK_STAGE, (hipStream_t)stream>>>(qkv, o, lse, B, H, S, perxcd);
 #ifdef ATTN_STAMP
     else attn_fwd2_kernel<<<dim3(grid), dim3(256), 2 * QK_STAGE, (hipStream_t)stream>>>(qkv, o, lse, B, H, S, perxcd, g_dbg_buf);
 #else
@@ -911,18 +1018,41 @@ extern "C" int dmi_attention_fwd(const uint16_t* qkv, uint16_t* o, float* lse, i
 // The kernel also produces delta[q] = sum_d dO[q,d] O[q,d] itself (a lane pair holds the whole dO row of its query as MFMA
 // fragments; O is read in the same layout) and publishes the (lse, delta) pairs the dK/dV kernel streams in -- the
 // separate delta pass (17 us per layer) is gone.
-template <int rowstore>      // [r06] 1: whole-row epilogue stores through LDS strips; 0: the round-2 form (A/B)
+// MASKED: the same kernel walking a query block's live key tiles (instantiated with rowstore = 1 only).  Two waves per SIMD.
+template <int rowstore, bool MASKED, typename... PLAN>   // [r06] rowstore 1: whole-row epilogue stores through LDS strips; 0: the round-2 form (A/B)
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
                                                              const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
                                                              float* __restrict__ delta, float* __restrict__ stats,
-                                                             bf16_t* __restrict__ dqkv, int B, int H, int S, int perxcd) {
+                                                             bf16_t* __restrict__ dqkv, PLAN __restrict__... plan_, int B, int H, int S, int perxcd) {
+  static_assert(sizeof...(PLAN) == (MASKED ? 1 : 0), "the plan pointer is an argument of the masked instance only");
   extern __shared__ __attribute__((aligned(16))) char sm[];  // 2 x QK_STAGE
   const int d = H * HD, ld3 = 3 * d;
-  const int T = (S + 127) / 128;
+  int T = (S + 127) / 128, W = 0;
+  const int* __restrict__ fptr = nullptr;
+  const int* __restrict__ flist = nullptr;
+  const int* __restrict__ forder = nullptr;
+  const unsigned* __restrict__ rowbits = nullptr;
+  if constexpr (MASKED) {
+    const int* __restrict__ plan = (plan_, ...);
+    T = plan[AMP_NB], W = plan[AMP_W];
+    fptr = plan + plan[AMP_FPTR];
+    flist = plan + plan[AMP_FLIST];
+    forder = plan + plan[AMP_FORDER];
+    rowbits = (const unsigned*)(plan + plan[AMP_ROWBITS]);
+  }
   const AttnSched sched = attn_sched(T, B * H, perxcd);
   int tile_, bh;
   for (int round = 0; attn_item(sched, round, tile_, bh); ++round) {   // persistent: two blocks per CU walk their item lists
-  const int qt = T - 1 - tile_;
+  // which key tiles the item walks: as in attn_fwd_kernel
+  int qt, nsteps;
+  const int* __restrict__ list = nullptr;
+  if constexpr (MASKED) {
+    qt = forder[tile_];
+    list = flist + fptr[qt];
+    nsteps = fptr[qt + 1] - fptr[qt];
+  } else {
+    qt = T - 1 - tile_;
+  }
   const int b = bh / H, hh = bh % H;
   const int q0 = qt * 128;
   int tid = threadIdx.x;
@@ -932,6 +1062,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
   const int r = lane & 31, h = lane >> 5, g4 = lane >> 4, l16 = lane & 15;
   const int qrow = q0 + wid * 32 + r;
   const int qrow_c = qrow < S ? qrow : S - 1;
+  const unsigned* __restrict__ mrow = nullptr;
+  if constexpr (MASKED) mrow = rowbits + (int64_t)qrow_c * W;
   const bf16_t* qb = qkv + (int64_t)b * S * ld3 + hh * HD;
   const bf16_t* dob = d_o + (int64_t)b * S * d + hh * HD;
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
@@ -1003,12 +1135,25 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
 #pragma unroll
     for (int e = 0; e < 16; ++e) dq[i][e] = 0.f;
 
-  const int qlast = (q0 + 127 < S - 1) ? q0 + 127 : S - 1;
-  const int nsteps = qlast / 64 + 1;
-  const int wave_qmax = q0 + wid * 32 + 31;
+  int wave_qmax = 0;
+  if constexpr (!MASKED) {
+    const int qlast = (q0 + 127 < S - 1) ? q0 + 127 : S - 1;
+    nsteps = qlast / 64 + 1;
+    wave_qmax = q0 + wid * 32 + 31;
+  }
 
-  auto compute = [&](int st, int j) {
-    if (64 * j > wave_qmax) return;
+  // t names a tile and the wave skips it as in attn_fwd_kernel; the predicate goes on every causal tile (no branch), on class 2 of a plan
+  auto tile_skipped = [&](int t) {
+    if constexpr (MASKED) return ((t >> (16 + 2 * wid)) & 3) == 0;
+    else return 64 * t > wave_qmax;
+  };
+  auto tile_partial = [&](int t) {
+    if constexpr (MASKED) return ((t >> (16 + 2 * wid)) & 3) == 2;
+    else return true;
+  };
+  // one 64-key tile in stage st; (b0, b1) = amp_row_bits of the entry (masked only)
+  auto compute = [&](int st, int t, unsigned b0 = 0u, unsigned b1 = 0u) {
+    if (tile_skipped(t)) return;
     const char* base = sm + st * QK_STAGE;
 #pragma unroll
     for (int kt2 = 0; kt2 < 2; ++kt2) {
@@ -1031,11 +1176,23 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
       const unsigned t0 = ob + oft0[0], t1 = ob + oft0[1];   // (tile base + offset) ^ (dt << 6): the base is a multiple of 4096
       tr2_issue(tk[0], lds0 + t0, lds0 + t1, lds0 + (t0 ^ 64u), lds0 + (t1 ^ 64u));
       float ds[16];
+      if (tile_partial(t)) {   // masked scores -> exp2(-inf) = 0 by a select.  Unconditional exp: no per-element branches
+        const unsigned mb = kt2 ? b1 : b0;
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int key = 64 * j + kt2 * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        const float pe = __builtin_amdgcn_exp2f((key > qrow) ? -INFINITY : __builtin_fmaf(s[e], LOG2E_F, -lse2_q));  // unconditional exp: no per-element branches
-        ds[e] = pe * (dp[e] - delta_q);
+        for (int e = 0; e < 16; ++e) {
+          const int kb = (e & 3) + 8 * (e >> 2) + 4 * h;   // s[e]: key 32 kt2 + kb of the tile
+          bool live;
+          if constexpr (MASKED) live = (mb >> kb) & 1u;
+          else live = !(64 * t + kt2 * 32 + kb > qrow);
+          const float pe = __builtin_amdgcn_exp2f(live ? __builtin_fmaf(s[e], LOG2E_F, -lse2_q) : -INFINITY);
+          ds[e] = pe * (dp[e] - delta_q);
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const float pe = __builtin_amdgcn_exp2f(__builtin_fmaf(s[e], LOG2E_F, -lse2_q));
+          ds[e] = pe * (dp[e] - delta_q);
+        }
       }
       bf16x8 dsb[2];
       dsb[0] = pack_bf8(ds);
@@ -1056,24 +1213,41 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
     }
   };
 
-  stage(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  int j = 0;
-  for (; j + 2 <= nsteps; j += 2) {
-    stage(1, 64 * (j + 1));
-    compute(0, j);
+  // the two-stage ring of attn_fwd_kernel, each instance in its own loop form.  The masked loop ends with a barrier, the causal
+  // one with the last tile's compute.
+  if constexpr (MASKED) {
+    if (nsteps > 0) stage(0, 64 * (list[0] & 0xffff));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (j + 2 < nsteps) stage(0, 64 * (j + 2));
-    compute(1, j + 1);
+    for (int i = 0; i < nsteps; ++i) {
+      const int ent = list[i];
+      unsigned b0, b1;
+      amp_row_bits(ent, wid, mrow, W, b0, b1);
+      if (i + 1 < nsteps) stage((i + 1) & 1, 64 * (list[i + 1] & 0xffff));
+      compute(i & 1, ent, b0, b1);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+  } else {
+    stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    int j = 0;
+    for (; j + 2 <= nsteps; j += 2) {
+      stage(1, 64 * (j + 1));
+      compute(0, j);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (j + 2 < nsteps) stage(0, 64 * (j + 2));
+      compute(1, j + 1);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+    if (j < nsteps) compute(0, j);
   }
-  if (j < nsteps) compute(0, j);
 
   if constexpr (rowstore) {   // [r06] whole-row stores through a wave-private LDS strip (behind a barrier: the last tile's readers are done)
-    __syncthreads();
+    if constexpr (!MASKED) __syncthreads();
     store_rows_via_lds(sm + wid * (32 * ROWS_PITCH), dq, 1.0f, dqkv + ((int64_t)b * S + q0 + wid * 32) * ld3 + hh * HD, ld3, S - (q0 + wid * 32), lane);
   } else if (qrow < S) {
     bf16_t* op = dqkv + ((int64_t)b * S + qrow) * ld3 + hh * HD;
@@ -1107,6 +1281,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
 // A two-blocks-per-CU variant (<= 256 registers, 65 KiB LDS) spilled and was not faster.
 #define DKV_STAGE 16640  // Q 8192 | dO 8192 | (lse * log2 e, delta) pairs 256
 #define DKV_NSTAGE 4
+// the ring steps of both dK/dV kernels (causal and masked): wait for all but the N youngest DMAs of this wave; barrier behind the LDS reads
+#define DKV_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
+#define DKV_BARRIER()                                  \
+  do {                                                 \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
+    __builtin_amdgcn_s_barrier();                      \
+  } while (0)
 struct St8 {
   f32x4 v[8];   // (lse, delta) pairs of this lane's 16 query rows: v[2g], v[2g+1] = rows 8g + 4h + {0,1}, {2,3}
 };
@@ -1359,12 +1540,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
 
   // Ring: at the barrier that opens step t, tiles t and t+1 have landed (every wave waited for its own DMAs), tile t+2 is
   // in flight; step t issues tile t+3 into the slot of tile t-1, whose last reader (dV / dK of step t-1) is behind the barrier.
-#define DKV_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define DKV_BARRIER()                                  \
-  do {                                                 \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    __builtin_amdgcn_s_barrier();                      \
-  } while (0)
   if (nsteps > 0) stage(0, 32 * qi0);
   if (nsteps > 1) stage(1, 32 * (qi0 + 1));
   if (nsteps > 2) stage(2, 32 * (qi0 + 2));
@@ -1395,8 +1570,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
     DKV_STEP(sA, dpA, sB, dpB, false, true)
   }
 #undef DKV_STEP
-#undef DKV_WAIT
-#undef DKV_BARRIER
 
   if constexpr (rowstore) {   // [r06] whole-row stores (every step ended with a barrier: the ring and the V tile have no readers left)
     bf16_t* gk = dqkv + ((int64_t)b * S + key0 + wid * 32) * ld3 + d + hh * HD;
@@ -1435,8 +1608,8 @@ extern "C" int dmi_attention_bwd(const uint16_t* qkv, const uint16_t* o, const u
   static bool attr_done = false;
   const int shm = 32768 + DKV_NSTAGE * DKV_STAGE;
   if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
     (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
     (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
     attr_done = true;
@@ -1445,8 +1618,8 @@ extern "C" int dmi_attention_bwd(const uint16_t* qkv, const uint16_t* o, const u
   {
     const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();   // two persistent blocks per CU
     const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
-    if (g_opt_attn_bwd & 1) attn_bwd_dq_kernel<1><<<dim3(grid), dim3(256), 2 * QK_STAGE, st>>>(qkv, o, d_o, lse, delta, stats, dqkv, B, H, S, perxcd);
-    else attn_bwd_dq_kernel<0><<<dim3(grid), dim3(256), 2 * QK_STAGE, st>>>(qkv, o, d_o, lse, delta, stats, dqkv, B, H, S, perxcd);
+    if (g_opt_attn_bwd & 1) attn_bwd_dq_kernel<1, false><<<dim3(grid), dim3(256), 2 * QK_STAGE, st>>>(qkv, o, d_o, lse, delta, stats, dqkv, B, H, S, perxcd);
+    else attn_bwd_dq_kernel<0, false><<<dim3(grid), dim3(256), 2 * QK_STAGE, st>>>(qkv, o, d_o, lse, delta, stats, dqkv, B, H, S, perxcd);
   }
   DMI_CHECK_LAUNCH("attention_bwd_dq");
   {
@@ -1479,45 +1652,78 @@ extern "C" int dmi_attention_bwd(const uint16_t* qkv, const uint16_t* o, const u
 // q | k | v into cache row `pos` for the steps to come, and reads key / value `pos` from the staging row itself (no reliance
 // on the block seeing its own global stores).
 #define DEC_WAVES 16   // 1024 threads: a (batch, head) pair streams <= S keys through ONE block, so the block must itself hold the loads in flight
-// Lane (c = lane & 15, g = lane >> 4) owns head dims [8c, 8c + 8) and, per 64-key chunk, keys 4i + g (i = 0..15): every load
-// instruction of the wave fetches four whole 256-B rows (16 B per lane) -- the first form read one row per LANE, 16 B at a time,
-// and re-fetched each 128-B line from L2 up to eight times.  The 16 partial dot products per lane are combined across the 16
-// lanes of a group by a reduce-scatter butterfly (15 exchanges): lane (c, g) ends up with the whole score of key 4c + g.
+// One kernel, three instances: <128, false> and <64, false> (the causal row of `pos`) and <128, true> (row `pos` of a plan's row
+// bitmap -- pos from pos_dev on the graph-replayable path, so one captured graph serves every position; a 64-key chunk whose two
+// mask words are 0 is skipped without loads, masked keys of a chunk get probability exactly 0).  Head dim 64 with a plan is
+// refused by the host.  PLAN is `const int*` in the masked instance and empty otherwise, so the unmasked instances keep the
+// argument list -- and with it the code -- they had as kernels of their own.
+// A key row is HEAD_DIM / 8 lanes of 16 B.  Lane (c = lane % LPR, g = lane / LPR) owns head dims [8c, 8c + 8) and, per 64-key chunk,
+// keys G i + g (i = 0..LPR-1), G = 64 / LPR: every load instruction of the wave fetches G whole rows (head dim 128: four 256-B rows,
+// 16 of them in flight per lane; 64: eight 128-B rows, 8 in flight) -- the first form read one row per LANE, 16 B at a time, and
+// re-fetched each 128-B line from L2 up to eight times.  The LPR partial dot products per lane are combined across the LPR lanes
+// of a group by a reduce-scatter butterfly (LPR - 1 exchanges): lane (c, g) ends up with the whole score of key G c + g.
+// sum over the lanes that are a multiple of STRIDE apart: exchanges at STRIDE, 2 STRIDE, ..., 32
+template <int STRIDE>
+__device__ __forceinline__ float lane_groups_sum(float v) {
+  if constexpr (STRIDE < 64) {
+    v += __shfl_xor(v, STRIDE, 64);
+    return lane_groups_sum<2 * STRIDE>(v);
+  }
+  return v;
+}
+template <int HEAD_DIM, bool MASKED, typename... PLAN>
 __global__ __launch_bounds__(64 * DEC_WAVES) void attn_decode_kernel(bf16_t* qkv, const bf16_t* __restrict__ fresh, bf16_t* __restrict__ o,
-                                                                     int H, int S, int pos_arg, const int* __restrict__ pos_dev) {
+                                                                     PLAN __restrict__... plan_, int H, int S, int pos_arg,
+                                                                     const int* __restrict__ pos_dev) {
+  static_assert(sizeof...(PLAN) == (MASKED ? 1 : 0) && (HEAD_DIM == 128 || (HEAD_DIM == 64 && !MASKED)), "attn_decode_kernel instance");
+  constexpr int LPR = HEAD_DIM / 8;   // lanes per key row = rows in flight per lane = values a lane brings to the butterfly
+  constexpr int G = 64 / LPR;         // lane groups = keys per load instruction
   __shared__ float ps[DEC_WAVES][64];
   __shared__ float red_m[DEC_WAVES], red_l[DEC_WAVES];
-  __shared__ float oacc[DEC_WAVES][HD];
+  __shared__ float oacc[DEC_WAVES][HEAD_DIM];
   const int bh = blockIdx.x, b = bh / H, hh = bh % H;
-  const int d = H * HD;
+  const int d = H * HEAD_DIM;
   const int64_t ld3 = 3 * (int64_t)d;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int c = lane & 15, g = lane >> 4;
+  const int c = lane & (LPR - 1), g = lane / LPR;
   const int pos = pos_dev ? *pos_dev : pos_arg;
   if (pos < 0 || pos >= S) return;                     // (block-uniform; the host checks the by-value form)
-  bf16_t* base = qkv + (int64_t)b * S * ld3 + hh * HD;
-  const bf16_t* fr = fresh ? fresh + (int64_t)b * ld3 + hh * HD : nullptr;
+  int W = 0;                                           // MASKED: row `pos` of the row bitmap, W words
+  const unsigned* __restrict__ mrow = nullptr;
+  if constexpr (MASKED) {
+    const int* __restrict__ plan = (plan_, ...);
+    W = plan[AMP_W];
+    mrow = (const unsigned*)(plan + plan[AMP_ROWBITS]) + (int64_t)pos * W;
+  }
+  bf16_t* base = qkv + (int64_t)b * S * ld3 + hh * HEAD_DIM;
+  const bf16_t* fr = fresh ? fresh + (int64_t)b * ld3 + hh * HEAD_DIM : nullptr;
   float q[8];
   unpack8(*(const u32x4*)((fr ? fr : base + (int64_t)pos * ld3) + 8 * c), q);
-  if (fr && threadIdx.x < 3 * HD / 8) {   // q | k | v of this head: 3 x 256 B -> cache row pos (read back by no one in this launch)
-    const int part = threadIdx.x / (HD / 8), ch = threadIdx.x % (HD / 8);
+  if (fr && threadIdx.x < 3 * LPR) {   // q | k | v of this head: 3 x HEAD_DIM bf16 -> cache row pos (read back by no one in this launch)
+    const int part = threadIdx.x / LPR, ch = threadIdx.x % LPR;
     *(u32x4*)(base + (int64_t)pos * ld3 + part * d + ch * 8) = *(const u32x4*)(fr + part * d + ch * 8);
   }
   float m = -1e30f, l = 0.f;
   float oa[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int ch0 = wid; ch0 * 64 <= pos; ch0 += DEC_WAVES) {
+    unsigned w0 = 0u, w1 = 0u;                           // MASKED: the chunk's 64 bits of the row (words past the row read as 0)
+    if constexpr (MASKED) {
+      w0 = mrow[2 * ch0];
+      w1 = 2 * ch0 + 1 < W ? mrow[2 * ch0 + 1] : 0u;
+      if ((w0 | w1) == 0u) continue;                     // (wave-uniform) nothing of this chunk is attended to
+    }
     const int k0 = ch0 * 64;
-    auto row_ptr = [&](int i, int which) -> const u32x4* {   // key k0 + 4i + g, clamped to pos; row pos comes from the staging buffer
-      int key = k0 + 4 * i + g;
+    auto row_ptr = [&](int i, int which) -> const u32x4* {   // key k0 + G i + g, clamped to pos; row pos comes from the staging buffer
+      int key = k0 + G * i + g;
       key = key < pos ? key : pos;
       return (const u32x4*)((fr && key == pos) ? fr + which * d + 8 * c : base + which * d + (int64_t)key * ld3 + 8 * c);
     };
-    u32x4 raw[16];
+    u32x4 raw[LPR];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) raw[i] = *row_ptr(i, 1);
-    float p[16];
+    for (int i = 0; i < LPR; ++i) raw[i] = *row_ptr(i, 1);
+    float p[LPR];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
+    for (int i = 0; i < LPR; ++i) {
       float f[8];
       unpack8(raw[i], f);
       float t = 0.f;
@@ -1525,10 +1731,10 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void attn_decode_kernel(bf16_t* qkv
       for (int j = 0; j < 8; ++j) t = __builtin_fmaf(f[j], q[j], t);
       p[i] = t;
     }
-    // reduce-scatter over the 16 lanes of a group: after the stage with mask w, a lane keeps the half of its values whose
+    // reduce-scatter over the LPR lanes of a group: after the stage with mask w, a lane keeps the half of its values whose
     // index has bit w equal to its own bit w of c
 #pragma unroll
-    for (int w = 8; w >= 1; w >>= 1) {
+    for (int w = LPR / 2; w >= 1; w >>= 1) {
       const bool up = (c & w) != 0;
 #pragma unroll
       for (int j = 0; j < w; ++j) {
@@ -1538,35 +1744,39 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void attn_decode_kernel(bf16_t* qkv
       }
     }
 #pragma unroll
-    for (int i = 0; i < 16; ++i) raw[i] = *row_ptr(i, 2);     // value rows requested before the softmax' wave reductions
-    const int key = k0 + 4 * c + g;
-    const bool valid = key <= pos;
+    for (int i = 0; i < LPR; ++i) raw[i] = *row_ptr(i, 2);    // value rows requested before the softmax' wave reductions
+    // This lane's key is k0 + G c + g.  (The sum is associated as each instance had it as a kernel of its own: that alone keeps
+    // the address arithmetic hipcc derives from it, and so both instruction streams, what they were.)
+    bool valid;
+    if constexpr (MASKED) {
+      const int kb = G * c + g;                               // the key's bit of (w0, w1)
+      valid = k0 + kb <= pos && (((kb < 32 ? w0 : w1) >> (kb & 31)) & 1u);
+    } else {
+      valid = k0 + G * c + g <= pos;
+    }
     const float sc = valid ? p[0] : -1e30f;
     const float mn = fmaxf(m, wave_max(sc));
     const float alpha = __expf(m - mn);
     const float pe = valid ? __expf(sc - mn) : 0.f;
     l = l * alpha + wave_sum(pe);
     m = mn;
-    ps[wid][4 * c + g] = bf2f(f2bf(pe));
+    ps[wid][G * c + g] = bf2f(f2bf(pe));
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // wave-private strip: in-order LDS, no block barrier needed
 #pragma unroll
     for (int j = 0; j < 8; ++j) oa[j] *= alpha;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
+    for (int i = 0; i < LPR; ++i) {
       float f[8];
       unpack8(raw[i], f);
-      const float pj = ps[wid][4 * i + g];               // 0 for keys past pos (their rows were clamped to row pos)
+      const float pj = ps[wid][G * i + g];               // 0 for masked keys and keys past pos (their rows were clamped to row pos)
 #pragma unroll
       for (int j = 0; j < 8; ++j) oa[j] = __builtin_fmaf(pj, f[j], oa[j]);
     }
     __builtin_amdgcn_wave_barrier();
   }
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {                          // the four lane groups hold disjoint key subsets of the same dims
-    oa[j] += __shfl_xor(oa[j], 16, 64);
-    oa[j] += __shfl_xor(oa[j], 32, 64);
-  }
+  for (int j = 0; j < 8; ++j) oa[j] = lane_groups_sum<LPR>(oa[j]);   // the G lane groups hold disjoint key subsets of the same dims
   if (lane == 0) { red_m[wid] = m; red_l[wid] = l; }
   if (g == 0) {
 #pragma unroll
@@ -1577,31 +1787,50 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void attn_decode_kernel(bf16_t* qkv
     float M = red_m[0];
 #pragma unroll
     for (int w = 1; w < DEC_WAVES; ++w) M = fmaxf(M, red_m[w]);
-    float L = 0.f, a0 = 0.f, a1 = 0.f;
+    float L = 0.f, a0 = 0.f, a1 = 0.f;         // head dim 128: lane owns dims 2 lane, 2 lane + 1; head dim 64: dim lane (a0 alone)
 #pragma unroll
     for (int w = 0; w < DEC_WAVES; ++w) {      // fixed order: deterministic
       const float sc = __expf(red_m[w] - M);
       L += red_l[w] * sc;
-      a0 += oacc[w][2 * lane] * sc;
-      a1 += oacc[w][2 * lane + 1] * sc;
+      if constexpr (HEAD_DIM == 128) {
+        a0 += oacc[w][2 * lane] * sc;
+        a1 += oacc[w][2 * lane + 1] * sc;
+      } else {
+        a0 += oacc[w][lane] * sc;
+      }
     }
-    const float inv = 1.f / L;
-    *(unsigned*)(o + (int64_t)b * d + hh * HD + 2 * lane) = pack2bf(a0 * inv, a1 * inv);
+    if constexpr (HEAD_DIM == 128) {
+      const float inv = 1.f / L;
+      *(unsigned*)(o + (int64_t)b * d + hh * HEAD_DIM + 2 * lane) = pack2bf(a0 * inv, a1 * inv);
+    } else {
+      o[(int64_t)b * d + hh * HEAD_DIM + lane] = f2bf(a0 / L);
+    }
   }
+}
+
+// the three decode entry points: one set of checks, one launch (plan != nullptr: the masked instance, head dim 128 only -- amp_route)
+static int attn_decode_launch(const char* name, uint16_t* qkv, const uint16_t* fresh, uint16_t* o, const int* plan, int B, int H, int S,
+                              int pos, const int* pos_dev, int head_dim, void* stream) {
+  DMI_REQUIRE(qkv && o, "%s: null pointer", name);
+  DMI_REQUIRE(B > 0 && H > 0 && S > 0, "%s: bad shape", name);
+  DMI_REQUIRE(pos_dev || (pos >= 0 && pos < S), "%s: need 0 <= pos < S (pos=%d, S=%d)", name, pos, S);
+  const dim3 grid((unsigned)(B * H)), block(64 * DEC_WAVES);
+  hipStream_t st = (hipStream_t)stream;
+  if (plan) attn_decode_kernel<128, true, const int*><<<grid, block, 0, st>>>(qkv, fresh, o, plan, H, S, pos, pos_dev);
+  else if (head_dim == 64) attn_decode_kernel<64, false><<<grid, block, 0, st>>>(qkv, fresh, o, H, S, pos, pos_dev);
+  else attn_decode_kernel<128, false><<<grid, block, 0, st>>>(qkv, fresh, o, H, S, pos, pos_dev);
+  DMI_CHECK_LAUNCH(name);
+  return DMI_OK;
 }
 
 extern "C" int dmi_attention_decode(uint16_t* qkv, const uint16_t* fresh, uint16_t* o, int B, int H, int S, int pos, const int* pos_dev,
                                     void* stream) {
-  DMI_REQUIRE(qkv && o, "attention_decode: null pointer");
-  DMI_REQUIRE(B > 0 && H > 0 && S > 0, "attention_decode: bad shape");
-  DMI_REQUIRE(pos_dev || (pos >= 0 && pos < S), "attention_decode: need 0 <= pos < S (pos=%d, S=%d)", pos, S);
-  attn_decode_kernel<<<dim3((unsigned)(B * H)), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream>>>(qkv, fresh, o, H, S, pos, pos_dev);
-  DMI_CHECK_LAUNCH("attention_decode");
-  return DMI_OK;
+  return attn_decode_launch("attention_decode", qkv, fresh, o, nullptr, B, H, S, pos, pos_dev, 128, stream);
 }
 
 // =====================================================================================
-// head dim 64 (n_embd / n_heads = 64): the same four operations, semantics and buffer layouts as the kernels above
+// head dim 64 (n_embd / n_heads = 64): forward, dQ and dK/dV with the semantics and buffer layouts of the kernels above
+// (decode: attn_decode_kernel<64, false>)
 // =====================================================================================
 // The operand roles are those of the 128 kernels (softmax row = lane, reduction index in the accumulator registers, P / dS straight
 // from registers into the next MFMA, every transposed fragment a ds_read_b64_tr_b16 of a natural tile); what changes is the width:
@@ -2091,116 +2320,7 @@ __global__ __launch_bounds__(256, A64_DKV_WAVES) void attn64_bwd_dkv_kernel(cons
   }   // items
 }
 
-// ---- decode: one query position against the K/V cache, the contract of attn_decode_kernel.  Lane (c = lane & 7, g = lane >> 3) owns
-// head dims [8c, 8c + 8) and, per 64-key chunk, keys 8i + g (i = 0..7): a load instruction fetches eight whole 128-B rows; the eight partial
-// dot products per lane are combined over the 8 lanes of a group by a reduce-scatter (7 exchanges): lane (c, g) ends with key 8c + g.
-__global__ __launch_bounds__(64 * DEC_WAVES) void attn64_decode_kernel(bf16_t* qkv, const bf16_t* __restrict__ fresh, bf16_t* __restrict__ o,
-                                                                       int H, int S, int pos_arg, const int* __restrict__ pos_dev) {
-  __shared__ float ps[DEC_WAVES][64];
-  __shared__ float red_m[DEC_WAVES], red_l[DEC_WAVES];
-  __shared__ float oacc[DEC_WAVES][HD64];
-  const int bh = blockIdx.x, b = bh / H, hh = bh % H;
-  const int d = H * HD64;
-  const int64_t ld3 = 3 * (int64_t)d;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int c = lane & 7, g = lane >> 3;
-  const int pos = pos_dev ? *pos_dev : pos_arg;
-  if (pos < 0 || pos >= S) return;                     // (block-uniform; the host checks the by-value form)
-  bf16_t* base = qkv + (int64_t)b * S * ld3 + hh * HD64;
-  const bf16_t* fr = fresh ? fresh + (int64_t)b * ld3 + hh * HD64 : nullptr;
-  float q[8];
-  unpack8(*(const u32x4*)((fr ? fr : base + (int64_t)pos * ld3) + 8 * c), q);
-  if (fr && threadIdx.x < 3 * HD64 / 8) {   // q | k | v of this head: 3 x 128 B -> cache row pos (read back by no one in this launch)
-    const int part = threadIdx.x / (HD64 / 8), ch = threadIdx.x % (HD64 / 8);
-    *(u32x4*)(base + (int64_t)pos * ld3 + part * d + ch * 8) = *(const u32x4*)(fr + part * d + ch * 8);
-  }
-  float m = -1e30f, l = 0.f;
-  float oa[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int ch0 = wid; ch0 * 64 <= pos; ch0 += DEC_WAVES) {
-    const int k0 = ch0 * 64;
-    auto row_ptr = [&](int i, int which) -> const u32x4* {   // key k0 + 8i + g, clamped to pos; row pos comes from the staging buffer
-      int key = k0 + 8 * i + g;
-      key = key < pos ? key : pos;
-      return (const u32x4*)((fr && key == pos) ? fr + which * d + 8 * c : base + which * d + (int64_t)key * ld3 + 8 * c);
-    };
-    u32x4 raw[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) raw[i] = *row_ptr(i, 1);
-    float p[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float f[8];
-      unpack8(raw[i], f);
-      float t = 0.f;
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) t = __builtin_fmaf(f[jj], q[jj], t);
-      p[i] = t;
-    }
-    // reduce-scatter over the 8 lanes of a group: after the stage with mask w, a lane keeps the half of its values whose index has
-    // bit w equal to its own bit w of c
-#pragma unroll
-    for (int w = 4; w >= 1; w >>= 1) {
-      const bool up = (c & w) != 0;
-#pragma unroll
-      for (int jj = 0; jj < w; ++jj) {
-        const float send = up ? p[jj] : p[jj + w];
-        const float keep = up ? p[jj + w] : p[jj];
-        p[jj] = keep + __shfl_xor(send, w, 64);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) raw[i] = *row_ptr(i, 2);     // value rows requested before the softmax' wave reductions
-    const int key = k0 + 8 * c + g;
-    const bool valid = key <= pos;
-    const float sc = valid ? p[0] : -1e30f;
-    const float mn = fmaxf(m, wave_max(sc));
-    const float alpha = __expf(m - mn);
-    const float pe = valid ? __expf(sc - mn) : 0.f;
-    l = l * alpha + wave_sum(pe);
-    m = mn;
-    ps[wid][8 * c + g] = bf2f(f2bf(pe));
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // wave-private strip: in-order LDS, no block barrier needed
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj) oa[jj] *= alpha;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float f[8];
-      unpack8(raw[i], f);
-      const float pj = ps[wid][8 * i + g];               // 0 for keys past pos (their rows were clamped to row pos)
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) oa[jj] = __builtin_fmaf(pj, f[jj], oa[jj]);
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) {                        // the eight lane groups hold disjoint key subsets of the same dims
-    oa[jj] += __shfl_xor(oa[jj], 8, 64);
-    oa[jj] += __shfl_xor(oa[jj], 16, 64);
-    oa[jj] += __shfl_xor(oa[jj], 32, 64);
-  }
-  if (lane == 0) { red_m[wid] = m; red_l[wid] = l; }
-  if (g == 0) {
-#pragma unroll
-    for (int jj = 0; jj < 8; ++jj) oacc[wid][8 * c + jj] = oa[jj];
-  }
-  __syncthreads();
-  if (wid == 0) {
-    float M = red_m[0];
-#pragma unroll
-    for (int w = 1; w < DEC_WAVES; ++w) M = fmaxf(M, red_m[w]);
-    float L = 0.f, a = 0.f;
-#pragma unroll
-    for (int w = 0; w < DEC_WAVES; ++w) {      // fixed order: deterministic
-      const float sc = __expf(red_m[w] - M);
-      L += red_l[w] * sc;
-      a += oacc[w][lane] * sc;
-    }
-    o[(int64_t)b * d + hh * HD64 + lane] = f2bf(a / L);
-  }
-}
-
-// ---- C ABI with a head-dim argument: 128 -> the calls above, 64 -> the kernels of this section
+// ---- C ABI with a head-dim argument: 128 -> the calls above, 64 -> the kernels of this section (decode: the <64, false> instance)
 #define A64_HEAD_DIM_CHECK(name)                                                                             \
   do {                                                                                                       \
     if (head_dim != 64 && head_dim != 128) {                                                                 \
@@ -2256,409 +2376,15 @@ extern "C" int dmi_attention_bwd_hd(const uint16_t* qkv, const uint16_t* o, cons
 extern "C" int dmi_attention_decode_hd(uint16_t* qkv, const uint16_t* fresh, uint16_t* o, int B, int H, int S, int pos, const int* pos_dev,
                                        int head_dim, void* stream) {
   A64_HEAD_DIM_CHECK("attention_decode");
-  if (head_dim == 128) return dmi_attention_decode(qkv, fresh, o, B, H, S, pos, pos_dev, stream);
-  DMI_REQUIRE(qkv && o, "attention_decode: null pointer");
-  DMI_REQUIRE(B > 0 && H > 0 && S > 0, "attention_decode: bad shape");
-  DMI_REQUIRE(pos_dev || (pos >= 0 && pos < S), "attention_decode: need 0 <= pos < S (pos=%d, S=%d)", pos, S);
-  attn64_decode_kernel<<<dim3((unsigned)(B * H)), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream>>>((bf16_t*)qkv, (const bf16_t*)fresh,
-                                                                                                   (bf16_t*)o, H, S, pos, pos_dev);
-  DMI_CHECK_LAUNCH("attention_decode");
-  return DMI_OK;
+  return attn_decode_launch("attention_decode", qkv, fresh, o, nullptr, B, H, S, pos, pos_dev, head_dim, stream);
 }
 
 // =====================================================================================
-// custom attention masks, head dim 128: block-sparse forms of the forward, dQ, dK/dV and decode kernels
+// custom attention masks, head dim 128: the masked dK/dV kernel, the plan builder and the C ABI
 // =====================================================================================
-// A mask is a boolean [S, S] matrix M (M[i][j]: query i may attend to key j), causal and with no empty row; where M is false the
-// probability is exactly 0.  dmi_attn_mask_plan compiles it on the host into a plan of int32 words (DESIGN.md §4 "Attention masks"):
-//   header (AMP_HDR words)  magic, S, NB = ceil(S/128), W = ceil(S/32), causal flag, word offsets of the sections below, tile counts;
-//   forward / dQ lists      per 128-query block (CSR: NB + 1 pointers, then entries): its live 64-key tiles in key order, entry =
-//                           tile | (class of each wave's 32 x 64 sub-tile << 16 + 2 wave), class 0 empty (the wave skips the tile),
-//                           1 full (no predicate), 2 partial (the row bitmap is applied with a select: masked scores are -inf);
-//   dK/dV lists             per 128-key block: its live 32-query tiles in query order, entry = tile | (partial << 16);
-//   two work orders         the blocks of each kind sorted by their number of live tiles, heaviest first -- the persistent kernels
-//                           deal (order position, batch * head) items in the serpentine of attn_sched / attn_item, as the causal
-//                           kernels deal their 40, 36, ..., 4-step tiles;
-//   row bitmap [S][W]       bit b of word w of row i = M[i][32 w + b] (partial forward / dQ tiles, the decode row of `pos`);
-//   column bitmap [S][W]    bit b of word w of row j = M[32 w + b][j] (partial dK/dV tiles).
-// A tile no query of a block attends to is never loaded.  Bits of keys >= S are 0, so a tile that reaches past S is partial.
-// The kernels below keep the buffer layouts, the unscaled fp32 softmax, the tile shapes and the persistent schedule of the causal
-// kernels; the causal kernels themselves are unchanged (a causal plan is routed to them unless the option attn_mask_force is set).
-#define AMP_MAGIC 0x504d4144
-#define AMP_HDR 32
-enum {
-  AMP_S = 1, AMP_NB, AMP_W, AMP_CAUSAL, AMP_FPTR, AMP_FLIST, AMP_KPTR, AMP_KLIST, AMP_FORDER, AMP_KORDER, AMP_ROWBITS, AMP_COLBITS,
-  AMP_WORDS, AMP_LIVE_F, AMP_CAUSAL_F, AMP_LIVE_K, AMP_CAUSAL_K
-};
+// The plan format and the masked instances of the forward, dQ and decode kernels: "attention-mask plans" at the top of this file.
+// A causal plan is routed to the causal entry points (so to the default kernels) unless the option attn_mask_force is set.
 extern int g_opt_attn_mask_force;   // 1: a causal plan runs the masked kernels too (tests, tools/attn_mask_bench.py)
-
-// ---- forward: attn_fwd_kernel (the round-2 program-order form, not the default software-pipelined attn_fwd2_kernel) walking a
-// block's live key tiles.  Built for two waves per SIMD.
-__global__ __launch_bounds__(256, 2) void attn_fwd_masked_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o,
-                                                                 float* __restrict__ lse, const int* __restrict__ plan, int B, int H,
-                                                                 int S, int perxcd) {
-  extern __shared__ __attribute__((aligned(16))) char sm[];  // 2 x QK_STAGE
-  const int d = H * HD, ld3 = 3 * d;
-  const int T = plan[AMP_NB], W = plan[AMP_W];
-  const int* __restrict__ fptr = plan + plan[AMP_FPTR];
-  const int* __restrict__ flist = plan + plan[AMP_FLIST];
-  const int* __restrict__ forder = plan + plan[AMP_FORDER];
-  const unsigned* __restrict__ rowbits = (const unsigned*)(plan + plan[AMP_ROWBITS]);
-  const AttnSched sched = attn_sched(T, B * H, perxcd);
-  int tile_, bh;
-  for (int round = 0; attn_item(sched, round, tile_, bh); ++round) {
-  const int qt = forder[tile_];   // heaviest query blocks first
-  const int* __restrict__ list = flist + fptr[qt];
-  const int nsteps = fptr[qt + 1] - fptr[qt];
-  const int b = bh / H, hh = bh % H;
-  const int q0 = qt * 128;
-  int tid = threadIdx.x;
-  asm volatile("" : "+v"(tid));
-  const int lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, h = lane >> 5, g4 = lane >> 4, l16 = lane & 15;
-  const int qrow = q0 + wid * 32 + r;
-  const int qrow_c = qrow < S ? qrow : S - 1;
-  const unsigned* __restrict__ mrow = rowbits + (int64_t)qrow_c * W;
-  const bf16_t* qb = qkv + (int64_t)b * S * ld3 + hh * HD;
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
-  const int nbytes = (int)(((int64_t)(S - 1) * ld3 + HD) * 2);
-  const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)(qb + d), 0, nbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)(qb + 2 * d), 0, nbytes, 0x00020000);
-
-  bf16x8 qf[8];
-#pragma unroll
-  for (int kk = 0; kk < 8; ++kk) qf[kk] = *(const bf16x8*)(qb + (int64_t)qrow_c * ld3 + 16 * kk + 8 * h);
-
-  int vo[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = tid + 256 * i, row = c >> 4, pc = c & 15;
-    vo[i] = (row * ld3 + 8 * (pc ^ swz(row))) * 2;
-  }
-  auto stage = [&](int st, int key0) {
-    char* base = sm + st * QK_STAGE;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      dma16(rk, base + (wid * 64 + 256 * i) * 16, vo[i] + key0 * ld3 * 2);
-      dma16(rv, base + 16384 + (wid * 64 + 256 * i) * 16, vo[i] + key0 * ld3 * 2);
-    }
-  };
-  int ofa[8];
-#pragma unroll
-  for (int kk = 0; kk < 8; ++kk) ofa[kk] = r * 256 + (((2 * kk + h) ^ swz(r)) << 4);
-  const int rr = l16 >> 2;
-  unsigned oft[4][2];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int w2 = 0; w2 < 2; ++w2) {
-      const int row = 4 * h + rr + 8 * w2;
-      const int chunk = dt * 4 + 2 * (g4 & 1) + ((l16 & 3) >> 1);
-      oft[dt][w2] = row * 256 + ((chunk ^ swz(row)) << 4) + 8 * (l16 & 1);
-    }
-
-  f32x16 oacc[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) oacc[i][e] = 0.f;
-  float m = -1e30f, l = 0.f;
-
-  // row bits of a partial tile: keys 64 j + 0..31 and + 32..63 of this lane's query row (words past the row read as 0)
-  auto bits = [&](int ent, unsigned& b0, unsigned& b1) {
-    const int j = ent & 0xffff;
-    b0 = b1 = 0xffffffffu;
-    if (((ent >> (16 + 2 * wid)) & 3) == 2) {
-      b0 = mrow[2 * j];
-      b1 = 2 * j + 1 < W ? mrow[2 * j + 1] : 0u;
-    }
-  };
-  auto compute = [&](int st, int ent, unsigned b0, unsigned b1) {
-    const int cls = (ent >> (16 + 2 * wid)) & 3;
-    if (cls == 0) return;  // wave-uniform: no query row of this wave attends to the tile
-    const char* base = sm + st * QK_STAGE;
-    const unsigned vb = lds0 + st * QK_STAGE + 16384;
-    f32x16 s0, s1;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) s0[e] = s1[e] = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-      const bf16x8 a0 = *(const bf16x8*)(base + ofa[kk]);
-      const bf16x8 a1 = *(const bf16x8*)(base + 8192 + ofa[kk]);
-      s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, qf[kk], s0, 0, 0, 0);  // S^T[key][q]
-      s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, qf[kk], s1, 0, 0, 0);
-    }
-    Tr4 tv[2];
-    tr4_issue(tv[0], vb + oft[0][0], vb + oft[0][1], vb + oft[1][0], vb + oft[1][1], vb + oft[2][0], vb + oft[2][1], vb + oft[3][0], vb + oft[3][1]);
-    if (cls == 2) {  // partial tile: select, so masked scores are -inf (probability exactly 0, never NaN)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int kb = (e & 3) + 8 * (e >> 2) + 4 * h;
-        s0[e] = ((b0 >> kb) & 1u) ? s0[e] : -INFINITY;
-        s1[e] = ((b1 >> kb) & 1u) ? s1[e] : -INFINITY;
-      }
-    }
-    float mx = -1e30f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) mx = fmaxf(mx, fmaxf(s0[e], s1[e]));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    if (__any(mx > m)) {
-      const float mn = fmaxf(m, mx);
-      const float alpha = __builtin_amdgcn_exp2f((m - mn) * LOG2E_F);
-      m = mn;
-      l *= alpha;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) oacc[i][e] *= alpha;
-    }
-    const float m2 = m * LOG2E_F;
-    float rs = 0.f;
-    bf16x8 pb[4];
-    {
-      float pe[16];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        pe[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[e], LOG2E_F, -m2));
-        rs += pe[e];
-      }
-      pb[0] = pack_bf8(pe);
-      pb[1] = pack_bf8(pe + 8);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        pe[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[e], LOG2E_F, -m2));
-        rs += pe[e];
-      }
-      pb[2] = pack_bf8(pe);
-      pb[3] = pack_bf8(pe + 8);
-    }
-    l += rs;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      Tr4& c = tv[ks & 1];
-      tr4_wait(c);
-      if (ks < 3) {
-        const unsigned o2 = vb + (ks + 1) * 4096;
-        tr4_issue(tv[(ks + 1) & 1], o2 + oft[0][0], o2 + oft[0][1], o2 + oft[1][0], o2 + oft[1][1], o2 + oft[2][0], o2 + oft[2][1], o2 + oft[3][0], o2 + oft[3][1]);
-      }
-      oacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.a0, c.a1), pb[ks], oacc[0], 0, 0, 0);  // O^T[d][q]
-      oacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.b0, c.b1), pb[ks], oacc[1], 0, 0, 0);
-      oacc[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.c0, c.c1), pb[ks], oacc[2], 0, 0, 0);
-      oacc[3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.d0, c.d1), pb[ks], oacc[3], 0, 0, 0);
-    }
-  };
-
-  // The row-bit loads of step i are issued ahead of the DMA of step i + 1, but hipcc's wait for them is a vmcnt(0): on a partial
-  // tile the select, softmax and P.V wait for the next tile's DMA too (measured cost: DESIGN.md §4 "Attention masks").
-  if (nsteps > 0) stage(0, 64 * (list[0] & 0xffff));
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  for (int i = 0; i < nsteps; ++i) {
-    const int ent = list[i];
-    unsigned b0, b1;
-    bits(ent, b0, b1);
-    if (i + 1 < nsteps) stage((i + 1) & 1, 64 * (list[i + 1] & 0xffff));
-    compute(i & 1, ent, b0, b1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-
-  l += __shfl_xor(l, 32, 64);
-  if (qrow < S) {
-    const float inv = 1.f / l;
-    bf16_t* op = o + ((int64_t)b * S + qrow) * d + hh * HD;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const int dd = dt * 32 + 8 * q4 + 4 * h;
-        *(u32x2*)(op + dd) = u32x2{pack2bf(oacc[dt][4 * q4] * inv, oacc[dt][4 * q4 + 1] * inv),
-                                   pack2bf(oacc[dt][4 * q4 + 2] * inv, oacc[dt][4 * q4 + 3] * inv)};
-      }
-    if (h == 0) lse[(int64_t)bh * S + qrow] = m + __logf(l);
-  }
-  __syncthreads();
-  }   // items
-}
-
-// ---- dQ (+ delta and the (lse, delta) pairs): attn_bwd_dq_kernel<1> walking a block's live key tiles.  Two waves per SIMD.
-__global__ __launch_bounds__(256, 2) void attn_bwd_dq_masked_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
-                                                                    const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
-                                                                    float* __restrict__ delta, float* __restrict__ stats,
-                                                                    bf16_t* __restrict__ dqkv, const int* __restrict__ plan, int B, int H,
-                                                                    int S, int perxcd) {
-  extern __shared__ __attribute__((aligned(16))) char sm[];  // 2 x QK_STAGE
-  const int d = H * HD, ld3 = 3 * d;
-  const int T = plan[AMP_NB], W = plan[AMP_W];
-  const int* __restrict__ fptr = plan + plan[AMP_FPTR];
-  const int* __restrict__ flist = plan + plan[AMP_FLIST];
-  const int* __restrict__ forder = plan + plan[AMP_FORDER];
-  const unsigned* __restrict__ rowbits = (const unsigned*)(plan + plan[AMP_ROWBITS]);
-  const AttnSched sched = attn_sched(T, B * H, perxcd);
-  int tile_, bh;
-  for (int round = 0; attn_item(sched, round, tile_, bh); ++round) {
-  const int qt = forder[tile_];
-  const int* __restrict__ list = flist + fptr[qt];
-  const int nsteps = fptr[qt + 1] - fptr[qt];
-  const int b = bh / H, hh = bh % H;
-  const int q0 = qt * 128;
-  int tid = threadIdx.x;
-  asm volatile("" : "+v"(tid));
-  const int lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, h = lane >> 5, g4 = lane >> 4, l16 = lane & 15;
-  const int qrow = q0 + wid * 32 + r;
-  const int qrow_c = qrow < S ? qrow : S - 1;
-  const unsigned* __restrict__ mrow = rowbits + (int64_t)qrow_c * W;
-  const bf16_t* qb = qkv + (int64_t)b * S * ld3 + hh * HD;
-  const bf16_t* dob = d_o + (int64_t)b * S * d + hh * HD;
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
-  const int nbytes = (int)(((int64_t)(S - 1) * ld3 + HD) * 2);
-  const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc((void*)(qb + d), 0, nbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)(qb + 2 * d), 0, nbytes, 0x00020000);
-
-  bf16x8 qf[8], dof[8], of_[8];
-#pragma unroll
-  for (int kk = 0; kk < 8; ++kk) {
-    qf[kk] = *(const bf16x8*)(qb + (int64_t)qrow_c * ld3 + 16 * kk + 8 * h);
-    dof[kk] = *(const bf16x8*)(dob + (int64_t)qrow_c * d + 16 * kk + 8 * h);
-    of_[kk] = *(const bf16x8*)(o + ((int64_t)b * S + qrow_c) * d + hh * HD + 16 * kk + 8 * h);
-  }
-  const float lse_q = lse[(int64_t)bh * S + qrow_c];
-  const float lse2_q = lse_q * LOG2E_F;
-  float delta_q = 0.f;
-  {
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-      float fo[8], fd[8];
-      unpack8(__builtin_bit_cast(u32x4, of_[kk]), fo);
-      unpack8(__builtin_bit_cast(u32x4, dof[kk]), fd);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) delta_q += fo[j] * fd[j];
-    }
-    delta_q += __shfl_xor(delta_q, 32, 64);
-    if (h == 0 && qrow < S) {
-      const int64_t idx = (int64_t)bh * S + qrow;
-      delta[idx] = delta_q;
-      stats[2 * idx] = lse2_q;
-      stats[2 * idx + 1] = delta_q;
-    }
-  }
-
-  int vo[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = tid + 256 * i, row = c >> 4, pc = c & 15;
-    vo[i] = (row * ld3 + 8 * (pc ^ swz(row))) * 2;
-  }
-  auto stage = [&](int st, int key0) {
-    char* base = sm + st * QK_STAGE;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      dma16(rk, base + (wid * 64 + 256 * i) * 16, vo[i] + key0 * ld3 * 2);
-      dma16(rv, base + 16384 + (wid * 64 + 256 * i) * 16, vo[i] + key0 * ld3 * 2);
-    }
-  };
-  int ofa[8];
-#pragma unroll
-  for (int kk = 0; kk < 8; ++kk) ofa[kk] = r * 256 + (((2 * kk + h) ^ swz(r)) << 4);
-  const int rr = l16 >> 2;
-  unsigned oft0[2];
-#pragma unroll
-  for (int w2 = 0; w2 < 2; ++w2) {
-    const int row = 4 * h + rr + 8 * w2;
-    const int chunk = 2 * (g4 & 1) + ((l16 & 3) >> 1);
-    oft0[w2] = row * 256 + ((chunk ^ swz(row)) << 4) + 8 * (l16 & 1);
-  }
-
-  f32x16 dq[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) dq[i][e] = 0.f;
-
-  auto bits = [&](int ent, unsigned& b0, unsigned& b1) {
-    const int j = ent & 0xffff;
-    b0 = b1 = 0xffffffffu;
-    if (((ent >> (16 + 2 * wid)) & 3) == 2) {
-      b0 = mrow[2 * j];
-      b1 = 2 * j + 1 < W ? mrow[2 * j + 1] : 0u;
-    }
-  };
-  auto compute = [&](int st, int ent, unsigned b0, unsigned b1) {
-    const int cls = (ent >> (16 + 2 * wid)) & 3;
-    if (cls == 0) return;
-    const char* base = sm + st * QK_STAGE;
-#pragma unroll
-    for (int kt2 = 0; kt2 < 2; ++kt2) {
-      f32x16 s, dp;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) s[e] = dp[e] = 0.f;
-#pragma unroll
-      for (int kk = 0; kk < 8; ++kk) {
-        const bf16x8 ka = *(const bf16x8*)(base + kt2 * 8192 + ofa[kk]);
-        const bf16x8 va = *(const bf16x8*)(base + 16384 + kt2 * 8192 + ofa[kk]);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qf[kk], s, 0, 0, 0);     // S^T[key][q]
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, dof[kk], dp, 0, 0, 0);  // dP^T[key][q]
-      }
-      Tr2 tk[2];
-      unsigned ob = st * QK_STAGE + kt2 * 8192;
-      asm volatile("" : "+v"(ob));
-      const unsigned t0 = ob + oft0[0], t1 = ob + oft0[1];
-      tr2_issue(tk[0], lds0 + t0, lds0 + t1, lds0 + (t0 ^ 64u), lds0 + (t1 ^ 64u));
-      float ds[16];
-      if (cls == 2) {   // partial tile: masked scores -> exp2(-inf) = 0 by a select
-        const unsigned mb = kt2 ? b1 : b0;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int kb = (e & 3) + 8 * (e >> 2) + 4 * h;
-          const float pe = __builtin_amdgcn_exp2f(((mb >> kb) & 1u) ? __builtin_fmaf(s[e], LOG2E_F, -lse2_q) : -INFINITY);
-          ds[e] = pe * (dp[e] - delta_q);
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const float pe = __builtin_amdgcn_exp2f(__builtin_fmaf(s[e], LOG2E_F, -lse2_q));
-          ds[e] = pe * (dp[e] - delta_q);
-        }
-      }
-      bf16x8 dsb[2];
-      dsb[0] = pack_bf8(ds);
-      dsb[1] = pack_bf8(ds + 8);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int s2 = q >> 1, dp2 = (q & 1) * 2;
-        Tr2& c = tk[q & 1];
-        tr2_wait(c);
-        if (q < 3) {
-          const int s2n = (q + 1) >> 1, dn = ((q + 1) & 1) * 2;
-          const unsigned u0 = t0 + s2n * 4096, u1 = t1 + s2n * 4096;
-          tr2_issue(tk[(q + 1) & 1], lds0 + (u0 ^ (dn << 6)), lds0 + (u1 ^ (dn << 6)), lds0 + (u0 ^ ((dn + 1) << 6)), lds0 + (u1 ^ ((dn + 1) << 6)));
-        }
-        dq[dp2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.a0, c.a1), dsb[s2], dq[dp2], 0, 0, 0);          // dQ^T[d][q]
-        dq[dp2 + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(c.b0, c.b1), dsb[s2], dq[dp2 + 1], 0, 0, 0);
-      }
-    }
-  };
-
-  if (nsteps > 0) stage(0, 64 * (list[0] & 0xffff));
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  for (int i = 0; i < nsteps; ++i) {
-    const int ent = list[i];
-    unsigned b0, b1;
-    bits(ent, b0, b1);
-    if (i + 1 < nsteps) stage((i + 1) & 1, 64 * (list[i + 1] & 0xffff));
-    compute(i & 1, ent, b0, b1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  // whole-row stores through a wave-private LDS strip (the loop ended with a barrier: the last tile's readers are done)
-  store_rows_via_lds(sm + wid * (32 * ROWS_PITCH), dq, 1.0f, dqkv + ((int64_t)b * S + q0 + wid * 32) * ld3 + hh * HD, ld3, S - (q0 + wid * 32), lane);
-  __syncthreads();
-  }   // items
-}
 
 // ---- dK/dV: attn_bwd_dkv_kernel<1> (the software-pipelined 4-slot ring) walking a key block's live 32-query tiles.  Every tile
 // applies the column bitmap word of this lane's key (bit = query row within the tile) with a select; a full tile takes an all-ones
@@ -2883,12 +2609,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_masked_kernel(const bf16_
     }
   };
 
-#define DKV_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define DKV_BARRIER()                                  \
-  do {                                                 \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-    __builtin_amdgcn_s_barrier();                      \
-  } while (0)
   if (nsteps > 0) stage(0, 32 * (list[0] & 0xffff));
   if (nsteps > 1) stage(1, 32 * (list[1] & 0xffff));
   if (nsteps > 2) stage(2, 32 * (list[2] & 0xffff));
@@ -2916,8 +2636,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_masked_kernel(const bf16_
     DKVM_STEP(sA, dpA, sB, dpB, false)
   }
 #undef DKVM_STEP
-#undef DKV_WAIT
-#undef DKV_BARRIER
 
   bf16_t* gk = dqkv + ((int64_t)b * S + key0 + wid * 32) * ld3 + d + hh * HD;
   char* strip = sm + wid * (2 * 32 * ROWS_PITCH);
@@ -2925,119 +2643,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_masked_kernel(const bf16_
   store_rows_via_lds(strip + 32 * ROWS_PITCH, dv, 1.0f, gk + d, ld3, S - (key0 + wid * 32), lane);
   __syncthreads();
   }   // items
-}
-
-// ---- decode: attn_decode_kernel reading row `pos` of the row bitmap (pos from pos_dev on the graph-replayable path, so one
-// captured graph serves every position).  A 64-key chunk whose two mask words are 0 is skipped (no loads); masked keys of a
-// chunk get probability exactly 0.
-__global__ __launch_bounds__(64 * DEC_WAVES) void attn_decode_masked_kernel(bf16_t* qkv, const bf16_t* __restrict__ fresh, bf16_t* __restrict__ o,
-                                                                            const int* __restrict__ plan, int H, int S, int pos_arg,
-                                                                            const int* __restrict__ pos_dev) {
-  __shared__ float ps[DEC_WAVES][64];
-  __shared__ float red_m[DEC_WAVES], red_l[DEC_WAVES];
-  __shared__ float oacc[DEC_WAVES][HD];
-  const int bh = blockIdx.x, b = bh / H, hh = bh % H;
-  const int d = H * HD;
-  const int64_t ld3 = 3 * (int64_t)d;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int c = lane & 15, g = lane >> 4;
-  const int pos = pos_dev ? *pos_dev : pos_arg;
-  if (pos < 0 || pos >= S) return;
-  const int W = plan[AMP_W];
-  const unsigned* __restrict__ mrow = (const unsigned*)(plan + plan[AMP_ROWBITS]) + (int64_t)pos * W;
-  bf16_t* base = qkv + (int64_t)b * S * ld3 + hh * HD;
-  const bf16_t* fr = fresh ? fresh + (int64_t)b * ld3 + hh * HD : nullptr;
-  float q[8];
-  unpack8(*(const u32x4*)((fr ? fr : base + (int64_t)pos * ld3) + 8 * c), q);
-  if (fr && threadIdx.x < 3 * HD / 8) {
-    const int part = threadIdx.x / (HD / 8), ch = threadIdx.x % (HD / 8);
-    *(u32x4*)(base + (int64_t)pos * ld3 + part * d + ch * 8) = *(const u32x4*)(fr + part * d + ch * 8);
-  }
-  float m = -1e30f, l = 0.f;
-  float oa[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int ch0 = wid; ch0 * 64 <= pos; ch0 += DEC_WAVES) {
-    const unsigned w0 = mrow[2 * ch0], w1 = 2 * ch0 + 1 < W ? mrow[2 * ch0 + 1] : 0u;
-    if ((w0 | w1) == 0u) continue;                       // (wave-uniform) nothing of this chunk is attended to
-    const int k0 = ch0 * 64;
-    auto row_ptr = [&](int i, int which) -> const u32x4* {
-      int key = k0 + 4 * i + g;
-      key = key < pos ? key : pos;
-      return (const u32x4*)((fr && key == pos) ? fr + which * d + 8 * c : base + which * d + (int64_t)key * ld3 + 8 * c);
-    };
-    u32x4 raw[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) raw[i] = *row_ptr(i, 1);
-    float p[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      float f[8];
-      unpack8(raw[i], f);
-      float t = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) t = __builtin_fmaf(f[j], q[j], t);
-      p[i] = t;
-    }
-#pragma unroll
-    for (int w = 8; w >= 1; w >>= 1) {
-      const bool up = (c & w) != 0;
-#pragma unroll
-      for (int j = 0; j < w; ++j) {
-        const float send = up ? p[j] : p[j + w];
-        const float keep = up ? p[j + w] : p[j];
-        p[j] = keep + __shfl_xor(send, w, 64);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) raw[i] = *row_ptr(i, 2);
-    const int kb = 4 * c + g;                              // this lane's key k0 + kb
-    const bool valid = k0 + kb <= pos && (((kb < 32 ? w0 : w1) >> (kb & 31)) & 1u);
-    const float sc = valid ? p[0] : -1e30f;
-    const float mn = fmaxf(m, wave_max(sc));
-    const float alpha = __expf(m - mn);
-    const float pe = valid ? __expf(sc - mn) : 0.f;
-    l = l * alpha + wave_sum(pe);
-    m = mn;
-    ps[wid][4 * c + g] = bf2f(f2bf(pe));
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int j = 0; j < 8; ++j) oa[j] *= alpha;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      float f[8];
-      unpack8(raw[i], f);
-      const float pj = ps[wid][4 * i + g];               // 0 for masked keys and keys past pos
-#pragma unroll
-      for (int j = 0; j < 8; ++j) oa[j] = __builtin_fmaf(pj, f[j], oa[j]);
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    oa[j] += __shfl_xor(oa[j], 16, 64);
-    oa[j] += __shfl_xor(oa[j], 32, 64);
-  }
-  if (lane == 0) { red_m[wid] = m; red_l[wid] = l; }
-  if (g == 0) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) oacc[wid][8 * c + j] = oa[j];
-  }
-  __syncthreads();
-  if (wid == 0) {
-    float M = red_m[0];
-#pragma unroll
-    for (int w = 1; w < DEC_WAVES; ++w) M = fmaxf(M, red_m[w]);
-    float L = 0.f, a0 = 0.f, a1 = 0.f;
-#pragma unroll
-    for (int w = 0; w < DEC_WAVES; ++w) {
-      const float sc = __expf(red_m[w] - M);
-      L += red_l[w] * sc;
-      a0 += oacc[w][2 * lane] * sc;
-      a1 += oacc[w][2 * lane + 1] * sc;
-    }
-    const float inv = 1.f / L;
-    *(unsigned*)(o + (int64_t)b * d + hh * HD + 2 * lane) = pack2bf(a0 * inv, a1 * inv);
-  }
 }
 
 // ---- host: the plan builder and the C ABI of the masked kernels
@@ -3182,14 +2787,14 @@ extern "C" int dmi_attention_fwd_masked(const uint16_t* qkv, uint16_t* o, float*
   DMI_REQUIRE((int64_t)S * 3 * H * HD * 2 < 0x7fffffff, "attention_fwd_masked: sequence too long for 32-bit buffer offsets");
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<true, const int*>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
     attr_done = true;
   }
   const int items = ((S + 127) / 128) * B * H;
   const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();   // two persistent blocks per CU
   const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
-  attn_fwd_masked_kernel<<<dim3(grid), dim3(256), 2 * QK_STAGE, (hipStream_t)stream>>>((const bf16_t*)qkv, (bf16_t*)o, lse, (const int*)plan,
-                                                                                      B, H, S, perxcd);
+  attn_fwd_kernel<true, const int*><<<dim3(grid), dim3(256), 2 * QK_STAGE, (hipStream_t)stream>>>((const bf16_t*)qkv, (bf16_t*)o, lse,
+                                                                                                 (const int*)plan, B, H, S, perxcd);
   DMI_CHECK_LAUNCH("attention_fwd_masked");
   return DMI_OK;
 }
@@ -3208,7 +2813,7 @@ extern "C" int dmi_attention_bwd_masked(const uint16_t* qkv, const uint16_t* o, 
   const int shm = 32768 + DKV_NSTAGE * DKV_STAGE;
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<1, true, const int*>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
     (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
     attr_done = true;
   }
@@ -3216,8 +2821,8 @@ extern "C" int dmi_attention_bwd_masked(const uint16_t* qkv, const uint16_t* o, 
   {
     const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();
     const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
-    attn_bwd_dq_masked_kernel<<<dim3(grid), dim3(256), 2 * QK_STAGE, st>>>((const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o, lse, delta,
-                                                                         stats, (bf16_t*)dqkv, (const int*)plan, B, H, S, perxcd);
+    attn_bwd_dq_kernel<1, true, const int*><<<dim3(grid), dim3(256), 2 * QK_STAGE, st>>>((const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o,
+                                                                                       lse, delta, stats, (bf16_t*)dqkv, (const int*)plan, B, H, S, perxcd);
   }
   DMI_CHECK_LAUNCH("attention_bwd_dq_masked");
   {
@@ -3236,10 +2841,5 @@ extern "C" int dmi_attention_decode_masked(uint16_t* qkv, const uint16_t* fresh,
   const int rt = amp_route(plan, plan_host, S, head_dim, "attention_decode_masked");
   if (rt < 0) return rt;
   if (rt == 1) return dmi_attention_decode_hd(qkv, fresh, o, B, H, S, pos, pos_dev, head_dim, stream);
-  DMI_REQUIRE(B > 0 && H > 0 && S > 0, "attention_decode_masked: bad shape");
-  DMI_REQUIRE(pos_dev || (pos >= 0 && pos < S), "attention_decode_masked: need 0 <= pos < S (pos=%d, S=%d)", pos, S);
-  attn_decode_masked_kernel<<<dim3((unsigned)(B * H)), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream>>>((bf16_t*)qkv, (const bf16_t*)fresh,
-                                                                                                      (bf16_t*)o, (const int*)plan, H, S, pos, pos_dev);
-  DMI_CHECK_LAUNCH("attention_decode_masked");
-  return DMI_OK;
+  return attn_decode_launch("attention_decode_masked", qkv, fresh, o, (const int*)plan, B, H, S, pos, pos_dev, head_dim, stream);
 }

@@ -199,7 +199,8 @@ def test_mask_entry_points_are_declared_exported_and_bound():
     assert dh.get_option("attn_mask_force") == 0
 
 
-MASKED = {"attn_fwd_masked_kernel": 2, "attn_bwd_dq_masked_kernel": 2, "attn_bwd_dkv_masked_kernel": 1, "attn_decode_masked_kernel": 4}
+# the masked instances (MASKED = true, as the symbol spells it) of the forward, dQ and decode templates, and the masked dK/dV kernel
+MASKED = {"attn_fwd_kernelILb1E": 2, "attn_bwd_dq_kernelILi1ELb1E": 2, "attn_bwd_dkv_masked_kernel": 1, "attn_decode_kernelILi128ELb1E": 4}
 
 
 def test_masked_kernels_use_no_scratch_and_reach_their_occupancy():

@@ -100,7 +100,8 @@ def test_head_dim64_kernels_use_no_scratch_and_reach_their_occupancy():
         g = lambda k: int(re.search(k + r": (\d+)", blk).group(1))   # noqa: E731
         usage[blk.split()[0]] = dict(vgpr=g(" VGPRs"), agpr=g("AGPRs"), scratch=g(r"ScratchSize \[bytes/lane\]"),
                                      occupancy=g(r"Occupancy \[waves/SIMD\]"), sgpr_spill=g("SGPRs Spill"), vgpr_spill=g("VGPRs Spill"))
-    mine = {k: v for k, v in usage.items() if "attn64_" in k}
+    # the three tile kernels and the head-dim-64 instance of the decode template (HEAD_DIM = 64, as the symbol spells it)
+    mine = {k: v for k, v in usage.items() if "attn64_" in k or "attn_decode_kernelILi64E" in k}
     assert len(mine) == 4, sorted(mine)
     for k, u in mine.items():
         assert u["scratch"] == 0 and u["vgpr_spill"] == 0 and u["sgpr_spill"] == 0, (k, u)
