@@ -1506,11 +1506,25 @@ __device__ __forceinline__ uint64_t block_sum_u64(uint64_t x, uint64_t* red, int
   __syncthreads();
   return x;
 }
-__global__ __launch_bounds__(256) void sample_tokens_p_kernel(const bf16_t* __restrict__ z, int ldz, const bf16_t* __restrict__ bias, int nv,
-                                                              float inv_temp, int top_k, uint64_t seed, float top_p,
-                                                              const unsigned* __restrict__ params_dev, int pos_arg, int* pos_dev, int advance,
-                                                              int token_offset, int* __restrict__ next_tok, int* __restrict__ out, int out_ld,
-                                                              int out_col0, float* __restrict__ logp) {
+// Classifier-free guidance (GUIDED): z holds 2 * Bc rows, the conditional ones first; block b draws for the pair (b, Bc + b) from
+//   zc = z[b] + bias, zu = z[Bc + b] + bias, g = zc + (scale - 1) * (zc - zu)  -- difference, product and sum each rounded to
+//   fp32 on their own (no fused multiply-add: a numpy float32 restatement gives the same bits); scale - 1 == 0 takes g = zc itself,
+//   so that scale 1 is the unguided draw on the conditional rows whatever the unconditional ones hold;
+//   v = g * (1/temperature), and from there on everything is the nucleus draw above, the noise hashed with the pair index b;
+//   next_tok[b] = next_tok[Bc + b] (both halves of the KV cache are fed the drawn token), out has Bc rows, and logp scores the
+//   choice under the conditional row alone: log softmax(zc)[c], the model's own likelihood, comparable across guidance scales.
+// The body is shared: the unguided instance compiles to the kernel it was before the guided one existed.
+__device__ __forceinline__ float guided_logit(float zc, float zu, float sm1) {
+#pragma clang fp contract(off)
+  const float d = zc - zu;
+  const float t = sm1 * d;
+  return sm1 == 0.f ? zc : zc + t;
+}
+template <bool GUIDED>
+__device__ __forceinline__ void nucleus_draw(const bf16_t* __restrict__ z, int ldz, const bf16_t* __restrict__ bias, int nv, float inv_temp,
+                                             int top_k, uint64_t seed, float top_p, float scale, const unsigned* __restrict__ params_dev,
+                                             int pos_arg, int* pos_dev, int advance, int token_offset, int* __restrict__ next_tok,
+                                             int* __restrict__ out, int out_ld, int out_col0, float* __restrict__ logp) {
   __shared__ unsigned keys[SAMPLE_MAX_VOCAB];
   __shared__ unsigned qu[SAMPLE_MAX_VOCAB];
   __shared__ int cnt[4];
@@ -1524,6 +1538,7 @@ __global__ __launch_bounds__(256) void sample_tokens_p_kernel(const bf16_t* __re
     top_k = (int)params_dev[1];
     seed = (uint64_t)params_dev[2] | ((uint64_t)params_dev[3] << 32);
     top_p = __uint_as_float(params_dev[4]);
+    if (GUIDED) scale = __uint_as_float(params_dev[5]);
   }
   const int counter = pos_dev ? *pos_dev : pos_arg;
   const bool greedy = !(inv_temp > 0.f);
@@ -1531,6 +1546,11 @@ __global__ __launch_bounds__(256) void sample_tokens_p_kernel(const bf16_t* __re
   for (int i = tid; i < nv; i += 256) {
     float v = bf2f(z[(int64_t)b * ldz + i]);
     if (bias) v += bf2f(bias[i]);
+    if (GUIDED) {
+      float vu = bf2f(z[(int64_t)(gridDim.x + b) * ldz + i]);
+      if (bias) vu += bf2f(bias[i]);
+      v = guided_logit(v, vu, scale - 1.f);
+    }
     if (!greedy) v *= inv_temp;
     const unsigned k = order_key(v);
     keys[i] = k;
@@ -1641,6 +1661,7 @@ __global__ __launch_bounds__(256) void sample_tokens_p_kernel(const bf16_t* __re
       if (bval[w] > best || (bval[w] == best && bidx[w] < besti)) { best = bval[w]; besti = bidx[w]; }
     if (besti >= nv) besti = 0;          // all-NaN row: defined output
     if (next_tok) next_tok[b] = token_offset + besti;
+    if (GUIDED && next_tok) next_tok[gridDim.x + b] = token_offset + besti;
     const int col = counter - out_col0;
     if (out && col >= 0 && col < out_ld) out[(int64_t)b * out_ld + col] = besti;
     if (advance && pos_dev) {            // the last block to finish moves the position on (every block has read it by then)
@@ -1651,6 +1672,22 @@ __global__ __launch_bounds__(256) void sample_tokens_p_kernel(const bf16_t* __re
       }
     }
   }
+}
+__global__ __launch_bounds__(256) void sample_tokens_p_kernel(const bf16_t* __restrict__ z, int ldz, const bf16_t* __restrict__ bias, int nv,
+                                                              float inv_temp, int top_k, uint64_t seed, float top_p,
+                                                              const unsigned* __restrict__ params_dev, int pos_arg, int* pos_dev, int advance,
+                                                              int token_offset, int* __restrict__ next_tok, int* __restrict__ out, int out_ld,
+                                                              int out_col0, float* __restrict__ logp) {
+  nucleus_draw<false>(z, ldz, bias, nv, inv_temp, top_k, seed, top_p, 1.f, params_dev, pos_arg, pos_dev, advance, token_offset, next_tok, out,
+                      out_ld, out_col0, logp);
+}
+__global__ __launch_bounds__(256) void sample_tokens_guided_kernel(const bf16_t* __restrict__ z, int ldz, const bf16_t* __restrict__ bias, int nv,
+                                                                   float inv_temp, int top_k, uint64_t seed, float top_p, float scale,
+                                                                   const unsigned* __restrict__ params_dev, int pos_arg, int* pos_dev,
+                                                                   int advance, int token_offset, int* __restrict__ next_tok,
+                                                                   int* __restrict__ out, int out_ld, int out_col0, float* __restrict__ logp) {
+  nucleus_draw<true>(z, ldz, bias, nv, inv_temp, top_k, seed, top_p, scale, params_dev, pos_arg, pos_dev, advance, token_offset, next_tok, out,
+                     out_ld, out_col0, logp);
 }
 extern "C" int dmi_sample_tokens_p(const uint16_t* z, int ldz, const uint16_t* bias, int B, int nv, float temperature, int top_k,
                                    uint64_t seed, float top_p, const uint32_t* params_dev, int pos, int32_t* pos_dev, int advance,
@@ -1664,6 +1701,24 @@ extern "C" int dmi_sample_tokens_p(const uint16_t* z, int ldz, const uint16_t* b
   sample_tokens_p_kernel<<<dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream>>>(z, ldz, bias, nv, inv_temp, top_k, seed, top_p, params_dev, pos,
                                                                                   pos_dev, advance, token_offset, next_tok, out, out_ld, out_col0, logp);
   DMI_CHECK_LAUNCH("sample_tokens_p");
+  return DMI_OK;
+}
+extern "C" int dmi_sample_tokens_guided(const uint16_t* z, int ldz, const uint16_t* bias, int Bc, int nv, float temperature, int top_k,
+                                        uint64_t seed, float top_p, float scale, const uint32_t* params_dev, int pos, int32_t* pos_dev,
+                                        int advance, int token_offset, int32_t* next_tok, int32_t* out, int out_ld, int out_col0, float* logp,
+                                        void* stream) {
+  DMI_REQUIRE(z && (next_tok || out), "sample_tokens_guided: null pointer");
+  DMI_REQUIRE(Bc > 0 && nv > 0 && nv <= SAMPLE_MAX_VOCAB && ldz >= nv, "sample_tokens_guided: need Bc > 0 and 0 < nv <= %d (Bc=%d, nv=%d)",
+              SAMPLE_MAX_VOCAB, Bc, nv);
+  DMI_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_tokens_guided: top_p must lie in (0, 1] (top_p=%g)", (double)top_p);
+  DMI_REQUIRE(scale >= 0.f && scale <= 3.402823466e38f, "sample_tokens_guided: scale must be finite and >= 0 (scale=%g)", (double)scale);
+  DMI_REQUIRE(!out || out_ld > 0, "sample_tokens_guided: out_ld");
+  DMI_REQUIRE(!advance || pos_dev, "sample_tokens_guided: advance needs pos_dev");
+  const float inv_temp = temperature > 0.f ? 1.f / temperature : 0.f;
+  sample_tokens_guided_kernel<<<dim3((unsigned)Bc), dim3(256), 0, (hipStream_t)stream>>>(z, ldz, bias, nv, inv_temp, top_k, seed, top_p, scale, params_dev,
+                                                                                       pos, pos_dev, advance, token_offset, next_tok, out, out_ld,
+                                                                                       out_col0, logp);
+  DMI_CHECK_LAUNCH("sample_tokens_guided");
   return DMI_OK;
 }
 

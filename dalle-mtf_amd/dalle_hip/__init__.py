@@ -100,6 +100,7 @@ def _declare(L):
         "dmi_assemble_tokens": (I, [P, P, P, I, I, I, I, I, P]),
         "dmi_sample_tokens": (I, [P, I, P, I, I, F, I, ctypes.c_uint64, P, I, P, I, I, P, P, I, I, P]),
         "dmi_sample_tokens_p": (I, [P, I, P, I, I, F, I, ctypes.c_uint64, F, P, I, P, I, I, P, P, I, I, P, P]),
+        "dmi_sample_tokens_guided": (I, [P, I, P, I, I, F, I, ctypes.c_uint64, F, F, P, I, P, I, I, P, P, I, I, P, P]),
         "dmi_ln_gemm_nt": (I, [P, I, P, P, F, P, I, P, I, I, I, I, I, P, P]),
         "dmi_logits_f32": (I, [P, I, P, P, I, I, P]),
         "dmi_gemm_nt_ln": (I, [P, I, P, I, P, I, I, I, I, P, P, P, P, F, P, I, P, P, P]),
@@ -595,13 +596,46 @@ def sample_tokens_p(z, ldz, bias, B, nv, temperature=1.0, top_k=0, seed=0, top_p
                                      _p(next_tok), _p(out), out_ld, int(out_col0), _p(logp), _stream()), "sample_tokens_p")
 
 
-def sample_params(temperature=1.0, top_k=0, seed=0, top_p=None):
+def sample_tokens_guided(z, ldz, bias, Bc, nv, temperature=1.0, top_k=0, seed=0, top_p=1.0, scale=1.0, pos=0, token_offset=0,
+                         next_tok=None, out=None, out_col0=0, params_dev=None, pos_dev=None, advance=False, logp=None):
+    """classifier-free guidance: sample_tokens_p drawn from g = zc + (scale - 1) * (zc - zu), zc / zu rows b / Bc + b of
+    z bf16 [2 * Bc, ldz] (+ bias); one token per pair, written to next_tok[b] and next_tok[Bc + b] (int32 [2 * Bc]) and to
+    out int32 [Bc, out_ld]; logp fp32 [Bc] += log_softmax(zc)[choice].  params_dev is uint32 [6] with word 5 = bits of scale
+    (sample_params(..., guidance_scale=)).  scale = 1 draws sample_tokens_p's tokens of the first Bc rows (include/dalle_hip.h)."""
+    _dev(z)
+    assert z.dtype == torch.bfloat16 and (bias is None or bias.dtype == torch.bfloat16)
+    if pos_dev is not None:
+        assert pos_dev.dtype == torch.int32 and pos_dev.numel() >= (2 if advance else 1), \
+            "sample_tokens_guided: pos_dev must be int32 [2] ([position, zeroed counter]) when advance=True, int32 [1] otherwise"
+    if params_dev is not None:
+        assert params_dev.numel() >= 6 and params_dev.element_size() == 4, "sample_tokens_guided: params_dev must be 32-bit [6]"
+    if next_tok is not None:
+        assert next_tok.dtype == torch.int32 and next_tok.numel() >= 2 * Bc, "sample_tokens_guided: next_tok must be int32 [2 * Bc]"
+    if out is not None:
+        assert out.dtype == torch.int32 and out.dim() == 2 and out.shape[0] >= Bc, "sample_tokens_guided: out must be int32 [Bc, n]"
+    if logp is not None:
+        assert logp.dtype == torch.float32 and logp.numel() >= Bc, "sample_tokens_guided: logp must be fp32 [Bc]"
+    for t in (bias, next_tok, out, params_dev, pos_dev, logp):
+        if t is not None:
+            _dev(t)
+    out_ld = int(out.shape[1]) if out is not None else 0
+    _check(lib().dmi_sample_tokens_guided(_p(z), ldz, _p(bias), Bc, nv, float(temperature), int(top_k), int(seed) & (2 ** 64 - 1),
+                                          float(top_p), float(scale), _p(params_dev), int(pos), _p(pos_dev), int(bool(advance)),
+                                          int(token_offset), _p(next_tok), _p(out), out_ld, int(out_col0), _p(logp), _stream()),
+           "sample_tokens_guided")
+
+
+def sample_params(temperature=1.0, top_k=0, seed=0, top_p=None, guidance_scale=None):
     """the device parameter block of the draw kernels as int32 (bit pattern of the uint32 words): [4] for sample_tokens,
-    [6] for sample_tokens_p when top_p is given"""
+    [6] for sample_tokens_p when top_p is given; guidance_scale (with top_p) puts the bits of the scale into word 5 for
+    sample_tokens_guided -- without it word 5 is 0, as the unguided kernels have always been given"""
     def bits(x):
         return struct.unpack("<I", struct.pack("<f", x))[0]
     words = [bits(1.0 / temperature if temperature > 0 else 0.0), int(top_k), int(seed) & 0xffffffff, (int(seed) >> 32) & 0xffffffff]
-    if top_p is not None:
+    if guidance_scale is not None:
+        assert top_p is not None, "sample_params: guidance_scale goes with top_p (the six-word block)"
+        words += [bits(top_p), bits(guidance_scale)]
+    elif top_p is not None:
         words += [bits(top_p), 0]
     return torch.tensor([w - (1 << 32) if w >= (1 << 31) else w for w in words], dtype=torch.int32)
 

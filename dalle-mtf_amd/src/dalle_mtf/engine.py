@@ -19,6 +19,8 @@ Activations needed by backward are kept in bf16 per layer (no recompute; 288 GB 
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import hashlib
 import math
 import os
@@ -31,6 +33,22 @@ import torch
 import dalle_hip as dh
 from ..dp import GradReducer
 from .activations import check_activation
+
+@contextlib.contextmanager
+def _no_gc_in_capture():
+    """For the span of a stream capture: collect garbage first, then keep the cyclic collector off.  torch.cuda.graph no longer
+    collects before it captures, and a collection that starts inside the capture runs finalisers there -- a dead model's
+    CUDAGraph among them, whose destruction synchronises the device, a call the capturing thread may not make: the runtime
+    reports it from a destructor and the process aborts.  Collecting first also finalises such objects where that is legal."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
+
 
 HEAD_DIMS = (64, 128)   # n_embd / n_heads values the attention kernels are built for
 ALIGN = 128  # elements
@@ -585,7 +603,8 @@ class DalleEngine:
     # ------------------------------------------------------------------ sampling
     def sample_image_tokens(self, text: torch.Tensor, temperature: float = 1.0, top_k: int = 0, seed: int = 0,
                             top_p: float = 1.0, image_prefix: Optional[torch.Tensor] = None, return_logprobs: bool = False,
-                            kv_cache: bool = True, decode_graph: bool = True, fused_sampling: bool = True):
+                            kv_cache: bool = True, decode_graph: bool = True, fused_sampling: bool = True,
+                            guidance_scale: float = 1.0, uncond_text: Optional[torch.Tensor] = None):
         """Autoregressive image-token sampling: text int32 [B, T] -> image-token ids [B, P] in [0, image_vocab_size).
         The reference scaffolds this (is_incremental_inference, models.py:246-254,281-285) but its predict path raises
         NotImplementedError (model_fns.py:135-136).  Logits are restricted to the image vocabulary; temperature / top-k /
@@ -614,9 +633,41 @@ class DalleEngine:
         image_prefix (int [B, k], ids in [0, image_vocab_size), 0 <= k < P): image completion.  The returned tokens start with
         the prefix; positions T-1 .. T+k-2 go through the same decode steps as sampled positions, teacher-forced (the
         decode_step body), and drawing starts at position T+k-1 -- so sampling s and then completing s[:, :k] returns s
-        bit for bit.  Prefix tokens are not drawn and add nothing to logp."""
+        bit for bit.  Prefix tokens are not drawn and add nothing to logp.
+
+        Classifier-free guidance (guidance_scale != 1 or uncond_text given; with both at their defaults every launch is as
+        above): the engine's B rows are Bc = B // 2 pairs.  text is [Bc, T] and fills rows 0 .. Bc-1; rows Bc .. B-1 take
+        uncond_text (int [T] or [Bc, T]; default the null caption, T copies of hparams["padding_id"], or of
+        text_vocab_size - 1 when that is unset -- the padding rule of src/input_fns.py, which is also what "caption_dropout"
+        trains on).  The decode step is row-independent, so both halves ride through the same prefill and decode graph; the
+        draw is dmi_sample_tokens_guided (include/dalle_hip.h) on every path: pair b draws ONE token from
+        l_uncond + guidance_scale * (l_cond - l_uncond) and both rows are fed it.  image_prefix is [Bc, k] and is
+        teacher-forced into both halves.  Returns tokens [Bc, P] (and logp [Bc]: the conditional rows' own log-likelihood of
+        the drawn tokens, unguided, temperature 1)."""
         B, T, S, P = self.B, self.T, self.S, self.S - self.T
-        assert text.shape == (B, T)
+        gs = float(guidance_scale)
+        if not (gs >= 0.0 and math.isfinite(gs)):
+            raise ValueError(f"sample_image_tokens: guidance_scale must be finite and >= 0 (got {guidance_scale})")
+        guided = gs != 1.0 or uncond_text is not None
+        R = B                                            # rows of text / image_prefix / the result
+        if guided:
+            if B % 2:
+                raise ValueError(f"sample_image_tokens: guidance pairs the engine's rows, so its batch must be even (B = {B})")
+            R = B // 2
+            if tuple(text.shape) != (R, T):
+                raise ValueError(f"sample_image_tokens: with guidance text must be [B / 2 = {R}, T = {T}] (got {tuple(text.shape)})")
+            if uncond_text is None:
+                pad = self.hp.get("padding_id")
+                uncond_text = torch.full((T,), self.text_vocab_size - 1 if pad is None else int(pad), dtype=torch.int32)
+            uncond_text = torch.as_tensor(uncond_text)
+            if uncond_text.dtype.is_floating_point or uncond_text.dtype == torch.bool:
+                raise ValueError("sample_image_tokens: uncond_text must hold integer token ids")
+            if tuple(uncond_text.shape) not in ((T,), (R, T)):
+                raise ValueError(f"sample_image_tokens: uncond_text must be [T = {T}] or [B / 2 = {R}, T = {T}] "
+                                 f"(got {tuple(uncond_text.shape)})")
+            if int(uncond_text.min()) < 0 or int(uncond_text.max()) >= self.text_vocab_size:
+                raise ValueError(f"sample_image_tokens: uncond_text ids must lie in [0, {self.text_vocab_size})")
+        assert text.shape == (R, T)
         top_p = float(top_p)
         if not (0.0 < top_p <= 1.0):
             raise ValueError(f"sample_image_tokens: top_p must lie in (0, 1] (got {top_p})")
@@ -625,8 +676,8 @@ class DalleEngine:
         k = 0
         if image_prefix is not None:
             image_prefix = torch.as_tensor(image_prefix)
-            if image_prefix.dim() != 2 or image_prefix.shape[0] != B or not (0 <= image_prefix.shape[1] < P):
-                raise ValueError(f"sample_image_tokens: image_prefix must be [B={B}, k] with 0 <= k < {P} (got {tuple(image_prefix.shape)})")
+            if image_prefix.dim() != 2 or image_prefix.shape[0] != R or not (0 <= image_prefix.shape[1] < P):
+                raise ValueError(f"sample_image_tokens: image_prefix must be [B={R}, k] with 0 <= k < {P} (got {tuple(image_prefix.shape)})")
             if image_prefix.dtype.is_floating_point or image_prefix.dtype == torch.bool:
                 raise ValueError("sample_image_tokens: image_prefix must hold integer token ids")
             k = int(image_prefix.shape[1])
@@ -634,10 +685,14 @@ class DalleEngine:
                 raise ValueError(f"sample_image_tokens: image_prefix ids must lie in [0, {nv})")
         nucleus = top_p < 1.0 or return_logprobs
         toks = torch.full((B, S), lo, dtype=torch.int32, device=self.dev)
-        toks[:, :T] = text.to(device=self.dev, dtype=torch.int32)
+        toks[:R, :T] = text.to(device=self.dev, dtype=torch.int32)
+        if guided:
+            toks[R:, :T] = uncond_text.to(device=self.dev, dtype=torch.int32)       # [T] broadcasts over the rows
         if k:
-            toks[:, T:T + k] = image_prefix.to(device=self.dev, dtype=torch.int32) + lo
-        logp = torch.zeros(B, dtype=torch.float32, device=self.dev) if return_logprobs else None
+            toks[:R, T:T + k] = image_prefix.to(device=self.dev, dtype=torch.int32) + lo
+            if guided:
+                toks[R:, T:T + k] = toks[:R, T:T + k]
+        logp = torch.zeros(R, dtype=torch.float32, device=self.dev) if return_logprobs else None
 
         def result(img):
             return (img, logp) if return_logprobs else img
@@ -649,7 +704,12 @@ class DalleEngine:
                 self.decode_step(toks[:, pos].contiguous(), pos, graph=True)
             D["tok"].copy_(toks[:, T - 1 + k])
             D["pos_i"][0:1].fill_(T - 1 + k)
-            if nucleus:
+            if guided:
+                D["params"].copy_(dh.sample_params(temperature, top_k, seed, top_p, guidance_scale=gs))
+                variant = "g+logp" if return_logprobs else "g"
+                if return_logprobs:
+                    D["logp"].zero_()
+            elif nucleus:
                 D["params"].copy_(dh.sample_params(temperature, top_k, seed, top_p))
                 variant = "p+logp" if return_logprobs else "p"
                 if return_logprobs:
@@ -661,11 +721,11 @@ class DalleEngine:
                 variant = True
             for _ in range(P - k):                       # position T-1+i predicts image token i; the graph advances the position itself
                 self._run_decode(sample=variant, graph=True)
-            img = D["out"].clone()
+            img = D["out"][:R].clone()                   # guided: the kernel writes one row per pair
             if k:
-                img[:, :k] = toks[:, T:T + k] - lo
+                img[:, :k] = toks[:R, T:T + k] - lo
             if return_logprobs:
-                logp.copy_(D["logp"])
+                logp.copy_(D["logp"][:R])
             return result(img)
 
         if nv > 8192:
@@ -677,8 +737,11 @@ class DalleEngine:
             """the draw itself is dmi_sample_tokens (dmi_sample_tokens_p for top_p / logp) on every path (temperature / top-k /
             Gumbel-max with counter-based noise hash(seed, position, row, index), first maximum when temperature <= 0):
             host-launched here, the last node of the replayed graph on the fused path -- the same (seed, position) gives the
-            same draw on both."""
-            if nucleus:
+            same draw on both.  Guided: dmi_sample_tokens_guided, one draw per pair, written to both of its rows of nxt."""
+            if guided:
+                dh.sample_tokens_guided(z, ldz, zbias, R, nv, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p, scale=gs,
+                                        pos=position, token_offset=lo, next_tok=nxt, logp=logp)
+            elif nucleus:
                 dh.sample_tokens_p(z, ldz, zbias, B, nv, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p, pos=position,
                                    token_offset=lo, next_tok=nxt, logp=logp)
             else:
@@ -704,7 +767,7 @@ class DalleEngine:
                     continue                             # teacher-forced: the prefix token is already in toks
                 tok = pick(self._dec["z"], nv, bias, T + pos - 1)      # bf16 head output + bias, as the fused path draws
             toks[:, T + pos] = tok
-        return result((toks[:, T:] - lo).contiguous())
+        return result((toks[:R, T:] - lo).contiguous())
 
     def _kv_caches(self):
         """the per-layer [B*S, 3d] key/value caches the decode step reads: the forward's own projection buffers, or under
@@ -764,7 +827,8 @@ class DalleEngine:
 
     def _run_decode(self, sample, graph: bool):
         """sample: False (the decode_step body) or the draw variant (True: dmi_sample_tokens, "p" / "p+logp":
-        dmi_sample_tokens_p without / with logp) -- one captured graph per variant, the draw node differs"""
+        dmi_sample_tokens_p without / with logp, "g" / "g+logp": dmi_sample_tokens_guided over B / 2 pairs) -- one captured
+        graph per variant, the draw node differs"""
         D = self._dec
         if not graph:
             self._decode_body(sample)
@@ -775,7 +839,8 @@ class DalleEngine:
             if sample not in D["graphs"]:
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):   # other host threads (input producer) stay free to call HIP
+                # other host threads (input producer) stay free to call HIP; no finaliser runs inside the capture
+                with _no_gc_in_capture(), torch.cuda.graph(g, capture_error_mode="thread_local"):
                     self._decode_body(sample)
                 D["graphs"][sample] = g    # (capture records, it does not execute: the replay below is the step)
             D["graphs"][sample].replay()
@@ -784,7 +849,8 @@ class DalleEngine:
         """the launches of one decode step; reads D[tok] and the position D[pos_i][0] from device memory.  sample=False: writes
         D[logits].  sample=True / "p" / "p+logp": draws the next token (settings in D[params]) into D[tok] and
         column pos - (T - 1) of D[out], then advances the position (inside the sampling kernel); "p" draws with the nucleus
-        kernel, "p+logp" also adds the choice's log-probability to D[logp].
+        kernel, "p+logp" also adds the choice's log-probability to D[logp]; "g" / "g+logp" draw one token per pair of rows
+        (b, B/2 + b) with the guided kernel (scale in D[params][5]) into both rows of D[tok] and rows 0 .. B/2-1 of D[out] / D[logp].
         B <= 32: LayerNorm rides in the prologue of the product that consumes it (dmi_ln_gemm_nt) -- 5 dependent launches per
         block instead of 7; a dependent launch costs ~7 us on this part, more than any of these kernels' work."""
         B, d, L, H, S = self.B, self.d, self.L, self.H, self.S
@@ -822,7 +888,10 @@ class DalleEngine:
         Wt = self.tview("to_logits/linear_out/kernel")                 # [Vp, d]: rows lo .. lo + nv are the image vocabulary
         ln_dense(x, "to_logits/layer_norm", Wt[lo:lo + nv], z, nv)
         bias = self._w("to_logits/linear_out/bias")[lo:lo + nv]
-        if sample in ("p", "p+logp"):
+        if sample in ("g", "g+logp"):
+            dh.sample_tokens_guided(z, nv, bias, B // 2, nv, params_dev=D["params"], pos_dev=D["pos_i"], advance=True, token_offset=lo,
+                                    next_tok=D["tok"], out=D["out"], out_col0=self.T - 1, logp=D["logp"] if sample == "g+logp" else None)
+        elif sample in ("p", "p+logp"):
             dh.sample_tokens_p(z, nv, bias, B, nv, params_dev=D["params"], pos_dev=D["pos_i"], advance=True, token_offset=lo,
                                next_tok=D["tok"], out=D["out"], out_col0=self.T - 1, logp=D["logp"] if sample == "p+logp" else None)
         elif sample:

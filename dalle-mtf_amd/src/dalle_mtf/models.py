@@ -93,14 +93,18 @@ class DALLE:
                     "to_logits/linear_out/kernel": (d, V), "to_logits/linear_out/bias": (V,)})
         return out
 
-    def sample(self, text_tokens, vae=None, temperature=1.0, top_k=0, seed=0, top_p=1.0, image_prefix=None, return_logprobs=False):
+    def sample(self, text_tokens, vae=None, temperature=1.0, top_k=0, seed=0, top_p=1.0, image_prefix=None, return_logprobs=False,
+               guidance_scale=1.0, uncond_text=None):
         """text ids [B, text_seq_len] -> image-token ids [B, image_seq_len] (and the decoded images when a DiscreteVAE is
         given): the generation path the reference leaves unfinished (model_fns.py:135-136).  top_p < 1: nucleus filter after
         top-k; image_prefix int [B, k]: complete images from their first k tokens; return_logprobs: also the model's
-        log-likelihood of each sample, fp32 [B] (DalleEngine.sample_image_tokens).  Returns toks, (toks, images),
-        (toks, logp) or (toks, images, logp)."""
+        log-likelihood of each sample, fp32 [B] (DalleEngine.sample_image_tokens).  guidance_scale != 1 / uncond_text:
+        classifier-free guidance -- text_tokens (and image_prefix) are [B / 2, ...], the other half of the batch carries
+        uncond_text (default: the null caption), and B / 2 rows come back.  Returns toks, (toks, images), (toks, logp) or
+        (toks, images, logp)."""
         res = self.engine.sample_image_tokens(text_tokens, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p,
-                                              image_prefix=image_prefix, return_logprobs=return_logprobs)
+                                              image_prefix=image_prefix, return_logprobs=return_logprobs,
+                                              guidance_scale=guidance_scale, uncond_text=uncond_text)
         toks, logp = res if return_logprobs else (res, None)
         out = (toks, vae.decode_tokens(toks)) if vae is not None else (toks,)
         if return_logprobs:

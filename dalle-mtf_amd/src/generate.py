@@ -11,10 +11,13 @@ top-p, image completion, the model's log-likelihood of each sample), decodes the
     generate.json the settings, the checkpoints and the timings
 
 Rows are generated in batches of --batch (the last one padded by repeating its rows); batch j draws with seed + j, and rows
-of a batch draw different noise because the counter-based noise hashes the row.  Every argument is checked before the GPU
-is touched."""
+of a batch draw different noise because the counter-based noise hashes the row.  --guidance-scale S != 1 (classifier-free
+guidance) pairs every row with a null-caption row in the same batch, so a batch of --batch engine rows generates --batch / 2
+output rows; the files keep their shapes per caption and per sample, and logprob.npy stays the conditional model's own score.
+Every argument is checked before the GPU is touched."""
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -42,6 +45,9 @@ def build_parser():
     p.add_argument("--temperature", type=float, default=1.0, help="0 = greedy")
     p.add_argument("--top-k", dest="top_k", type=int, default=0, help="0 = no top-k filter")
     p.add_argument("--top-p", dest="top_p", type=float, default=1.0, help="nucleus mass in (0, 1]; 1 = no nucleus filter")
+    p.add_argument("--guidance-scale", dest="guidance_scale", type=float, default=1.0,
+                   help="classifier-free guidance: draw from l_uncond + S (l_cond - l_uncond), the unconditional rows carrying the "
+                        "null caption; a batch then generates --batch / 2 rows.  1 = off (default)")
     p.add_argument("--seed", type=int, default=0, help="batch j draws with seed + j")
     p.add_argument("--no-images", dest="no_images", action="store_true", help="write tokens and scores only")
     return p
@@ -75,6 +81,11 @@ def check_args(parser, args, params):
         _fail(parser, f"--batch must be >= 1 (got {args.batch})")
     if args.batch is None and not params["predict_batch_size"]:
         _fail(parser, "--batch is needed: the config has no predict_batch_size")
+    if not (args.guidance_scale >= 0.0 and math.isfinite(args.guidance_scale)):
+        _fail(parser, f"--guidance-scale must be finite and >= 0 (got {args.guidance_scale})")
+    if args.guidance_scale != 1.0 and (args.batch or int(params["predict_batch_size"])) % 2:
+        _fail(parser, f"--guidance-scale pairs the rows of a batch, so the batch must be even "
+                      f"(got {args.batch or int(params['predict_batch_size'])})")
     if not (0 <= args.image_prefix < P):
         _fail(parser, f"--image-prefix must lie in [0, image_seq_len = {P}) (got {args.image_prefix})")
     if args.image_prefix and args.from_eval is None:
@@ -188,22 +199,24 @@ def generate(argv=None):
     logprob = np.empty((rows,), np.float32)
     images = []
     t_sample = t_decode = 0.0
-    nb = (rows + B - 1) // B
+    guided = args.guidance_scale != 1.0
+    Bg = B // 2 if guided else B                  # output rows per batch: guidance spends the other half on the null caption
+    nb = (rows + Bg - 1) // Bg
     for j in range(nb):
-        r = np.minimum(np.arange(j * B, (j + 1) * B), rows - 1)     # the last batch repeats its last row
+        r = np.minimum(np.arange(j * Bg, (j + 1) * Bg), rows - 1)   # the last batch repeats its last row
         cap = torch.from_numpy(captions[r // n])
         pre = torch.from_numpy(prefixes[r // n, :K]) if K else None
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         toks, lp = model.sample(cap, temperature=args.temperature, top_k=args.top_k, seed=args.seed + j, top_p=args.top_p,
-                                image_prefix=pre, return_logprobs=True)
+                                image_prefix=pre, return_logprobs=True, guidance_scale=args.guidance_scale)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
-        m = min(B, rows - j * B)
-        tokens[j * B:j * B + m] = toks[:m].cpu().numpy()
-        logprob[j * B:j * B + m] = lp[:m].cpu().numpy()
+        m = min(Bg, rows - j * Bg)
+        tokens[j * Bg:j * Bg + m] = toks[:m].cpu().numpy()
+        logprob[j * Bg:j * Bg + m] = lp[:m].cpu().numpy()
         if vae is not None and not args.no_images:
-            img = vae.decode_tokens(toks)
+            img = vae.decode_tokens(torch.cat([toks, toks]) if guided else toks)      # the VAE is built at the batch B
             images.extend(img[:m].detach().cpu())
             torch.cuda.synchronize()
         t_sample += t2 - t1
@@ -221,11 +234,11 @@ def generate(argv=None):
     vae_ck = (params.get("vae_checkpoint_path") or None) if vae is not None else None
     info = dict(model=args.model, checkpoint=st["restored_from"], vae_checkpoint=vae_ck, captions=int(N), samples_per_caption=n,
                 rows=int(rows), batch=int(B), batches=int(nb), seed=args.seed, seeds=f"batch j draws with seed + j",
-                temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, image_prefix=K, image_seq_len=int(P),
+                temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, guidance_scale=args.guidance_scale, image_prefix=K, image_seq_len=int(P),
                 source=next(s for s in SOURCES if getattr(args, s) is not None), images_written=len(images),
                 recompute_grad=bool(eng.recompute),
                 seconds=dict(load=round(t_load, 3), sample=round(t_sample, 3), decode_and_copy=round(t_decode, 3)),
-                tokens_per_s=round(nb * B * (P - K) / t_sample, 1) if t_sample > 0 else None)
+                tokens_per_s=round(nb * Bg * (P - K) / t_sample, 1) if t_sample > 0 else None)
     with open(os.path.join(args.out, "generate.json"), "w") as f:
         json.dump(info, f, indent=1)
     print(json.dumps(info))

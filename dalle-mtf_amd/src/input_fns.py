@@ -305,7 +305,7 @@ def _synthetic_dalle(params, eval):
     ds = params["dataset"]
     B = _batch_size(params, eval)
     size, ch = ds["image_size"], params.get("n_channels") or 3
-    pad = params["padding_id"] if params.get("padding_id") is not None else params["text_vocab_size"] - 1
+    pad = _pad_id(params)
     rng = np.random.default_rng(_stream_seed(params, 1, eval) if not eval else 101)
     while True:
         img = rng.integers(0, 256, size=(B, size, size, ch), dtype=np.uint8)
@@ -324,9 +324,65 @@ def _synthetic_vae(params, eval):
         yield img, img
 
 
+def _pad_id(params):
+    return params["padding_id"] if params.get("padding_id") is not None else params["text_vocab_size"] - 1
+
+
+def caption_dropout_rate(params):
+    """the config key "caption_dropout" (a project extension, like "attention_pattern"): the probability with which a training
+    caption is replaced by the null caption, so that the model also learns p(image) and can be sampled with classifier-free
+    guidance (DalleEngine.sample_image_tokens(guidance_scale=...)).  Absent / 0: off."""
+    p = params.get("caption_dropout")
+    if p is None:
+        return 0.0
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not (0.0 <= p < 1.0):
+        raise ValueError(f"config key caption_dropout: expected a probability in [0, 1) (got {p!r})")
+    return float(p)
+
+
+class _CaptionDropout:
+    """wraps a training stream of (image, caption) batches: each caption row becomes the null caption (text_seq_len copies of
+    the padding id) with probability p.  The draws come from a generator of their own, so which images and captions the
+    wrapped stream reads or synthesises does not depend on p."""
+
+    def __init__(self, it, p, pad, seed):
+        self._it, self._p, self._pad = it, p, int(pad)
+        self._rng = np.random.default_rng([0x63667264, int(seed)])
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        img, cap = next(self._it)
+        drop = self._rng.random(cap.shape[0]) < self._p
+        if drop.any():
+            cap = cap.clone()
+            cap[torch.from_numpy(drop)] = self._pad
+        return img, cap
+
+    def close(self):
+        if hasattr(self._it, "close"):
+            self._it.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def dalle_input_fn(params, eval=False):
     """reference input_fns.py:104-120.  Yields (image [B,H,W,C] fp32 in [-1,1], caption ids [B,text_seq_len] int32)
-    forever."""
+    forever.  "caption_dropout": p (train mode only) replaces each caption by the null caption with probability p."""
+    p = caption_dropout_rate(params)
+    it = _dalle_stream(params, eval)
+    if eval or p == 0.0:
+        return it
+    base = 1 if _is_synthetic(params["dataset"]["train_path"]) else int(params.get("input_seed", 0)) + 1
+    return _CaptionDropout(it, p, _pad_id(params), _stream_seed(params, base, eval))
+
+
+def _dalle_stream(params, eval):
     ds = params["dataset"]
     path = ds["train_path"] if not eval else ds["eval_path"]
     if _is_synthetic(path):

@@ -311,6 +311,26 @@ int dmi_sample_tokens_p(const uint16_t* z, int ldz, const uint16_t* bias, int B,
                         uint64_t seed, float top_p, const uint32_t* params_dev, int pos, int32_t* pos_dev, int advance,
                         int token_offset, int32_t* next_tok, int32_t* out, int out_ld, int out_col0, float* logp, void* stream);
 
+/* Classifier-free guidance: the nucleus draw from l_uncond + scale * (l_cond - l_uncond).  z bf16 [2 * Bc, ldz]: rows 0 .. Bc-1 are
+ * the conditional rows, rows Bc .. 2 Bc - 1 the unconditional ones, pair b = rows b and Bc + b; one 256-thread block per pair
+ * (grid Bc).  Per column i < nv, in fp32:  zc = z[b, i] + bias[i];  zu = z[Bc + b, i] + bias[i];  d = zc - zu;
+ * g = zc + (scale - 1) * d, the difference, the product and the sum each rounded on their own (no fused multiply-add), so that
+ * numpy float32 restates g bit for bit; scale - 1 == 0 takes g = zc itself.  v = g * (1/temperature), and from v on the kernel is
+ * dmi_sample_tokens_p: top-k with ties kept, the fixed-point nucleus, Gumbel-max with the noise hash(seed, position, b, i) (b the
+ * pair index), first maximum of g when temperature <= 0.  scale = 1 gives dmi_sample_tokens_p's tokens on the conditional rows bit
+ * for bit; scale = 0 draws from the unconditional rows.
+ * next_tok[b] = next_tok[Bc + b] = token_offset + choice (both halves of the KV cache are fed the same token; int32 [2 * Bc]);
+ * out[b, position - out_col0] = choice, out int32 [Bc, out_ld];  logp (nullable, fp32 [Bc]): logp[b] += log softmax(zc)[choice] --
+ * the CONDITIONAL model's own score at temperature 1, unfiltered, so that samples drawn at different scales rank on one measure.
+ * params_dev (optional, device uint32[6]): dmi_sample_tokens_p's block with word 5 = bits of scale (the unguided kernels ignore
+ * word 5; a device scale is taken as it is).  By value: 0 < top_p <= 1 and scale finite and >= 0, else DMI_ERR_INVALID (NaN
+ * included); Bc > 0; nv <= 8192.  pos_dev / advance as for dmi_sample_tokens: the last of the Bc blocks stores position + 1.
+ * 64 KB of LDS per block, as the nucleus kernel. */
+int dmi_sample_tokens_guided(const uint16_t* z, int ldz, const uint16_t* bias, int Bc, int nv, float temperature, int top_k,
+                             uint64_t seed, float top_p, float scale, const uint32_t* params_dev, int pos, int32_t* pos_dev,
+                             int advance, int token_offset, int32_t* next_tok, int32_t* out, int out_ld, int out_col0, float* logp,
+                             void* stream);
+
 /* "Go to full precision for the logits" (src/dalle_mtf/models.py:394-395) for a slice of the head's output:
  * out[b, i] = float(z[b, i]) + float(bias[i]), z bf16 [B, ldz] (first nv columns), bias bf16 [nv] (nullable), out fp32 [B, nv]. */
 int dmi_logits_f32(const uint16_t* z, int ldz, const uint16_t* bias, float* out, int B, int nv, void* stream);

@@ -1,9 +1,11 @@
 """Generation throughput in one process (random weights): the KV-cached graph sampler against the plain sampler (one full
 forward per position), and the per-position cost of the draw variants (top-k, top-k + top-p, + log-likelihood).
-    python tools/genbench.py --shape example|coco --batch B [--out FILE.json]
+    python tools/genbench.py --shape example|coco --batch B [--guidance-scale S] [--out FILE.json]
     python tools/genbench.py --kernels        # the two draw kernels alone (time them under rocprofv3 --kernel-trace --stats)
 The plain sampler is timed over its last --plain-positions positions (an image prefix teacher-forces the rest; each of its
-positions is one full forward, so the rate does not depend on which positions are timed)."""
+positions is one full forward, so the rate does not depend on which positions are timed).
+--guidance-scale S != 1 times the guided sampler instead: the engine's B rows are B / 2 (caption, null caption) pairs, rates count
+the B / 2 generated rows, and the plain sampler is left out."""
 import argparse
 import json
 import os
@@ -27,25 +29,31 @@ def timed(fn, reps=1):
     return (time.perf_counter() - t0) / reps, r
 
 
-def engine_bench(shape, B, plain_positions):
+def engine_bench(shape, B, plain_positions, guidance_scale=1.0):
     from src.dalle_mtf.engine import DalleEngine
     c = SHAPES[shape]
     T, P, tv = 256, 1024, 50258
     eng = DalleEngine(c["d"], c["L"], c["H"], tv, c["iv"], T, P, batch_size=B, hparams=dict(lr=1e-3, train_steps=10, **c["hp"]))
     eng.init_params(seed=1)
-    text = torch.randint(0, tv - 1, (B, T), dtype=torch.int32, device="cuda")
-    res = dict(shape=shape, batch=B, n_embd=c["d"], n_layers=c["L"], n_heads=c["H"], seq=T + P, image_vocab=c["iv"],
+    guided = guidance_scale != 1.0
+    R = B // 2 if guided else B                   # generated rows per call
+    gkw = dict(guidance_scale=guidance_scale) if guided else {}
+    text = torch.randint(0, tv - 1, (R, T), dtype=torch.int32, device="cuda")
+    res = dict(shape=shape, batch=B, guidance_scale=guidance_scale, rows_generated=R, n_embd=c["d"], n_layers=c["L"], n_heads=c["H"], seq=T + P, image_vocab=c["iv"],
                recompute_grad=bool(eng.recompute))
     variants = (("top_k", dict(temperature=1.0, top_k=32)), ("top_k+top_p", dict(temperature=1.0, top_k=32, top_p=0.9)),
                 ("top_k+top_p+logp", dict(temperature=1.0, top_k=32, top_p=0.9, return_logprobs=True)),
                 ("top_p", dict(temperature=1.0, top_p=0.9)))
     for _, kw in variants:
-        eng.sample_image_tokens(text, seed=0, **kw)        # warm-up: caches, graph capture per variant
-        eng.sample_image_tokens(text, seed=0, **kw)
+        eng.sample_image_tokens(text, seed=0, **kw, **gkw)        # warm-up: caches, graph capture per variant
+        eng.sample_image_tokens(text, seed=0, **kw, **gkw)
     for name, kw in variants:
-        dt, _ = timed(lambda: eng.sample_image_tokens(text, seed=1, **kw))
-        res[f"cached_graph_{name}_tokens_per_s"] = round(B * P / dt, 1)
+        dt, _ = timed(lambda: eng.sample_image_tokens(text, seed=1, **kw, **gkw))
+        res[f"cached_graph_{name}_tokens_per_s"] = round(R * P / dt, 1)
         res[f"cached_graph_{name}_ms_per_position"] = round(dt / P * 1e3, 4)
+        res[f"cached_graph_{name}_images_per_s"] = round(R / dt, 3)
+    if guided:
+        return res
     k = P - plain_positions
     prefix = torch.zeros(B, k, dtype=torch.int32)
     eng.sample_image_tokens(text, seed=0, temperature=1.0, top_k=32, kv_cache=False, image_prefix=prefix[:, :P - 1])   # warm-up
@@ -86,11 +94,12 @@ def main():
     ap.add_argument("--shape", choices=sorted(SHAPES), default="example")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--plain-positions", type=int, default=16)
+    ap.add_argument("--guidance-scale", dest="guidance_scale", type=float, default=1.0)
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = kernel_bench(a.reps) if a.kernels else engine_bench(a.shape, a.batch, a.plain_positions)
+    res = kernel_bench(a.reps) if a.kernels else engine_bench(a.shape, a.batch, a.plain_positions, a.guidance_scale)
     res["device"] = torch.cuda.get_device_name(0)
     line = json.dumps(res)
     print(line)
