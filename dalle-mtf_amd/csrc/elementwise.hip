@@ -1044,7 +1044,13 @@ struct SoftmaxFinishArgs {
 };
 #define SF_ROWS 64
 #define SF_PARTS 16
-__global__ __launch_bounds__(256) void softmax_finish_kernel(SoftmaxFinishArgs a) {
+// PW = PosWeight (dmi_softmax_finish_w): row m carries the static loss weight w[m % period] in its gradient scale,
+// rowscale[m] = (dz_scale * w) / S[m]; loss_rows, the label patch of E and the flag logic never see the weight.  PW = NoWeight is an
+// empty argument: that instance's kernel arguments and instructions are those of the untemplated kernel.
+struct NoWeight { static constexpr bool on = false; };
+struct PosWeight { static constexpr bool on = true; const float* w; int period; };
+template <class PW>
+__global__ __launch_bounds__(256) void softmax_finish_kernel(SoftmaxFinishArgs a, PW pw) {
   // 64 rows per block, the partials of a row summed by 16 threads (p = q mod 16) with 16-byte loads of 4 adjacent rows: 640
   // blocks x 4 waves for the dalle_example batch (the 160-block version left 2.5 waves per CU and ran latency-bound)
   __shared__ float sm[SF_PARTS][SF_ROWS];
@@ -1081,7 +1087,9 @@ __global__ __launch_bounds__(256) void softmax_finish_kernel(SoftmaxFinishArgs a
       if (bad) a.flag[0] = 1;
       // loss = logsumexp - label logit = log S + shift - zl   (models.py:348-359: the reference's loss_batch)
       a.loss_rows[mr] = bad ? INFINITY : __logf(S) + (a.rowshift ? a.rowshift[mr] : 0.f) - a.zl[mr];
-      scale = bad ? 0.f : a.dz_scale / S;
+      float dz = a.dz_scale;
+      if constexpr (PW::on) dz *= pw.w[(int)(((int64_t)(m0 % pw.period) + r) % pw.period)];   // the product first, then the division
+      scale = bad ? 0.f : dz / S;
       if (a.dz_scale != 0.f) {
         a.rowscale[mr] = scale;
         a.rowscale_bf16[mr] = f2bf(scale);
@@ -1110,8 +1118,9 @@ __global__ __launch_bounds__(256) void softmax_finish_kernel(SoftmaxFinishArgs a
 }
 // Exact redo of the flagged rows (loss_rows[m] == inf): logits recomputed from x and Wt with the row maximum as the shift.
 #define FIX_MAXK 8192
+template <class PW>
 __global__ __launch_bounds__(256) void softmax_fixup_kernel(SoftmaxFinishArgs a, const bf16_t* __restrict__ Wt, int ldw,
-                                                            const bf16_t* __restrict__ bias, int N) {
+                                                            const bf16_t* __restrict__ bias, int N, PW pw) {
   if (a.flag[0] == 0) return;
   __shared__ float xs[FIX_MAXK];
   __shared__ float red[4];
@@ -1155,7 +1164,9 @@ __global__ __launch_bounds__(256) void softmax_fixup_kernel(SoftmaxFinishArgs a,
     if (lane == 0) red[wid] = sum;
     __syncthreads();
     const float S = ((red[0] + red[1]) + red[2]) + red[3];
-    const float scale = a.dz_scale / S;
+    float dz = a.dz_scale;
+    if constexpr (PW::on) dz *= pw.w[(int)(m % pw.period)];   // a redone row keeps its weight (same arithmetic as softmax_finish_kernel)
+    const float scale = dz / S;
     __syncthreads();   // E row complete (block scope) before the label entry is patched
     if (tid == 0) {
       a.loss_rows[m] = mx + __logf(S) - zl;
@@ -1174,11 +1185,12 @@ __global__ __launch_bounds__(256) void softmax_fixup_kernel(SoftmaxFinishArgs a,
       }
   }
 }
-extern "C" int dmi_softmax_finish(const float* rowsum_part, int nparts, const float* label_logit, const float* rowshift,
-                                  const int32_t* labels, const uint16_t* X, int ldx,
-                                  const uint16_t* Wt, int ldw, const uint16_t* bias, uint16_t* E, int lde, int N,
-                                  float* loss_rows, float* rowscale, uint16_t* rowscale_bf16, uint16_t* Xs, int32_t* flag,
-                                  int64_t M, int K, int V, float dz_scale, void* stream) {
+// pos_weight == nullptr: the unweighted entry point
+static int softmax_finish_launch(const float* rowsum_part, int nparts, const float* label_logit, const float* rowshift,
+                                 const int32_t* labels, const uint16_t* X, int ldx,
+                                 const uint16_t* Wt, int ldw, const uint16_t* bias, uint16_t* E, int lde, int N,
+                                 float* loss_rows, float* rowscale, uint16_t* rowscale_bf16, uint16_t* Xs, int32_t* flag,
+                                 int64_t M, int K, int V, float dz_scale, const float* pos_weight, int period, void* stream) {
   DMI_REQUIRE(rowsum_part && label_logit && labels && X && Wt && bias && E && loss_rows && flag, "softmax_finish: null pointer");
   DMI_REQUIRE(dz_scale == 0.f || (rowscale && rowscale_bf16 && Xs), "softmax_finish: gradient outputs missing");
   DMI_REQUIRE(M > 0 && K % 8 == 0 && K <= FIX_MAXK && ldx % 8 == 0 && ldw % 8 == 0 && nparts > 0 && V > 0 && V <= N && N <= lde,
@@ -1188,11 +1200,34 @@ extern "C" int dmi_softmax_finish(const float* rowsum_part, int nparts, const fl
   a.loss_rows = loss_rows; a.rowscale = rowscale; a.rowscale_bf16 = rowscale_bf16; a.Xs = Xs; a.flag = flag;
   a.M = M; a.K = K; a.V = V; a.dz_scale = dz_scale;
   hipStream_t st = (hipStream_t)stream;
-  softmax_finish_kernel<<<dim3((unsigned)cdiv64(M, SF_ROWS)), dim3(256), 0, st>>>(a);
+  const PosWeight pw{pos_weight, period};
+  if (pos_weight) softmax_finish_kernel<<<dim3((unsigned)cdiv64(M, SF_ROWS)), dim3(256), 0, st>>>(a, pw);
+  else softmax_finish_kernel<<<dim3((unsigned)cdiv64(M, SF_ROWS)), dim3(256), 0, st>>>(a, NoWeight{});
   DMI_CHECK_LAUNCH("softmax_finish");
-  softmax_fixup_kernel<<<dim3(256), dim3(256), 0, st>>>(a, Wt, ldw, bias, N);   // returns at once unless a row was flagged
+  // returns at once unless a row was flagged
+  if (pos_weight) softmax_fixup_kernel<<<dim3(256), dim3(256), 0, st>>>(a, Wt, ldw, bias, N, pw);
+  else softmax_fixup_kernel<<<dim3(256), dim3(256), 0, st>>>(a, Wt, ldw, bias, N, NoWeight{});
   DMI_CHECK_LAUNCH("softmax_fixup");
   return DMI_OK;
+}
+extern "C" int dmi_softmax_finish(const float* rowsum_part, int nparts, const float* label_logit, const float* rowshift,
+                                  const int32_t* labels, const uint16_t* X, int ldx,
+                                  const uint16_t* Wt, int ldw, const uint16_t* bias, uint16_t* E, int lde, int N,
+                                  float* loss_rows, float* rowscale, uint16_t* rowscale_bf16, uint16_t* Xs, int32_t* flag,
+                                  int64_t M, int K, int V, float dz_scale, void* stream) {
+  return softmax_finish_launch(rowsum_part, nparts, label_logit, rowshift, labels, X, ldx, Wt, ldw, bias, E, lde, N, loss_rows, rowscale,
+                               rowscale_bf16, Xs, flag, M, K, V, dz_scale, nullptr, 0, stream);
+}
+// Text/image loss weights (a project extension; the reference's loss is the plain mean, models.py:348-359): see the kernels above.
+extern "C" int dmi_softmax_finish_w(const float* rowsum_part, int nparts, const float* label_logit, const float* rowshift,
+                                    const int32_t* labels, const uint16_t* X, int ldx,
+                                    const uint16_t* Wt, int ldw, const uint16_t* bias, uint16_t* E, int lde, int N,
+                                    float* loss_rows, float* rowscale, uint16_t* rowscale_bf16, uint16_t* Xs, int32_t* flag,
+                                    int64_t M, int K, int V, float dz_scale, const float* pos_weight, int period, void* stream) {
+  DMI_REQUIRE(pos_weight, "softmax_finish_w: null pos_weight");
+  DMI_REQUIRE(period > 0, "softmax_finish_w: period must be > 0");
+  return softmax_finish_launch(rowsum_part, nparts, label_logit, rowshift, labels, X, ldx, Wt, ldw, bias, E, lde, N, loss_rows, rowscale,
+                               rowscale_bf16, Xs, flag, M, K, V, dz_scale, pos_weight, period, stream);
 }
 
 // =====================================================================================
@@ -1244,6 +1279,48 @@ extern "C" int dmi_sum_f32(const float* x, int64_t n, float scale, float* out, v
   DMI_REQUIRE(x && out && n > 0, "sum_f32: bad args");
   sum_f32_kernel<<<dim3(1), dim3(1024), 0, (hipStream_t)stream>>>(x, n, scale, out);
   DMI_CHECK_LAUNCH("sum_f32");
+  return DMI_OK;
+}
+
+// The weighted loss and its two per-modality means from the per-row losses, one block (fixed order -> deterministic, no atomics):
+//   out3[0] = scale * sum_m w[m % period] * loss_rows[m];  out3[1] = mean over rows with m % period < split (text positions),
+//   out3[2] = mean over the others (image positions); a mean over no rows is 0.
+// Thread t owns rows t, t + 1024, ...; its position advances by 1024 mod period, so the loop has no division.
+__global__ __launch_bounds__(1024) void loss_reduce_kernel(const float* __restrict__ loss_rows, int64_t M,
+                                                           const float* __restrict__ pos_weight, int period, int split,
+                                                           float scale, float inv_text, float inv_image, float* __restrict__ out3) {
+  __shared__ float sm[3][16];
+  const int tid = threadIdx.x;
+  const int step = 1024 % period;
+  int pos = tid % period;
+  float aw = 0.f, at = 0.f, ai = 0.f;
+  for (int64_t m = tid; m < M; m += 1024) {
+    const float l = loss_rows[m];
+    aw = __builtin_fmaf(pos_weight[pos], l, aw);
+    if (pos < split) at += l; else ai += l;
+    pos += step;
+    if (pos >= period) pos -= period;
+  }
+  aw = wave_sum(aw); at = wave_sum(at); ai = wave_sum(ai);
+  if ((tid & 63) == 0) { sm[0][tid >> 6] = aw; sm[1][tid >> 6] = at; sm[2][tid >> 6] = ai; }
+  __syncthreads();
+  if (tid < 3) {
+    const float* s = sm[tid];
+    const float r = (((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]))) +
+                    (((s[8] + s[9]) + (s[10] + s[11])) + ((s[12] + s[13]) + (s[14] + s[15])));
+    out3[tid] = r * (tid == 0 ? scale : tid == 1 ? inv_text : inv_image);
+  }
+}
+extern "C" int dmi_loss_reduce(const float* loss_rows, int64_t M, const float* pos_weight, int period, int split, float scale,
+                               float* out3, void* stream) {
+  DMI_REQUIRE(loss_rows && pos_weight && out3, "loss_reduce: null pointer");
+  DMI_REQUIRE(M > 0 && period > 0 && split >= 0 && split <= period, "loss_reduce: bad sizes (M > 0, period > 0, 0 <= split <= period)");
+  const int64_t full = M / period, rem = M % period;
+  const int64_t ntext = full * split + (rem < split ? rem : split), nimage = M - ntext;
+  loss_reduce_kernel<<<dim3(1), dim3(1024), 0, (hipStream_t)stream>>>(loss_rows, M, pos_weight, period, split, scale,
+                                                                      ntext ? (float)(1.0 / (double)ntext) : 0.f,
+                                                                      nimage ? (float)(1.0 / (double)nimage) : 0.f, out3);
+  DMI_CHECK_LAUNCH("loss_reduce");
   return DMI_OK;
 }
 

@@ -94,6 +94,8 @@ def _declare(L):
         "dmi_gemm_nt_softmax_partials": (L64, [I]),
         "dmi_gemm_nt_softmax": (I, [P, I, P, I, P, P, P, I, P, I, I, I, P]),
         "dmi_softmax_finish": (I, [P, I, P, P, P, P, I, P, I, P, P, I, I, P, P, P, P, P, L64, I, I, F, P]),
+        "dmi_softmax_finish_w": (I, [P, I, P, P, P, P, I, P, I, P, P, I, I, P, P, P, P, P, L64, I, I, F, P, I, P]),
+        "dmi_loss_reduce": (I, [P, L64, P, I, I, F, P, P]),
         "dmi_shift_labels": (I, [P, P, I, I, I, P]),
         "dmi_cross_entropy": (I, [P, I, P, P, P, L64, I, F, P]),
         "dmi_sum_f32": (I, [P, L64, F, P, P]),
@@ -542,9 +544,26 @@ def softmax_finish(rowsum_part, nparts, label_logit, rowshift, labels, X, ldx, W
                                     _stream()), "softmax_finish")
 
 
+def softmax_finish_w(rowsum_part, nparts, label_logit, rowshift, labels, X, ldx, Wt, ldw, bias, E, lde, N, loss_rows, rowscale,
+                     rowscale_bf16, Xs, flag, M, K, V, dz_scale, pos_weight, period):
+    """softmax_finish with the static loss weight pos_weight[m % period] (fp32) in row m's gradient scale"""
+    _dev(rowsum_part, label_logit, rowshift, labels, X, Wt, bias, E, loss_rows, flag, pos_weight)
+    _check(lib().dmi_softmax_finish_w(_p(rowsum_part), nparts, _p(label_logit), _p(rowshift), _p(labels), _p(X), ldx, _p(Wt), ldw,
+                                      _p(bias), _p(E), lde, N,
+                                      _p(loss_rows), _p(rowscale), _p(rowscale_bf16), _p(Xs), _p(flag), M, K, V, float(dz_scale),
+                                      _p(pos_weight), int(period), _stream()), "softmax_finish_w")
+
+
 def sum_f32(x, n, scale, out):
     _dev(x, out)
     _check(lib().dmi_sum_f32(_p(x), n, scale, _p(out), _stream()), "sum_f32")
+
+
+def loss_reduce(loss_rows, n, pos_weight, period, split, scale, out3):
+    """out3 fp32 [3] = (scale * sum_m pos_weight[m % period] * loss_rows[m], mean over m % period < split, mean over the rest)"""
+    _dev(loss_rows, pos_weight, out3)
+    _check(lib().dmi_loss_reduce(_p(loss_rows), n, _p(pos_weight), int(period), int(split), float(scale), _p(out3), _stream()),
+           "loss_reduce")
 
 
 def assemble_tokens(text, vae_logits, tokens_out, B, T, P, C, text_vocab):

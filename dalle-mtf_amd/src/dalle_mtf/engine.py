@@ -33,6 +33,7 @@ import torch
 import dalle_hip as dh
 from ..dp import GradReducer
 from .activations import check_activation
+from .loss_weights import position_weights, resolve_loss_weights
 
 @contextlib.contextmanager
 def _no_gc_in_capture():
@@ -167,6 +168,7 @@ class DalleEngine:
     def __init__(self, n_embd, n_layers, n_heads, text_vocab_size, image_vocab_size, text_seq_len, image_seq_len,
                  batch_size, global_batch_size=None, eos_token_id=None, hparams: Optional[dict] = None,
                  device="cuda", process_group=None, world_size=1, comm=None, attn_masks=None):
+        self.loss_weights = resolve_loss_weights(hparams, text_seq_len)   # None: the reference's plain mean
         if not torch.cuda.is_available():
             raise dh.DalleHipError("DalleEngine needs a HIP device (MI355X); there is no CPU fallback")
         dh.lib()
@@ -425,6 +427,14 @@ class DalleEngine:
         self.z = torch.empty(M, Vp, **b16)      # eval: logits; train: E = exp(logit), patched into unnormalised dlogits
         self.loss_rows = torch.empty(M, **f32)
         self.loss = torch.zeros(1, **f32)
+        # hparams["text_loss_weight"] / ["image_loss_weight"] (dalle_mtf.loss_weights): the static weight of every position, computed
+        # in float64 and uploaded once; loss3 = (weighted loss | text mean, image mean), written by dmi_loss_reduce
+        self.pos_weight = self.loss_parts = None
+        if self.loss_weights is not None:
+            w = position_weights(self.T, S - self.T, *self.loss_weights)
+            self.pos_weight = torch.from_numpy(w.astype(np.float32)).to(self.dev)
+            self.loss3 = torch.zeros(3, **f32)
+            self.loss, self.loss_parts = self.loss3[0:1], self.loss3[1:3]
         self.gnorm_sq = torch.zeros(1, **f32)
         # fused softmax head (training path, include/dalle_hip.h K7/K8 (b))
         self.nparts = dh.gemm_nt_softmax_partials(Vp)
@@ -506,6 +516,8 @@ class DalleEngine:
     def forward(self, tokens: torch.Tensor, need_grad=True) -> torch.Tensor:
         """tokens int32 [B,S] on device.  Returns the device scalar loss = mean over ALL B*S positions of
         -log softmax(logits)[label] (src/dalle_mtf/models.py:348-359), labels = shift(tokens) (:407-410).
+        With loss weights set (self.pos_weight): the weighted loss sum_{b,p} w[p] NLL[b,p] / B instead, self.loss_parts = the
+        unweighted (text mean, image mean), and rowscale carries w[p]; self.loss_rows stays the unweighted NLL.
         need_grad=True (training): the softmax is fused into the vocabulary projection -- self.z then holds the
         unnormalised dlogits E, self.rowscale their per-row factor (already scaled by 1/(global B*S*microbatches)).
         need_grad=False (evaluation): self.z holds the bf16 logits (see logits()); the loss is the plain mean
@@ -539,13 +551,21 @@ class DalleEngine:
             e1 = torch.cuda.Event(enable_timing=True)
             e1.record()
             hook().append((e0, e1))
-        if need_grad:
+        weighted = self.pos_weight is not None
+        if need_grad and weighted:
+            dh.softmax_finish_w(self.rowsum_part, self.nparts, self.zl, None, self.labels, self.xnf, d, Wt, d, bias, self.z, Vp, Vp,
+                                self.loss_rows, self.rowscale, self.rowscale_bf, self.xs, self.head_flag, M, d, self.V,
+                                1.0 / (self.B_global * nmb), self.pos_weight, S)
+        elif need_grad:
             dh.softmax_finish(self.rowsum_part, self.nparts, self.zl, None, self.labels, self.xnf, d, Wt, d, bias, self.z, Vp, Vp,
                               self.loss_rows, self.rowscale, self.rowscale_bf, self.xs, self.head_flag, M, d, self.V,
                               1.0 / (self.B_global * S * nmb))
         else:
             dh.cross_entropy(self.z, Vp, self.labels, self.loss_rows, None, M, self.V, 0.0)
-        dh.sum_f32(self.loss_rows, M, 1.0 / (M * nmb), self.loss)
+        if weighted:
+            dh.loss_reduce(self.loss_rows, M, self.pos_weight, S, self.T - 1, 1.0 / (B * nmb), self.loss3)
+        else:
+            dh.sum_f32(self.loss_rows, M, 1.0 / (M * nmb), self.loss)
         return self.loss
 
     def _block_forward(self, l):
@@ -1151,7 +1171,8 @@ class DalleEngine:
     def train_step(self, tokens: torch.Tensor) -> torch.Tensor:
         """One optimizer step.  With hparams["num_microbatches"] = n > 1, `tokens` holds n micro-batches of B rows
         ([n*B, S]): gradients are accumulated locally and reduced once, and the loss is the sum of the micro-batch
-        means / n (mtf.serialize_training_step as used at src/model_fns.py:156-166; src/dalle_mtf/models.py:356)."""
+        means / n (mtf.serialize_training_step as used at src/model_fns.py:156-166; src/dalle_mtf/models.py:356).  With loss
+        weights set, self.loss_parts_acc accumulates the micro-batches' (text mean, image mean) / n the same way."""
         nmb = self.hp.get("num_microbatches", 1) or 1
         if nmb == 1:
             loss = self.forward(tokens, need_grad=True)
@@ -1164,9 +1185,15 @@ class DalleEngine:
         if getattr(self, "loss_acc", None) is None:
             self.loss_acc = torch.zeros_like(self.loss)
         self.loss_acc.zero_()
+        if self.loss_parts is not None:
+            if getattr(self, "loss_parts_acc", None) is None:
+                self.loss_parts_acc = torch.zeros_like(self.loss_parts)
+            self.loss_parts_acc.zero_()
         for i in range(nmb):
             loss = self.forward(tokens[i * self.B:(i + 1) * self.B], need_grad=True)
             self.loss_acc += loss
+            if self.loss_parts is not None:
+                self.loss_parts_acc.add_(self.loss_parts, alpha=1.0 / nmb)
             self.backward(allreduce=False)
             if i == 0:
                 self.gacc.copy_(self.g)

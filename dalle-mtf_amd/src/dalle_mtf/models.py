@@ -8,6 +8,7 @@ import numpy as np
 
 from .activations import resolve_activation
 from .engine import DalleEngine
+from .loss_weights import resolve_loss_weights
 from .masks import layer_masks
 from .ops import get_variable_dtype
 
@@ -52,6 +53,8 @@ class DALLE:
         # activation_fn (reference models.py:317-324, the FFN's hidden layer): "relu" | "gelu" | None -> config key "activation_fn"
         # -> "relu" (dalle_mtf.activations)
         self.activation_fn = resolve_activation(activation_fn, params)
+        # "text_loss_weight" / "image_loss_weight" (dalle_mtf.loss_weights): checked here, before any device work
+        resolve_loss_weights(params, text_seq_len)
         for k in ("embed_dropout", "attention_dropout", "residual_dropout"):
             if self.params.get(k):
                 raise NotImplementedError(f"{k} > 0 is not supported (all shipped configs use 0)")
@@ -113,7 +116,8 @@ class DALLE:
 
     def forward(self, features, return_loss=True, return_logits=False):
         """features["tokens"]: int32 [B, S] device tensor.  Returns (loss, loss_batch[, logits]) like the
-        reference (models.py:397-416); with return_loss=False returns the fp32 logits only."""
+        reference (models.py:397-416); with return_loss=False returns the fp32 logits only.  With loss weights set, loss is
+        the weighted loss; loss_batch stays the unweighted per-position NLL."""
         tokens = features["tokens"] if isinstance(features, dict) else features
         tokens = tokens.to(device=self.engine.dev, dtype=torch.int32)
         need_grad = self.mode == "train" and return_loss and not return_logits

@@ -6,6 +6,7 @@ gradient all-reduce over the data axis, clip + Adam -> EstimatorSpec(loss, train
 The TF graph/session split becomes: the model is built once and cached on `params`; each call runs the
 forward eagerly and returns a spec whose train_op() runs backward + optimizer and returns the new
 global step.  predict raises NotImplementedError exactly like the reference (model_fns.py:135-136)."""
+import logging
 import os
 
 import torch
@@ -150,6 +151,11 @@ def _build(params, mode_str):
                   batch_size=local_bs // nmb, bf_16=params["bf_16"], mode=mode_str, params=params,
                   process_group=pg, world_size=world, global_batch_size=gbs // nmb, comm=comm)
     eng = model.engine
+    if eng.loss_weights is not None and rank == 0:
+        # "text_loss_weight" / "image_loss_weight" (dalle_mtf.loss_weights; they reach the engine's hparams through `params`)
+        logging.getLogger("dalle_mtf_amd").info(
+            "%s loss weights: text %g, image %g -> loss = (%g * mean_text + %g * mean_image) / %g over %d text and %d image positions",
+            mode_str, *eng.loss_weights, *eng.loss_weights, sum(eng.loss_weights), eng.T - 1, image_seq_len + 1)
     eng.hp["num_microbatches"] = nmb   # reference model_fns.py:141-154 (1 when tokens_per_mb_per_replica is unset)
     params["num_microbatches"] = nmb
     state["local_bs"] = local_bs
@@ -234,6 +240,11 @@ def dalle_model_fn(features, labels, mode, params):
             eng.train_step(tokens)
             return eng.global_step
         scalar_summary("loss", eng.loss_acc[0])
+        if eng.loss_parts is not None:
+            if getattr(eng, "loss_parts_acc", None) is None:
+                eng.loss_parts_acc = torch.zeros_like(eng.loss_parts)
+            scalar_summary("loss_text", eng.loss_parts_acc[0])
+            scalar_summary("loss_image", eng.loss_parts_acc[1])
         scalar_summary("lr", st["lr_fn"]())
         return EstimatorSpec(mode=mode, loss=eng.loss_acc[0], train_op=train_op_mb,
                              host_call=create_host_call(params["model_path"]) if (params.get("model_path") and st["rank"] == 0) else None,
@@ -241,13 +252,21 @@ def dalle_model_fn(features, labels, mode, params):
     if mode == ModeKeys.EVAL:
         # the engine may have been sized for one training micro-batch: evaluate the batch in engine-sized chunks (equal
         # sizes, so the mean of the chunk means is the batch mean, src/dalle_mtf/models.py:354)
-        total = None
+        total = parts = None
         for c in range(B // eng.B):
             l, _ = model.forward({"tokens": tokens[c * eng.B:(c + 1) * eng.B]}, return_loss=True)
             total = l.clone() if total is None else total + l
+            if eng.loss_parts is not None:
+                parts = eng.loss_parts.clone() if parts is None else parts + eng.loss_parts
+        if parts is not None:
+            scalar_summary("loss_text", parts[0] / (B // eng.B))
+            scalar_summary("loss_image", parts[1] / (B // eng.B))
         return EstimatorSpec(mode=mode, loss=total / (B // eng.B))
     loss, _loss_batch = model.forward({"tokens": tokens}, return_loss=True)
     scalar_summary("loss", loss)
+    if eng.loss_parts is not None:
+        scalar_summary("loss_text", eng.loss_parts[0])
+        scalar_summary("loss_image", eng.loss_parts[1])
     scalar_summary("lr", st["lr_fn"]())
 
     def train_op():

@@ -273,6 +273,26 @@ int dmi_softmax_finish(const float* rowsum_part, int nparts, const float* label_
                        int64_t M, int K, int V, float dz_scale, void* stream);
 /* out[0] = scale * sum(x[0..n))  deterministic single-block reduce (loss mean; grad-norm finish) */
 int dmi_sum_f32(const float* x, int64_t n, float scale, float* out, void* stream);
+/* Text/image loss weights (a project extension: the reference's loss is the plain mean over all positions,
+ * src/dalle_mtf/models.py:348-359; position p predicts token p + 1, models.py:407-410).  Every row m carries the static weight
+ * w = pos_weight[m % period] (fp32 [period], period = the sequence length):
+ *   dmi_softmax_finish_w  dmi_softmax_finish with rowscale[m] = (dz_scale * w) / S[m] (fp32, the product first); rowscale_bf16 and Xs
+ *                         derive from that rowscale, in the exact redo of flagged rows too.  loss_rows (the reference's unweighted
+ *                         loss_batch), the label patch E[m,label] -= S[m] and the flag logic are those of dmi_softmax_finish, bit for
+ *                         bit: the weight reaches both gradient products through rowscale alone.  w == 0 gives rowscale,
+ *                         rowscale_bf16 and the Xs row exactly 0.  pos_weight non-null, period > 0; otherwise as dmi_softmax_finish.
+ *   dmi_loss_reduce       out3[0] = scale * sum_m pos_weight[m % period] * loss_rows[m] (the weighted loss);
+ *                         out3[1] = plain mean of loss_rows over rows with m % period < split (the text positions),
+ *                         out3[2] = plain mean over the other rows (the image positions); a mean over no rows is 0.
+ *                         Deterministic single-block reduce (fixed order, no atomics), in place of dmi_sum_f32 when weights are set.
+ *                         M > 0, period > 0, 0 <= split <= period. */
+int dmi_softmax_finish_w(const float* rowsum_part, int nparts, const float* label_logit, const float* rowshift,
+                         const int32_t* labels, const uint16_t* X, int ldx,
+                         const uint16_t* Wt, int ldw, const uint16_t* bias, uint16_t* E, int lde, int N,
+                         float* loss_rows, float* rowscale, uint16_t* rowscale_bf16, uint16_t* Xs, int32_t* flag,
+                         int64_t M, int K, int V, float dz_scale, const float* pos_weight, int period, void* stream);
+int dmi_loss_reduce(const float* loss_rows, int64_t M, const float* pos_weight, int period, int split, float scale,
+                    float* out3, void* stream);
 
 /* ---- K10  image-token indexing   src/model_fns.py:76-77,118-119 (bit-exact)
  * tokens_out[b, 0:T] = text[b]; tokens_out[b, T + p] = argmax_c logits[b, p, c] (first max) + text_vocab */
