@@ -460,3 +460,65 @@ extern "C" int dmi_adafactor_step(const int64_t* table_dev, int nvars, const int
   DMI_CHECK_LAUNCH("adafactor_apply");
   return DMI_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------- weight EMA
+// tf.train.ExponentialMovingAverage (assign_moving_average): ema -= (ema - p) * one_minus_decay over the flat parameter buffer,
+// one streaming pass per optimizer step (DESIGN.md §4 "Weight EMA").  Difference, product and second difference are each rounded
+// to fp32 on their own (no fused multiply-add: a numpy float32 restatement gives the same bits); the bf16 copy is rounded from the
+// fp32 value that is stored.  16-byte loads and stores (8-byte for the bf16 quad) over the n / 4 whole quads, the n % 4 tail
+// element-wise by block 0; 64-bit indices; the grid follows the CU count, not n.  No atomics, no workspace.
+__device__ __forceinline__ float ema_update(float e, float p, float omd) {
+#pragma clang fp contract(off)
+  const float d = e - p;
+  const float t = d * omd;
+  return e - t;
+}
+
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, bf16_t* __restrict__ eb, int64_t n,
+                                                  float omd) {
+  const int64_t n4 = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    f32x4 ev = ((const f32x4*)ema)[i];
+    const f32x4 pv = ((const f32x4*)p)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ev[j] = ema_update(ev[j], pv[j], omd);
+    ((f32x4*)ema)[i] = ev;
+    if (eb) *(u32x2*)(eb + i * 4) = u32x2{pack2bf(ev[0], ev[1]), pack2bf(ev[2], ev[3])};
+  }
+  if (blockIdx.x == 0 && (int64_t)threadIdx.x < (n & 3)) {
+    const int64_t i = n4 * 4 + threadIdx.x;
+    const float e = ema_update(ema[i], p[i], omd);
+    ema[i] = e;
+    if (eb) eb[i] = f2bf(e);
+  }
+}
+
+static int ema_num_cus() {
+  static int n = 0;
+  if (!n) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+      n = prop.multiProcessorCount;
+    else
+      n = 256;
+  }
+  return n;
+}
+
+#define EMA_BLOCKS_PER_CU 8   // 8 blocks of 4 waves: every CU's 32 wave slots hold a stream of 16-byte requests
+
+extern "C" int dmi_ema_step(float* ema, const float* p, uint16_t* ema_bf16, int64_t n, float one_minus_decay, void* stream) {
+  DMI_REQUIRE(ema && p, "ema_step: null pointer (ema or p)");
+  DMI_REQUIRE(n > 0, "ema_step: n must be positive (n=%lld)", (long long)n);
+  DMI_REQUIRE((((uintptr_t)ema | (uintptr_t)p | (uintptr_t)ema_bf16) & 15) == 0, "ema_step: buffers must be 16-byte aligned");
+  DMI_REQUIRE(one_minus_decay >= 0.f && one_minus_decay <= 1.f, "ema_step: one_minus_decay must lie in [0, 1] (one_minus_decay=%g)",
+              (double)one_minus_decay);   // (NaN fails both comparisons)
+  int64_t blocks = cdiv64(n / 4 + 1, 256);
+  const int64_t cap = (int64_t)ema_num_cus() * EMA_BLOCKS_PER_CU;
+  if (blocks > cap) blocks = cap;
+  ema_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(ema, p, ema_bf16, n, one_minus_decay);
+  DMI_CHECK_LAUNCH("ema_step");
+  return DMI_OK;
+}

@@ -119,6 +119,7 @@ def _declare(L):
         "dmi_sumsq_workspace_bytes": (L64, [L64]),
         "dmi_sumsq": (I, [P, L64, P, P, P]),
         "dmi_adam_step": (I, [P, P, P, P, P, L64, P, F, F, F, F, F, F, F, P, P]),
+        "dmi_ema_step": (I, [P, P, P, L64, F, P]),
         "dmi_adafactor_plan": (I, [P, I, P]),
         "dmi_adafactor_step": (I, [P, I, P, P, P, P, P, P, P, F, F, P, F, F, F, F, P, L64, P]),
         "dmi_cast_f32_bf16": (I, [P, P, L64, P]),
@@ -683,6 +684,15 @@ def adam_step(p, g, m, v, p_bf16, n, gnorm_sq, clip, lr, beta1, beta2, eps, wd, 
     _dev(p, g, m, v)
     _check(lib().dmi_adam_step(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), n, _p(gnorm_sq), clip, lr, beta1, beta2, eps,
                                wd, grad_scale, _p(lr_dev), _stream()), "adam_step")
+
+
+def ema_step(ema, p, ema_bf16, n, one_minus_decay):
+    """ema <- ema - (ema - p) * one_minus_decay over n fp32 elements (tf.train.ExponentialMovingAverage); ema_bf16 (optional)
+    takes bf16(new ema).  Three separately rounded fp32 operations per element."""
+    _dev(ema, p, ema_bf16)
+    assert ema.dtype == torch.float32 and p.dtype == torch.float32 and ema.numel() >= n and p.numel() >= n
+    assert ema_bf16 is None or (ema_bf16.dtype == torch.bfloat16 and ema_bf16.numel() >= n)
+    _check(lib().dmi_ema_step(_p(ema), _p(p), _p(ema_bf16), int(n), float(one_minus_decay), _stream()), "ema_step")
 
 
 AF_FIELDS = 17   # DMI_AF_FIELDS: int64 per variable in an Adafactor descriptor table

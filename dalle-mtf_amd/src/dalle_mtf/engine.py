@@ -22,6 +22,7 @@ from __future__ import annotations
 import contextlib
 import gc
 import hashlib
+import logging
 import math
 import os
 from collections import OrderedDict
@@ -33,6 +34,7 @@ import torch
 import dalle_hip as dh
 from ..dp import GradReducer
 from .activations import check_activation
+from .ema import ema_decay_at, one_minus_decay, resolve_ema, resolve_weights   # noqa: F401  (ema_decay_at: part of the engine's surface)
 from .loss_weights import position_weights, resolve_loss_weights
 
 @contextlib.contextmanager
@@ -169,6 +171,7 @@ class DalleEngine:
                  batch_size, global_batch_size=None, eos_token_id=None, hparams: Optional[dict] = None,
                  device="cuda", process_group=None, world_size=1, comm=None, attn_masks=None):
         self.loss_weights = resolve_loss_weights(hparams, text_seq_len)   # None: the reference's plain mean
+        self.ema_decay, self.ema_eval = resolve_ema(hparams)              # None: no weight average (dalle_mtf.ema)
         if not torch.cuda.is_available():
             raise dh.DalleHipError("DalleEngine needs a HIP device (MI355X); there is no CPU fallback")
         dh.lib()
@@ -201,6 +204,13 @@ class DalleEngine:
         self.set_optimizer(self.hp.get("optimizer") or "adam")
         self.pb = torch.zeros(n, **b16)
         self.pbt = torch.zeros(self.lay.t_total, **b16)
+        # hparams["ema_decay"]: tf.train.ExponentialMovingAverage of the flat buffer, fp32 + its bf16 copy (6 bytes per parameter),
+        # updated by one launch per optimizer step (DESIGN.md §4 "Weight EMA"); unset: no buffer, no launch
+        self.ema = self.ema_b = None
+        self._in_ema = False        # inside ema_weights(): pb / pbt hold the average
+        self._ema_logged = False
+        if self.ema_decay is not None:
+            self._alloc_ema()
         self.global_step = 0
         # The exchange's RCCL channels run beside the BACKWARD: there the persistent kernels leave CUs for them (a block of a
         # one-block-per-CU kernel whose CU an intruder holds starts when the others have finished: the launch takes twice as long --
@@ -328,6 +338,7 @@ class DalleEngine:
                 else:
                     dst.copy_(torch.from_numpy(np.ascontiguousarray(P[name])).view(shp))
         self.refresh_compute_copies(cast=True)
+        self._ema_from_p()
 
     def export_reference(self, buf=None) -> "OrderedDict[str, np.ndarray]":
         """Inverse of load_reference_params for any flat buffer (params, grads, m, v)."""
@@ -346,6 +357,50 @@ class DalleEngine:
             else:
                 out[name] = a
         return out
+
+    # ------------------------------------------------------------------ weight EMA
+    def _alloc_ema(self):
+        self.ema = torch.zeros(self.lay.total, dtype=torch.float32, device=self.dev)
+        self.ema_b = torch.zeros(self.lay.total, dtype=torch.bfloat16, device=self.dev)
+
+    def _ema_from_p(self):
+        """the average restarts from the parameters wherever they are set as a whole (pb = bf16(p) at that point)"""
+        if self.ema is not None:
+            self.ema.copy_(self.p)
+            self.ema_b.copy_(self.pb)
+
+    def _ema_update(self):
+        """ema <- ema - (ema - p) * (1 - decay_t), t = the 0-based step of this update; behind the optimizer's launch.  An
+        average that came with a checkpoint into a run without the key stays as loaded."""
+        if self.ema_decay is not None:
+            dh.ema_step(self.ema, self.p, self.ema_b, self.lay.total, one_minus_decay(self.ema_decay, self.global_step))
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """forward / evaluation / decode_step / sample_image_tokens inside the block compute from the averaged weights.  The
+        average is COPIED into the storage of pb (and pbt re-derived from it by the batched transpose); the raw pb is stashed
+        and copied back on exit.  No tensor is rebound: the captured decode graphs hold the addresses of pb and pbt.  p and
+        the optimizer state are not touched; training inside the block raises RuntimeError."""
+        if self.ema is None:
+            raise ValueError("ema_weights(): this engine keeps no weight average (hparams['ema_decay'] is unset and no checkpoint "
+                             "brought one)")
+        if self._in_ema:            # nested: already computing from the average
+            yield self
+            return
+        stash = self.pb.clone()
+        self.pb.copy_(self.ema_b)
+        self.refresh_compute_copies(cast=False)
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            self.pb.copy_(stash)
+            self.refresh_compute_copies(cast=False)
+            self._in_ema = False
+
+    def _not_in_ema(self, what):
+        if self._in_ema:
+            raise RuntimeError(f"{what} inside ema_weights(): the compute copies hold the averaged weights, not the ones being trained")
 
     def init_params(self, seed=1234):
         """Reference initialisers drawn with torch's generator on the host."""
@@ -624,7 +679,7 @@ class DalleEngine:
     def sample_image_tokens(self, text: torch.Tensor, temperature: float = 1.0, top_k: int = 0, seed: int = 0,
                             top_p: float = 1.0, image_prefix: Optional[torch.Tensor] = None, return_logprobs: bool = False,
                             kv_cache: bool = True, decode_graph: bool = True, fused_sampling: bool = True,
-                            guidance_scale: float = 1.0, uncond_text: Optional[torch.Tensor] = None):
+                            guidance_scale: float = 1.0, uncond_text: Optional[torch.Tensor] = None, weights: Optional[str] = None):
         """Autoregressive image-token sampling: text int32 [B, T] -> image-token ids [B, P] in [0, image_vocab_size).
         The reference scaffolds this (is_incremental_inference, models.py:246-254,281-285) but its predict path raises
         NotImplementedError (model_fns.py:135-136).  Logits are restricted to the image vocabulary; temperature / top-k /
@@ -663,7 +718,19 @@ class DalleEngine:
         draw is dmi_sample_tokens_guided (include/dalle_hip.h) on every path: pair b draws ONE token from
         l_uncond + guidance_scale * (l_cond - l_uncond) and both rows are fed it.  image_prefix is [Bc, k] and is
         teacher-forced into both halves.  Returns tokens [Bc, P] (and logp [Bc]: the conditional rows' own log-likelihood of
-        the drawn tokens, unguided, temperature 1)."""
+        the drawn tokens, unguided, temperature 1).
+
+        weights: "ema" samples from the weight average (inside ema_weights()), "raw" from the raw iterate, None from the
+        average when the engine has one.  "ema" without an average raises ValueError."""
+        which = resolve_weights(weights, self.ema is not None)
+        if which == "ema" and not self._in_ema:
+            with self.ema_weights():
+                return self.sample_image_tokens(text, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p,
+                                                image_prefix=image_prefix, return_logprobs=return_logprobs, kv_cache=kv_cache,
+                                                decode_graph=decode_graph, fused_sampling=fused_sampling,
+                                                guidance_scale=guidance_scale, uncond_text=uncond_text, weights="ema")
+        if which == "raw" and self._in_ema:
+            raise RuntimeError("sample_image_tokens(weights='raw') inside ema_weights(): the compute copies hold the average")
         B, T, S, P = self.B, self.T, self.S, self.S - self.T
         gs = float(guidance_scale)
         if not (gs >= 0.0 and math.isfinite(gs)):
@@ -945,6 +1012,7 @@ class DalleEngine:
         """Gradients of the last forward(need_grad=True) into the flat fp32 buffer.  With world_size > 1 every finished
         prefix of the buffer is handed to the exchange (src/dp.py: SUM all-reduce in <= 64 MB pieces on the side stream) --
         the explicit form of mtf's implicit all-reduce over the `data` mesh axis (src/model_fns.py:81-82,189)."""
+        self._not_in_ema("backward")
         reserve = self.dp_reserve_cus if allreduce else 0
         if not reserve:
             return self._backward(allreduce)
@@ -1120,6 +1188,7 @@ class DalleEngine:
     def optimizer_step(self):
         """the optimizer src/optimizers.py:78-99 selects, on the all-reduced gradients; refreshes the bf16 compute copies"""
         self.wait_grads()
+        self._not_in_ema("optimizer_step")
         if self.optimizer == "adafactor":
             return self._adafactor_step()
         return self._adam_step()
@@ -1136,6 +1205,7 @@ class DalleEngine:
         dh.adafactor_step(self.af_table, len(self.af_vars), self.af_totals, self.p, self.g, self.m, self.af_slots, self.pb,
                           self.gnorm_sq, 0.0 if clip is None else float(clip), lr, get("weight_decay", 0.0), self._af_beta1(),
                           get("epsilon_1", 1e-30), get("epsilon_2", 1e-3), self.af_ws)
+        self._ema_update()
         self.refresh_compute_copies(cast=False)
         self.global_step += 1
         return lr
@@ -1164,6 +1234,7 @@ class DalleEngine:
                 use = ("norm" not in name) and ("bias" not in name) and not name.endswith("o_b")
                 dh.adam_step(self.p[o:o + k], self.g[o:o + k], self.m[o:o + k], self.v[o:o + k], self.pb[o:o + k], k, gn, cl,
                              lr, b1, b2, eps, wd if use else 0.0)
+        self._ema_update()
         self.refresh_compute_copies(cast=False)
         self.global_step += 1
         return lr
@@ -1173,6 +1244,7 @@ class DalleEngine:
         ([n*B, S]): gradients are accumulated locally and reduced once, and the loss is the sum of the micro-batch
         means / n (mtf.serialize_training_step as used at src/model_fns.py:156-166; src/dalle_mtf/models.py:356).  With loss
         weights set, self.loss_parts_acc accumulates the micro-batches' (text mean, image mean) / n the same way."""
+        self._not_in_ema("train_step")
         nmb = self.hp.get("num_microbatches", 1) or 1
         if nmb == 1:
             loss = self.forward(tokens, need_grad=True)
@@ -1213,6 +1285,8 @@ class DalleEngine:
         for k in ("m", "v", "af_slots"):
             if getattr(self, k) is not None:
                 sd[k] = getattr(self, k).detach().cpu()
+        if self.ema is not None:       # the bf16 copy is recomputed on load
+            sd["ema"] = self.ema.detach().cpu()
         return sd
 
     def load_state_dict(self, sd):
@@ -1232,3 +1306,14 @@ class DalleEngine:
                 getattr(self, k).copy_(sd[k])
         self.global_step = int(sd["global_step"])
         self.refresh_compute_copies(cast=True)
+        if "ema" in sd:
+            if self.ema is None:       # the run's config keeps no average: hold the checkpoint's for sampling, never update it
+                self._alloc_ema()
+            self.ema.copy_(sd["ema"])
+            dh.cast_f32_bf16(self.ema, self.ema_b, self.lay.total)
+        elif self.ema is not None:
+            self._ema_from_p()
+            if not self._ema_logged:
+                self._ema_logged = True
+                logging.getLogger("dalle_mtf_amd").info("checkpoint (step %d) carries no weight average: ema starts from its weights",
+                                                        self.global_step)

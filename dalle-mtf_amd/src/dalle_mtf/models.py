@@ -7,6 +7,7 @@ import torch
 import numpy as np
 
 from .activations import resolve_activation
+from .ema import resolve_ema
 from .engine import DalleEngine
 from .loss_weights import resolve_loss_weights
 from .masks import layer_masks
@@ -55,6 +56,8 @@ class DALLE:
         self.activation_fn = resolve_activation(activation_fn, params)
         # "text_loss_weight" / "image_loss_weight" (dalle_mtf.loss_weights): checked here, before any device work
         resolve_loss_weights(params, text_seq_len)
+        # "ema_decay" / "ema_eval" (dalle_mtf.ema): likewise
+        resolve_ema(params)
         for k in ("embed_dropout", "attention_dropout", "residual_dropout"):
             if self.params.get(k):
                 raise NotImplementedError(f"{k} > 0 is not supported (all shipped configs use 0)")
@@ -97,17 +100,19 @@ class DALLE:
         return out
 
     def sample(self, text_tokens, vae=None, temperature=1.0, top_k=0, seed=0, top_p=1.0, image_prefix=None, return_logprobs=False,
-               guidance_scale=1.0, uncond_text=None):
+               guidance_scale=1.0, uncond_text=None, weights=None):
         """text ids [B, text_seq_len] -> image-token ids [B, image_seq_len] (and the decoded images when a DiscreteVAE is
         given): the generation path the reference leaves unfinished (model_fns.py:135-136).  top_p < 1: nucleus filter after
         top-k; image_prefix int [B, k]: complete images from their first k tokens; return_logprobs: also the model's
         log-likelihood of each sample, fp32 [B] (DalleEngine.sample_image_tokens).  guidance_scale != 1 / uncond_text:
         classifier-free guidance -- text_tokens (and image_prefix) are [B / 2, ...], the other half of the batch carries
-        uncond_text (default: the null caption), and B / 2 rows come back.  Returns toks, (toks, images), (toks, logp) or
+        uncond_text (default: the null caption), and B / 2 rows come back.  weights: "ema" samples from the weight average
+        (config key "ema_decay"), "raw" from the raw iterate, None from the average when the engine has one; "ema" without an
+        average raises ValueError.  Returns toks, (toks, images), (toks, logp) or
         (toks, images, logp)."""
         res = self.engine.sample_image_tokens(text_tokens, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p,
                                               image_prefix=image_prefix, return_logprobs=return_logprobs,
-                                              guidance_scale=guidance_scale, uncond_text=uncond_text)
+                                              guidance_scale=guidance_scale, uncond_text=uncond_text, weights=weights)
         toks, logp = res if return_logprobs else (res, None)
         out = (toks, vae.decode_tokens(toks)) if vae is not None else (toks,)
         if return_logprobs:

@@ -14,6 +14,8 @@ Rows are generated in batches of --batch (the last one padded by repeating its r
 of a batch draw different noise because the counter-based noise hashes the row.  --guidance-scale S != 1 (classifier-free
 guidance) pairs every row with a null-caption row in the same batch, so a batch of --batch engine rows generates --batch / 2
 output rows; the files keep their shapes per caption and per sample, and logprob.npy stays the conditional model's own score.
+--weights ema | raw samples from the run's weight average (config key "ema_decay") or from the raw iterate; auto (default)
+takes the average when the checkpoint or the config has one.  generate.json records the resolved choice.
 Every argument is checked before the GPU is touched."""
 import argparse
 import json
@@ -48,6 +50,9 @@ def build_parser():
     p.add_argument("--guidance-scale", dest="guidance_scale", type=float, default=1.0,
                    help="classifier-free guidance: draw from l_uncond + S (l_cond - l_uncond), the unconditional rows carrying the "
                         "null caption; a batch then generates --batch / 2 rows.  1 = off (default)")
+    p.add_argument("--weights", choices=("auto", "ema", "raw"), default="auto",
+                   help="sample from the weight average (ema), the raw iterate (raw), or the average when the run has one (auto, "
+                        "default)")
     p.add_argument("--seed", type=int, default=0, help="batch j draws with seed + j")
     p.add_argument("--no-images", dest="no_images", action="store_true", help="write tokens and scores only")
     return p
@@ -177,6 +182,12 @@ def generate(argv=None):
     if st["restored_from"] is None:
         print("generate: no DALL-E checkpoint found (model_path / --checkpoint / tf_checkpoint): sampling from freshly "
               "initialised weights", file=sys.stderr)
+    from src.dalle_mtf.ema import resolve_weights
+    try:
+        which = resolve_weights(args.weights, eng.ema is not None)
+    except ValueError:
+        raise SystemExit(f"generate_dalle.py: --weights ema: no weight average to sample from: the checkpoint "
+                         f"({st['restored_from']}) carries none and the config sets no ema_decay")
     torch.cuda.synchronize()
     t_load = time.perf_counter() - t0
 
@@ -209,7 +220,7 @@ def generate(argv=None):
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         toks, lp = model.sample(cap, temperature=args.temperature, top_k=args.top_k, seed=args.seed + j, top_p=args.top_p,
-                                image_prefix=pre, return_logprobs=True, guidance_scale=args.guidance_scale)
+                                image_prefix=pre, return_logprobs=True, guidance_scale=args.guidance_scale, weights=which)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         m = min(Bg, rows - j * Bg)
@@ -234,7 +245,7 @@ def generate(argv=None):
     vae_ck = (params.get("vae_checkpoint_path") or None) if vae is not None else None
     info = dict(model=args.model, checkpoint=st["restored_from"], vae_checkpoint=vae_ck, captions=int(N), samples_per_caption=n,
                 rows=int(rows), batch=int(B), batches=int(nb), seed=args.seed, seeds=f"batch j draws with seed + j",
-                temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, guidance_scale=args.guidance_scale, image_prefix=K, image_seq_len=int(P),
+                temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, guidance_scale=args.guidance_scale, weights=which, image_prefix=K, image_seq_len=int(P),
                 source=next(s for s in SOURCES if getattr(args, s) is not None), images_written=len(images),
                 recompute_grad=bool(eng.recompute),
                 seconds=dict(load=round(t_load, 3), sample=round(t_sample, 3), decode_and_copy=round(t_decode, 3)),

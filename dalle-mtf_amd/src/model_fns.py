@@ -6,6 +6,7 @@ gradient all-reduce over the data axis, clip + Adam -> EstimatorSpec(loss, train
 The TF graph/session split becomes: the model is built once and cached on `params`; each call runs the
 forward eagerly and returns a spec whose train_op() runs backward + optimizer and returns the new
 global step.  predict raises NotImplementedError exactly like the reference (model_fns.py:135-136)."""
+import contextlib
 import logging
 import os
 
@@ -156,6 +157,11 @@ def _build(params, mode_str):
         logging.getLogger("dalle_mtf_amd").info(
             "%s loss weights: text %g, image %g -> loss = (%g * mean_text + %g * mean_image) / %g over %d text and %d image positions",
             mode_str, *eng.loss_weights, *eng.loss_weights, sum(eng.loss_weights), eng.T - 1, image_seq_len + 1)
+    if eng.ema_decay is not None and rank == 0:
+        # "ema_decay" / "ema_eval" (dalle_mtf.ema; they reach the engine's hparams through `params`)
+        logging.getLogger("dalle_mtf_amd").info(
+            "%s weight EMA: ema_decay %g (decay at step t = min(%g, (1 + t) / (10 + t))), evaluation from the %s weights",
+            mode_str, eng.ema_decay, eng.ema_decay, "averaged" if eng.ema_eval else "raw")
     eng.hp["num_microbatches"] = nmb   # reference model_fns.py:141-154 (1 when tokens_per_mb_per_replica is unset)
     params["num_microbatches"] = nmb
     state["local_bs"] = local_bs
@@ -163,12 +169,14 @@ def _build(params, mode_str):
     if world > 1:
         # every rank starts from rank 0's weights, optimizer state AND step (the LR schedule and the loop length depend on it)
         import torch.distributed as dist
-        for buf in [eng.p] + eng.optimizer_buffers():
+        for buf in [eng.p] + eng.optimizer_buffers() + ([eng.ema] if eng.ema is not None else []):
             eng.reducer.broadcast(buf, root=0)
         box = [eng.global_step]
         dist.broadcast_object_list(box, src=0, group=pg)
         eng.global_step = int(box[0])
         eng.refresh_compute_copies(cast=True)
+        if eng.ema is not None:
+            dh.cast_f32_bf16(eng.ema, eng.ema_b, eng.lay.total)
     lr_fn, update_op = get_optimizer(eng, params)
     if rank == 0:
         get_graph_info(model.variables())
@@ -202,6 +210,9 @@ def dalle_model_fn(features, labels, mode, params):
             if st.get("_synced_step") != tr["model"].engine.global_step:
                 eng.p.copy_(tr["model"].engine.p)
                 eng.refresh_compute_copies(cast=True)
+                if eng.ema is not None and tr["model"].engine.ema is not None:
+                    eng.ema.copy_(tr["model"].engine.ema)
+                    eng.ema_b.copy_(tr["model"].engine.ema_b)
                 st["_synced_step"] = tr["model"].engine.global_step
         else:
             ck = latest_checkpoint(params["model_path"]) if params.get("model_path") else None
@@ -252,12 +263,14 @@ def dalle_model_fn(features, labels, mode, params):
     if mode == ModeKeys.EVAL:
         # the engine may have been sized for one training micro-batch: evaluate the batch in engine-sized chunks (equal
         # sizes, so the mean of the chunk means is the batch mean, src/dalle_mtf/models.py:354)
+        # "ema_eval": the losses of the averaged weights (DalleEngine.ema_weights)
         total = parts = None
-        for c in range(B // eng.B):
-            l, _ = model.forward({"tokens": tokens[c * eng.B:(c + 1) * eng.B]}, return_loss=True)
-            total = l.clone() if total is None else total + l
-            if eng.loss_parts is not None:
-                parts = eng.loss_parts.clone() if parts is None else parts + eng.loss_parts
+        with eng.ema_weights() if eng.ema_eval else contextlib.nullcontext():
+            for c in range(B // eng.B):
+                l, _ = model.forward({"tokens": tokens[c * eng.B:(c + 1) * eng.B]}, return_loss=True)
+                total = l.clone() if total is None else total + l
+                if eng.loss_parts is not None:
+                    parts = eng.loss_parts.clone() if parts is None else parts + eng.loss_parts
         if parts is not None:
             scalar_summary("loss_text", parts[0] / (B // eng.B))
             scalar_summary("loss_image", parts[1] / (B // eng.B))

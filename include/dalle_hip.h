@@ -369,6 +369,14 @@ int dmi_adam_step(float* p, const float* g, float* m, float* v, uint16_t* p_bf16
                   const float* gnorm_sq, float clip, float lr, float beta1, float beta2, float eps,
                   float weight_decay, float grad_scale, const float* lr_dev, void* stream);
 
+/* Weight EMA over the flat parameter buffer (a project extension: hparams "ema_decay"), once per optimizer step:
+ * ema[i] <- ema[i] - (ema[i] - p[i]) * one_minus_decay   (tf.train.ExponentialMovingAverage / assign_moving_average);
+ * ema_bf16[i] (nullable) = bf16(new ema[i]), round-to-nearest-even as dmi_cast_f32_bf16.
+ * Difference, product and second difference are each rounded to fp32 (no fused multiply-add); NaN / Inf propagate as IEEE gives
+ * them.  Nothing at or past index n is touched; no workspace, deterministic.  DMI_ERR_INVALID: null ema or p, n <= 0, a buffer
+ * that is not 16-byte aligned, one_minus_decay NaN or outside [0, 1]. */
+int dmi_ema_step(float* ema, const float* p, uint16_t* ema_bf16, int64_t n, float one_minus_decay, void* stream);
+
 /* ---- K9b  mtf.optimize.AdafactorOptimizer   src/optimizers.py:91-97 (get_optimizer, "optimizer": "adafactor"), clip :100-103
  * Per variable, with gc = mult * g the clipped gradient (mult as for dmi_adam_step) and w the variable before the step:
  *   g2 = gc^2 + eps1;  scale = lr * max(rms(w), eps2)   (rms over the variable's real elements)
