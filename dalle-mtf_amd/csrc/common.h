@@ -59,6 +59,42 @@ __device__ __forceinline__ float wave_max(float x) {
   return x;
 }
 
+// ------------------------------------------------------------------ stateless dropout mask (DESIGN.md §4 "Dropout")
+__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+// One dropout site: element e of the site's tensor (row-major) is kept iff ((splitmix64(key + (e >> 2)) >> 16 (e & 3)) & 0xffff)
+// >= thresh, kept elements are multiplied by scale = fp32(65536 / (65536 - thresh)), dropped ones are +0.  One hash serves
+// four elements; nothing is stored: forward, its re-run under recompute_grad and backward restate the mask from the key.
+struct DropSite {
+  uint64_t key;
+  unsigned thresh;
+  float scale;
+};
+static inline DropSite drop_site(uint64_t key, int thresh) { return DropSite{key, (unsigned)thresh, (float)(65536.0 / (65536 - thresh))}; }
+// f[0..8) = the eight elements starting at element index e0 (a multiple of 8); the product is rounded on its own (never fused into
+// a following add), so a numpy float32 restatement gives the same bits
+__host__ __device__ __forceinline__ void drop8(float* f, const DropSite& s, int64_t e0) {
+#pragma clang fp contract(off)
+  const uint64_t g = (uint64_t)e0 >> 2;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const uint64_t r = splitmix64(s.key + g + h);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float t = f[4 * h + j] * s.scale;
+      f[4 * h + j] = ((unsigned)(r >> (16 * j)) & 0xffffu) >= s.thresh ? t : 0.f;
+    }
+  }
+}
+__host__ __device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
 // ------------------------------------------------------------------ host-side error plumbing
 void dmi_set_error(const char* fmt, ...);
 #define DMI_REQUIRE(cond, ...)            \

@@ -18,10 +18,15 @@ extern "C" int dmi_version(void) { return 100; }
 // =====================================================================================
 // K1 embedding   (src/dalle_mtf/models.py:186-219)
 // =====================================================================================
+// DROP (dmi_embed_fwd_dropout, training forwards): x = bf16(drop_tok(wte[tok]) + drop_pos(wpe[s])); the token mask is indexed by
+// (b S + s) d + c, the positional mask by s d + c -- shared over the batch, as the reference's pos_emb is [seq, embd] when
+// mtf.dropout sees it (src/dalle_mtf/models.py:215-217)
+template <bool DROP>
 __global__ __launch_bounds__(256) void embed_fwd_kernel(const int* __restrict__ tokens,
                                                         const bf16_t* __restrict__ wte,
                                                         const bf16_t* __restrict__ wpe, bf16_t* __restrict__ x,
-                                                        int64_t rows, int S, int d, int vocab, const int* __restrict__ pos_dev) {
+                                                        int64_t rows, int S, int d, int vocab, const int* __restrict__ pos_dev,
+                                                        DropSite dtok, DropSite dpos) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int64_t row = (int64_t)blockIdx.x * 4 + wid;
   if (row >= rows) return;
@@ -39,8 +44,15 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int* __restrict__ 
     float fa[8], fp[8];
     unpack8(a[c], fa);
     unpack8(p[c], fp);
+    if constexpr (DROP) {
+      drop8(fa, dtok, row * d + c * 8);
+      drop8(fp, dpos, (int64_t)s * d + c * 8);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) fa[j] += fp[j];
+      for (int j = 0; j < 8; ++j) fa[j] = add_rn(fa[j], fp[j]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) fa[j] += fp[j];
+    }
     o[c] = pack8(fa);
   }
 }
@@ -49,14 +61,31 @@ extern "C" int dmi_embed_fwd(const int32_t* tokens, const uint16_t* wte, const u
                              int64_t rows, int S, int d, int vocab, const int* pos_dev, void* stream) {
   DMI_REQUIRE(tokens && wte && wpe && x, "embed_fwd: null pointer");
   DMI_REQUIRE(d % 8 == 0 && rows > 0 && S > 0, "embed_fwd: d %% 8 != 0 or empty (d=%d rows=%lld)", d, (long long)rows);
-  embed_fwd_kernel<<<dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, (hipStream_t)stream>>>(tokens, wte, wpe, x, rows, S, d, vocab, pos_dev);
+  embed_fwd_kernel<false><<<dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, (hipStream_t)stream>>>(tokens, wte, wpe, x, rows, S, d, vocab, pos_dev,
+                                                                                                 DropSite{}, DropSite{});
   DMI_CHECK_LAUNCH("embed_fwd");
   return DMI_OK;
 }
 
+#define DMI_REQUIRE_THRESH(name, thresh) \
+  DMI_REQUIRE((thresh) >= 0 && (thresh) <= 65535, name ": thresh must lie in [0, 65535] (thresh=%d)", (int)(thresh))
+
+extern "C" int dmi_embed_fwd_dropout(const int32_t* tokens, const uint16_t* wte, const uint16_t* wpe, uint16_t* x, int64_t rows, int S,
+                                     int d, int vocab, uint64_t key_tok, uint64_t key_pos, int thresh, void* stream) {
+  DMI_REQUIRE(tokens && wte && wpe && x, "embed_fwd_dropout: null pointer");
+  DMI_REQUIRE(d % 8 == 0 && rows > 0 && S > 0, "embed_fwd_dropout: d %% 8 != 0 or empty (d=%d rows=%lld)", d, (long long)rows);
+  DMI_REQUIRE_THRESH("embed_fwd_dropout", thresh);
+  embed_fwd_kernel<true><<<dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, (hipStream_t)stream>>>(
+      tokens, wte, wpe, x, rows, S, d, vocab, nullptr, drop_site(key_tok, thresh), drop_site(key_pos, thresh));
+  DMI_CHECK_LAUNCH("embed_fwd_dropout");
+  return DMI_OK;
+}
+
 // dwpe[s, :] = sum_b dx[b, s, :]      (one wave per position; deterministic)
+// DROP: ... times the positional mask of row s (the same for every b), applied to the finished sum
+template <bool DROP>
 __global__ __launch_bounds__(256) void embed_bwd_wpe_kernel(const bf16_t* __restrict__ dx, float* __restrict__ dwpe,
-                                                            int B, int S, int d) {
+                                                            int B, int S, int d, DropSite dpos) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int s = blockIdx.x * 4 + wid;
   if (s >= S) return;
@@ -68,6 +97,7 @@ __global__ __launch_bounds__(256) void embed_bwd_wpe_kernel(const bf16_t* __rest
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[j] += f[j];
     }
+    if constexpr (DROP) drop8(acc, dpos, (int64_t)s * d + c * 8);
     float* o = dwpe + (int64_t)s * d + c * 8;
     *(f32x4*)o = f32x4{acc[0], acc[1], acc[2], acc[3]};
     *(f32x4*)(o + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
@@ -182,11 +212,13 @@ extern "C" int dmi_sort_tokens(const int32_t* tokens, int32_t* sorted_tokens, in
 // from the batch have zero gradient).
 #define EB_CH 32
 __device__ __forceinline__ int eb_clamp(int t, int vocab) { return t < 0 ? 0 : (t >= vocab ? vocab - 1 : t); }
+// DROP: every dx row is masked and scaled with the token mask of its own position (perm[i]) before it is added
+template <bool DROP>
 __global__ __launch_bounds__(256) void embed_bwd_wte_sorted_kernel(const int* __restrict__ sorted_tok,
                                                                    const int* __restrict__ perm,
                                                                    const bf16_t* __restrict__ dx,
                                                                    float* __restrict__ dwte, float* __restrict__ part,
-                                                                   int64_t n, int d, int vocab) {
+                                                                   int64_t n, int d, int vocab, DropSite dtok) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int64_t chunk = (int64_t)blockIdx.x * 4 + wid;
   const int64_t i0 = chunk * EB_CH;
@@ -212,7 +244,9 @@ __global__ __launch_bounds__(256) void embed_bwd_wte_sorted_kernel(const int* __
         first = false;
       }
       float f[8];
-      unpack8(*(const u32x4*)(dx + (int64_t)perm[i] * d + c * 8), f);
+      const int64_t e0 = (int64_t)perm[i] * d + c * 8;
+      unpack8(*(const u32x4*)(dx + e0), f);
+      if constexpr (DROP) drop8(f, dtok, e0);
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[j] += f[j];
     }
@@ -283,47 +317,49 @@ __global__ __launch_bounds__(256) void embed_bwd_wte_combine_kernel(const int* _
 extern "C" int64_t dmi_embed_bwd_workspace_bytes(int B, int S, int d) {
   return (((int64_t)B * S + EB_CH - 1) / EB_CH) * 2 * d * 4 + 256;
 }
-extern "C" int dmi_embed_bwd(const int32_t* sorted_tokens, const int32_t* perm, const uint16_t* dx, float* dwte,
-                             float* dwpe, int B, int S, int d, int vocab, void* workspace, void* stream) {
-  DMI_REQUIRE(sorted_tokens && perm && dx && dwte && dwpe && workspace, "embed_bwd: null pointer");
-  DMI_REQUIRE(d % 8 == 0 && B > 0 && S > 0 && vocab > 0, "embed_bwd: bad sizes");
+template <bool DROP>
+static int embed_bwd_launch(const int32_t* sorted_tokens, const int32_t* perm, const uint16_t* dx, float* dwte, float* dwpe, int B, int S,
+                            int d, int vocab, void* workspace, DropSite dtok, DropSite dpos, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  embed_bwd_wpe_kernel<<<dim3((S + 3) / 4), dim3(256), 0, st>>>(dx, dwpe, B, S, d);
+  embed_bwd_wpe_kernel<DROP><<<dim3((S + 3) / 4), dim3(256), 0, st>>>(dx, dwpe, B, S, d, dpos);
   DMI_CHECK_LAUNCH("embed_bwd_wpe");
   DMI_REQUIRE(hipMemsetAsync(dwte, 0, (size_t)vocab * d * 4, st) == hipSuccess, "embed_bwd: memset failed");
   const int64_t n = (int64_t)B * S;
   const int64_t chunks = cdiv64(n, EB_CH);
-  embed_bwd_wte_sorted_kernel<<<dim3((unsigned)cdiv64(chunks, 4)), dim3(256), 0, st>>>(sorted_tokens, perm, dx, dwte, (float*)workspace, n, d, vocab);
+  embed_bwd_wte_sorted_kernel<DROP><<<dim3((unsigned)cdiv64(chunks, 4)), dim3(256), 0, st>>>(sorted_tokens, perm, dx, dwte, (float*)workspace, n,
+                                                                                         d, vocab, dtok);
   DMI_CHECK_LAUNCH("embed_bwd_wte_sorted");
   embed_bwd_wte_combine_kernel<<<dim3((unsigned)cdiv64(chunks, 4)), dim3(256), 0, st>>>(sorted_tokens, dwte, (const float*)workspace, n, d, vocab);
   DMI_CHECK_LAUNCH("embed_bwd_wte_combine");
   return DMI_OK;
+}
+extern "C" int dmi_embed_bwd(const int32_t* sorted_tokens, const int32_t* perm, const uint16_t* dx, float* dwte,
+                             float* dwpe, int B, int S, int d, int vocab, void* workspace, void* stream) {
+  DMI_REQUIRE(sorted_tokens && perm && dx && dwte && dwpe && workspace, "embed_bwd: null pointer");
+  DMI_REQUIRE(d % 8 == 0 && B > 0 && S > 0 && vocab > 0, "embed_bwd: bad sizes");
+  return embed_bwd_launch<false>(sorted_tokens, perm, dx, dwte, dwpe, B, S, d, vocab, workspace, DropSite{}, DropSite{}, stream);
+}
+extern "C" int dmi_embed_bwd_dropout(const int32_t* sorted_tokens, const int32_t* perm, const uint16_t* dx, float* dwte, float* dwpe,
+                                     int B, int S, int d, int vocab, void* workspace, uint64_t key_tok, uint64_t key_pos, int thresh,
+                                     void* stream) {
+  DMI_REQUIRE(sorted_tokens && perm && dx && dwte && dwpe && workspace, "embed_bwd_dropout: null pointer");
+  DMI_REQUIRE(d % 8 == 0 && B > 0 && S > 0 && vocab > 0, "embed_bwd_dropout: bad sizes (d %% 8 != 0 or empty: d=%d B=%d S=%d)", d, B, S);
+  DMI_REQUIRE_THRESH("embed_bwd_dropout", thresh);
+  return embed_bwd_launch<true>(sorted_tokens, perm, dx, dwte, dwpe, B, S, d, vocab, workspace, drop_site(key_tok, thresh),
+                                drop_site(key_pos, thresh), stream);
 }
 
 // =====================================================================================
 // K2 LayerNorm (src/dalle_mtf/models.py:373-389, layers.py:30-33): biased variance of the
 // centred row, eps inside rsqrt.  One wave per row, row cached in registers (d <= 512*NC).
 // =====================================================================================
+// the LayerNorm of one row held in registers (lane owns chunks lane + 64 i; sum = the lane's partial row sum): shared by
+// ln_fwd_kernel and dropout_add_ln_kernel, so both compute the same bits from the same row
 template <int NC>
-__global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ g,
-                                                     const bf16_t* __restrict__ b, bf16_t* __restrict__ y,
-                                                     float* __restrict__ mean, float* __restrict__ rstd,
-                                                     int64_t rows, int d, float eps) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t row = (int64_t)blockIdx.x * 4 + wid;
-  if (row >= rows) return;
+__device__ __forceinline__ void ln_row(float (&v)[NC][8], float sum, const bf16_t* __restrict__ g, const bf16_t* __restrict__ b,
+                                       bf16_t* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd, int64_t row, int d,
+                                       float eps, int lane) {
   const int nch = d / 8;
-  float v[NC][8];
-  float sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < NC; ++i) {
-    const int c = lane + 64 * i;
-    if (c < nch) {
-      unpack8(*(const u32x4*)(x + row * d + c * 8), v[i]);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) sum += v[i][j];
-    }
-  }
   const float mu = wave_sum(sum) / (float)d;
   float sq = 0.f;
 #pragma unroll
@@ -356,6 +392,29 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* __restrict__ 
   }
 }
 
+template <int NC>
+__global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ g,
+                                                     const bf16_t* __restrict__ b, bf16_t* __restrict__ y,
+                                                     float* __restrict__ mean, float* __restrict__ rstd,
+                                                     int64_t rows, int d, float eps) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + wid;
+  if (row >= rows) return;
+  const int nch = d / 8;
+  float v[NC][8];
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < NC; ++i) {
+    const int c = lane + 64 * i;
+    if (c < nch) {
+      unpack8(*(const u32x4*)(x + row * d + c * 8), v[i]);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) sum += v[i][j];
+    }
+  }
+  ln_row<NC>(v, sum, g, b, y, mean, rstd, row, d, eps, lane);
+}
+
 extern "C" int dmi_layernorm_fwd(const uint16_t* x, const uint16_t* g, const uint16_t* b, uint16_t* y, float* mean,
                                  float* rstd, int64_t rows, int d, float eps, void* stream) {
   DMI_REQUIRE(x && g && b && y && mean && rstd, "layernorm_fwd: null pointer");
@@ -367,6 +426,87 @@ extern "C" int dmi_layernorm_fwd(const uint16_t* x, const uint16_t* g, const uin
   else if (d <= 2048) ln_fwd_kernel<4><<<grid, blk, 0, st>>>(x, g, b, y, mean, rstd, rows, d, eps);
   else ln_fwd_kernel<8><<<grid, blk, 0, st>>>(x, g, b, y, mean, rstd, rows, d, eps);
   DMI_CHECK_LAUNCH("layernorm_fwd");
+  return DMI_OK;
+}
+
+// ---- residual dropout (src/dalle_mtf/models.py:312-314, 322-323): x_out = bf16(residual + drop(a)), then the LayerNorm that
+// follows it from the ROUNDED row, which never leaves the registers -- one pass, 8 bytes of HBM traffic per element where the
+// bias-only product + dropout + add + LayerNorm as separate kernels would move 16.  g == NULL: x_out only.
+template <int NC>
+__global__ __launch_bounds__(256) void dropout_add_ln_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ res,
+                                                             bf16_t* __restrict__ x, const bf16_t* __restrict__ g,
+                                                             const bf16_t* __restrict__ b, bf16_t* __restrict__ y,
+                                                             float* __restrict__ mean, float* __restrict__ rstd, int64_t rows, int d,
+                                                             float eps, DropSite site) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + wid;
+  if (row >= rows) return;
+  const int nch = d / 8;
+  float v[NC][8];
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < NC; ++i) {
+    const int c = lane + 64 * i;
+    if (c < nch) {
+      const int64_t e0 = row * d + c * 8;
+      float fr[8];
+      unpack8(*(const u32x4*)(a + e0), v[i]);
+      unpack8(*(const u32x4*)(res + e0), fr);
+      drop8(v[i], site, e0);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[i][j] = add_rn(fr[j], v[i][j]);
+      const u32x4 packed = pack8(v[i]);
+      *(u32x4*)(x + e0) = packed;
+      unpack8(packed, v[i]);      // the LayerNorm sees what was stored
+#pragma unroll
+      for (int j = 0; j < 8; ++j) sum += v[i][j];
+    }
+  }
+  if (g) ln_row<NC>(v, sum, g, b, y, mean, rstd, row, d, eps, lane);
+}
+
+extern "C" int dmi_dropout_add_ln(const uint16_t* a, const uint16_t* residual, uint16_t* x_out, const uint16_t* gamma,
+                                  const uint16_t* beta, uint16_t* y, float* mean, float* rstd, int64_t M, int d, uint64_t key,
+                                  int thresh, float eps, void* stream) {
+  DMI_REQUIRE(a && residual && x_out, "dropout_add_ln: null pointer (a, residual or x_out)");
+  DMI_REQUIRE(!gamma || (beta && y && mean && rstd), "dropout_add_ln: null pointer (beta, y, mean or rstd with gamma given)");
+  DMI_REQUIRE(d > 0 && d % 8 == 0 && d <= 4096 && M > 0, "dropout_add_ln: unsupported shape (need d %% 8 == 0, d <= 4096, M > 0: d=%d M=%lld)",
+              d, (long long)M);
+  DMI_REQUIRE_THRESH("dropout_add_ln", thresh);
+  DMI_REQUIRE((((uintptr_t)a | (uintptr_t)residual | (uintptr_t)x_out | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)y) & 15) == 0,
+              "dropout_add_ln: buffers must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const DropSite site = drop_site(key, thresh);
+  dim3 grid((unsigned)cdiv64(M, 4)), blk(256);
+  if (d <= 512) dropout_add_ln_kernel<1><<<grid, blk, 0, st>>>(a, residual, x_out, gamma, beta, y, mean, rstd, M, d, eps, site);
+  else if (d <= 1024) dropout_add_ln_kernel<2><<<grid, blk, 0, st>>>(a, residual, x_out, gamma, beta, y, mean, rstd, M, d, eps, site);
+  else if (d <= 2048) dropout_add_ln_kernel<4><<<grid, blk, 0, st>>>(a, residual, x_out, gamma, beta, y, mean, rstd, M, d, eps, site);
+  else dropout_add_ln_kernel<8><<<grid, blk, 0, st>>>(a, residual, x_out, gamma, beta, y, mean, rstd, M, d, eps, site);
+  DMI_CHECK_LAUNCH("dropout_add_ln");
+  return DMI_OK;
+}
+
+// dy = drop(dx): the gradient of a dropped branch output.  A flat stream of 16-byte pieces (8 elements, two hashes) over M d elements.
+__global__ __launch_bounds__(256) void dropout_bwd_kernel(const bf16_t* __restrict__ dx, bf16_t* __restrict__ dy, int64_t n8, DropSite site) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += stride) {
+    float f[8];
+    unpack8(*(const u32x4*)(dx + i * 8), f);
+    drop8(f, site, i * 8);
+    *(u32x4*)(dy + i * 8) = pack8(f);
+  }
+}
+
+extern "C" int dmi_dropout_bwd(const uint16_t* dx, uint16_t* dy, int64_t M, int d, uint64_t key, int thresh, void* stream) {
+  DMI_REQUIRE(dx && dy, "dropout_bwd: null pointer");
+  DMI_REQUIRE(d > 0 && d % 8 == 0 && M > 0, "dropout_bwd: unsupported shape (need d %% 8 == 0, M > 0: d=%d M=%lld)", d, (long long)M);
+  DMI_REQUIRE_THRESH("dropout_bwd", thresh);
+  DMI_REQUIRE((((uintptr_t)dx | (uintptr_t)dy) & 15) == 0, "dropout_bwd: buffers must be 16-byte aligned");
+  const int64_t n8 = M * (int64_t)d / 8;
+  int64_t blocks = cdiv64(n8, 256);
+  if (blocks > 256 * 8) blocks = 256 * 8;     // 8 blocks of 4 waves per CU hold a stream of 16-byte requests; the rest is the grid stride
+  dropout_bwd_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(dx, dy, n8, drop_site(key, thresh));
+  DMI_CHECK_LAUNCH("dropout_bwd");
   return DMI_OK;
 }
 
@@ -1442,12 +1582,7 @@ __device__ __forceinline__ unsigned order_key(float v) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float key_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
+// (splitmix64: common.h)
 #define SAMPLE_MAX_VOCAB 8192
 __global__ __launch_bounds__(256) void sample_tokens_kernel(const bf16_t* __restrict__ z, int ldz, const bf16_t* __restrict__ bias, int nv,
                                                             float inv_temp, int top_k, uint64_t seed, const unsigned* __restrict__ params_dev,

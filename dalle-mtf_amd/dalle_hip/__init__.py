@@ -12,7 +12,7 @@ import re
 import struct
 
 import numpy as np
-from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
 
 import torch
 
@@ -53,7 +53,7 @@ def lib():
 
 
 def _declare(L):
-    P, I, L64, F = c_void_p, c_int, c_int64, c_float
+    P, I, L64, F, U64 = c_void_p, c_int, c_int64, c_float, c_uint64
     sig = {
         "dmi_last_error_string": (c_char_p, []),
         "dmi_version": (I, []),
@@ -66,6 +66,10 @@ def _declare(L):
         "dmi_embed_bwd_workspace_bytes": (L64, [I, I, I]),
         "dmi_embed_bwd": (I, [P, P, P, P, P, I, I, I, I, P, P]),
         "dmi_layernorm_fwd": (I, [P, P, P, P, P, P, L64, I, F, P]),
+        "dmi_embed_fwd_dropout": (I, [P, P, P, P, L64, I, I, I, U64, U64, I, P]),
+        "dmi_embed_bwd_dropout": (I, [P, P, P, P, P, I, I, I, I, P, U64, U64, I, P]),
+        "dmi_dropout_add_ln": (I, [P, P, P, P, P, P, P, P, L64, I, U64, I, F, P]),
+        "dmi_dropout_bwd": (I, [P, P, L64, I, U64, I, P]),
         "dmi_layernorm_bwd_workspace_bytes": (L64, [L64, I]),
         "dmi_layernorm_bwd": (I, [P, P, P, P, P, P, P, P, P, P, L64, I, P]),
         "dmi_layernorm_bwd_finish_batch": (I, [P, P, P, P, I, I, P]),
@@ -218,6 +222,38 @@ def embed_bwd(sorted_tokens, perm, dx, dwte, dwpe, B, S, d, vocab, ws):
 def layernorm_fwd(x, g, b, y, mean, rstd, rows, d, eps=1e-5):
     _dev(x, g, b, y, mean, rstd)
     _check(lib().dmi_layernorm_fwd(_p(x), _p(g), _p(b), _p(y), _p(mean), _p(rstd), rows, d, eps, _stream()), "layernorm_fwd")
+
+
+def embed_fwd_dropout(tokens, wte, wpe, x, S, d, vocab, key_tok, key_pos, thresh):
+    """embed_fwd with the token mask (key_tok) and the positional mask (key_pos, shared over the batch) of one threshold"""
+    _dev(tokens, wte, wpe, x)
+    _check(lib().dmi_embed_fwd_dropout(_p(tokens), _p(wte), _p(wpe), _p(x), tokens.numel(), S, d, vocab, int(key_tok), int(key_pos),
+                                       int(thresh), _stream()), "embed_fwd_dropout")
+
+
+def embed_bwd_dropout(sorted_tokens, perm, dx, dwte, dwpe, B, S, d, vocab, ws, key_tok, key_pos, thresh):
+    _dev(sorted_tokens, perm, dx, dwte, dwpe, ws)
+    _check(lib().dmi_embed_bwd_dropout(_p(sorted_tokens), _p(perm), _p(dx), _p(dwte), _p(dwpe), B, S, d, vocab, _p(ws), int(key_tok),
+                                       int(key_pos), int(thresh), _stream()), "embed_bwd_dropout")
+
+
+def dropout_add_ln(a, residual, x_out, gamma, beta, y, mean, rstd, M, d, key, thresh, eps=1e-5):
+    """x_out = bf16(residual + drop(a)) and, in the same pass, y / mean / rstd = layernorm_fwd(x_out); gamma None: x_out only"""
+    _dev(a, residual, x_out, gamma, beta, y, mean, rstd)
+    for t in (a, residual, x_out):
+        assert t.dtype == torch.bfloat16 and t.numel() >= M * d
+    if gamma is not None:
+        assert y.dtype == torch.bfloat16 and y.numel() >= M * d and mean.dtype == torch.float32 and rstd.dtype == torch.float32
+        assert mean.numel() >= M and rstd.numel() >= M and gamma.numel() >= d and beta.numel() >= d
+    _check(lib().dmi_dropout_add_ln(_p(a), _p(residual), _p(x_out), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), M, d, int(key),
+                                    int(thresh), float(eps), _stream()), "dropout_add_ln")
+
+
+def dropout_bwd(dx, dy, M, d, key, thresh):
+    """dy = bf16(drop(dx)): the gradient of a dropped branch output"""
+    _dev(dx, dy)
+    assert dx.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16 and dx.numel() >= M * d and dy.numel() >= M * d
+    _check(lib().dmi_dropout_bwd(_p(dx), _p(dy), M, d, int(key), int(thresh), _stream()), "dropout_bwd")
 
 
 def layernorm_bwd_workspace_bytes(rows, d):

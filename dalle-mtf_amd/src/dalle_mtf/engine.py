@@ -34,6 +34,7 @@ import torch
 import dalle_hip as dh
 from ..dp import GradReducer
 from .activations import check_activation
+from .dropout import SITE_POSITION, SITE_TOKEN, resolve_dropout, site_attention, site_key, site_mlp
 from .ema import ema_decay_at, one_minus_decay, resolve_ema, resolve_weights   # noqa: F401  (ema_decay_at: part of the engine's surface)
 from .loss_weights import position_weights, resolve_loss_weights
 
@@ -172,6 +173,8 @@ class DalleEngine:
                  device="cuda", process_group=None, world_size=1, comm=None, attn_masks=None):
         self.loss_weights = resolve_loss_weights(hparams, text_seq_len)   # None: the reference's plain mean
         self.ema_decay, self.ema_eval = resolve_ema(hparams)              # None: no weight average (dalle_mtf.ema)
+        # hparams["embed_dropout"] / ["residual_dropout"] as 16-bit thresholds (0: off) and ["dropout_seed"] (dalle_mtf.dropout)
+        self.embed_thresh, self.resid_thresh, self.dropout_seed = resolve_dropout(hparams)
         if not torch.cuda.is_available():
             raise dh.DalleHipError("DalleEngine needs a HIP device (MI355X); there is no CPU fallback")
         dh.lib()
@@ -212,6 +215,12 @@ class DalleEngine:
         if self.ema_decay is not None:
             self._alloc_ema()
         self.global_step = 0
+        # the masks of a training forward are keyed by (seed, global_step, microbatch, data-parallel rank, site); last_dropout =
+        # {site: (key, thresh)} of the last one (empty with both rates 0).  _drop: the last forward was a dropped training forward.
+        self.dropout_rank = int(self.hp.get("dp_rank") or 0)
+        self.last_dropout: Dict[int, Tuple[int, int]] = {}
+        self._microbatch = 0
+        self._drop = False
         # The exchange's RCCL channels run beside the BACKWARD: there the persistent kernels leave CUs for them (a block of a
         # one-block-per-CU kernel whose CU an intruder holds starts when the others have finished: the launch takes twice as long --
         # measured with the token sort as the intruder).  16 CUs cost 3.7 % of a single-GPU step when applied to
@@ -514,6 +523,11 @@ class DalleEngine:
         self.dh = torch.empty(M, 4 * d, **b16)
         self.dqkv = torch.empty(M, 3 * d, **b16)
         self.d_o = torch.empty(M, d, **b16)
+        # residual dropout: drop_y is where the out-projection and FFN-2 land (bias only) before dmi_dropout_add_ln, in the forward
+        # and in its re-run; dyd are the masked gradients of the two branch outputs (dya -> FFN-2, dyb -> out-projection), which
+        # must stay untouched until the block's grouped weight-gradient launch behind the attention backward
+        self.drop_y = torch.empty(M, d, **b16) if self.resid_thresh else None
+        self.dyd = [torch.empty(M, d, **b16) for _ in range(2)] if self.resid_thresh else None
         self.delta = torch.empty(3, B, H, S, **f32)   # delta | (lse, delta) pairs for the dK/dV kernel's DMA
         wsz = max(dh.gemm_tn_workspace_bytes(M, d, Vp), dh.gemm_tn_workspace_bytes(M, 4 * d, d),
                   dh.gemm_tn_workspace_bytes(M, d, 4 * d), dh.gemm_tn_workspace_bytes(M, d, 3 * d),
@@ -584,10 +598,15 @@ class DalleEngine:
         if need_grad:   # token-id order for the embedding backward: twelve 3-5 us launches on a side stream (see dmi_sort_tokens)
             self._launch_sort()
         dh.shift_labels(self.tokens, self.labels, B, S, self.eos)
-        dh.embed_fwd(self.tokens, self._w("embedding/wte"), self._w("positional_embedding/wpe"), self.X[0], S, d, self.V)
+        self._draw_dropout(need_grad)
+        if self._drop and self.embed_thresh:
+            dh.embed_fwd_dropout(self.tokens, self._w("embedding/wte"), self._w("positional_embedding/wpe"), self.X[0], S, d, self.V,
+                                 self.last_dropout[SITE_TOKEN][0], self.last_dropout[SITE_POSITION][0], self.embed_thresh)
+        else:
+            dh.embed_fwd(self.tokens, self._w("embedding/wte"), self._w("positional_embedding/wpe"), self.X[0], S, d, self.V)
         for l in range(L):
             self._block_forward(l)
-        if not (self.fuse_ln1 and L > 0):      # (fused: written by the last block's FFN-2)
+        if not (self._ln1_by_prev() and L > 0):      # (fused: written by the last block's FFN-2)
             dh.layernorm_fwd(self.X[L], self._w("to_logits/layer_norm/g"), self._w("to_logits/layer_norm/b"), self.xnf,
                              self.statf[0], self.statf[1], M, d)
         Wt, bias = self.tview("to_logits/linear_out/kernel"), self._w("to_logits/linear_out/bias")
@@ -623,22 +642,52 @@ class DalleEngine:
             dh.sum_f32(self.loss_rows, M, 1.0 / (M * nmb), self.loss)
         return self.loss
 
+    def _draw_dropout(self, training):
+        """the keys of this forward's masks: a training forward with a rate above 0 draws one per site, anything else none"""
+        self._drop = bool(training and (self.embed_thresh or self.resid_thresh))
+        self.last_dropout = {}
+        if not self._drop:
+            return
+        key = lambda site: site_key(self.dropout_seed, self.global_step, self._microbatch, self.dropout_rank, site)   # noqa: E731
+        if self.embed_thresh:
+            self.last_dropout.update({s_: (key(s_), self.embed_thresh) for s_ in (SITE_TOKEN, SITE_POSITION)})
+        if self.resid_thresh:
+            for l in range(self.L):
+                self.last_dropout.update({s_: (key(s_), self.resid_thresh) for s_ in (site_attention(l), site_mlp(l))})
+
+    def _drop_resid(self):
+        return self._drop and self.resid_thresh > 0
+
+    def _ln1_by_prev(self):
+        """norm_1 of block l + 1 (and to_logits' norm) is written by block l's FFN-2: the fused product, or under residual dropout
+        dmi_dropout_add_ln -- neither under recompute_grad, whose re-run starts from a standalone norm_1"""
+        return self.fuse_ln1 or (self._drop_resid() and not self.recompute)
+
     def _block_forward(self, l):
         """one transformer block (src/dalle_mtf/models.py:326-335): X[l] -> X[l+1]; also what backward() re-runs under
         recompute_grad.
         fuse_ln (n_embd = 512): the two products that end in the residual stream run on full-row tiles and emit the LayerNorm
         that follows them in the same pass (dmi_gemm_nt_ln) -- out-projection + residual -> norm_2, FFN-2 + residual -> the
-        NEXT block's norm_1 (or to_logits' norm): 12 of the 13 standalone LayerNorm launches of a forward pass disappear."""
+        NEXT block's norm_1 (or to_logits' norm): 12 of the 13 standalone LayerNorm launches of a forward pass disappear.
+        Residual dropout (a training forward with residual_dropout > 0, and its re-run): those two products run with their bias
+        only into a scratch buffer and dmi_dropout_add_ln drops, adds the residual and emits the LayerNorm in one pass, at
+        every width; the keys are last_dropout's, so the re-run restates the same masks."""
         M, d, B, H, S, L = self.M, self.d, self.B, self.H, self.S, self.L
         p = f"layer_{l}/"
         x = self.X[l]
         st = self.stats[l]
         rerun = getattr(self, "_in_backward", False)
-        if not (self.fuse_ln1 and l > 0):   # (fused: written by block l-1's FFN-2)
+        drop = self._drop_resid()
+        if not (self._ln1_by_prev() and l > 0):   # (fused: written by block l-1's FFN-2)
             dh.layernorm_fwd(x, self._w(p + "norm_1/g"), self._w(p + "norm_1/b"), self.xn1[l], st[0], st[1], M, d)
         dh.gemm_nt(self.xn1[l], d, self.tview(p + "attn/qkv"), d, self.qkv[l], 3 * d, M, 3 * d, d)
         self._attn_fwd(l, self.qkv[l], self.o[l], self.lse[l])   # no transposed copies: hardware transpose reads
-        if self.fuse_ln:
+        if drop:
+            dh.gemm_nt(self.o[l], d, self.tview(p + "attn/o"), d, self.drop_y, d, M, d, d, dh.GEMM_BIAS,
+                       bias=self._w(p + "attn/compute_output_bias/o_b"))
+            dh.dropout_add_ln(self.drop_y, x, self.x1[l], self._w(p + "norm_2/g"), self._w(p + "norm_2/b"), self.xn2[l], st[2], st[3],
+                              M, d, *self.last_dropout[site_attention(l)])
+        elif self.fuse_ln:
             dh.gemm_nt_ln(self.o[l], d, self.tview(p + "attn/o"), d, self.x1[l], d, M, d, d,
                           self._w(p + "norm_2/g"), self._w(p + "norm_2/b"), self.xn2[l], d, st[2], st[3],
                           bias=self._w(p + "attn/compute_output_bias/o_b"), residual=x)
@@ -658,7 +707,15 @@ class DalleEngine:
         if rerun:   # the re-run stops here: X[l+1] is already stored
             return
         W2, b2 = self.tview(p + "mlp/mlp_linear_2/kernel"), self._w(p + "mlp/mlp_linear_2/bias")
-        if self.fuse_ln1:
+        if drop:
+            dh.gemm_nt(self.h[l], 4 * d, W2, 4 * d, self.drop_y, d, M, d, 4 * d, dh.GEMM_BIAS, bias=b2)
+            y = mean = rstd = g_ = b_ = None          # under recompute_grad the next LayerNorm is launched on its own
+            if not self.recompute:
+                q = f"layer_{l + 1}/norm_1/" if l + 1 < L else "to_logits/layer_norm/"
+                y, mean, rstd = (self.xn1[l + 1], *self.stats[l + 1][:2]) if l + 1 < L else (self.xnf, *self.statf)
+                g_, b_ = self._w(q + "g"), self._w(q + "b")
+            dh.dropout_add_ln(self.drop_y, self.x1[l], self.X[l + 1], g_, b_, y, mean, rstd, M, d, *self.last_dropout[site_mlp(l)])
+        elif self.fuse_ln1:
             if l + 1 < L:
                 q = f"layer_{l + 1}/norm_1/"
                 y, mean, rstd = self.xn1[l + 1], self.stats[l + 1][0], self.stats[l + 1][1]
@@ -1093,23 +1150,31 @@ class DalleEngine:
                 self._in_backward = True
                 self._block_forward(l)
                 self._in_backward = False
+            # residual dropout: the two branch outputs' gradients are the masked stream gradients (dya below, dyb after norm_2's
+            # backward); the unmasked dxa / dxb stay the residual pass-through
+            drop = self._drop_resid()
+            dya = dxa
+            if drop:
+                dya = self.dyd[0]
+                dh.dropout_bwd(dxa, dya, M, d, *self.last_dropout[site_mlp(l)])
             # FFN
             pair = self.hp["wgrad_pair"] and self.hp["defer_reduces"]
             group4 = pair and self.wgrad_group4    # (dxa, self.dh, dxb stay untouched until the group's launch behind the attention backward)
             if not group4:
-                self._wgrad(self.h[l], 4 * d, dxa, d, self._gv(p + "mlp/mlp_linear_2/kernel"), M, 4 * d, d,
+                self._wgrad(self.h[l], 4 * d, dya, d, self._gv(p + "mlp/mlp_linear_2/kernel"), M, 4 * d, d,
                             dbias=self._gv(p + "mlp/mlp_linear_2/bias"), slot=0)
             if self.hpre is not None:
-                dh.gemm_nt_gelu_grad(dxa, d, self._w(p + "mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d, self.hpre[l], 4 * d)
+                dh.gemm_nt_gelu_grad(dya, d, self._w(p + "mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d, self.hpre[l], 4 * d)
             elif self.use_relu_bits:
-                dh.gemm_nt_mask_bits(dxa, d, self._w(p + "mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d, self.hbits[l])
+                dh.gemm_nt_mask_bits(dya, d, self._w(p + "mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d, self.hbits[l])
             else:
-                dh.gemm_nt(dxa, d, self._w(p + "mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d, dh.GEMM_RELU_MASK,
+                dh.gemm_nt(dya, d, self._w(p + "mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d, dh.GEMM_RELU_MASK,
                            relu_src=self.h[l])
             if not group4:
                 self._wgrad(self.xn2[l], d, self.dh, 4 * d, self._gv(p + "mlp/mlp_linear_1/kernel"), M, d, 4 * d,
                             dbias=self._gv(p + "mlp/mlp_linear_1/bias"), slot=1)
-            chain = self.fuse_lnbwd and self.hp["lnbwd_chain"]     # ... and the out-projection's input gradient d_o = dxb . Wo^T in the same launch
+            # ... and the out-projection's input gradient d_o = dxb . Wo^T in the same launch (not under residual dropout: d_o = dyb . Wo^T)
+            chain = self.fuse_lnbwd and self.hp["lnbwd_chain"] and not drop
             if self.fuse_lnbwd:
                 lnbwd(2 * l + 1, self.dh, 4 * d, self._w(p + "mlp/mlp_linear_1/kernel"), self.x1[l], self._w(p + "norm_2/g"), st[2], st[3],
                       dxa, dxb, self._gv(p + "norm_2/g"), self._gv(p + "norm_2/b"),
@@ -1119,22 +1184,26 @@ class DalleEngine:
                 ln_bwd(2 * l + 1, self.dxn, self.x1[l], self._w(p + "norm_2/g"), st[2], st[3], dxa, dxb,
                        self._gv(p + "norm_2/g"), self._gv(p + "norm_2/b"))
             # attention
+            dyb = dxb
+            if drop:
+                dyb = self.dyd[1]
+                dh.dropout_bwd(dxb, dyb, M, d, *self.last_dropout[site_attention(l)])
             if not pair:
-                self._wgrad(self.o[l], d, dxb, d, self._gv(p + "attn/o"), M, d, d,
+                self._wgrad(self.o[l], d, dyb, d, self._gv(p + "attn/o"), M, d, d,
                             dbias=self._gv(p + "attn/compute_output_bias/o_b"), slot=2)
             if not chain:
-                dh.gemm_nt(dxb, d, self._w(p + "attn/o"), d, self.d_o, d, M, d, d)
+                dh.gemm_nt(dyb, d, self._w(p + "attn/o"), d, self.d_o, d, M, d, d)
             if self.attn_plan[l] is None:
                 dh.attention_bwd(self.qkv[l], self.o[l], self.d_o, self.lse[l], self.delta, self.dqkv, B, H, S, head_dim=self.hd)
             else:
                 dh.attention_bwd_masked(self.qkv[l], self.o[l], self.d_o, self.lse[l], self.delta, self.dqkv, self.attn_plan[l],
                                         B, H, S, head_dim=self.hd)
             if pair:   # [r05] the out-projection and QKV kernels' gradients in ONE launch: 16 + 48 tiles fill the chip together
-                probs = [dict(X=self.o[l], ldx=d, dY=dxb, ldy=d, dW=self._gv(p + "attn/o"), I=d, J=d, ws=self.ws_blk[2],
+                probs = [dict(X=self.o[l], ldx=d, dY=dyb, ldy=d, dW=self._gv(p + "attn/o"), I=d, J=d, ws=self.ws_blk[2],
                               dbias=self._gv(p + "attn/compute_output_bias/o_b")),
                          dict(X=self.xn1[l], ldx=d, dY=self.dqkv, ldy=3 * d, dW=self._gv(p + "attn/qkv"), I=d, J=3 * d, ws=self.ws_blk[3])]
                 if group4:   # [r06] ... and the two FFN gradients with them
-                    probs = [dict(X=self.h[l], ldx=4 * d, dY=dxa, ldy=d, dW=self._gv(p + "mlp/mlp_linear_2/kernel"), I=4 * d, J=d,
+                    probs = [dict(X=self.h[l], ldx=4 * d, dY=dya, ldy=d, dW=self._gv(p + "mlp/mlp_linear_2/kernel"), I=4 * d, J=d,
                                   ws=self.ws_blk[0], dbias=self._gv(p + "mlp/mlp_linear_2/bias")),
                              dict(X=self.xn2[l], ldx=d, dY=self.dh, ldy=4 * d, dW=self._gv(p + "mlp/mlp_linear_1/kernel"), I=d, J=4 * d,
                                   ws=self.ws_blk[1], dbias=self._gv(p + "mlp/mlp_linear_1/bias"))] + probs
@@ -1155,8 +1224,13 @@ class DalleEngine:
         # embeddings: positions visited in token-id order (sorted on the side stream during the forward)
         if self._sort_done is not None:
             torch.cuda.current_stream().wait_event(self._sort_done)
-        dh.embed_bwd(self.tok_sorted, self.tok_perm, dxa, self._gv("embedding/wte"), self._gv("positional_embedding/wpe"),
-                     B, S, d, self.V, self.embed_ws)
+        if self._drop and self.embed_thresh:
+            dh.embed_bwd_dropout(self.tok_sorted, self.tok_perm, dxa, self._gv("embedding/wte"), self._gv("positional_embedding/wpe"),
+                                 B, S, d, self.V, self.embed_ws, self.last_dropout[SITE_TOKEN][0], self.last_dropout[SITE_POSITION][0],
+                                 self.embed_thresh)
+        else:
+            dh.embed_bwd(self.tok_sorted, self.tok_perm, dxa, self._gv("embedding/wte"), self._gv("positional_embedding/wpe"),
+                         B, S, d, self.V, self.embed_ws)
         flush_ln()
         ready(rp[L + 1])
 
@@ -1262,6 +1336,7 @@ class DalleEngine:
                 self.loss_parts_acc = torch.zeros_like(self.loss_parts)
             self.loss_parts_acc.zero_()
         for i in range(nmb):
+            self._microbatch = i          # (keys the dropout masks: every micro-batch draws its own)
             loss = self.forward(tokens[i * self.B:(i + 1) * self.B], need_grad=True)
             self.loss_acc += loss
             if self.loss_parts is not None:
@@ -1271,6 +1346,7 @@ class DalleEngine:
                 self.gacc.copy_(self.g)
             else:
                 dh.add_f32(self.gacc, self.g, self.lay.total)
+        self._microbatch = 0
         self.g.copy_(self.gacc)
         self.reducer.ready(0, self.lay.total)
         self.optimizer_step()

@@ -7,6 +7,7 @@ import torch
 import numpy as np
 
 from .activations import resolve_activation
+from .dropout import resolve_dropout
 from .ema import resolve_ema
 from .engine import DalleEngine
 from .loss_weights import resolve_loss_weights
@@ -58,9 +59,11 @@ class DALLE:
         resolve_loss_weights(params, text_seq_len)
         # "ema_decay" / "ema_eval" (dalle_mtf.ema): likewise
         resolve_ema(params)
-        for k in ("embed_dropout", "attention_dropout", "residual_dropout"):
-            if self.params.get(k):
-                raise NotImplementedError(f"{k} > 0 is not supported (all shipped configs use 0)")
+        # "embed_dropout" / "residual_dropout" / "dropout_seed" (dalle_mtf.dropout): likewise
+        resolve_dropout(params)
+        if self.params.get("attention_dropout"):
+            raise NotImplementedError("attention_dropout > 0 is not supported: embed_dropout and residual_dropout are; dropout of "
+                                      "the attention weights would live inside the attention kernels (all shipped configs use 0)")
         if (self.params.get("scale_type") or "scale_by_depth") != "scale_by_depth":
             raise NotImplementedError("scale_type other than scale_by_depth")
         # attn_mask (reference models.py:221-227, the attention bias at :292-299): a bool [S, S] mask, an additive float mask (0 or
@@ -122,7 +125,8 @@ class DALLE:
     def forward(self, features, return_loss=True, return_logits=False):
         """features["tokens"]: int32 [B, S] device tensor.  Returns (loss, loss_batch[, logits]) like the
         reference (models.py:397-416); with return_loss=False returns the fp32 logits only.  With loss weights set, loss is
-        the weighted loss; loss_batch stays the unweighted per-position NLL."""
+        the weighted loss; loss_batch stays the unweighted per-position NLL.  Dropout applies to the training forward only:
+        return_logits=True (or return_loss=False) runs the evaluation path, undropped, in train mode too."""
         tokens = features["tokens"] if isinstance(features, dict) else features
         tokens = tokens.to(device=self.engine.dev, dtype=torch.int32)
         need_grad = self.mode == "train" and return_loss and not return_logits

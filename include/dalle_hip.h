@@ -60,6 +60,31 @@ int64_t dmi_embed_bwd_workspace_bytes(int B, int S, int d);
 int dmi_embed_bwd(const int32_t* sorted_tokens, const int32_t* perm, const uint16_t* dx, float* dwte,
                   float* dwpe, int B, int S, int d, int vocab, void* workspace, void* stream);
 
+/* ---- Dropout (reference embed_dropout / residual_dropout, src/dalle_mtf/models.py:198-200, 215-217, 312-314, 322-323) ----
+ * A dropout SITE is a 64-bit key and a 16-bit threshold thresh in [0, 65535] (= round(rate * 65536), clamped).  Element e of the
+ * site's tensor (row-major, e = row * d + col), with g = e >> 2 and j = e & 3, draws r = (splitmix64(key + g) >> 16 j) & 0xffff and
+ * is kept iff r >= thresh; drop(v) = kept ? v * scale : +0 with scale = fp32(65536.0 / (65536 - thresh)), the product rounded to
+ * fp32 on its own.  thresh 0 keeps everything with scale 1.  The mask is a pure function of (key, e): it is never stored, and the
+ * forward, its re-run under recompute_grad and the backward restate it from the key.  All four entry points: stream-ordered, no
+ * allocation, DMI_ERR_INVALID with a message before any launch for a null pointer, d % 8 != 0, an empty shape or a thresh
+ * outside [0, 65535]; the two dmi_dropout_* also for a buffer that is not 16-byte aligned.
+ *
+ * dmi_embed_fwd_dropout: x[b,s,:] = bf16(drop_tok(wte[tok]) + drop_pos(wpe[s])); the token mask's element index is
+ * (b S + s) d + c, the positional mask's is s d + c (shared over the batch: the reference drops pos_emb as a [seq, embd] tensor).
+ * dmi_embed_bwd_dropout: dwte[tok] = sum over the positions holding tok of drop_tok(dx), dwpe[s] = drop_pos(sum_b dx[b,s]);
+ * order, workspace and determinism of dmi_embed_bwd. */
+int dmi_embed_fwd_dropout(const int32_t* tokens, const uint16_t* wte, const uint16_t* wpe, uint16_t* x, int64_t rows /*B*S*/, int S,
+                          int d, int vocab, uint64_t key_tok, uint64_t key_pos, int thresh, void* stream);
+int dmi_embed_bwd_dropout(const int32_t* sorted_tokens, const int32_t* perm, const uint16_t* dx, float* dwte, float* dwpe, int B, int S,
+                          int d, int vocab, void* workspace, uint64_t key_tok, uint64_t key_pos, int thresh, void* stream);
+/* dmi_dropout_add_ln: x_out[m, c] = bf16(float(residual) + drop(float(a))) (one fp32 product, one fp32 sum, one rounding), then
+ * y, mean, rstd = what dmi_layernorm_fwd computes from the stored x_out, bit for bit, in the same pass (the row stays in
+ * registers; d <= 4096).  gamma == NULL: x_out only -- beta, y, mean, rstd are not touched (a LayerNorm launched elsewhere).
+ * dmi_dropout_bwd: dy[m, c] = bf16(drop(float(dx))), the gradient of a dropped branch output; nothing past M * d is touched. */
+int dmi_dropout_add_ln(const uint16_t* a, const uint16_t* residual, uint16_t* x_out, const uint16_t* gamma, const uint16_t* beta,
+                       uint16_t* y, float* mean, float* rstd, int64_t M, int d, uint64_t key, int thresh, float eps, void* stream);
+int dmi_dropout_bwd(const uint16_t* dx, uint16_t* dy, int64_t M, int d, uint64_t key, int thresh, void* stream);
+
 /* ---- K2  LayerNorm eps=1e-5 biased variance   models.py:373-389, layers.py:30-33 ---- */
 int dmi_layernorm_fwd(const uint16_t* x, const uint16_t* g, const uint16_t* b, uint16_t* y,
                       float* mean, float* rstd, int64_t rows, int d, float eps, void* stream);
