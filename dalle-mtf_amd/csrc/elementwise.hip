@@ -1567,16 +1567,40 @@ extern "C" int dmi_cast_f32_bf16(const float* in, uint16_t* out, int64_t n, void
 // sampling of the next image token from one row of head logits
 // =====================================================================================
 // The reference stops at the logits (predict raises NotImplementedError, src/model_fns.py:135-136); the sampler around the
-// incremental-inference hooks (src/dalle_mtf/models.py:246-254,281-285) is this repo's.  One block per sequence:
-//   v[i] = (z[b, i] + bias[i]) / temperature;  top-k filter: keep v[i] >= (k-th largest v)  (ties kept, as a masked_fill
-//   of v < kth would);  choice ~ softmax(v) over the kept entries, drawn as argmax_i (v[i] + Gumbel noise) -- the Gumbel-max
-//   form of the same categorical draw -- with counter-based noise hash(seed, position, b, i): reproducible, no RNG state.
-//   temperature <= 0: greedy (first maximum).
+// incremental-inference hooks (src/dalle_mtf/models.py:246-254,281-285) is this repo's.  ONE draw body, draw_tokens<NUCLEUS, GUIDED>,
+// and three kernels over it: sample_tokens_kernel <false, false>, sample_tokens_p_kernel <true, false> and
+// sample_tokens_guided_kernel <true, true>.  One block per row (GUIDED: per pair of rows):
+//   v[i] = (z[b, i] + bias[i]) * (1/temperature);  top-k filter: keep v[i] >= (k-th largest v)  (ties kept, as a masked_fill of
+//   v < kth would);  choice ~ softmax(v) over the kept entries, drawn as argmax_i (v[i] + Gumbel noise) -- the Gumbel-max form of
+//   the same categorical draw -- with counter-based noise hash(seed, position, b, i): reproducible, no RNG state.  The uniform
+//   takes 23 random bits so that the + 0.5 is exact in fp32: u in [2^-24, 1 - 2^-24], strictly inside (0, 1) -- with 24 bits
+//   16777215.5 rounds to 2^24, u == 1 and the noise -log(-log u) is +inf (the entry then wins regardless of its logit).
+//   temperature <= 0: greedy (first maximum), top_k and top_p ignored.
 // The k-th largest value is found without a sort: 32 steps of a bitwise binary search on order-preserving integer keys
 // (count(key >= candidate) >= k), a block-wide count per step.
-// Everything that changes between calls may come from device memory (params_dev: {1/temperature or 0, top_k, seed lo, seed hi};
-// pos_dev), and the choice is written where the next decode step reads its input token, so that decode + sampling replay as one
-// HIP graph with no host round trip per position.
+// NUCLEUS adds the top-p filter after the top-k one, and the row's log-likelihood:
+//   q = softmax(v) over the top-k survivors, quantised: u[i] = floor(exp(v[i] - max v) * 2^31) (the maximum has u = 2^31), the
+//   mass of a set is the 64-bit integer sum of its u, the whole survivor set has mass Z, and the target is
+//   ceil(double(top_p) * double(Z)) (one IEEE double product: a numpy restatement reproduces it bit for bit);
+//   tau = the largest u-candidate with mass(u >= tau) >= target, found by the same 32-step bitwise search as the k-th value (the
+//   predicate "mass of entries with u >= candidate >= target") -- tau is the u of the last entry of the shortest descending prefix
+//   that reaches top_p, and EVERY survivor with u >= tau is kept (ties at tau kept, as for top-k).  No sort; the kept set does not
+//   depend on summation order.  Entries with u = 0 (q < 2^-31) are never in a nucleus with top_p < 1;
+//   top_p >= 1 (or not in (0, 1), or a row whose maximum is not finite) skips the nucleus step: the kept set is the top-k set and
+//   the choice is the plain instance's, bit for bit -- the same statements draw it;
+//   logp (nullable): logp[b] += (z + bias)[c] - logsumexp_i (z + bias)[i] (fp32, temperature 1, unfiltered; c the choice).
+// GUIDED (classifier-free guidance): z holds 2 * Bc rows, the conditional ones first; block b draws for the pair (b, Bc + b) from
+//   zc = z[b] + bias, zu = z[Bc + b] + bias, g = zc + (scale - 1) * (zc - zu)  -- difference, product and sum each rounded to
+//   fp32 on their own (no fused multiply-add: a numpy float32 restatement gives the same bits); scale - 1 == 0 takes g = zc itself,
+//   so that scale 1 is the unguided draw on the conditional rows whatever the unconditional ones hold;
+//   v = g * (1/temperature), and from there on everything is the nucleus draw, the noise hashed with the pair index b;
+//   next_tok[b] = next_tok[Bc + b] (both halves of the KV cache are fed the drawn token), out has Bc rows, and logp scores the
+//   choice under the conditional row alone: log softmax(zc)[c], the model's own likelihood, comparable across guidance scales.
+// Everything that changes between calls may come from device memory (params_dev: {1/temperature or 0, top_k, seed lo, seed hi} and,
+// NUCLEUS, {top_p, scale}: the plain instance reads four words; pos_dev), and the choice is written where the next decode step
+// reads its input token, so that decode + sampling replay as one HIP graph with no host round trip per position.
+// LDS: the keys, 32 KB at nv = 8192, and under NUCLEUS as much again for u -- at most two such blocks per CU, so a B <= 128
+// launch is resident at once.
 __device__ __forceinline__ unsigned order_key(float v) {
   const unsigned u = __float_as_uint(v);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -1584,113 +1608,6 @@ __device__ __forceinline__ unsigned order_key(float v) {
 __device__ __forceinline__ float key_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 // (splitmix64: common.h)
 #define SAMPLE_MAX_VOCAB 8192
-__global__ __launch_bounds__(256) void sample_tokens_kernel(const bf16_t* __restrict__ z, int ldz, const bf16_t* __restrict__ bias, int nv,
-                                                            float inv_temp, int top_k, uint64_t seed, const unsigned* __restrict__ params_dev,
-                                                            int pos_arg, int* pos_dev, int advance, int token_offset,
-                                                            int* __restrict__ next_tok, int* __restrict__ out, int out_ld, int out_col0) {
-  __shared__ unsigned keys[SAMPLE_MAX_VOCAB];
-  __shared__ int cnt[4];
-  __shared__ float bval[4];
-  __shared__ int bidx[4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  if (params_dev) {
-    inv_temp = __uint_as_float(params_dev[0]);
-    top_k = (int)params_dev[1];
-    seed = (uint64_t)params_dev[2] | ((uint64_t)params_dev[3] << 32);
-  }
-  const int counter = pos_dev ? *pos_dev : pos_arg;
-  const bool greedy = !(inv_temp > 0.f);
-  for (int i = tid; i < nv; i += 256) {
-    float v = bf2f(z[(int64_t)b * ldz + i]);
-    if (bias) v += bf2f(bias[i]);
-    if (!greedy) v *= inv_temp;
-    keys[i] = order_key(v);
-  }
-  __syncthreads();
-  unsigned thr = 0u;
-  if (!greedy && top_k > 0 && top_k < nv) {
-    for (int bit = 31; bit >= 0; --bit) {
-      const unsigned cand = thr | (1u << bit);
-      int c = 0;
-      for (int i = tid; i < nv; i += 256) c += keys[i] >= cand;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-      if (lane == 0) cnt[wid] = c;
-      __syncthreads();
-      const int total = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-      __syncthreads();
-      if (total >= top_k) thr = cand;   // block-uniform
-    }
-  }
-  const uint64_t stream_key = splitmix64(seed ^ ((uint64_t)(unsigned)counter * 0xD2B74407B1CE6E93ull));
-  float best = -INFINITY;
-  int besti = nv;
-  for (int i = tid; i < nv; i += 256) {   // ascending i per thread: strict > keeps the first maximum
-    const unsigned k = keys[i];
-    if (k < thr) continue;
-    float s = key_value(k);
-    if (!greedy) {
-      const uint64_t h = splitmix64(stream_key + (((uint64_t)(unsigned)b << 32) | (unsigned)i));
-      // 23 random bits so that the + 0.5 is exact in fp32: u in [2^-24, 1 - 2^-24], strictly inside (0, 1) -- with 24 bits
-      // 16777215.5 rounds to 2^24, u == 1 and the Gumbel noise -log(-log u) is +inf (the entry then wins regardless of its logit)
-      const float u = ((float)(unsigned)(h >> 41) + 0.5f) * (1.0f / 8388608.0f);
-      s -= __logf(-__logf(u));
-    }
-    if (s > best) { best = s; besti = i; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(besti, o, 64);
-    if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
-  }
-  if (lane == 0) { bval[wid] = best; bidx[wid] = besti; }
-  __syncthreads();
-  if (tid == 0) {
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-      if (bval[w] > best || (bval[w] == best && bidx[w] < besti)) { best = bval[w]; besti = bidx[w]; }
-    if (besti >= nv) besti = 0;          // all-NaN row: defined output
-    if (next_tok) next_tok[b] = token_offset + besti;
-    const int col = counter - out_col0;
-    if (out && col >= 0 && col < out_ld) out[(int64_t)b * out_ld + col] = besti;
-    if (advance && pos_dev) {            // the last block to finish moves the position on (every block has read it by then)
-      __threadfence();
-      if (atomicAdd(pos_dev + 1, 1) == (int)gridDim.x - 1) {
-        pos_dev[1] = 0;
-        pos_dev[0] = counter + 1;
-      }
-    }
-  }
-}
-extern "C" int dmi_sample_tokens(const uint16_t* z, int ldz, const uint16_t* bias, int B, int nv, float temperature, int top_k,
-                                 uint64_t seed, const uint32_t* params_dev, int pos, int32_t* pos_dev, int advance, int token_offset,
-                                 int32_t* next_tok, int32_t* out, int out_ld, int out_col0, void* stream) {
-  DMI_REQUIRE(z && (next_tok || out), "sample_tokens: null pointer");
-  DMI_REQUIRE(B > 0 && nv > 0 && nv <= SAMPLE_MAX_VOCAB && ldz >= nv, "sample_tokens: need 0 < nv <= %d (nv=%d)", SAMPLE_MAX_VOCAB, nv);
-  DMI_REQUIRE(!out || out_ld > 0, "sample_tokens: out_ld");
-  DMI_REQUIRE(!advance || pos_dev, "sample_tokens: advance needs pos_dev");
-  const float inv_temp = temperature > 0.f ? 1.f / temperature : 0.f;
-  sample_tokens_kernel<<<dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream>>>(z, ldz, bias, nv, inv_temp, top_k, seed, params_dev, pos, pos_dev,
-                                                                                advance, token_offset, next_tok, out, out_ld, out_col0);
-  DMI_CHECK_LAUNCH("sample_tokens");
-  return DMI_OK;
-}
-
-// Nucleus (top-p) draw with the row's log-likelihood, beside sample_tokens_kernel (which stays as it is).  One block per row:
-//   v = (z + bias) * (1/temperature); top-k filter as above (ties of the k-th value kept);
-//   q = softmax(v) over the top-k survivors, quantised: u[i] = floor(exp(v[i] - max v) * 2^31) (the maximum has u = 2^31), the
-//   mass of a set is the 64-bit integer sum of its u, the whole survivor set has mass Z, and the target is
-//   ceil(double(top_p) * double(Z)) (one IEEE double product: a numpy restatement reproduces it bit for bit);
-//   nucleus: tau = the largest u-candidate with mass(u >= tau) >= target, found by the same 32-step bitwise search as the k-th
-//   value (the predicate "mass of entries with u >= candidate >= target") -- tau is the u of the last entry of the shortest
-//   descending prefix that reaches top_p, and EVERY survivor with u >= tau is kept (ties at tau kept, as for top-k).  No sort;
-//   the kept set does not depend on summation order.  Entries with u = 0 (q < 2^-31) are never in a nucleus with top_p < 1;
-//   the draw is Gumbel-max over the kept set with the noise of sample_tokens_kernel, hash(seed, position, b, i);
-//   top_p >= 1 (or not in (0, 1), or a row whose maximum is not finite) skips the nucleus step: the kept set is the top-k set
-//   and the choice is sample_tokens_kernel's, bit for bit.  temperature <= 0: first maximum, top_k and top_p ignored.
-//   logp (nullable): logp[b] += (z + bias)[c] - logsumexp_i (z + bias)[i] (fp32, temperature 1, unfiltered; c the choice).
-// LDS: keys and u, 2 x 32 KB at nv = 8192 -- at most two blocks per CU, so a B <= 128 launch is resident at once.
 __device__ __forceinline__ float block_max_f32(float x, float* red, int lane, int wid) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
@@ -1718,30 +1635,23 @@ __device__ __forceinline__ uint64_t block_sum_u64(uint64_t x, uint64_t* red, int
   __syncthreads();
   return x;
 }
-// Classifier-free guidance (GUIDED): z holds 2 * Bc rows, the conditional ones first; block b draws for the pair (b, Bc + b) from
-//   zc = z[b] + bias, zu = z[Bc + b] + bias, g = zc + (scale - 1) * (zc - zu)  -- difference, product and sum each rounded to
-//   fp32 on their own (no fused multiply-add: a numpy float32 restatement gives the same bits); scale - 1 == 0 takes g = zc itself,
-//   so that scale 1 is the unguided draw on the conditional rows whatever the unconditional ones hold;
-//   v = g * (1/temperature), and from there on everything is the nucleus draw above, the noise hashed with the pair index b;
-//   next_tok[b] = next_tok[Bc + b] (both halves of the KV cache are fed the drawn token), out has Bc rows, and logp scores the
-//   choice under the conditional row alone: log softmax(zc)[c], the model's own likelihood, comparable across guidance scales.
-// The body is shared: the unguided instance compiles to the kernel it was before the guided one existed.
 __device__ __forceinline__ float guided_logit(float zc, float zu, float sm1) {
 #pragma clang fp contract(off)
   const float d = zc - zu;
   const float t = sm1 * d;
   return sm1 == 0.f ? zc : zc + t;
 }
-template <bool GUIDED>
-__device__ __forceinline__ void nucleus_draw(const bf16_t* __restrict__ z, int ldz, const bf16_t* __restrict__ bias, int nv, float inv_temp,
-                                             int top_k, uint64_t seed, float top_p, float scale, const unsigned* __restrict__ params_dev,
-                                             int pos_arg, int* pos_dev, int advance, int token_offset, int* __restrict__ next_tok,
-                                             int* __restrict__ out, int out_ld, int out_col0, float* __restrict__ logp) {
+template <bool NUCLEUS, bool GUIDED>
+__device__ __forceinline__ void draw_tokens(const bf16_t* __restrict__ z, int ldz, const bf16_t* __restrict__ bias, int nv, float inv_temp,
+                                            int top_k, uint64_t seed, float top_p, float scale, const unsigned* __restrict__ params_dev,
+                                            int pos_arg, int* pos_dev, int advance, int token_offset, int* __restrict__ next_tok,
+                                            int* __restrict__ out, int out_ld, int out_col0, float* __restrict__ logp) {
+  static_assert(NUCLEUS || !GUIDED, "the guided draw is a nucleus draw");
   __shared__ unsigned keys[SAMPLE_MAX_VOCAB];
-  __shared__ unsigned qu[SAMPLE_MAX_VOCAB];
+  __shared__ unsigned qu[NUCLEUS ? SAMPLE_MAX_VOCAB : 1];   // (the one-element forms are never referenced and take no LDS)
   __shared__ int cnt[4];
-  __shared__ uint64_t red64[4];
-  __shared__ float redf[4];
+  __shared__ uint64_t red64[NUCLEUS ? 4 : 1];
+  __shared__ float redf[NUCLEUS ? 4 : 1];
   __shared__ float bval[4];
   __shared__ int bidx[4];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -1749,8 +1659,8 @@ __device__ __forceinline__ void nucleus_draw(const bf16_t* __restrict__ z, int l
     inv_temp = __uint_as_float(params_dev[0]);
     top_k = (int)params_dev[1];
     seed = (uint64_t)params_dev[2] | ((uint64_t)params_dev[3] << 32);
-    top_p = __uint_as_float(params_dev[4]);
-    if (GUIDED) scale = __uint_as_float(params_dev[5]);
+    if constexpr (NUCLEUS) top_p = __uint_as_float(params_dev[4]);
+    if constexpr (GUIDED) scale = __uint_as_float(params_dev[5]);
   }
   const int counter = pos_dev ? *pos_dev : pos_arg;
   const bool greedy = !(inv_temp > 0.f);
@@ -1758,7 +1668,7 @@ __device__ __forceinline__ void nucleus_draw(const bf16_t* __restrict__ z, int l
   for (int i = tid; i < nv; i += 256) {
     float v = bf2f(z[(int64_t)b * ldz + i]);
     if (bias) v += bf2f(bias[i]);
-    if (GUIDED) {
+    if constexpr (GUIDED) {
       float vu = bf2f(z[(int64_t)(gridDim.x + b) * ldz + i]);
       if (bias) vu += bf2f(bias[i]);
       v = guided_logit(v, vu, scale - 1.f);
@@ -1766,7 +1676,7 @@ __device__ __forceinline__ void nucleus_draw(const bf16_t* __restrict__ z, int l
     if (!greedy) v *= inv_temp;
     const unsigned k = order_key(v);
     keys[i] = k;
-    kmax = max(kmax, k);
+    if constexpr (NUCLEUS) kmax = max(kmax, k);
   }
   __syncthreads();
   unsigned thr = 0u;
@@ -1786,36 +1696,38 @@ __device__ __forceinline__ void nucleus_draw(const bf16_t* __restrict__ z, int l
   }
   // nucleus threshold on the quantised probabilities (block-uniform; 0 = no nucleus step)
   unsigned qthr = 0u;
-  if (!greedy && top_p > 0.f && top_p < 1.f) {
+  if constexpr (NUCLEUS) {
+    if (!greedy && top_p > 0.f && top_p < 1.f) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o, 64));
-    if (lane == 0) cnt[wid] = (int)kmax;
-    __syncthreads();
-    kmax = max(max((unsigned)cnt[0], (unsigned)cnt[1]), max((unsigned)cnt[2], (unsigned)cnt[3]));
-    __syncthreads();
-    const float vmax = key_value(kmax);
-    if (isfinite(vmax)) {
-      uint64_t part = 0;
-      for (int i = tid; i < nv; i += 256) {
-        const unsigned k = keys[i];
-        unsigned u = 0u;
-        if (k >= thr) {
-          const float e = expf(key_value(k) - vmax);     // in [0, 1]; NaN entries compare false and weigh nothing
-          u = e >= 0.f ? (unsigned)(e * 2147483648.0f) : 0u;
-        }
-        qu[i] = u;
-        part += u;
-      }
-      const uint64_t mass = block_sum_u64(part, red64, lane, wid);   // __syncthreads inside: qu is complete
-      const uint64_t target = (uint64_t)ceil((double)top_p * (double)mass);
-      for (int bit = 31; bit >= 0; --bit) {
-        const unsigned cand = qthr | (1u << bit);
-        uint64_t s = 0;
+      for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o, 64));
+      if (lane == 0) cnt[wid] = (int)kmax;
+      __syncthreads();
+      kmax = max(max((unsigned)cnt[0], (unsigned)cnt[1]), max((unsigned)cnt[2], (unsigned)cnt[3]));
+      __syncthreads();
+      const float vmax = key_value(kmax);
+      if (isfinite(vmax)) {
+        uint64_t part = 0;
         for (int i = tid; i < nv; i += 256) {
-          const unsigned u = qu[i];
-          s += u >= cand ? u : 0u;
+          const unsigned k = keys[i];
+          unsigned u = 0u;
+          if (k >= thr) {
+            const float e = expf(key_value(k) - vmax);     // in [0, 1]; NaN entries compare false and weigh nothing
+            u = e >= 0.f ? (unsigned)(e * 2147483648.0f) : 0u;
+          }
+          qu[i] = u;
+          part += u;
         }
-        if (block_sum_u64(s, red64, lane, wid) >= target) qthr = cand;   // block-uniform
+        const uint64_t mass = block_sum_u64(part, red64, lane, wid);   // __syncthreads inside: qu is complete
+        const uint64_t target = (uint64_t)ceil((double)top_p * (double)mass);
+        for (int bit = 31; bit >= 0; --bit) {
+          const unsigned cand = qthr | (1u << bit);
+          uint64_t s = 0;
+          for (int i = tid; i < nv; i += 256) {
+            const unsigned u = qu[i];
+            s += u >= cand ? u : 0u;
+          }
+          if (block_sum_u64(s, red64, lane, wid) >= target) qthr = cand;   // block-uniform
+        }
       }
     }
   }
@@ -1825,11 +1737,12 @@ __device__ __forceinline__ void nucleus_draw(const bf16_t* __restrict__ z, int l
   for (int i = tid; i < nv; i += 256) {   // ascending i per thread: strict > keeps the first maximum
     const unsigned k = keys[i];
     if (k < thr) continue;
-    if (qthr && qu[i] < qthr) continue;
+    if constexpr (NUCLEUS)
+      if (qthr && qu[i] < qthr) continue;
     float s = key_value(k);
     if (!greedy) {
       const uint64_t h = splitmix64(stream_key + (((uint64_t)(unsigned)b << 32) | (unsigned)i));
-      const float u = ((float)(unsigned)(h >> 41) + 0.5f) * (1.0f / 8388608.0f);   // as sample_tokens_kernel: u strictly in (0, 1)
+      const float u = ((float)(unsigned)(h >> 41) + 0.5f) * (1.0f / 8388608.0f);   // 23 bits: u strictly in (0, 1), see above
       s -= __logf(-__logf(u));
     }
     if (s > best) { best = s; besti = i; }
@@ -1842,29 +1755,31 @@ __device__ __forceinline__ void nucleus_draw(const bf16_t* __restrict__ z, int l
   }
   if (lane == 0) { bval[wid] = best; bidx[wid] = besti; }
   __syncthreads();
-  if (logp) {   // log-softmax of the unscaled row at the choice (every thread takes the choice from the wave winners)
+  if constexpr (NUCLEUS) {
+    if (logp) {   // log-softmax of the unscaled row at the choice (every thread takes the choice from the wave winners)
 #pragma unroll
-    for (int w = 0; w < 4; ++w)
-      if (bval[w] > best || (bval[w] == best && bidx[w] < besti)) { best = bval[w]; besti = bidx[w]; }
-    float m = -INFINITY;
-    for (int i = tid; i < nv; i += 256) {
-      float v = bf2f(z[(int64_t)b * ldz + i]);
-      if (bias) v += bf2f(bias[i]);
-      m = fmaxf(m, v);
-    }
-    m = block_max_f32(m, redf, lane, wid);
-    float se = 0.f;
-    for (int i = tid; i < nv; i += 256) {
-      float v = bf2f(z[(int64_t)b * ldz + i]);
-      if (bias) v += bf2f(bias[i]);
-      se += expf(v - m);
-    }
-    se = block_sum_f32(se, redf, lane, wid);
-    if (tid == 0) {
-      const int c = besti >= nv ? 0 : besti;
-      float vc = bf2f(z[(int64_t)b * ldz + c]);
-      if (bias) vc += bf2f(bias[c]);
-      logp[b] += (vc - m) - logf(se);
+      for (int w = 0; w < 4; ++w)
+        if (bval[w] > best || (bval[w] == best && bidx[w] < besti)) { best = bval[w]; besti = bidx[w]; }
+      float m = -INFINITY;
+      for (int i = tid; i < nv; i += 256) {
+        float v = bf2f(z[(int64_t)b * ldz + i]);
+        if (bias) v += bf2f(bias[i]);
+        m = fmaxf(m, v);
+      }
+      m = block_max_f32(m, redf, lane, wid);
+      float se = 0.f;
+      for (int i = tid; i < nv; i += 256) {
+        float v = bf2f(z[(int64_t)b * ldz + i]);
+        if (bias) v += bf2f(bias[i]);
+        se += expf(v - m);
+      }
+      se = block_sum_f32(se, redf, lane, wid);
+      if (tid == 0) {
+        const int c = besti >= nv ? 0 : besti;
+        float vc = bf2f(z[(int64_t)b * ldz + c]);
+        if (bias) vc += bf2f(bias[c]);
+        logp[b] += (vc - m) - logf(se);
+      }
     }
   }
   if (tid == 0) {
@@ -1885,53 +1800,77 @@ __device__ __forceinline__ void nucleus_draw(const bf16_t* __restrict__ z, int l
     }
   }
 }
+__global__ __launch_bounds__(256) void sample_tokens_kernel(const bf16_t* __restrict__ z, int ldz, const bf16_t* __restrict__ bias, int nv,
+                                                            float inv_temp, int top_k, uint64_t seed, const unsigned* __restrict__ params_dev,
+                                                            int pos_arg, int* pos_dev, int advance, int token_offset,
+                                                            int* __restrict__ next_tok, int* __restrict__ out, int out_ld, int out_col0) {
+  draw_tokens<false, false>(z, ldz, bias, nv, inv_temp, top_k, seed, 1.f, 1.f, params_dev, pos_arg, pos_dev, advance, token_offset, next_tok,
+                            out, out_ld, out_col0, nullptr);
+}
 __global__ __launch_bounds__(256) void sample_tokens_p_kernel(const bf16_t* __restrict__ z, int ldz, const bf16_t* __restrict__ bias, int nv,
                                                               float inv_temp, int top_k, uint64_t seed, float top_p,
                                                               const unsigned* __restrict__ params_dev, int pos_arg, int* pos_dev, int advance,
                                                               int token_offset, int* __restrict__ next_tok, int* __restrict__ out, int out_ld,
                                                               int out_col0, float* __restrict__ logp) {
-  nucleus_draw<false>(z, ldz, bias, nv, inv_temp, top_k, seed, top_p, 1.f, params_dev, pos_arg, pos_dev, advance, token_offset, next_tok, out,
-                      out_ld, out_col0, logp);
+  draw_tokens<true, false>(z, ldz, bias, nv, inv_temp, top_k, seed, top_p, 1.f, params_dev, pos_arg, pos_dev, advance, token_offset, next_tok,
+                           out, out_ld, out_col0, logp);
 }
 __global__ __launch_bounds__(256) void sample_tokens_guided_kernel(const bf16_t* __restrict__ z, int ldz, const bf16_t* __restrict__ bias, int nv,
                                                                    float inv_temp, int top_k, uint64_t seed, float top_p, float scale,
                                                                    const unsigned* __restrict__ params_dev, int pos_arg, int* pos_dev,
                                                                    int advance, int token_offset, int* __restrict__ next_tok,
                                                                    int* __restrict__ out, int out_ld, int out_col0, float* __restrict__ logp) {
-  nucleus_draw<true>(z, ldz, bias, nv, inv_temp, top_k, seed, top_p, scale, params_dev, pos_arg, pos_dev, advance, token_offset, next_tok, out,
-                     out_ld, out_col0, logp);
+  draw_tokens<true, true>(z, ldz, bias, nv, inv_temp, top_k, seed, top_p, scale, params_dev, pos_arg, pos_dev, advance, token_offset, next_tok,
+                          out, out_ld, out_col0, logp);
+}
+// the checks and the launch that the three entry points share; name prefixes the messages.  rows: B, or the Bc pairs of the guided
+// form, which has checked them with nv under its own message
+enum DrawKind { DRAW_PLAIN, DRAW_NUCLEUS, DRAW_GUIDED };
+static int launch_draw(const char* name, DrawKind kind, const uint16_t* z, int ldz, const uint16_t* bias, int rows, int nv, float temperature,
+                       int top_k, uint64_t seed, float top_p, float scale, const uint32_t* params_dev, int pos, int32_t* pos_dev,
+                       int advance, int token_offset, int32_t* next_tok, int32_t* out, int out_ld, int out_col0, float* logp, void* stream) {
+  DMI_REQUIRE(z && (next_tok || out), "%s: null pointer", name);
+  DMI_REQUIRE(rows > 0 && nv > 0 && nv <= SAMPLE_MAX_VOCAB && ldz >= nv, "%s: need 0 < nv <= %d (nv=%d)", name, SAMPLE_MAX_VOCAB, nv);
+  DMI_REQUIRE(!out || out_ld > 0, "%s: out_ld", name);
+  DMI_REQUIRE(!advance || pos_dev, "%s: advance needs pos_dev", name);
+  const float inv_temp = temperature > 0.f ? 1.f / temperature : 0.f;
+  const dim3 grid((unsigned)rows), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (kind == DRAW_PLAIN)
+    sample_tokens_kernel<<<grid, block, 0, s>>>(z, ldz, bias, nv, inv_temp, top_k, seed, params_dev, pos, pos_dev, advance, token_offset, next_tok,
+                                                out, out_ld, out_col0);
+  else if (kind == DRAW_NUCLEUS)
+    sample_tokens_p_kernel<<<grid, block, 0, s>>>(z, ldz, bias, nv, inv_temp, top_k, seed, top_p, params_dev, pos, pos_dev, advance, token_offset,
+                                                  next_tok, out, out_ld, out_col0, logp);
+  else
+    sample_tokens_guided_kernel<<<grid, block, 0, s>>>(z, ldz, bias, nv, inv_temp, top_k, seed, top_p, scale, params_dev, pos, pos_dev, advance,
+                                                       token_offset, next_tok, out, out_ld, out_col0, logp);
+  DMI_CHECK_LAUNCH(name);
+  return DMI_OK;
+}
+extern "C" int dmi_sample_tokens(const uint16_t* z, int ldz, const uint16_t* bias, int B, int nv, float temperature, int top_k,
+                                 uint64_t seed, const uint32_t* params_dev, int pos, int32_t* pos_dev, int advance, int token_offset,
+                                 int32_t* next_tok, int32_t* out, int out_ld, int out_col0, void* stream) {
+  return launch_draw("sample_tokens", DRAW_PLAIN, z, ldz, bias, B, nv, temperature, top_k, seed, 1.f, 1.f, params_dev, pos, pos_dev, advance,
+                     token_offset, next_tok, out, out_ld, out_col0, nullptr, stream);
 }
 extern "C" int dmi_sample_tokens_p(const uint16_t* z, int ldz, const uint16_t* bias, int B, int nv, float temperature, int top_k,
                                    uint64_t seed, float top_p, const uint32_t* params_dev, int pos, int32_t* pos_dev, int advance,
                                    int token_offset, int32_t* next_tok, int32_t* out, int out_ld, int out_col0, float* logp, void* stream) {
-  DMI_REQUIRE(z && (next_tok || out), "sample_tokens_p: null pointer");
-  DMI_REQUIRE(B > 0 && nv > 0 && nv <= SAMPLE_MAX_VOCAB && ldz >= nv, "sample_tokens_p: need 0 < nv <= %d (nv=%d)", SAMPLE_MAX_VOCAB, nv);
   DMI_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_tokens_p: top_p must lie in (0, 1] (top_p=%g)", (double)top_p);
-  DMI_REQUIRE(!out || out_ld > 0, "sample_tokens_p: out_ld");
-  DMI_REQUIRE(!advance || pos_dev, "sample_tokens_p: advance needs pos_dev");
-  const float inv_temp = temperature > 0.f ? 1.f / temperature : 0.f;
-  sample_tokens_p_kernel<<<dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream>>>(z, ldz, bias, nv, inv_temp, top_k, seed, top_p, params_dev, pos,
-                                                                                  pos_dev, advance, token_offset, next_tok, out, out_ld, out_col0, logp);
-  DMI_CHECK_LAUNCH("sample_tokens_p");
-  return DMI_OK;
+  return launch_draw("sample_tokens_p", DRAW_NUCLEUS, z, ldz, bias, B, nv, temperature, top_k, seed, top_p, 1.f, params_dev, pos, pos_dev,
+                     advance, token_offset, next_tok, out, out_ld, out_col0, logp, stream);
 }
 extern "C" int dmi_sample_tokens_guided(const uint16_t* z, int ldz, const uint16_t* bias, int Bc, int nv, float temperature, int top_k,
                                         uint64_t seed, float top_p, float scale, const uint32_t* params_dev, int pos, int32_t* pos_dev,
                                         int advance, int token_offset, int32_t* next_tok, int32_t* out, int out_ld, int out_col0, float* logp,
                                         void* stream) {
-  DMI_REQUIRE(z && (next_tok || out), "sample_tokens_guided: null pointer");
   DMI_REQUIRE(Bc > 0 && nv > 0 && nv <= SAMPLE_MAX_VOCAB && ldz >= nv, "sample_tokens_guided: need Bc > 0 and 0 < nv <= %d (Bc=%d, nv=%d)",
               SAMPLE_MAX_VOCAB, Bc, nv);
   DMI_REQUIRE(top_p > 0.f && top_p <= 1.f, "sample_tokens_guided: top_p must lie in (0, 1] (top_p=%g)", (double)top_p);
   DMI_REQUIRE(scale >= 0.f && scale <= 3.402823466e38f, "sample_tokens_guided: scale must be finite and >= 0 (scale=%g)", (double)scale);
-  DMI_REQUIRE(!out || out_ld > 0, "sample_tokens_guided: out_ld");
-  DMI_REQUIRE(!advance || pos_dev, "sample_tokens_guided: advance needs pos_dev");
-  const float inv_temp = temperature > 0.f ? 1.f / temperature : 0.f;
-  sample_tokens_guided_kernel<<<dim3((unsigned)Bc), dim3(256), 0, (hipStream_t)stream>>>(z, ldz, bias, nv, inv_temp, top_k, seed, top_p, scale, params_dev,
-                                                                                       pos, pos_dev, advance, token_offset, next_tok, out, out_ld,
-                                                                                       out_col0, logp);
-  DMI_CHECK_LAUNCH("sample_tokens_guided");
-  return DMI_OK;
+  return launch_draw("sample_tokens_guided", DRAW_GUIDED, z, ldz, bias, Bc, nv, temperature, top_k, seed, top_p, scale, params_dev, pos, pos_dev,
+                     advance, token_offset, next_tok, out, out_ld, out_col0, logp, stream);
 }
 
 // fp32 logits of a head-output slice: out[b, i] = float(z[b, i]) + float(bias[i])  (src/dalle_mtf/models.py:394-395)

@@ -608,24 +608,43 @@ def assemble_tokens(text, vae_logits, tokens_out, B, T, P, C, text_vocab):
     _check(lib().dmi_assemble_tokens(_p(text), _p(vae_logits), _p(tokens_out), B, T, P, C, text_vocab, _stream()), "assemble_tokens")
 
 
+def _draw(name, z, ldz, bias, rows, nv, temperature, top_k, seed, extra, pos, token_offset, next_tok, out, out_col0, params_dev,
+          pos_dev, advance, logp=None, tok_rows=None):
+    """the checks that the three draws share, then dmi_<name>.  extra: the by-value arguments that the entry point takes after
+    seed -- () / (top_p,) / (top_p, scale); with any of them the device parameter block has six words.  rows: B, or the Bc pairs
+    of the guided draw, whose next_tok holds tok_rows = 2 * Bc"""
+    _dev(z)
+    assert z.dtype == torch.bfloat16 and (bias is None or bias.dtype == torch.bfloat16)
+    if pos_dev is not None:
+        assert pos_dev.dtype == torch.int32 and pos_dev.numel() >= (2 if advance else 1), \
+            f"{name}: pos_dev must be int32 [2] ([position, zeroed counter]) when advance=True, int32 [1] otherwise"
+    if params_dev is not None and extra:
+        assert params_dev.numel() >= 6 and params_dev.element_size() == 4, f"{name}: params_dev must be 32-bit [6]"
+    if tok_rows is not None:
+        if next_tok is not None:
+            assert next_tok.dtype == torch.int32 and next_tok.numel() >= tok_rows, f"{name}: next_tok must be int32 [2 * Bc]"
+        if out is not None:
+            assert out.dtype == torch.int32 and out.dim() == 2 and out.shape[0] >= rows, f"{name}: out must be int32 [Bc, n]"
+    if logp is not None:
+        assert logp.dtype == torch.float32 and logp.numel() >= rows, f"{name}: logp must be fp32 [{'Bc' if tok_rows else 'B'}]"
+    for t in (bias, next_tok, out, params_dev, pos_dev, logp):
+        if t is not None:
+            _dev(t)
+    out_ld = int(out.shape[1]) if out is not None else 0
+    tail = (_p(logp),) if extra else ()
+    _check(getattr(lib(), "dmi_" + name)(_p(z), ldz, _p(bias), rows, nv, float(temperature), int(top_k), int(seed) & (2 ** 64 - 1),
+                                         *map(float, extra), _p(params_dev), int(pos), _p(pos_dev), int(bool(advance)),
+                                         int(token_offset), _p(next_tok), _p(out), out_ld, int(out_col0), *tail, _stream()), name)
+
+
 def sample_tokens(z, ldz, bias, B, nv, temperature=1.0, top_k=0, seed=0, pos=0, token_offset=0, next_tok=None, out=None,
                   out_col0=0, params_dev=None, pos_dev=None, advance=False):
     """next image token per row of head logits z bf16 [B, ldz] (+ bias bf16 [nv]): temperature / top-k / greedy; the draw is
     a pure function of (seed, position, row).  params_dev (uint32 [4]) / pos_dev (int32) override the by-value settings.
     pos_dev is int32 [1] (the position) -- or, with advance=True, int32 [2]: [position, arrival counter]; the kernel's last
     block to finish increments [0] and resets [1], which must be zero on entry (include/dalle_hip.h)."""
-    _dev(z)
-    assert z.dtype == torch.bfloat16 and (bias is None or bias.dtype == torch.bfloat16)
-    if pos_dev is not None:
-        assert pos_dev.dtype == torch.int32 and pos_dev.numel() >= (2 if advance else 1), \
-            "sample_tokens: pos_dev must be int32 [2] ([position, zeroed counter]) when advance=True, int32 [1] otherwise"
-    for t in (bias, next_tok, out, params_dev, pos_dev):
-        if t is not None:
-            _dev(t)
-    out_ld = int(out.shape[1]) if out is not None else 0
-    _check(lib().dmi_sample_tokens(_p(z), ldz, _p(bias), B, nv, float(temperature), int(top_k), int(seed) & (2 ** 64 - 1),
-                                   _p(params_dev), int(pos), _p(pos_dev), int(bool(advance)), int(token_offset), _p(next_tok), _p(out), out_ld,
-                                   int(out_col0), _stream()), "sample_tokens")
+    _draw("sample_tokens", z, ldz, bias, B, nv, temperature, top_k, seed, (), pos, token_offset, next_tok, out, out_col0, params_dev,
+          pos_dev, advance)
 
 
 def sample_tokens_p(z, ldz, bias, B, nv, temperature=1.0, top_k=0, seed=0, top_p=1.0, pos=0, token_offset=0, next_tok=None,
@@ -634,22 +653,8 @@ def sample_tokens_p(z, ldz, bias, B, nv, temperature=1.0, top_k=0, seed=0, top_p
     logp fp32 [B] (zeroed by the caller) += log_softmax(z + bias)[choice] at temperature 1, unfiltered.  params_dev is uint32 [6]:
     {bits of 1/temperature (0: greedy), top_k, seed lo, seed hi, bits of top_p, 0}.  At top_p = 1 the tokens are sample_tokens'
     bit for bit (include/dalle_hip.h)."""
-    _dev(z)
-    assert z.dtype == torch.bfloat16 and (bias is None or bias.dtype == torch.bfloat16)
-    if pos_dev is not None:
-        assert pos_dev.dtype == torch.int32 and pos_dev.numel() >= (2 if advance else 1), \
-            "sample_tokens_p: pos_dev must be int32 [2] ([position, zeroed counter]) when advance=True, int32 [1] otherwise"
-    if params_dev is not None:
-        assert params_dev.numel() >= 6 and params_dev.element_size() == 4, "sample_tokens_p: params_dev must be 32-bit [6]"
-    if logp is not None:
-        assert logp.dtype == torch.float32 and logp.numel() >= B, "sample_tokens_p: logp must be fp32 [B]"
-    for t in (bias, next_tok, out, params_dev, pos_dev, logp):
-        if t is not None:
-            _dev(t)
-    out_ld = int(out.shape[1]) if out is not None else 0
-    _check(lib().dmi_sample_tokens_p(_p(z), ldz, _p(bias), B, nv, float(temperature), int(top_k), int(seed) & (2 ** 64 - 1),
-                                     float(top_p), _p(params_dev), int(pos), _p(pos_dev), int(bool(advance)), int(token_offset),
-                                     _p(next_tok), _p(out), out_ld, int(out_col0), _p(logp), _stream()), "sample_tokens_p")
+    _draw("sample_tokens_p", z, ldz, bias, B, nv, temperature, top_k, seed, (top_p,), pos, token_offset, next_tok, out, out_col0,
+          params_dev, pos_dev, advance, logp)
 
 
 def sample_tokens_guided(z, ldz, bias, Bc, nv, temperature=1.0, top_k=0, seed=0, top_p=1.0, scale=1.0, pos=0, token_offset=0,
@@ -658,27 +663,8 @@ def sample_tokens_guided(z, ldz, bias, Bc, nv, temperature=1.0, top_k=0, seed=0,
     z bf16 [2 * Bc, ldz] (+ bias); one token per pair, written to next_tok[b] and next_tok[Bc + b] (int32 [2 * Bc]) and to
     out int32 [Bc, out_ld]; logp fp32 [Bc] += log_softmax(zc)[choice].  params_dev is uint32 [6] with word 5 = bits of scale
     (sample_params(..., guidance_scale=)).  scale = 1 draws sample_tokens_p's tokens of the first Bc rows (include/dalle_hip.h)."""
-    _dev(z)
-    assert z.dtype == torch.bfloat16 and (bias is None or bias.dtype == torch.bfloat16)
-    if pos_dev is not None:
-        assert pos_dev.dtype == torch.int32 and pos_dev.numel() >= (2 if advance else 1), \
-            "sample_tokens_guided: pos_dev must be int32 [2] ([position, zeroed counter]) when advance=True, int32 [1] otherwise"
-    if params_dev is not None:
-        assert params_dev.numel() >= 6 and params_dev.element_size() == 4, "sample_tokens_guided: params_dev must be 32-bit [6]"
-    if next_tok is not None:
-        assert next_tok.dtype == torch.int32 and next_tok.numel() >= 2 * Bc, "sample_tokens_guided: next_tok must be int32 [2 * Bc]"
-    if out is not None:
-        assert out.dtype == torch.int32 and out.dim() == 2 and out.shape[0] >= Bc, "sample_tokens_guided: out must be int32 [Bc, n]"
-    if logp is not None:
-        assert logp.dtype == torch.float32 and logp.numel() >= Bc, "sample_tokens_guided: logp must be fp32 [Bc]"
-    for t in (bias, next_tok, out, params_dev, pos_dev, logp):
-        if t is not None:
-            _dev(t)
-    out_ld = int(out.shape[1]) if out is not None else 0
-    _check(lib().dmi_sample_tokens_guided(_p(z), ldz, _p(bias), Bc, nv, float(temperature), int(top_k), int(seed) & (2 ** 64 - 1),
-                                          float(top_p), float(scale), _p(params_dev), int(pos), _p(pos_dev), int(bool(advance)),
-                                          int(token_offset), _p(next_tok), _p(out), out_ld, int(out_col0), _p(logp), _stream()),
-           "sample_tokens_guided")
+    _draw("sample_tokens_guided", z, ldz, bias, Bc, nv, temperature, top_k, seed, (top_p, scale), pos, token_offset, next_tok, out,
+          out_col0, params_dev, pos_dev, advance, logp, tok_rows=2 * Bc)
 
 
 def sample_params(temperature=1.0, top_k=0, seed=0, top_p=None, guidance_scale=None):

@@ -25,7 +25,7 @@ import hashlib
 import logging
 import math
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -55,6 +55,14 @@ def _no_gc_in_capture():
 
 
 HEAD_DIMS = (64, 128)   # n_embd / n_heads values the attention kernels are built for
+# the variant of the sampler's draw: the plain, the nucleus (with or without the log-likelihood) or the guided kernel, which is a
+# nucleus one.  Keys the captured decode graphs; False there is the decode_step body, which draws nothing
+Draw = namedtuple("Draw", "nucleus guided logp")
+
+
+def draw_params(v, temperature, top_k, seed, top_p, guidance_scale):
+    """the device parameter block of variant v (a Draw): four words for the plain draw, six for the others (dalle_hip.sample_params)"""
+    return dh.sample_params(temperature, top_k, seed, top_p if v.nucleus else None, guidance_scale if v.guided else None)
 ALIGN = 128  # elements
 
 
@@ -827,7 +835,7 @@ class DalleEngine:
             k = int(image_prefix.shape[1])
             if k and (int(image_prefix.min()) < 0 or int(image_prefix.max()) >= nv):
                 raise ValueError(f"sample_image_tokens: image_prefix ids must lie in [0, {nv})")
-        nucleus = top_p < 1.0 or return_logprobs
+        variant = Draw(nucleus=guided or top_p < 1.0 or return_logprobs, guided=guided, logp=return_logprobs)
         toks = torch.full((B, S), lo, dtype=torch.int32, device=self.dev)
         toks[:R, :T] = text.to(device=self.dev, dtype=torch.int32)
         if guided:
@@ -848,21 +856,10 @@ class DalleEngine:
                 self.decode_step(toks[:, pos].contiguous(), pos, graph=True)
             D["tok"].copy_(toks[:, T - 1 + k])
             D["pos_i"][0:1].fill_(T - 1 + k)
-            if guided:
-                D["params"].copy_(dh.sample_params(temperature, top_k, seed, top_p, guidance_scale=gs))
-                variant = "g+logp" if return_logprobs else "g"
-                if return_logprobs:
-                    D["logp"].zero_()
-            elif nucleus:
-                D["params"].copy_(dh.sample_params(temperature, top_k, seed, top_p))
-                variant = "p+logp" if return_logprobs else "p"
-                if return_logprobs:
-                    D["logp"].zero_()
-            else:
-                inv_t = np.array([1.0 / temperature if temperature > 0 else 0.0], dtype=np.float32).view(np.uint32)[0]
-                prm = np.array([inv_t, int(top_k), seed & 0xffffffff, (seed >> 32) & 0xffffffff], dtype=np.uint32).view(np.int32)
-                D["params"][:4].copy_(torch.from_numpy(prm))
-                variant = True
+            prm = draw_params(variant, temperature, top_k, seed, top_p, gs)
+            D["params"][:prm.numel()].copy_(prm)         # the plain draw has four words and leaves words 4, 5 alone
+            if return_logprobs:
+                D["logp"].zero_()
             for _ in range(P - k):                       # position T-1+i predicts image token i; the graph advances the position itself
                 self._run_decode(sample=variant, graph=True)
             img = D["out"][:R].clone()                   # guided: the kernel writes one row per pair
@@ -878,19 +875,11 @@ class DalleEngine:
         nxt = torch.empty(B, dtype=torch.int32, device=self.dev)
 
         def pick(z, ldz, zbias, position):
-            """the draw itself is dmi_sample_tokens (dmi_sample_tokens_p for top_p / logp) on every path (temperature / top-k /
-            Gumbel-max with counter-based noise hash(seed, position, row, index), first maximum when temperature <= 0):
-            host-launched here, the last node of the replayed graph on the fused path -- the same (seed, position) gives the
-            same draw on both.  Guided: dmi_sample_tokens_guided, one draw per pair, written to both of its rows of nxt."""
-            if guided:
-                dh.sample_tokens_guided(z, ldz, zbias, R, nv, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p, scale=gs,
-                                        pos=position, token_offset=lo, next_tok=nxt, logp=logp)
-            elif nucleus:
-                dh.sample_tokens_p(z, ldz, zbias, B, nv, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p, pos=position,
-                                   token_offset=lo, next_tok=nxt, logp=logp)
-            else:
-                dh.sample_tokens(z, ldz, zbias, B, nv, temperature=temperature, top_k=top_k, seed=seed, pos=position,
-                                 token_offset=lo, next_tok=nxt)
+            """the draw itself is the same kernel on every path (temperature / top-k / Gumbel-max with counter-based noise
+            hash(seed, position, row, index), first maximum when temperature <= 0): host-launched here, the last node of the
+            replayed graph on the fused path -- the same (seed, position) gives the same draw on both."""
+            self._draw(variant, z, ldz, zbias, nxt, logp, top_p=top_p, scale=gs, temperature=temperature, top_k=top_k, seed=seed,
+                       pos=position)
             return nxt
 
         for pos in range(P):
@@ -970,9 +959,8 @@ class DalleEngine:
         return D["logits"]
 
     def _run_decode(self, sample, graph: bool):
-        """sample: False (the decode_step body) or the draw variant (True: dmi_sample_tokens, "p" / "p+logp":
-        dmi_sample_tokens_p without / with logp, "g" / "g+logp": dmi_sample_tokens_guided over B / 2 pairs) -- one captured
-        graph per variant, the draw node differs"""
+        """sample: False (the decode_step body) or the draw variant (a Draw) -- one captured graph per variant, the draw node
+        differs"""
         D = self._dec
         if not graph:
             self._decode_body(sample)
@@ -991,10 +979,8 @@ class DalleEngine:
 
     def _decode_body(self, sample=False):
         """the launches of one decode step; reads D[tok] and the position D[pos_i][0] from device memory.  sample=False: writes
-        D[logits].  sample=True / "p" / "p+logp": draws the next token (settings in D[params]) into D[tok] and
-        column pos - (T - 1) of D[out], then advances the position (inside the sampling kernel); "p" draws with the nucleus
-        kernel, "p+logp" also adds the choice's log-probability to D[logp]; "g" / "g+logp" draw one token per pair of rows
-        (b, B/2 + b) with the guided kernel (scale in D[params][5]) into both rows of D[tok] and rows 0 .. B/2-1 of D[out] / D[logp].
+        D[logits].  sample a Draw: draws the next token (settings in D[params]) into D[tok] and column pos - (T - 1) of D[out]
+        (and D[logp], see _draw), then advances the position (inside the sampling kernel).
         B <= 32: LayerNorm rides in the prologue of the product that consumes it (dmi_ln_gemm_nt) -- 5 dependent launches per
         block instead of 7; a dependent launch costs ~7 us on this part, more than any of these kernels' work."""
         B, d, L, H, S = self.B, self.d, self.L, self.H, self.S
@@ -1032,17 +1018,27 @@ class DalleEngine:
         Wt = self.tview("to_logits/linear_out/kernel")                 # [Vp, d]: rows lo .. lo + nv are the image vocabulary
         ln_dense(x, "to_logits/layer_norm", Wt[lo:lo + nv], z, nv)
         bias = self._w("to_logits/linear_out/bias")[lo:lo + nv]
-        if sample in ("g", "g+logp"):
-            dh.sample_tokens_guided(z, nv, bias, B // 2, nv, params_dev=D["params"], pos_dev=D["pos_i"], advance=True, token_offset=lo,
-                                    next_tok=D["tok"], out=D["out"], out_col0=self.T - 1, logp=D["logp"] if sample == "g+logp" else None)
-        elif sample in ("p", "p+logp"):
-            dh.sample_tokens_p(z, nv, bias, B, nv, params_dev=D["params"], pos_dev=D["pos_i"], advance=True, token_offset=lo,
-                               next_tok=D["tok"], out=D["out"], out_col0=self.T - 1, logp=D["logp"] if sample == "p+logp" else None)
-        elif sample:
-            dh.sample_tokens(z, nv, bias, B, nv, params_dev=D["params"], pos_dev=D["pos_i"], advance=True, token_offset=lo,
-                             next_tok=D["tok"], out=D["out"], out_col0=self.T - 1)
+        if sample:
+            self._draw(sample, z, nv, bias, D["tok"], D["logp"], params_dev=D["params"], pos_dev=D["pos_i"], advance=True, out=D["out"],
+                       out_col0=self.T - 1)
         else:
             dh.logits_f32(z, nv, bias, D["logits"], B, nv)       # "go to full precision for the logits" (models.py:394-395)
+
+    def _draw(self, v, z, ldz, bias, next_tok, logp, top_p=1.0, scale=1.0, **kw):
+        """launches the draw of variant v (a Draw) over the engine's B rows of head output z into next_tok; kw: the settings by
+        value or in device memory (dalle_hip.sample_tokens).  v.nucleus: the nucleus kernel; v.logp: it adds the choice's
+        log-probability to logp; v.guided: one token per pair of rows (b, B/2 + b) with the guided kernel, into both rows of
+        next_tok and rows 0 .. B/2-1 of out / logp"""
+        B, nv = self.B, self.image_vocab_size
+        kw.update(token_offset=self.text_vocab_size, next_tok=next_tok)
+        if v.nucleus:
+            kw.update(top_p=top_p, logp=logp if v.logp else None)
+        if v.guided:
+            dh.sample_tokens_guided(z, ldz, bias, B // 2, nv, scale=scale, **kw)
+        elif v.nucleus:
+            dh.sample_tokens_p(z, ldz, bias, B, nv, **kw)
+        else:
+            dh.sample_tokens(z, ldz, bias, B, nv, **kw)
 
     # ------------------------------------------------------------------ backward
     def _gv(self, name):

@@ -325,7 +325,11 @@ int dmi_assemble_tokens(const int32_t* text, const float* vae_logits, int32_t* t
                         int B, int T, int P, int C, int text_vocab, void* stream);
 
 /* Sampling of the next image token from head logits (the sampler around the reference's unfinished incremental-inference path,
- * src/dalle_mtf/models.py:246-254,281-285; src/model_fns.py:135-136 raises).  Per row b of z bf16 [B, ldz] (first nv columns;
+ * src/dalle_mtf/models.py:246-254,281-285; src/model_fns.py:135-136 raises).  ONE draw, three instances of one kernel body
+ * (csrc/elementwise.hip, draw_tokens<NUCLEUS, GUIDED>): dmi_sample_tokens is the plain instance, described here with everything
+ * the three share; dmi_sample_tokens_p adds the nucleus filter and logp, dmi_sample_tokens_guided adds the guided logit in front of
+ * that -- each states below only what it adds.  The shared checks carry the entry point's own name in front of their message.
+ * Per row b of z bf16 [B, ldz] (first nv columns;
  * bias bf16 [nv] optional, added in fp32): v = (z + bias) / temperature; top_k > 0 keeps v >= the k-th largest v (ties kept); the choice is a
  * categorical draw from softmax(v) over the kept entries (Gumbel-max with counter-based noise hash(seed, position, b, i):
  * reproducible, stateless); temperature <= 0: first maximum.  nv <= 8192.
@@ -338,8 +342,7 @@ int dmi_sample_tokens(const uint16_t* z, int ldz, const uint16_t* bias, int B, i
                       uint64_t seed, const uint32_t* params_dev, int pos, int32_t* pos_dev, int advance, int token_offset,
                       int32_t* next_tok, int32_t* out, int out_ld, int out_col0, void* stream);
 
-/* Nucleus (top-p) draw with the log-likelihood of the choice: dmi_sample_tokens's arguments plus top_p and logp.
- * v and the top-k filter as above; then q = softmax(v) over the top-k survivors, in fixed point: u[i] = floor(exp(v[i] - max v) * 2^31),
+/* The NUCLEUS instance: dmi_sample_tokens's arguments plus top_p and logp.  v and the top-k filter as above; then q = softmax(v) over the top-k survivors, in fixed point: u[i] = floor(exp(v[i] - max v) * 2^31),
  * the mass of a set is the 64-bit integer sum of its u, Z the mass of all survivors, target = ceil(double(top_p) * double(Z)).
  * Nucleus: the shortest prefix of the survivors sorted by q (descending) whose mass reaches top_p; tau = the u of its last entry;
  * EVERY survivor with u >= tau is kept (ties at tau kept, the top-k rule).  Found without a sort: a 32-step bitwise search for the
@@ -351,17 +354,18 @@ int dmi_sample_tokens(const uint16_t* z, int ldz, const uint16_t* bias, int B, i
  * sample's score.
  * params_dev (optional, device uint32[6] = {bits of 1/temperature (0: greedy), top_k, seed low, seed high, bits of top_p, 0})
  * overrides temperature / top_k / seed / top_p (a device top_p outside (0, 1) skips the nucleus step); pos_dev / advance /
- * next_tok / out as for dmi_sample_tokens.  One 256-thread block per row, nv <= 8192, 64 KB of LDS per block. */
+ * next_tok / out as for dmi_sample_tokens.  One 256-thread block per row, nv <= 8192, 64 KB of LDS per block (the plain instance:
+ * 32 KB). */
 int dmi_sample_tokens_p(const uint16_t* z, int ldz, const uint16_t* bias, int B, int nv, float temperature, int top_k,
                         uint64_t seed, float top_p, const uint32_t* params_dev, int pos, int32_t* pos_dev, int advance,
                         int token_offset, int32_t* next_tok, int32_t* out, int out_ld, int out_col0, float* logp, void* stream);
 
-/* Classifier-free guidance: the nucleus draw from l_uncond + scale * (l_cond - l_uncond).  z bf16 [2 * Bc, ldz]: rows 0 .. Bc-1 are
+/* The GUIDED instance, classifier-free guidance: the nucleus draw from l_uncond + scale * (l_cond - l_uncond).  z bf16 [2 * Bc, ldz]: rows 0 .. Bc-1 are
  * the conditional rows, rows Bc .. 2 Bc - 1 the unconditional ones, pair b = rows b and Bc + b; one 256-thread block per pair
  * (grid Bc).  Per column i < nv, in fp32:  zc = z[b, i] + bias[i];  zu = z[Bc + b, i] + bias[i];  d = zc - zu;
  * g = zc + (scale - 1) * d, the difference, the product and the sum each rounded on their own (no fused multiply-add), so that
- * numpy float32 restates g bit for bit; scale - 1 == 0 takes g = zc itself.  v = g * (1/temperature), and from v on the kernel is
- * dmi_sample_tokens_p: top-k with ties kept, the fixed-point nucleus, Gumbel-max with the noise hash(seed, position, b, i) (b the
+ * numpy float32 restates g bit for bit; scale - 1 == 0 takes g = zc itself.  v = g * (1/temperature), and from v on the draw is
+ * dmi_sample_tokens_p's, the same statements: top-k with ties kept, the fixed-point nucleus, Gumbel-max with the noise hash(seed, position, b, i) (b the
  * pair index), first maximum of g when temperature <= 0.  scale = 1 gives dmi_sample_tokens_p's tokens on the conditional rows bit
  * for bit; scale = 0 draws from the unconditional rows.
  * next_tok[b] = next_tok[Bc + b] = token_offset + choice (both halves of the KV cache are fed the same token; int32 [2 * Bc]);

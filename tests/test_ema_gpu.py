@@ -155,7 +155,7 @@ def test_context_manager(batches, trained):
     other.refresh_compute_copies(cast=True)
     tok, text = batches[0], batches[0][:, :T]
     raw = eng.sample_image_tokens(text, seed=5, kv_cache=True, weights="raw")     # the decode graph exists before entering
-    assert any(k in eng._dec["graphs"] for k in (True, "p"))
+    assert any(k and not (k.guided or k.logp) for k in eng._dec["graphs"])       # the plain or the nucleus draw's (keys: engine.Draw)
     graphs = dict(eng._dec["graphs"])
     want_tok = other.sample_image_tokens(text, seed=5, kv_cache=True)
     other.forward(tok, need_grad=False)

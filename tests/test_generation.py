@@ -76,6 +76,28 @@ def test_nucleus_kernel_uses_no_scratch_and_no_spills():
     assert u["scratch"] == 0 and u["vgpr_spill"] == 0 and u["sgpr_spill"] == 0, u
     # two 32 KB tables: two 256-thread blocks fit a CU's 160 KB, so a B <= 128 launch is resident at once on 256 CUs
     assert u["lds"] <= 80 * 1024 and u["occupancy"] >= 2, u
+    # the plain instance of the same body: one 32 KB key table and the small reduce arrays, not the nucleus form's second table
+    (k,) = [k for k in usage if "sample_tokens_kernel" in k]
+    u = usage[k]
+    assert u["scratch"] == 0 and u["vgpr_spill"] == 0 and u["sgpr_spill"] == 0, u
+    assert u["lds"] <= 40 * 1024, u
+
+
+@pytest.mark.parametrize("temperature", [0.0, 0.5, 1.0])
+def test_engine_parameter_words_of_the_plain_draw(temperature):
+    """the engine fills the plain draw's device parameter block through dh.sample_params: the four words it used to pack by hand"""
+    from src.dalle_mtf.engine import Draw, draw_params
+    top_k, seed = 7, (5 << 32) | 0x9abcdef1
+    inv_t = np.array([1.0 / temperature if temperature > 0 else 0.0], dtype=np.float32).view(np.uint32)[0]
+    want = np.array([inv_t, int(top_k), seed & 0xffffffff, (seed >> 32) & 0xffffffff], dtype=np.uint32).view(np.int32)
+    got = draw_params(Draw(nucleus=False, guided=False, logp=False), temperature, top_k, seed, top_p=1.0, guidance_scale=1.0)
+    assert got.dtype == dh.sample_params(temperature, top_k, seed).dtype and got.shape == (4,)
+    assert got.tolist() == want.tolist() == dh.sample_params(temperature, top_k, seed).tolist()
+    # the other variants carry six words: top_p, and the scale only under guidance
+    assert draw_params(Draw(True, False, True), temperature, top_k, seed, 0.9, 2.0).tolist() == \
+        dh.sample_params(temperature, top_k, seed, 0.9).tolist()
+    assert draw_params(Draw(True, True, False), temperature, top_k, seed, 0.9, 2.0).tolist() == \
+        dh.sample_params(temperature, top_k, seed, 0.9, guidance_scale=2.0).tolist()
 
 
 # ---------------------------------------------------------------- the restated nucleus set on hand-built rows

@@ -153,6 +153,7 @@ MODES = {"greedy": dict(temperature=0.0), "top_k": dict(temperature=1.0, top_k=8
 
 @pytest.mark.parametrize("d,H", [(128, 1), (128, 2)])      # head dims 128 and 64
 def test_completion_reproduces_sampling_exactly(d, H):
+    from src.dalle_mtf.engine import Draw
     eng, text = _engine(d, H)
     P = eng.S - eng.T
     for name, kw in MODES.items():
@@ -168,13 +169,39 @@ def test_completion_reproduces_sampling_exactly(d, H):
             _near_tie_rule(eng, text, s, plain, 0.05)
             cp = eng.sample_image_tokens(text, kv_cache=False, image_prefix=s[:, :17], **kw)
             assert torch.equal(cp[:, :17], s[:, :17])
-    assert "p" in eng._dec["graphs"] and True in eng._dec["graphs"] and False in eng._dec["graphs"]
+    assert all(k in eng._dec["graphs"] for k in (Draw(True, False, False), Draw(False, False, False), False))
     with pytest.raises(ValueError):
         eng.sample_image_tokens(text, image_prefix=torch.zeros(3, P, dtype=torch.int32))
     with pytest.raises(ValueError):
         eng.sample_image_tokens(text, image_prefix=torch.full((3, 2), eng.image_vocab_size, dtype=torch.int32))
     with pytest.raises(ValueError):
         eng.sample_image_tokens(text, top_p=0.0)
+
+
+def test_every_draw_variant_is_bit_identical_across_the_decode_paths():
+    """the fused graph, the host-launched draw and the eager decode step launch the same draw kernel on the same bits: the same
+    tokens and the same logp, exactly, for the plain, the nucleus + logp and the guided variant (B = 2: one pair)"""
+    from oracle import dalle_oracle as do
+    from src.dalle_mtf.engine import DalleEngine, Draw
+    T, P, tv, iv, B = 16, 48, 60, 64, 2
+    eng = DalleEngine(128, 1, 1, tv, iv, T, P, batch_size=B, hparams=dict(lr=1e-3, train_steps=10))
+    eng.load_reference_params(do.init_params(do.DalleConfig(128, tv, iv, T, P, 1, 1), seed=9, perturb=0.05))
+    text = torch.from_numpy(do.synthetic_captions(B, T, tv, seed=1)).cuda()
+    seed = (5 << 32) | 11
+    variants = ((Draw(False, False, False), text, dict(temperature=1.0, top_k=8, seed=seed)),
+                (Draw(True, False, True), text, dict(temperature=0.9, top_k=12, top_p=0.8, seed=seed, return_logprobs=True)),
+                (Draw(True, True, True), text[:1], dict(temperature=1.0, top_p=0.9, seed=seed, guidance_scale=2.0, return_logprobs=True)))
+    for key, txt, kw in variants:
+        fused = eng.sample_image_tokens(txt, **kw)
+        assert key in eng._dec["graphs"], key
+        for path in (dict(fused_sampling=False), dict(decode_graph=False)):
+            got = eng.sample_image_tokens(txt, **kw, **path)
+            if key.logp:
+                assert fused[0].shape == (len(txt), P) and torch.equal(got[0], fused[0]), (key, path)
+                assert torch.equal(got[1], fused[1]), (key, path, got[1], fused[1])
+            else:
+                assert fused.shape == (len(txt), P) and torch.equal(got, fused), (key, path)
+    assert set(eng._dec["graphs"]) == {False} | {key for key, _, _ in variants}     # one graph per variant
 
 
 def test_recompute_engine_samples_from_its_own_kv_cache():

@@ -35,6 +35,12 @@ def _engine(d, H):
     return _ENGINES[(d, H)]
 
 
+def _draw(nucleus=False, guided=False, logp=False):
+    """the engine's key of a draw variant's captured graph"""
+    from src.dalle_mtf.engine import Draw
+    return Draw(nucleus, guided, logp)
+
+
 def _null(n=None):
     t = torch.full((T,), TV - 1, dtype=torch.int32, device="cuda")     # no padding_id in the hparams: text_vocab_size - 1
     return t if n is None else t.repeat(n, 1)
@@ -48,7 +54,7 @@ def test_scale_one_without_uncond_text_is_the_unguided_sampler(d, H):
         a = eng.sample_image_tokens(text, **kw)
         b = eng.sample_image_tokens(text, guidance_scale=1.0, uncond_text=None, **kw)
         assert a.shape == (B, P) and torch.equal(a, b), kw
-    assert set(eng._dec["graphs"]) - before <= {True, "p"}                  # the unguided graphs, no guided one
+    assert set(eng._dec["graphs"]) - before <= {_draw(), _draw(nucleus=True)}             # the unguided graphs, no guided one
 
 
 @pytest.mark.parametrize("d,H", SHAPES)
@@ -130,7 +136,7 @@ def test_guided_decode_paths_completion_and_logp(d, H):
             want += torch.log_softmax(z[:BC], -1)[torch.arange(BC), s[:, pos - T + 1].cpu().long()]
         got = lp.double().cpu()
         assert bool(((got - want).abs() <= 1e-4 * want.abs()).all()), (kw, got, want)
-    assert "g" in eng._dec["graphs"] and "g+logp" in eng._dec["graphs"]
+    assert _draw(True, True) in eng._dec["graphs"] and _draw(True, True, True) in eng._dec["graphs"]
     # the plain sampler (one full forward per position) by the agreement rule of the masked engine test
     g = eng.sample_image_tokens(cap, temperature=0.0, guidance_scale=2.5)
     b = eng.sample_image_tokens(cap, temperature=0.0, guidance_scale=2.5, kv_cache=False)
@@ -216,7 +222,7 @@ def test_no_garbage_is_finalised_inside_a_decode_graph_capture():
         del a, b
         assert seen == []
         toks = eng.sample_image_tokens(text[:BC], temperature=0.0, guidance_scale=2.0)
-        assert "g" in eng._dec["graphs"] and inside == [False]
+        assert _draw(True, True) in eng._dec["graphs"] and inside == [False]
         assert seen[:2] == [False, False], seen      # finalised by the collection in front of the capture, not inside it
         assert not gc.isenabled()                    # the collector is left as it was found
     finally:
@@ -224,9 +230,9 @@ def test_no_garbage_is_finalised_inside_a_decode_graph_capture():
     assert torch.equal(eng.sample_image_tokens(text[:BC], temperature=0.0, guidance_scale=2.0), toks)
     gc.collect()
     assert len(seen) == 4 and not any(seen), seen
-    assert gc.isenabled() and True not in eng._dec["graphs"]
+    assert gc.isenabled() and _draw() not in eng._dec["graphs"]
     eng.sample_image_tokens(text, temperature=0.0)   # one more capture, with the collector on: it is on again afterwards
-    assert True in eng._dec["graphs"] and gc.isenabled() and inside == [False, False]
+    assert _draw() in eng._dec["graphs"] and gc.isenabled() and inside == [False, False]
     eng._decode_body = body
 
 

@@ -274,7 +274,7 @@ def test_kv_cached_decode_equals_full_forward():
     every 64-key chunk count, batch 3), and the cached greedy sampler emits the same tokens as the one-forward-per-token
     sampler wherever the top-2 logit gap exceeds twice the measured logit difference."""
     from oracle import dalle_oracle as do
-    from src.dalle_mtf.engine import DalleEngine
+    from src.dalle_mtf.engine import DalleEngine, Draw
     T, P, tv, iv, B = 16, 304, 60, 64, 3
     cfg = do.DalleConfig(128, tv, iv, T, P, 2, 1)
     eng = DalleEngine(128, 2, 1, tv, iv, T, P, batch_size=B, hparams=dict(lr=1e-3, train_steps=10))
@@ -299,7 +299,7 @@ def test_kv_cached_decode_equals_full_forward():
     a = eng.sample_image_tokens(text, temperature=0.0, kv_cache=True)      # decode + draw replayed as one graph per position
     a2 = eng.sample_image_tokens(text, temperature=0.0, kv_cache=True, fused_sampling=False)   # draw kernel launched from the host
     a3 = eng.sample_image_tokens(text, temperature=0.0, kv_cache=True, decode_graph=False)     # host-launched
-    assert torch.equal(a, a2) and torch.equal(a, a3) and eng._dec["graphs"].get(True) is not None
+    assert torch.equal(a, a2) and torch.equal(a, a3) and eng._dec["graphs"].get(Draw(False, False, False)) is not None
     b = eng.sample_image_tokens(text, temperature=0.0, kv_cache=False)
     agree = (a == b)
     # positions after a first disagreement see different prefixes; compare up to and including it
