@@ -12,6 +12,7 @@ sys.path.insert(0, os.path.join(ROOT, "dalle-mtf_amd"))
 
 pytestmark = pytest.mark.gpu
 
+import attention_bwd_ref as ab  # noqa: E402
 import dalle_hip as dh  # noqa: E402
 from src.dalle_mtf.masks import pattern_mask  # noqa: E402
 
@@ -78,6 +79,8 @@ def _check(mask_np, B=2, H=2, seed=0, xcd=None, qkv=None):
     for name, got, ref in (("dq", d[0], q.grad), ("dk", d[1], k.grad), ("dv", d[2], v.grad)):
         assert torch.isfinite(got).all(), name
         close(got, ref, 3e-2, 2e-2 * float(ref.abs().max()), "masked " + name)
+    # per-row budget against the float64 spec of the backward on the kernel's own saved forward (tests/attention_bwd_ref.py)
+    ab.within_budget(dqkv, ab.make_inputs(qkv, o, lse, d_o, B, H, S, HD, mask_np), label=f"masked _check {(B, H, S)}")
     return qkv, d_o, plan, o, lse, dqkv
 
 
