@@ -510,6 +510,94 @@ extern "C" int dmi_dropout_bwd(const uint16_t* dx, uint16_t* dy, int64_t M, int 
   return DMI_OK;
 }
 
+// =====================================================================================
+// Rotary position embeddings (DESIGN.md §4 "Rotary"): q and k rotated in place in the qkv layout
+// =====================================================================================
+// One 16-byte piece = 8 bf16 = four adjacent pairs (2c, 2c+1) of one head; their (cos, sin) are 32 contiguous bytes of the table
+// row [n = head_dim / 2][2].  col = the piece's first column inside [0, 2 H head_dim); head_dim is 64 or 128, so the element's
+// place in its head is col & (head_dim - 1) and the table offset (in floats) equals it.  sgn = +1 rotates, -1 rotates back.
+__device__ __forceinline__ void rope_piece(bf16_t* __restrict__ p, const float* __restrict__ cs_row, int col, int head_dim, float sgn) {
+  const f32x4* t = (const f32x4*)(cs_row + (col & (head_dim - 1)));
+  const f32x4 t0 = t[0], t1 = t[1];
+  const float c[4] = {t0[0], t0[2], t1[0], t1[2]};
+  const float s[4] = {t0[1] * sgn, t0[3] * sgn, t1[1] * sgn, t1[3] * sgn};
+  float x[8], y[8];
+  unpack8(*(const u32x4*)p, x);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    y[2 * j] = x[2 * j] * c[j] - x[2 * j + 1] * s[j];
+    y[2 * j + 1] = x[2 * j] * s[j] + x[2 * j + 1] * c[j];
+  }
+  *(u32x4*)p = pack8(y);
+}
+
+// One wave per row and pass of the grid; lane l takes pieces l, l + 64, .. of the row's 2 H head_dim / 8.  The table row r % S
+// is carried along (one modulo per wave, then additions), the row offset r * ld is 64-bit.
+__global__ __launch_bounds__(256) void rope_qk_kernel(bf16_t* __restrict__ qkv, int ld, const float* __restrict__ cs, int64_t rows, int S,
+                                                      int pieces, int head_dim, float sgn) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  int64_t r = (int64_t)blockIdx.x * 4 + wid;
+  if (r >= rows) return;
+  int s = (int)(r % S);
+  const int ds = (int)(stride % S);
+  for (; r < rows; r += stride) {
+    bf16_t* row = qkv + r * (int64_t)ld;
+    const float* cs_row = cs + (int64_t)s * head_dim;
+#pragma unroll 2
+    for (int c = lane; c < pieces; c += 64) rope_piece(row + c * 8, cs_row, c * 8, head_dim, sgn);
+    s += ds;
+    if (s >= S) s -= S;
+  }
+}
+
+// The decode step: B rows of the [B, 3 H head_dim] staging buffer, all at table row pos (from device memory when pos_dev is given);
+// a position outside [0, S) writes nothing.  One block per row.
+__global__ __launch_bounds__(256) void rope_qk_decode_kernel(bf16_t* __restrict__ fresh, int ld, const float* __restrict__ cs, int S, int pieces,
+                                                             int head_dim, int pos, const int* __restrict__ pos_dev) {
+  if (pos_dev) pos = *pos_dev;
+  if (pos < 0 || pos >= S) return;
+  bf16_t* row = fresh + (int64_t)blockIdx.x * ld;
+  const float* cs_row = cs + (int64_t)pos * head_dim;
+  for (int c = threadIdx.x; c < pieces; c += 256) rope_piece(row + c * 8, cs_row, c * 8, head_dim, 1.f);
+}
+
+#define DMI_REQUIRE_ROPE(name, H, head_dim)                                                                                  \
+  do {                                                                                                                       \
+    if ((head_dim) != 64 && (head_dim) != 128) {                                                                             \
+      dmi_set_error(name ": head_dim must be 64 or 128 (head_dim=%d)", (int)(head_dim));                                     \
+      return DMI_ERR_UNSUPPORTED;                                                                                            \
+    }                                                                                                                        \
+    DMI_REQUIRE((H) > 0 && (int64_t)(H) * (head_dim) * 3 < (1ll << 31), name ": H must be positive and 3 H head_dim < 2^31 (H=%d)", (int)(H)); \
+  } while (0)
+
+extern "C" int dmi_rope_qk(uint16_t* qkv, int ld, const float* cs, int64_t rows, int S, int H, int head_dim, int inverse, void* stream) {
+  DMI_REQUIRE(qkv && cs, "rope_qk: null pointer");
+  DMI_REQUIRE_ROPE("rope_qk", H, head_dim);
+  DMI_REQUIRE(rows > 0 && S > 0, "rope_qk: empty shape (rows=%lld S=%d)", (long long)rows, S);
+  DMI_REQUIRE(ld >= 2 * H * head_dim && ld % 8 == 0, "rope_qk: ld must be a multiple of 8 and at least 2 H head_dim (ld=%d)", ld);
+  DMI_REQUIRE((((uintptr_t)qkv | (uintptr_t)cs) & 15) == 0, "rope_qk: buffers must be 16-byte aligned");
+  int64_t blocks = cdiv64(rows, 4);
+  if (blocks > 256 * 8) blocks = 256 * 8;     // as dmi_dropout_bwd: 8 blocks of 4 waves per CU, the rest is the grid stride
+  rope_qk_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(qkv, ld, cs, rows, S, 2 * H * head_dim / 8, head_dim,
+                                                                                inverse ? -1.f : 1.f);
+  DMI_CHECK_LAUNCH("rope_qk");
+  return DMI_OK;
+}
+
+extern "C" int dmi_rope_qk_decode(uint16_t* fresh, const float* cs, int B, int S, int H, int head_dim, int pos, const int* pos_dev,
+                                  void* stream) {
+  DMI_REQUIRE(fresh && cs, "rope_qk_decode: null pointer");
+  DMI_REQUIRE_ROPE("rope_qk_decode", H, head_dim);
+  DMI_REQUIRE(B > 0 && S > 0, "rope_qk_decode: empty shape (B=%d S=%d)", B, S);
+  DMI_REQUIRE(pos_dev || (pos >= 0 && pos < S), "rope_qk_decode: pos outside [0, S) (pos=%d S=%d)", pos, S);
+  DMI_REQUIRE((((uintptr_t)fresh | (uintptr_t)cs) & 15) == 0, "rope_qk_decode: buffers must be 16-byte aligned");
+  rope_qk_decode_kernel<<<dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream>>>(fresh, 3 * H * head_dim, cs, S, 2 * H * head_dim / 8, head_dim,
+                                                                                  pos, pos_dev);
+  DMI_CHECK_LAUNCH("rope_qk_decode");
+  return DMI_OK;
+}
+
 // ---- generic deterministic partial reduce: out[c] = sum_{p<P} part[p*ncols + c]
 __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __restrict__ part, float* __restrict__ out,
                                                               int P, int ncols) {

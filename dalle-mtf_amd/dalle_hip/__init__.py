@@ -70,6 +70,8 @@ def _declare(L):
         "dmi_embed_bwd_dropout": (I, [P, P, P, P, P, I, I, I, I, P, U64, U64, I, P]),
         "dmi_dropout_add_ln": (I, [P, P, P, P, P, P, P, P, L64, I, U64, I, F, P]),
         "dmi_dropout_bwd": (I, [P, P, L64, I, U64, I, P]),
+        "dmi_rope_qk": (I, [P, I, P, L64, I, I, I, I, P]),
+        "dmi_rope_qk_decode": (I, [P, P, I, I, I, I, I, P, P]),
         "dmi_layernorm_bwd_workspace_bytes": (L64, [L64, I]),
         "dmi_layernorm_bwd": (I, [P, P, P, P, P, P, P, P, P, P, L64, I, P]),
         "dmi_layernorm_bwd_finish_batch": (I, [P, P, P, P, I, I, P]),
@@ -254,6 +256,24 @@ def dropout_bwd(dx, dy, M, d, key, thresh):
     _dev(dx, dy)
     assert dx.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16 and dx.numel() >= M * d and dy.numel() >= M * d
     _check(lib().dmi_dropout_bwd(_p(dx), _p(dy), M, d, int(key), int(thresh), _stream()), "dropout_bwd")
+
+
+def rope_qk(qkv, cs, rows, S, H, head_dim, inverse=False, ld=None):
+    """rotates q | k of every row of the [rows, ld] bf16 buffer in the qkv layout in place (ld defaults to 3 H head_dim); row r
+    takes row r % S of the (cos, sin) table cs, fp32 [S, head_dim / 2, 2]; inverse: the transpose (the gradient's rotation)"""
+    _dev(qkv, cs)
+    ld = 3 * H * head_dim if ld is None else int(ld)
+    assert qkv.dtype == torch.bfloat16 and qkv.numel() >= rows * ld and cs.dtype == torch.float32 and cs.numel() >= S * head_dim
+    _check(lib().dmi_rope_qk(_p(qkv), ld, _p(cs), rows, S, H, head_dim, int(bool(inverse)), _stream()), "rope_qk")
+
+
+def rope_qk_decode(fresh, cs, B, S, H, head_dim, pos=0, pos_dev=None):
+    """rope_qk of the decode step's [B, 3 H head_dim] staging buffer, every row at position pos (pos_dev: read from device memory;
+    outside [0, S) the launch writes nothing)"""
+    _dev(fresh, cs, pos_dev)
+    assert fresh.dtype == torch.bfloat16 and fresh.numel() >= B * 3 * H * head_dim
+    assert cs.dtype == torch.float32 and cs.numel() >= S * head_dim and (pos_dev is None or pos_dev.dtype == torch.int32)
+    _check(lib().dmi_rope_qk_decode(_p(fresh), _p(cs), B, S, H, head_dim, int(pos), _p(pos_dev), _stream()), "rope_qk_decode")
 
 
 def layernorm_bwd_workspace_bytes(rows, d):

@@ -37,6 +37,7 @@ from .activations import check_activation
 from .dropout import SITE_POSITION, SITE_TOKEN, resolve_dropout, site_attention, site_key, site_mlp
 from .ema import ema_decay_at, one_minus_decay, resolve_ema, resolve_weights   # noqa: F401  (ema_decay_at: part of the engine's surface)
 from .loss_weights import position_weights, resolve_loss_weights
+from .rotary import DEFAULT_BASE, resolve_rotary, rotary_table
 
 @contextlib.contextmanager
 def _no_gc_in_capture():
@@ -183,6 +184,8 @@ class DalleEngine:
         self.ema_decay, self.ema_eval = resolve_ema(hparams)              # None: no weight average (dalle_mtf.ema)
         # hparams["embed_dropout"] / ["residual_dropout"] as 16-bit thresholds (0: off) and ["dropout_seed"] (dalle_mtf.dropout)
         self.embed_thresh, self.resid_thresh, self.dropout_seed = resolve_dropout(hparams)
+        # hparams["rotary_emb"] ("1d" / "axial"; None: off) and ["rotary_base"] (dalle_mtf.rotary)
+        self.rotary, self.rotary_base = resolve_rotary(hparams, image_seq_len)
         if not torch.cuda.is_available():
             raise dh.DalleHipError("DalleEngine needs a HIP device (MI355X); there is no CPU fallback")
         dh.lib()
@@ -237,6 +240,12 @@ class DalleEngine:
         # hparams["dp_reserve_cus"], DALLE_DP_RESERVE_CUS or bench.py --reserve-cus select it for the first multi-GPU A/B.
         self.dp_reserve_cus = int(self.hp.get("dp_reserve_cus", os.environ.get("DALLE_DP_RESERVE_CUS", "0"))) if world_size > 1 else 0
         self._build_attn_plans(attn_masks)
+        # rotary embeddings: the (cos, sin) of every (position, pair), fp32 [S, head_dim / 2, 2], computed in float64 and uploaded once;
+        # q | k of every projection buffer are rotated in place by dmi_rope_qk behind the QKV product, dqkv is rotated back behind
+        # the attention backward (DESIGN.md §4 "Rotary"); off: no table, no launch
+        self.rope_cs = None
+        if self.rotary is not None:
+            self.rope_cs = torch.from_numpy(rotary_table(self.rotary, self.T, self.S - self.T, self.hd, self.rotary_base)).to(self.dev)
         self._alloc_activations()
         # gradient exchange: RCCL behind the C ABI when `comm` (dp.init_comm) is given, torch.distributed otherwise
         self.reducer = GradReducer(self.g, world_size, comm=comm, pg=process_group)
@@ -689,6 +698,8 @@ class DalleEngine:
         if not (self._ln1_by_prev() and l > 0):   # (fused: written by block l-1's FFN-2)
             dh.layernorm_fwd(x, self._w(p + "norm_1/g"), self._w(p + "norm_1/b"), self.xn1[l], st[0], st[1], M, d)
         dh.gemm_nt(self.xn1[l], d, self.tview(p + "attn/qkv"), d, self.qkv[l], 3 * d, M, 3 * d, d)
+        if self.rope_cs is not None:   # the attention kernels, their backward and the decode caches see rotated q and k
+            dh.rope_qk(self.qkv[l], self.rope_cs, M, S, H, self.hd)
         self._attn_fwd(l, self.qkv[l], self.o[l], self.lse[l])   # no transposed copies: hardware transpose reads
         if drop:
             dh.gemm_nt(self.o[l], d, self.tview(p + "attn/o"), d, self.drop_y, d, M, d, d, dh.GEMM_BIAS,
@@ -1004,6 +1015,8 @@ class DalleEngine:
             p = f"layer_{l}/"
             cache = caches[l]                                          # [B*S, 3d]; row b*S + pos <- q | k | v of this step
             ln_dense(x, p + "norm_1", self.tview(p + "attn/qkv"), fresh, 3 * d)
+            if self.rope_cs is not None:                               # q | k of the step at table row pos, before they enter the cache
+                dh.rope_qk_decode(fresh, self.rope_cs, B, S, H, self.hd, pos_dev=D["pos_i"])
             if self.attn_plan[l] is None:
                 dh.attention_decode(cache, o, B, H, S, 0, fresh=fresh, pos_dev=D["pos_i"], head_dim=self.hd)
             else:                                                      # mask row of pos from the plan, pos from D[pos_i]
@@ -1194,6 +1207,8 @@ class DalleEngine:
             else:
                 dh.attention_bwd_masked(self.qkv[l], self.o[l], self.d_o, self.lse[l], self.delta, self.dqkv, self.attn_plan[l],
                                         B, H, S, head_dim=self.hd)
+            if self.rope_cs is not None:   # gradient w.r.t. the rotated q, k -> w.r.t. the projection's output (the rotation's transpose)
+                dh.rope_qk(self.dqkv, self.rope_cs, M, S, H, self.hd, inverse=True)
             if pair:   # [r05] the out-projection and QKV kernels' gradients in ONE launch: 16 + 48 tiles fill the chip together
                 probs = [dict(X=self.o[l], ldx=d, dY=dyb, ldy=d, dW=self._gv(p + "attn/o"), I=d, J=d, ws=self.ws_blk[2],
                               dbias=self._gv(p + "attn/compute_output_bias/o_b")),
@@ -1354,6 +1369,8 @@ class DalleEngine:
     # ------------------------------------------------------------------ checkpoint
     def state_dict(self):
         sd = {"p": self.p.detach().cpu(), "global_step": self.global_step, "optimizer": self.optimizer, "activation_fn": self.activation}
+        if self.rotary is not None:    # (a checkpoint without the key is a rotary-off model)
+            sd["rotary_emb"], sd["rotary_base"] = self.rotary, self.rotary_base
         for k in ("m", "v", "af_slots"):
             if getattr(self, k) is not None:
                 sd[k] = getattr(self, k).detach().cpu()
@@ -1369,6 +1386,12 @@ class DalleEngine:
         act = sd.get("activation_fn", "relu")   # checkpoints from before the activation was recorded are ReLU models
         if act != self.activation:
             raise ValueError(f"checkpoint was written by a {act} model; this run uses activation_fn {self.activation!r}: "
+                             "the weights of one do not compute the other")
+        rot = (sd.get("rotary_emb"), float(sd.get("rotary_base", DEFAULT_BASE)) if sd.get("rotary_emb") is not None else None)
+        mine = (self.rotary, self.rotary_base if self.rotary is not None else None)
+        if rot != mine:
+            say = lambda r: "no rotary embeddings" if r[0] is None else f"rotary_emb {r[0]!r} (rotary_base {r[1]:g})"   # noqa: E731
+            raise ValueError(f"checkpoint was written by a model with {say(rot)}; this run uses {say(mine)}: "
                              "the weights of one do not compute the other")
         self.p.copy_(sd["p"])
         for k in ("m", "v", "af_slots"):

@@ -13,6 +13,7 @@ from .engine import DalleEngine
 from .loss_weights import resolve_loss_weights
 from .masks import layer_masks
 from .ops import get_variable_dtype
+from .rotary import resolve_rotary
 
 
 def _causal(S):
@@ -61,6 +62,8 @@ class DALLE:
         resolve_ema(params)
         # "embed_dropout" / "residual_dropout" / "dropout_seed" (dalle_mtf.dropout): likewise
         resolve_dropout(params)
+        # "rotary_emb" / "rotary_base" (dalle_mtf.rotary): likewise; "axial" needs a square image grid
+        self.rotary_emb, self.rotary_base = resolve_rotary(params, image_seq_len)
         if self.params.get("attention_dropout"):
             raise NotImplementedError("attention_dropout > 0 is not supported: embed_dropout and residual_dropout are; dropout of "
                                       "the attention weights would live inside the attention kernels (all shipped configs use 0)")

@@ -162,6 +162,10 @@ def _build(params, mode_str):
         logging.getLogger("dalle_mtf_amd").info(
             "%s weight EMA: ema_decay %g (decay at step t = min(%g, (1 + t) / (10 + t))), evaluation from the %s weights",
             mode_str, eng.ema_decay, eng.ema_decay, "averaged" if eng.ema_eval else "raw")
+    if eng.rotary is not None and rank == 0:
+        # "rotary_emb" / "rotary_base" (dalle_mtf.rotary; they reach the engine's hparams through `params`)
+        logging.getLogger("dalle_mtf_amd").info("%s rotary embeddings: %s, base %g (in addition to the learned positions)",
+                                                mode_str, eng.rotary, eng.rotary_base)
     eng.hp["num_microbatches"] = nmb   # reference model_fns.py:141-154 (1 when tokens_per_mb_per_replica is unset)
     params["num_microbatches"] = nmb
     state["local_bs"] = local_bs

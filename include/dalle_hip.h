@@ -85,6 +85,23 @@ int dmi_dropout_add_ln(const uint16_t* a, const uint16_t* residual, uint16_t* x_
                        uint16_t* y, float* mean, float* rstd, int64_t M, int d, uint64_t key, int thresh, float eps, void* stream);
 int dmi_dropout_bwd(const uint16_t* dx, uint16_t* dy, int64_t M, int d, uint64_t key, int thresh, void* stream);
 
+/* ---- Rotary position embeddings (project extension, config key "rotary_emb"; DESIGN.md §4 "Rotary") ----
+ * cs = fp32 [S, head_dim / 2, 2]: interleaved (cos, sin) of pair c at sequence position s (dalle_mtf.rotary.rotary_table), shared by
+ * every layer, head and batch row.  Pair c of a head is its adjacent elements (2c, 2c + 1); in fp32
+ *   y0 = x0 cos - x1 sin,   y1 = x0 sin + x1 cos,   each rounded once to bf16.
+ * dmi_rope_qk: rotates, in place, columns [0, 2 H head_dim) (q and k) of every row of a [rows, ld] bf16 buffer in the qkv layout
+ * (row = [q | k | v] x [H, head_dim], ld >= 2 H head_dim, ld % 8 == 0); the v columns are neither read nor written.  Row r takes
+ * table row r % S; row offsets are 64-bit.  inverse != 0 uses -sin: the transpose of the rotation, i.e. the gradient with respect to
+ * the unrotated q, k from the gradient with respect to the rotated ones.
+ * dmi_rope_qk_decode: the same rotation of the decode step's [B, 3 H head_dim] staging buffer, every row at table row pos.
+ * pos_dev != NULL: the position is read from device memory (one int32; `pos` is then ignored and a position outside [0, S) makes
+ * the launch a no-op -- the dmi_attention_decode contract, so one captured graph serves every position).
+ * Both: stream-ordered, no allocation.  head_dim other than 64 / 128: DMI_ERR_UNSUPPORTED; a null pointer, an empty shape, a buffer
+ * that is not 16-byte aligned, or a by-value pos outside [0, S): DMI_ERR_INVALID -- with a message, before any launch. */
+int dmi_rope_qk(uint16_t* qkv, int ld, const float* cs, int64_t rows, int S, int H, int head_dim, int inverse, void* stream);
+int dmi_rope_qk_decode(uint16_t* fresh, const float* cs, int B, int S, int H, int head_dim, int pos, const int* pos_dev,
+                       void* stream);
+
 /* ---- K2  LayerNorm eps=1e-5 biased variance   models.py:373-389, layers.py:30-33 ---- */
 int dmi_layernorm_fwd(const uint16_t* x, const uint16_t* g, const uint16_t* b, uint16_t* y,
                       float* mean, float* rstd, int64_t rows, int d, float eps, void* stream);
