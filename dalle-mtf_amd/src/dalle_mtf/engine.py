@@ -26,7 +26,7 @@ import logging
 import math
 import os
 from collections import OrderedDict, namedtuple
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -35,6 +35,7 @@ import dalle_hip as dh
 from ..dp import GradReducer
 from .activations import check_activation
 from .dropout import SITE_POSITION, SITE_TOKEN, resolve_dropout, site_attention, site_key, site_mlp
+from .layout import ALIGN, ParamLayout, _round_up, adafactor_factored_dims, adafactor_table, reference_init   # noqa: F401  (re-exported)
 from .ema import ema_decay_at, one_minus_decay, resolve_ema, resolve_weights   # noqa: F401  (ema_decay_at: part of the engine's surface)
 from .loss_weights import position_weights, resolve_loss_weights
 from .rotary import DEFAULT_BASE, resolve_rotary, rotary_table
@@ -64,116 +65,53 @@ Draw = namedtuple("Draw", "nucleus guided logp")
 def draw_params(v, temperature, top_k, seed, top_p, guidance_scale):
     """the device parameter block of variant v (a Draw): four words for the plain draw, six for the others (dalle_hip.sample_params)"""
     return dh.sample_params(temperature, top_k, seed, top_p if v.nucleus else None, guidance_scale if v.guided else None)
-ALIGN = 128  # elements
 
 
-def _round_up(x, m):
-    return (x + m - 1) // m * m
+SampleArgs = namedtuple("SampleArgs", "rows guided guidance_scale top_p uncond_text image_prefix prefix_len")
 
 
-def adafactor_factored_dims(shape, min_dim_size_to_factor=128):
-    """mtf AdafactorOptimizer._factored_dims (mesh-tensorflow 0.1.18 optimize.py, restated from memory: no mesh-tensorflow was
-    available to check it against): None below rank 2; otherwise the axes sorted by size, descending and stable (ties keep axis
-    order), d0 = the largest, d1 = the second -- None when d1 is smaller than min_dim_size_to_factor.  Returns (d0, d1) axes."""
-    if len(shape) < 2:
-        return None
-    order = sorted(range(len(shape)), key=lambda i: -shape[i])
-    if shape[order[1]] < min_dim_size_to_factor:
-        return None
-    return order[0], order[1]
-
-
-def adafactor_table(lay):
-    """the Adafactor descriptor table of a ParamLayout (fields 0..8 of include/dalle_hip.h K9b; dmi_adafactor_plan fills the
-    rest), one row per reference variable, the per-variable slot records and the slot buffer's length.  Slots: the row vector [R]
-    and the column vector [C] of a factored variable, the dense v [R, C] otherwise, in 16-byte aligned pieces."""
-    rows, recs, so = [], [], 0
-    for name, shp, off, ld in lay.reference_variables():
-        R, C = (1, shp[0]) if len(shp) == 1 else shp
-        fd = adafactor_factored_dims(shp)
-        rec = dict(name=name, shape=shp, factored=fd is not None)
-        if fd is not None:
-            rec["row"], rec["col"] = so, so + _round_up(R, 4)
-            so += _round_up(R, 4) + _round_up(C, 4)
-            rec["vr_row"] = fd[0] == 1       # vr is indexed along d1: the rows when d0 is the column axis
-            rows.append([off, R, C, ld, 1, int(rec["vr_row"]), rec["row"], rec["col"], 0] + [0] * 8)
-        else:
-            rec["v"] = so
-            so += _round_up(R * C, 4)
-            rows.append([off, R, C, ld, 0, 0, 0, 0, rec["v"]] + [0] * 8)
-        recs.append(rec)
-    return torch.tensor(rows, dtype=torch.int64), recs, so
-
-
-class ParamLayout:
-    """Flat layout of the trainable variables.  Internal tensors fuse q|k|v into one [d, 3d] matrix and
-    pad the vocabulary axis of the output projection to a multiple of 128; `export`/`load` translate
-    to/from the reference's variable names and shapes."""
-
-    def __init__(self, n_embd, n_layers, n_heads, total_tokens, total_seq):
-        d, L, V, S = n_embd, n_layers, total_tokens, total_seq
-        self.d, self.L, self.V, self.S = d, L, V, S
-        self.Vp = _round_up(V, 128)
-        ent: List[Tuple[str, tuple]] = []
-        ent += [("to_logits/linear_out/kernel", (d, self.Vp)), ("to_logits/linear_out/bias", (self.Vp,)),
-                ("to_logits/layer_norm/g", (d,)), ("to_logits/layer_norm/b", (d,))]
-        for i in reversed(range(L)):
-            p = f"layer_{i}/"
-            ent += [(p + "mlp/mlp_linear_2/kernel", (4 * d, d)), (p + "mlp/mlp_linear_2/bias", (d,)),
-                    (p + "mlp/mlp_linear_1/kernel", (d, 4 * d)), (p + "mlp/mlp_linear_1/bias", (4 * d,)),
-                    (p + "norm_2/g", (d,)), (p + "norm_2/b", (d,)),
-                    (p + "attn/o", (d, d)), (p + "attn/compute_output_bias/o_b", (d,)),
-                    (p + "attn/qkv", (d, 3 * d)),
-                    (p + "norm_1/g", (d,)), (p + "norm_1/b", (d,))]
-        ent += [("positional_embedding/wpe", (S, d)), ("embedding/wte", (V, d))]
-        self.entries = ent
-        self.offset: Dict[str, int] = {}
-        self.shape: Dict[str, tuple] = {}
-        off = 0
-        for name, shp in ent:
-            self.offset[name] = off
-            self.shape[name] = shp
-            off += _round_up(int(np.prod(shp)), ALIGN)
-        self.total = off
-        # transposed ([out, in]) bf16 copies consumed by the forward GEMMs
-        self.t_offset: Dict[str, int] = {}
-        toff = 0
-        for name, shp in ent:
-            if len(shp) == 2 and ("kernel" in name or "attn/" in name):
-                self.t_offset[name] = toff
-                toff += _round_up(int(np.prod(shp)), ALIGN)
-        self.t_total = toff
-        # bucket boundaries (prefix ends) in element offsets: after head, after each layer, end
-        self.bucket_ends: List[int] = []
-        self.bucket_ends.append(self.offset[f"layer_{L-1}/mlp/mlp_linear_2/kernel"] if L > 0 else self.offset["positional_embedding/wpe"])
-        for i in reversed(range(L)):
-            nxt = f"layer_{i-1}/mlp/mlp_linear_2/kernel" if i > 0 else "positional_embedding/wpe"
-            self.bucket_ends.append(self.offset[nxt])
-        self.bucket_ends.append(self.total)
-        # offsets at which backward has finished a prefix of the flat gradient buffer, in completion order: the head's
-        # kernel + bias (right after its weight-gradient GEMM, before the input gradient), each layer (the head LayerNorm's
-        # gain / bias ride with layer L-1), finally the embeddings.  The exchange pieces follow these cuts (src/dp.py).
-        self.ready_points: List[int] = [self.offset["to_logits/layer_norm/g"]] + self.bucket_ends[1:]
-
-    def numel(self, name):
-        return int(np.prod(self.shape[name]))
-
-    def reference_variables(self):
-        """the reference's variables in flat-buffer order as (name, shape, offset, leading dimension):
-        q / k / v are column blocks of the fused [d, 3d] matrix; the head's kernel and bias keep V of their Vp columns"""
-        out = []
-        for name, shp in self.entries:
-            o = self.offset[name]
-            if name.endswith("attn/qkv"):
-                base = name[:-3]
-                out += [(base + t, (self.d, self.d), o + i * self.d, 3 * self.d) for i, t in enumerate("qkv")]
-            elif name == "to_logits/linear_out/kernel":
-                out.append((name, (self.d, self.V), o, self.Vp))
-            elif name == "to_logits/linear_out/bias":
-                out.append((name, (self.V,), o, self.V))
-            else:
-                out.append((name, shp, o, shp[-1]))
-        return out
+def check_sample_args(B, T, P, text_vocab_size, image_vocab_size, text, top_p=1.0, guidance_scale=1.0, uncond_text=None,
+                      image_prefix=None, padding_id=None):
+    """the argument checks of DalleEngine.sample_image_tokens for an engine of B rows, T text and P image positions; needs no
+    device.  Returns SampleArgs: rows = the rows of text / image_prefix / the result (B, or B / 2 under guidance), uncond_text
+    (guided: given or the null caption, T copies of padding_id, or of text_vocab_size - 1 when that is None) and image_prefix as
+    tensors, prefix_len = k."""
+    gs = float(guidance_scale)
+    if not (gs >= 0.0 and math.isfinite(gs)):
+        raise ValueError(f"sample_image_tokens: guidance_scale must be finite and >= 0 (got {guidance_scale})")
+    guided = gs != 1.0 or uncond_text is not None
+    R = B
+    if guided:
+        if B % 2:
+            raise ValueError(f"sample_image_tokens: guidance pairs the engine's rows, so its batch must be even (B = {B})")
+        R = B // 2
+        if tuple(text.shape) != (R, T):
+            raise ValueError(f"sample_image_tokens: with guidance text must be [B / 2 = {R}, T = {T}] (got {tuple(text.shape)})")
+        if uncond_text is None:
+            uncond_text = torch.full((T,), text_vocab_size - 1 if padding_id is None else int(padding_id), dtype=torch.int32)
+        uncond_text = torch.as_tensor(uncond_text)
+        if uncond_text.dtype.is_floating_point or uncond_text.dtype == torch.bool:
+            raise ValueError("sample_image_tokens: uncond_text must hold integer token ids")
+        if tuple(uncond_text.shape) not in ((T,), (R, T)):
+            raise ValueError(f"sample_image_tokens: uncond_text must be [T = {T}] or [B / 2 = {R}, T = {T}] "
+                             f"(got {tuple(uncond_text.shape)})")
+        if int(uncond_text.min()) < 0 or int(uncond_text.max()) >= text_vocab_size:
+            raise ValueError(f"sample_image_tokens: uncond_text ids must lie in [0, {text_vocab_size})")
+    assert text.shape == (R, T)
+    top_p = float(top_p)
+    if not (0.0 < top_p <= 1.0):
+        raise ValueError(f"sample_image_tokens: top_p must lie in (0, 1] (got {top_p})")
+    k = 0
+    if image_prefix is not None:
+        image_prefix = torch.as_tensor(image_prefix)
+        if image_prefix.dim() != 2 or image_prefix.shape[0] != R or not (0 <= image_prefix.shape[1] < P):
+            raise ValueError(f"sample_image_tokens: image_prefix must be [B={R}, k] with 0 <= k < {P} (got {tuple(image_prefix.shape)})")
+        if image_prefix.dtype.is_floating_point or image_prefix.dtype == torch.bool:
+            raise ValueError("sample_image_tokens: image_prefix must hold integer token ids")
+        k = int(image_prefix.shape[1])
+        if k and (int(image_prefix.min()) < 0 or int(image_prefix.max()) >= image_vocab_size):
+            raise ValueError(f"sample_image_tokens: image_prefix ids must lie in [0, {image_vocab_size})")
+    return SampleArgs(R, guided, gs, top_p, uncond_text if guided else None, image_prefix, k)
 
 
 class DalleEngine:
@@ -215,6 +153,7 @@ class DalleEngine:
         b16 = dict(dtype=torch.bfloat16, device=self.dev)
         self.p = torch.zeros(n, **f32)
         self.g = torch.zeros(n, **f32)
+        self.optimizer = None
         self.set_optimizer(self.hp.get("optimizer") or "adam")
         self.pb = torch.zeros(n, **b16)
         self.pbt = torch.zeros(self.lay.t_total, **b16)
@@ -232,13 +171,12 @@ class DalleEngine:
         self.last_dropout: Dict[int, Tuple[int, int]] = {}
         self._microbatch = 0
         self._drop = False
-        # The exchange's RCCL channels run beside the BACKWARD: there the persistent kernels leave CUs for them (a block of a
-        # one-block-per-CU kernel whose CU an intruder holds starts when the others have finished: the launch takes twice as long --
-        # measured with the token sort as the intruder).  16 CUs cost 3.7 % of a single-GPU step when applied to
-        # the whole step, so the option is set for the backward only; 0 = off.  Unmeasured on a multi-GPU node, hence OFF by
-        # default (it also hands the full-row products back to the 128x128 kernel and turns the fused LayerNorm forms off):
-        # hparams["dp_reserve_cus"], DALLE_DP_RESERVE_CUS or bench.py --reserve-cus select it for the first multi-GPU A/B.
-        self.dp_reserve_cus = int(self.hp.get("dp_reserve_cus", os.environ.get("DALLE_DP_RESERVE_CUS", "0"))) if world_size > 1 else 0
+        # state that comes into being on first use (None until then)
+        self._t_table = None                      # refresh_compute_copies: the batched transpose's descriptor table
+        self._kv = self._dec = None               # the sampler's key/value caches (under recompute_grad) and decode buffers
+        self.gacc = self.loss_acc = self.loss_parts_acc = None   # train_step's micro-batch accumulators
+        self.event_hook = None                    # bench.py: a callable returning the list that takes the head launch's event pair
+        self._ln_pend = []                        # LayerNorm gain / bias partials awaiting _flush_ln()
         self._build_attn_plans(attn_masks)
         # rotary embeddings: the (cos, sin) of every (position, pair), fp32 [S, head_dim / 2, 2], computed in float64 and uploaded once;
         # q | k of every projection buffer are rotated in place by dmi_rope_qk behind the QKV product, dqkv is rotated back behind
@@ -246,6 +184,7 @@ class DalleEngine:
         self.rope_cs = None
         if self.rotary is not None:
             self.rope_cs = torch.from_numpy(rotary_table(self.rotary, self.T, self.S - self.T, self.hd, self.rotary_base)).to(self.dev)
+        self._resolve_schedule()
         self._alloc_activations()
         # gradient exchange: RCCL behind the C ABI when `comm` (dp.init_comm) is given, torch.distributed otherwise
         self.reducer = GradReducer(self.g, world_size, comm=comm, pg=process_group)
@@ -273,11 +212,29 @@ class DalleEngine:
                                        "the head-dim-64 kernels implement the causal mask only")
             self.attn_plan[l] = plan
 
+    # layer l's attention: the causal entry, or the masked one with the layer's plan
     def _attn_fwd(self, l, qkv, o, lse):
         if self.attn_plan[l] is None:
             dh.attention_fwd(qkv, o, lse, self.B, self.H, self.S, head_dim=self.hd)
         else:
             dh.attention_fwd_masked(qkv, o, lse, self.attn_plan[l], self.B, self.H, self.S, head_dim=self.hd)
+
+    def _attn_bwd(self, l):
+        """self.dqkv from self.d_o and the block's stored q | k | v, output and log-sum-exp"""
+        args = (self.qkv[l], self.o[l], self.d_o, self.lse[l], self.delta, self.dqkv)
+        if self.attn_plan[l] is None:
+            dh.attention_bwd(*args, self.B, self.H, self.S, head_dim=self.hd)
+        else:
+            dh.attention_bwd_masked(*args, self.attn_plan[l], self.B, self.H, self.S, head_dim=self.hd)
+
+    def _attn_decode(self, l, cache, o, fresh, pos_dev):
+        """one query row per sequence at the position in pos_dev against cache rows 0 .. pos; `fresh` (q | k | v of the step)
+        enters the cache first.  Masked: the mask row of pos comes from the plan."""
+        if self.attn_plan[l] is None:
+            dh.attention_decode(cache, o, self.B, self.H, self.S, 0, fresh=fresh, pos_dev=pos_dev, head_dim=self.hd)
+        else:
+            dh.attention_decode_masked(cache, o, self.attn_plan[l], self.B, self.H, self.S, 0, fresh=fresh, pos_dev=pos_dev,
+                                       head_dim=self.hd)
 
     # ------------------------------------------------------------------ optimizer state
     OPTIMIZERS = ("adam", "adafactor")
@@ -290,7 +247,7 @@ class DalleEngine:
         name = (name or "adam").lower()
         if name not in self.OPTIMIZERS:
             raise ValueError(f"{name} not recognized")
-        if getattr(self, "optimizer", None) == name:
+        if self.optimizer == name:
             return
         self.optimizer = name
         n = self.lay.total
@@ -345,44 +302,25 @@ class DalleEngine:
         r, c = self.lay.shape[name]
         return self.pbt[o:o + r * c].view(c, r)
 
+    def _ref_view(self, buf, shp, off, ld):
+        """a reference variable (a row of ParamLayout.reference_variables) as a strided view of a flat buffer"""
+        return buf[off:].as_strided(shp, (ld, 1)[-len(shp):])
+
     def load_reference_params(self, P: Dict[str, np.ndarray]):
         """Load weights given under the reference's variable names/shapes."""
-        d, V = self.d, self.V
         with torch.no_grad():
-            for name, shp in self.lay.entries:
-                dst = self.view(self.p, name)
-                if name.endswith("attn/qkv"):
-                    base = name[:-3]
-                    cat = np.concatenate([P[base + "q"], P[base + "k"], P[base + "v"]], axis=1)
-                    dst.copy_(torch.from_numpy(np.ascontiguousarray(cat)))
-                elif name == "to_logits/linear_out/kernel":
-                    dst.zero_()
-                    dst[:, :V].copy_(torch.from_numpy(np.ascontiguousarray(P[name])))
-                elif name == "to_logits/linear_out/bias":
-                    dst.fill_(-30000.0)   # pad logits can never win the softmax (and are masked in the CE kernel)
-                    dst[:V].copy_(torch.from_numpy(np.ascontiguousarray(P[name])))
-                else:
-                    dst.copy_(torch.from_numpy(np.ascontiguousarray(P[name])).view(shp))
+            self.view(self.p, "to_logits/linear_out/kernel").zero_()
+            self.view(self.p, "to_logits/linear_out/bias").fill_(-30000.0)   # pad logits can never win the softmax (and are masked in the CE kernel)
+            for name, shp, off, ld in self.lay.reference_variables():
+                self._ref_view(self.p, shp, off, ld).copy_(torch.from_numpy(np.ascontiguousarray(P[name])).view(shp))
         self.refresh_compute_copies(cast=True)
         self._ema_from_p()
 
     def export_reference(self, buf=None) -> "OrderedDict[str, np.ndarray]":
         """Inverse of load_reference_params for any flat buffer (params, grads, m, v)."""
         buf = self.p if buf is None else buf
-        out: "OrderedDict[str, np.ndarray]" = OrderedDict()
-        d, V = self.d, self.V
-        for name, shp in self.lay.entries:
-            a = self.view(buf, name).detach().float().cpu().numpy()
-            if name.endswith("attn/qkv"):
-                base = name[:-3]
-                out[base + "q"], out[base + "k"], out[base + "v"] = (np.ascontiguousarray(a[:, i * d:(i + 1) * d]) for i in range(3))
-            elif name == "to_logits/linear_out/kernel":
-                out[name] = np.ascontiguousarray(a[:, :V])
-            elif name == "to_logits/linear_out/bias":
-                out[name] = np.ascontiguousarray(a[:V])
-            else:
-                out[name] = a
-        return out
+        return OrderedDict((name, np.ascontiguousarray(self._ref_view(buf, shp, off, ld).detach().float().cpu().numpy()))
+                           for name, shp, off, ld in self.lay.reference_variables())
 
     # ------------------------------------------------------------------ weight EMA
     def _alloc_ema(self):
@@ -430,35 +368,13 @@ class DalleEngine:
 
     def init_params(self, seed=1234):
         """Reference initialisers drawn with torch's generator on the host."""
-        g = torch.Generator().manual_seed(seed)
-        d, L, H = self.d, self.L, self.H
-        k = d // H
-        P = OrderedDict()
-
-        def nrm(shape, std):
-            return (torch.randn(*shape, generator=g) * std).numpy()
-        P["embedding/wte"] = nrm((self.V, d), 0.02)
-        P["positional_embedding/wpe"] = nrm((self.S, d), 0.01)
-        for i in range(L):
-            p = f"layer_{i}/"
-            P[p + "norm_1/g"], P[p + "norm_1/b"] = np.ones(d, np.float32), np.zeros(d, np.float32)
-            P[p + "attn/q"] = nrm((d, d), (d * k) ** -0.5)
-            P[p + "attn/k"] = nrm((d, d), d ** -0.5)
-            P[p + "attn/v"] = nrm((d, d), d ** -0.5)
-            P[p + "attn/o"] = nrm((d, d), (H * k) ** -0.5)
-            P[p + "attn/compute_output_bias/o_b"] = np.zeros(d, np.float32)
-            P[p + "norm_2/g"], P[p + "norm_2/b"] = np.ones(d, np.float32), np.zeros(d, np.float32)
-            P[p + "mlp/mlp_linear_1/kernel"], P[p + "mlp/mlp_linear_1/bias"] = nrm((d, 4 * d), 0.02), np.zeros(4 * d, np.float32)
-            P[p + "mlp/mlp_linear_2/kernel"], P[p + "mlp/mlp_linear_2/bias"] = nrm((4 * d, d), 0.02 / math.sqrt(L)), np.zeros(d, np.float32)
-        P["to_logits/layer_norm/g"], P["to_logits/layer_norm/b"] = np.ones(d, np.float32), np.zeros(d, np.float32)
-        P["to_logits/linear_out/kernel"], P["to_logits/linear_out/bias"] = nrm((d, self.V), 0.02), np.zeros(self.V, np.float32)
-        self.load_reference_params(P)
+        self.load_reference_params(reference_init(self.lay, self.H, seed))
 
     def refresh_compute_copies(self, cast=False):
         """bf16 natural copy (if not already written by the Adam kernel) + [out,in] copies for the fwd GEMMs."""
         if cast:
             dh.cast_f32_bf16(self.p, self.pb, self.lay.total)
-        if getattr(self, "_t_table", None) is None:   # one launch for all [in,out] -> [out,in] weight copies
+        if self._t_table is None:   # one launch for all [in,out] -> [out,in] weight copies
             rows, tile = [], 0
             for name in self.lay.t_offset:
                 r, c = self.lay.shape[name]
@@ -468,20 +384,62 @@ class DalleEngine:
             self._t_tiles = tile
         dh.transpose_batch(self.pb, self.pbt, self._t_table, self._t_table.shape[0], self._t_tiles)
 
+    # ------------------------------------------------------------------ schedule switches
+    def _resolve_schedule(self):
+        """every choice between launch forms that holds for the engine's lifetime, resolved once before any buffer exists: an
+        hparam wins, its environment variable gives the default, and a form also needs the library's own predicate for the
+        shape.  DESIGN.md §4 "Engine schedule" has the table and the measurements behind the defaults."""
+        hp, M, d = self.hp, self.M, self.d
+
+        def switch(key, env):      # on unless the hparam, or failing that the environment variable ("0"), says off
+            return bool(hp.get(key, os.environ.get(env, "1") != "0"))
+        # recompute_grad (the reference wraps every block in mtf.recompute_grad, src/dalle_mtf/models.py:342-343): only the
+        # residual stream X[l] is kept per layer; the block's inner activations live in ONE shared set of buffers and backward()
+        # re-runs the block's forward (bit-identical kernels) before differentiating it
+        self.recompute = bool(hp.get("recompute_grad", False))
+        # dp_reserve_cus: CUs the persistent kernels of the BACKWARD leave to the RCCL channels of a concurrent gradient
+        # exchange (DESIGN.md §6); data parallel only, 0 = off (the default: unmeasured on a multi-GPU node)
+        self.dp_reserve_cus = int(hp.get("dp_reserve_cus", os.environ.get("DALLE_DP_RESERVE_CUS", "0"))) if self.world > 1 else 0
+        # the FFN-1 product and the FFN-2 input gradient that matches it (_ffn1 / _ffn2_dgrad): GELU keeps the pre-activation
+        # (it cannot be inverted from h); ReLU hands its mask on as one bit per element where the library runs both products on
+        # the kernel that has the bit forms, and reads h back elsewhere (bit-identical)
+        self.ffn_form = "gelu" if self.activation == "gelu" else "relu_bits" if dh.relu_bits_auto(M, 4 * d, d) else "relu"
+        self.use_relu_bits = self.ffn_form == "relu_bits"
+        # the fused LayerNorm forms need the library's full-row kernel (n_embd = 512, operands inside its 32-bit offsets) and
+        # no CUs reserved; the two-kernel forms serve every other case
+        ln_ok = dh.gemm_nt_ln_auto(M, d, 4 * d) and self.dp_reserve_cus == 0
+        # fuse_ln: the products that end in the residual stream emit the LayerNorm that follows them (dmi_gemm_nt_ln)
+        self.fuse_ln = switch("fuse_ln", "DALLE_FUSE_LN") and ln_ok
+        # FFN-2 -> next norm_1: not under recompute_grad, whose re-run of a block starts from the stored residual stream with a
+        # standalone norm_1 (its statistics sum in another order; the re-run must reproduce the forward bit for bit)
+        self.fuse_ln1 = self.fuse_ln and not self.recompute
+        # fuse_lnbwd: LayerNorm backward inside the input-gradient product that feeds it (dmi_gemm_nt_lnbwd); dxn is never written
+        self.fuse_lnbwd = switch("fuse_lnbwd", "DALLE_FUSE_LNBWD") and ln_ok
+        # lnbwd_batch_finish: the fused forms leave their gain / bias partials in one buffer per LayerNorm and ONE batched launch
+        # sums them at the end of the backward (per block under data parallelism, where the exchange takes a block's gradients
+        # as soon as it is done)
+        self.lnb_batch = self.fuse_lnbwd and switch("lnbwd_batch_finish", "DALLE_LNBWD_BATCH")
+        # dgrad_tail_split: the rows of the head input gradient's ragged last residency run with K split (_backward)
+        self.dgrad_tail_split = switch("dgrad_tail_split", "DALLE_DGRAD_TAIL")
+        # decode_fuse_ln: the decode step's LayerNorms ride in the prologue of the product that reads them (_decode_body)
+        self.decode_fuse_ln = bool(hp.get("decode_fuse_ln", True))
+        # all FOUR weight gradients of a block in one launch where the library's plan for the four is the wide (128 x 256)
+        # tile; elsewhere (n_embd = 1024 / 2048: 384+ tiles, ragged residencies in ONE launch) the attention pair shares a
+        # launch and the FFN gradients keep their own
+        # (wgrad_shapes: (I, J) of the four in the order of _wgrad_problems and ws_blk -- FFN-2, FFN-1, out-projection, QKV)
+        self.wgrad_shapes = [(4 * d, d), (d, 4 * d), (d, d), (d, 3 * d)]
+        self.wgrad_group4 = dh.gemm_tn_group_plan(self.wgrad_shapes, M) > 0
+
     # ------------------------------------------------------------------ buffers
     def _alloc_activations(self):
         M, d, L, B, H, S, Vp = self.M, self.d, self.L, self.B, self.H, self.S, self.Vp
         b16 = dict(dtype=torch.bfloat16, device=self.dev)
         f32 = dict(dtype=torch.float32, device=self.dev)
+        u8 = dict(dtype=torch.uint8, device=self.dev)
         self.tokens = torch.zeros(B, S, dtype=torch.int32, device=self.dev)
         self.labels = torch.zeros(B, S, dtype=torch.int32, device=self.dev)
         self.X = [torch.empty(M, d, **b16) for _ in range(L + 1)]       # residual stream entering layer l
-        # hparams["recompute_grad"] (the reference wraps every block in mtf.recompute_grad, src/dalle_mtf/models.py:342-343):
-        # only the residual stream X[l] is kept per layer; the block's inner activations live in ONE shared set of buffers
-        # and backward() re-runs the block's forward (bit-identical kernels) before differentiating it: 0.63 GB -> 0.1 GB per
-        # layer at B=32, S=1280, for one extra block forward (~+30 % of the step's flops).
-        self.recompute = bool(self.hp.get("recompute_grad", False))
-        nl = 1 if self.recompute else L
+        nl = 1 if self.recompute else L     # recompute_grad: 0.63 GB -> 0.1 GB per layer at B=32, S=1280
 
         def per_layer(make):
             bufs = [make() for _ in range(nl)]
@@ -493,15 +451,10 @@ class DalleEngine:
         self.x1 = per_layer(lambda: torch.empty(M, d, **b16))
         self.xn2 = per_layer(lambda: torch.empty(M, d, **b16))
         self.h = per_layer(lambda: torch.empty(M, 4 * d, **b16))
-        # [r05] the ReLU mask of the FFN as bits: FFN-1's epilogue emits them, the FFN-2 input gradient reads M * 4d / 8 bytes instead
-        # of the whole h (168 MB per layer at dalle_example) -- where the library runs both products on the kernel that has the bit
-        # forms (dmi_relu_bits_auto); bit-identical to the relu_src form (tested)
-        gelu = self.activation == "gelu"
-        self.use_relu_bits = not gelu and bool(self.hp.get("relu_bits", True)) and dh.relu_bits_auto(M, 4 * d, d)
-        self.hbits = per_layer(lambda: torch.empty(dh.relu_bits_bytes(M, 4 * d), dtype=torch.uint8, device=self.dev)) if self.use_relu_bits else None
-        # GELU: FFN-1 also keeps its pre-activation a = xn2 . W1 + b1 (bf16, what the FFN-2 input gradient's gelu'(a) reads; GELU
-        # cannot be inverted from h) -- 2 bytes per hidden element, 168 MB per layer at dalle_example B = 32
-        self.hpre = per_layer(lambda: torch.empty(M, 4 * d, **b16)) if gelu else None
+        # what FFN-1 keeps beside h for the FFN-2 input gradient: the ReLU mask as bits (M * 4d / 8 bytes instead of a read of h,
+        # 168 MB per layer at dalle_example) or GELU's pre-activation a = xn2 . W1 + b1 (bf16, 2 bytes per hidden element)
+        self.hbits = per_layer(lambda: torch.empty(dh.relu_bits_bytes(M, 4 * d), **u8)) if self.ffn_form == "relu_bits" else None
+        self.hpre = per_layer(lambda: torch.empty(M, 4 * d, **b16)) if self.ffn_form == "gelu" else None
         self.stats = per_layer(lambda: [torch.empty(M, **f32) for _ in range(4)])  # mean1, rstd1, mean2, rstd2
         self.xnf = torch.empty(M, d, **b16)
         self.statf = [torch.empty(M, **f32) for _ in range(2)]
@@ -528,12 +481,10 @@ class DalleEngine:
         # token-id order for the embedding scatter-add: sorted on a side stream while the forward runs
         self.tok_sorted = torch.empty(M, dtype=torch.int32, device=self.dev)
         self.tok_perm = torch.empty(M, dtype=torch.int32, device=self.dev)
-        self.sort_ws = torch.empty(dh.sort_tokens_workspace_bytes(M), dtype=torch.uint8, device=self.dev)
-        self.embed_ws = torch.empty(dh.embed_bwd_workspace_bytes(B, S, d), dtype=torch.uint8, device=self.dev)
+        self.sort_ws = torch.empty(dh.sort_tokens_workspace_bytes(M), **u8)
+        self.embed_ws = torch.empty(dh.embed_bwd_workspace_bytes(B, S, d), **u8)
         self.sort_stream = torch.cuda.Stream(device=self.dev)
         self._sort_done = None
-        # (launching the sort at the start of the BACKWARD instead -- side stream under the head's weight gradient, or on the main stream -- measured
-        # the same within noise: 14.49 / 14.57 / 14.57 ms over three alternations, profiles/r06_ab_sort_at.log)
         # scratch
         self.dx = [torch.empty(M, d, **b16) for _ in range(2)]
         self.dxn = torch.empty(M, d, **b16)
@@ -546,54 +497,18 @@ class DalleEngine:
         self.drop_y = torch.empty(M, d, **b16) if self.resid_thresh else None
         self.dyd = [torch.empty(M, d, **b16) for _ in range(2)] if self.resid_thresh else None
         self.delta = torch.empty(3, B, H, S, **f32)   # delta | (lse, delta) pairs for the dK/dV kernel's DMA
-        wsz = max(dh.gemm_tn_workspace_bytes(M, d, Vp), dh.gemm_tn_workspace_bytes(M, 4 * d, d),
-                  dh.gemm_tn_workspace_bytes(M, d, 4 * d), dh.gemm_tn_workspace_bytes(M, d, 3 * d),
-                  dh.gemm_tn_workspace_bytes(M, d, d), dh.layernorm_bwd_workspace_bytes(M, d),
-                  dh.sumsq_workspace_bytes(self.lay.total), dh.gemm_nt_splitk_workspace_bytes(M // 2 + 256, d, 8))
-        self.ws = torch.empty(int(wsz) + 1024, dtype=torch.uint8, device=self.dev)
+        wsz = max(dh.gemm_tn_workspace_bytes(M, d, Vp), *(dh.gemm_tn_workspace_bytes(M, i_, j_) for i_, j_ in self.wgrad_shapes),
+                  dh.layernorm_bwd_workspace_bytes(M, d), dh.sumsq_workspace_bytes(self.lay.total),
+                  dh.gemm_nt_splitk_workspace_bytes(M // 2 + 256, d, 8))
+        self.ws = torch.empty(int(wsz) + 1024, **u8)
         # the four weight gradients of a block keep their split-m slabs in separate workspaces and their seven slab reduces
         # run as ONE launch at the end of the block's backward (dmi_reduce_slabs_batch)
-        self.ws_blk = [torch.empty(int(dh.gemm_tn_workspace_bytes(M, i_, j_)) + 256, dtype=torch.uint8, device=self.dev)
-                       for i_, j_ in ((4 * d, d), (d, 4 * d), (d, d), (d, 3 * d))]
+        self.ws_blk = [torch.empty(int(dh.gemm_tn_workspace_bytes(M, i_, j_)) + 256, **u8) for i_, j_ in self.wgrad_shapes]
         self.deferred = dh.DeferredReduces()
-        # tuning switch: hparams win, the environment variable gives the default (A/B runs: tools/ab_env.sh)
-        # LayerNorm fused into the products that feed it (dmi_gemm_nt_ln): the full-row tiles exist for n_embd = 512
-        # Measured (profiles/r04q_kbench_ln512.log, r04q_ab_fuse_ln.log): out-projection + norm_2 46.5 us fused vs 33.4 + 16.1 us,
-        # FFN-2 + norm 98.9 vs 77.9 + 16.4 us, step 15.98 vs 15.95 ms -- with ONE tile per CU nothing overlaps the fused epilogue,
-        # and its two 160-KB outputs per tile leave at the CU's ~14 B / clk store-issue rate, which costs what the HBM-bound
-        # standalone kernel costs.  (Round 4: off by default.)
-        # [r05] ON by default: with the residual rows fetched as 16-byte pieces (through the row swap) instead of 8-byte pieces in the
-        # accumulator layout the fused form wins: 14.92 -> 14.83 ms/step same-call (profiles/r05g_ab_fuse_ln.log)
-        # [r06] both fused LayerNorm forms are gated on the library's own predicate (dmi_gemm_nt_ln_auto: N = 512, operand sizes inside the
-        # 32-bit buffer offsets of the full-row kernel for the widest product that uses it, no CUs reserved for a concurrent exchange) at
-        # buffer-allocation time; the two-kernel path is the fallback (advisor finding, round 5: the fused calls have no fallback of their own)
-        ln_ok = dh.gemm_nt_ln_auto(M, d, 4 * d) and self.dp_reserve_cus == 0
-        self.fuse_ln = bool(self.hp.get("fuse_ln", os.environ.get("DALLE_FUSE_LN", "1") != "0")) and ln_ok
-        # FFN-2 -> next norm_1: not under recompute_grad, whose re-run of a block starts from the stored residual stream with a
-        # standalone norm_1 (its statistics sum in another order; the re-run must reproduce the forward bit for bit)
-        self.fuse_ln1 = self.fuse_ln and not self.recompute
-        self.hp.setdefault("dgrad_tail_split", os.environ.get("DALLE_DGRAD_TAIL", "1") != "0")
-        self.hp.setdefault("defer_reduces", os.environ.get("DALLE_DEFER_REDUCES", "1") != "0")
-        self.hp.setdefault("wgrad_pair", os.environ.get("DALLE_WGRAD_PAIR", "1") != "0")
-        # [r06] all FOUR weight gradients of a block in one launch, on 128 x 256 tiles (96 tiles x 5 row splits; the library picks the wide
-        # tile when the union fills the block slots within every problem's slab count): 335 -> 266 us per block in isolation
-        # (profiles/r06_tn_group_wide.log); needs the pair launch and the deferred reduces
-        self.hp.setdefault("wgrad_group4", os.environ.get("DALLE_WGRAD_GROUP4", "1") != "0")
-        # (only where the library's plan for the four is the wide one: at n_embd = 1024 / 2048 the union is 384+ tiles, which whole
-        # 128 x 128 tiles of ONE launch would run in ragged residencies -- those shapes keep the separate launches)
-        self.wgrad_group4 = bool(self.hp["wgrad_group4"] and self.hp["wgrad_pair"] and self.hp["defer_reduces"]
-                                 and dh.gemm_tn_group_plan([(4 * d, d), (d, 4 * d), (d, d), (d, 3 * d)], M) > 0)
-        self.hp.setdefault("lnbwd_chain", os.environ.get("DALLE_LNBWD_CHAIN", "1") != "0")
-        # [r05] LayerNorm backward fused into the two input-gradient products that feed a LayerNorm (dmi_gemm_nt_lnbwd: n_embd = 512,
-        # full-row tiles): dxn is never written, 12 of the 13 ln_bwd launches of a dalle_example step disappear
-        self.fuse_lnbwd = bool(self.hp.get("fuse_lnbwd", os.environ.get("DALLE_FUSE_LNBWD", "1") != "0")) and ln_ok
         if self.fuse_lnbwd:
-            # one partial buffer per LayerNorm: the 2L gain / bias reduces run as ONE batched launch at the end of the backward
-            # (per block under data parallelism, where the exchange takes a block's gradients as soon as it is done)
-            self.lnb_batch = bool(self.hp.get("lnbwd_batch_finish", os.environ.get("DALLE_LNBWD_BATCH", "1") != "0"))
             npart = dh.gemm_nt_lnbwd_parts(M) * 2 * d
-            self.lnb_part = [torch.empty(npart, dtype=torch.float32, device=self.dev) for _ in range(2 * L if self.lnb_batch else 1)]
-            self.ln_ws_final = torch.empty(int(dh.layernorm_bwd_workspace_bytes(M, d)) + 256, dtype=torch.uint8, device=self.dev)
+            self.lnb_part = [torch.empty(npart, **f32) for _ in range(2 * L if self.lnb_batch else 1)]
+            self.ln_ws_final = torch.empty(int(dh.layernorm_bwd_workspace_bytes(M, d)) + 256, **u8)
 
     # ------------------------------------------------------------------ forward
     def _w(self, name):
@@ -608,7 +523,7 @@ class DalleEngine:
         unnormalised dlogits E, self.rowscale their per-row factor (already scaled by 1/(global B*S*microbatches)).
         need_grad=False (evaluation): self.z holds the bf16 logits (see logits()); the loss is the plain mean
         (the reference forces num_microbatches = 1 outside training, src/model_fns.py:150-154)."""
-        M, d, L, B, H, S, Vp = self.M, self.d, self.L, self.B, self.H, self.S, self.Vp
+        B, S, L = self.B, self.S, self.L
         assert tokens.shape == (B, S) and tokens.dtype == torch.int32
         self.tokens.copy_(tokens)
         self._sort_done = None
@@ -616,21 +531,21 @@ class DalleEngine:
             self._launch_sort()
         dh.shift_labels(self.tokens, self.labels, B, S, self.eos)
         self._draw_dropout(need_grad)
-        if self._drop and self.embed_thresh:
-            dh.embed_fwd_dropout(self.tokens, self._w("embedding/wte"), self._w("positional_embedding/wpe"), self.X[0], S, d, self.V,
-                                 self.last_dropout[SITE_TOKEN][0], self.last_dropout[SITE_POSITION][0], self.embed_thresh)
-        else:
-            dh.embed_fwd(self.tokens, self._w("embedding/wte"), self._w("positional_embedding/wpe"), self.X[0], S, d, self.V)
+        self._embed_fwd()
         for l in range(L):
             self._block_forward(l)
-        if not (self._ln1_by_prev() and L > 0):      # (fused: written by the last block's FFN-2)
-            dh.layernorm_fwd(self.X[L], self._w("to_logits/layer_norm/g"), self._w("to_logits/layer_norm/b"), self.xnf,
-                             self.statf[0], self.statf[1], M, d)
+        self._ln_of_stream(L)
+        return self._loss_head(need_grad)
+
+    def _loss_head(self, need_grad):
+        """xnf -> the loss (and, training, what the head's backward reads: see forward)"""
+        M, d, S, Vp = self.M, self.d, self.S, self.Vp
         Wt, bias = self.tview("to_logits/linear_out/kernel"), self._w("to_logits/linear_out/bias")
         nmb = (self.hp.get("num_microbatches", 1) or 1) if need_grad else 1
+        weighted = self.pos_weight is not None
         if need_grad:
             dh.label_logit(self.xnf, d, Wt, d, bias, self.labels, self.zl, self.head_flag, M, d, self.V)
-        hook = getattr(self, "event_hook", None)  # bench.py: HIP events around the largest single launch
+        hook = self.event_hook       # bench.py: HIP events around the largest single launch
         if hook is not None:
             e0 = torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -642,19 +557,15 @@ class DalleEngine:
             e1 = torch.cuda.Event(enable_timing=True)
             e1.record()
             hook().append((e0, e1))
-        weighted = self.pos_weight is not None
-        if need_grad and weighted:
-            dh.softmax_finish_w(self.rowsum_part, self.nparts, self.zl, None, self.labels, self.xnf, d, Wt, d, bias, self.z, Vp, Vp,
-                                self.loss_rows, self.rowscale, self.rowscale_bf, self.xs, self.head_flag, M, d, self.V,
-                                1.0 / (self.B_global * nmb), self.pos_weight, S)
-        elif need_grad:
-            dh.softmax_finish(self.rowsum_part, self.nparts, self.zl, None, self.labels, self.xnf, d, Wt, d, bias, self.z, Vp, Vp,
-                              self.loss_rows, self.rowscale, self.rowscale_bf, self.xs, self.head_flag, M, d, self.V,
-                              1.0 / (self.B_global * S * nmb))
+        if need_grad:   # the weighted finish scales row (b, p) by w[p] / (global B), the plain one every row by 1 / (global B * S)
+            finish, scale = ((dh.softmax_finish_w, (1.0 / (self.B_global * nmb), self.pos_weight, S)) if weighted else
+                             (dh.softmax_finish, (1.0 / (self.B_global * S * nmb),)))
+            finish(self.rowsum_part, self.nparts, self.zl, None, self.labels, self.xnf, d, Wt, d, bias, self.z, Vp, Vp,
+                   self.loss_rows, self.rowscale, self.rowscale_bf, self.xs, self.head_flag, M, d, self.V, *scale)
         else:
             dh.cross_entropy(self.z, Vp, self.labels, self.loss_rows, None, M, self.V, 0.0)
         if weighted:
-            dh.loss_reduce(self.loss_rows, M, self.pos_weight, S, self.T - 1, 1.0 / (B * nmb), self.loss3)
+            dh.loss_reduce(self.loss_rows, M, self.pos_weight, S, self.T - 1, 1.0 / (self.B * nmb), self.loss3)
         else:
             dh.sum_f32(self.loss_rows, M, 1.0 / (M * nmb), self.loss)
         return self.loss
@@ -675,76 +586,107 @@ class DalleEngine:
     def _drop_resid(self):
         return self._drop and self.resid_thresh > 0
 
+    def _embed_args(self):
+        """the trailing arguments of the embedding's dropout entries: (token key, position key, threshold), or () undropped"""
+        if not (self._drop and self.embed_thresh):
+            return ()
+        return self.last_dropout[SITE_TOKEN][0], self.last_dropout[SITE_POSITION][0], self.embed_thresh
+
+    def _embed_fwd(self):
+        drop = self._embed_args()
+        (dh.embed_fwd_dropout if drop else dh.embed_fwd)(self.tokens, self._w("embedding/wte"), self._w("positional_embedding/wpe"),
+                                                         self.X[0], self.S, self.d, self.V, *drop)
+
+    def _embed_bwd(self, dx):
+        drop = self._embed_args()
+        (dh.embed_bwd_dropout if drop else dh.embed_bwd)(self.tok_sorted, self.tok_perm, dx, self._gv("embedding/wte"),
+                                                         self._gv("positional_embedding/wpe"), self.B, self.S, self.d, self.V,
+                                                         self.embed_ws, *drop)
+
+    # ---- the LayerNorm that reads the stream leaving a block
+    def _ln_after(self, l):
+        """(gain, bias, y, mean, rstd) of the LayerNorm that reads X[l + 1]: norm_1 of block l + 1, to_logits' after the last"""
+        if l + 1 < self.L:
+            q, y, (mean, rstd) = f"layer_{l + 1}/norm_1/", self.xn1[l + 1], self.stats[l + 1][:2]
+        else:
+            q, y, (mean, rstd) = "to_logits/layer_norm/", self.xnf, self.statf
+        return self._w(q + "g"), self._w(q + "b"), y, mean, rstd
+
     def _ln1_by_prev(self):
         """norm_1 of block l + 1 (and to_logits' norm) is written by block l's FFN-2: the fused product, or under residual dropout
         dmi_dropout_add_ln -- neither under recompute_grad, whose re-run starts from a standalone norm_1"""
         return self.fuse_ln1 or (self._drop_resid() and not self.recompute)
 
-    def _block_forward(self, l):
-        """one transformer block (src/dalle_mtf/models.py:326-335): X[l] -> X[l+1]; also what backward() re-runs under
-        recompute_grad.
-        fuse_ln (n_embd = 512): the two products that end in the residual stream run on full-row tiles and emit the LayerNorm
-        that follows them in the same pass (dmi_gemm_nt_ln) -- out-projection + residual -> norm_2, FFN-2 + residual -> the
-        NEXT block's norm_1 (or to_logits' norm): 12 of the 13 standalone LayerNorm launches of a forward pass disappear.
-        Residual dropout (a training forward with residual_dropout > 0, and its re-run): those two products run with their bias
-        only into a scratch buffer and dmi_dropout_add_ln drops, adds the residual and emits the LayerNorm in one pass, at
-        every width; the keys are last_dropout's, so the re-run restates the same masks."""
-        M, d, B, H, S, L = self.M, self.d, self.B, self.H, self.S, self.L
-        p = f"layer_{l}/"
-        x = self.X[l]
-        st = self.stats[l]
-        rerun = getattr(self, "_in_backward", False)
-        drop = self._drop_resid()
-        if not (self._ln1_by_prev() and l > 0):   # (fused: written by block l-1's FFN-2)
-            dh.layernorm_fwd(x, self._w(p + "norm_1/g"), self._w(p + "norm_1/b"), self.xn1[l], st[0], st[1], M, d)
+    def _ln_of_stream(self, l):
+        """the LayerNorm that reads X[l] on its own launch -- unless block l - 1's FFN-2 has written it"""
+        if not (self._ln1_by_prev() and l > 0):
+            g, b, y, mean, rstd = self._ln_after(l - 1)
+            dh.layernorm_fwd(self.X[l], g, b, y, mean, rstd, self.M, self.d)
+
+    def _join_branch(self, l, mlp):
+        """a branch of block l joins the residual stream, and the LayerNorm that reads the sum: the out-projection (x1 = X[l] + ..,
+        read by norm_2) or, mlp, FFN-2 (X[l + 1] = x1 + .., read by _ln_after(l) where this launch is to write it: _ln1_by_prev).
+        Residual dropout (a training forward, and its re-run): the product runs with its bias only into a scratch buffer and
+        dmi_dropout_add_ln drops, adds and normalises in one pass at every width; the keys are last_dropout's, so the re-run
+        restates the same masks.  fuse_ln: full-row tiles emit the LayerNorm in the product's pass (dmi_gemm_nt_ln)."""
+        M, d, p, st = self.M, self.d, f"layer_{l}/", self.stats[l]
+        if mlp:
+            A, K, W, bias = self.h[l], 4 * d, self.tview(p + "mlp/mlp_linear_2/kernel"), self._w(p + "mlp/mlp_linear_2/bias")
+            res, out, site = self.x1[l], self.X[l + 1], site_mlp(l)
+            ln = self._ln_after(l) if self._ln1_by_prev() else None
+        else:
+            A, K, W, bias = self.o[l], d, self.tview(p + "attn/o"), self._w(p + "attn/compute_output_bias/o_b")
+            res, out, site = self.X[l], self.x1[l], site_attention(l)
+            ln = (self._w(p + "norm_2/g"), self._w(p + "norm_2/b"), self.xn2[l], st[2], st[3])
+        if self._drop_resid():
+            dh.gemm_nt(A, K, W, K, self.drop_y, d, M, d, K, dh.GEMM_BIAS, bias=bias)
+            dh.dropout_add_ln(self.drop_y, res, out, *(ln or (None,) * 5), M, d, *self.last_dropout[site])
+        elif self.fuse_ln and ln is not None:
+            g, b, y, mean, rstd = ln
+            dh.gemm_nt_ln(A, K, W, K, out, d, M, d, K, g, b, y, d, mean, rstd, bias=bias, residual=res)
+        else:
+            dh.gemm_nt(A, K, W, K, out, d, M, d, K, dh.GEMM_BIAS | dh.GEMM_RESIDUAL, bias=bias, residual=res)
+            if ln is not None:
+                g, b, y, mean, rstd = ln
+                dh.layernorm_fwd(out, g, b, y, mean, rstd, M, d)
+
+    # ---- FFN-1 and the FFN-2 input gradient, one arm of self.ffn_form each
+    def _ffn1(self, l):
+        """h = act(xn2 . W1^T + b1), and what the form keeps for _ffn2_dgrad: the pre-activation, the mask bits, or nothing"""
+        M, d, p = self.M, self.d, f"layer_{l}/"
+        args = (self.xn2[l], d, self.tview(p + "mlp/mlp_linear_1/kernel"), d, self.h[l], 4 * d, M, 4 * d, d)
+        b1 = self._w(p + "mlp/mlp_linear_1/bias")
+        if self.ffn_form == "gelu":
+            dh.gemm_nt_gelu(*args, b1, self.hpre[l], 4 * d)
+        elif self.ffn_form == "relu_bits":
+            dh.gemm_nt_relu_bits(*args, b1, self.hbits[l])
+        else:
+            dh.gemm_nt(*args, dh.GEMM_BIAS | dh.GEMM_RELU, bias=b1)
+
+    def _ffn2_dgrad(self, l, dy):
+        """self.dh = (dy . W2^T) * act'(..): gelu' of the stored pre-activation, the mask bits, or h > 0 read back from h"""
+        M, d = self.M, self.d
+        args = (dy, d, self._w(f"layer_{l}/mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d)
+        if self.ffn_form == "gelu":
+            dh.gemm_nt_gelu_grad(*args, self.hpre[l], 4 * d)
+        elif self.ffn_form == "relu_bits":
+            dh.gemm_nt_mask_bits(*args, self.hbits[l])
+        else:
+            dh.gemm_nt(*args, dh.GEMM_RELU_MASK, relu_src=self.h[l])
+
+    def _block_forward(self, l, rerun=False):
+        """one transformer block (src/dalle_mtf/models.py:326-335): X[l] -> X[l+1].  rerun: what backward() re-runs under
+        recompute_grad -- the block's inner activations up to h; X[l+1] is already stored."""
+        M, d, p = self.M, self.d, f"layer_{l}/"
+        self._ln_of_stream(l)
         dh.gemm_nt(self.xn1[l], d, self.tview(p + "attn/qkv"), d, self.qkv[l], 3 * d, M, 3 * d, d)
         if self.rope_cs is not None:   # the attention kernels, their backward and the decode caches see rotated q and k
-            dh.rope_qk(self.qkv[l], self.rope_cs, M, S, H, self.hd)
+            dh.rope_qk(self.qkv[l], self.rope_cs, M, self.S, self.H, self.hd)
         self._attn_fwd(l, self.qkv[l], self.o[l], self.lse[l])   # no transposed copies: hardware transpose reads
-        if drop:
-            dh.gemm_nt(self.o[l], d, self.tview(p + "attn/o"), d, self.drop_y, d, M, d, d, dh.GEMM_BIAS,
-                       bias=self._w(p + "attn/compute_output_bias/o_b"))
-            dh.dropout_add_ln(self.drop_y, x, self.x1[l], self._w(p + "norm_2/g"), self._w(p + "norm_2/b"), self.xn2[l], st[2], st[3],
-                              M, d, *self.last_dropout[site_attention(l)])
-        elif self.fuse_ln:
-            dh.gemm_nt_ln(self.o[l], d, self.tview(p + "attn/o"), d, self.x1[l], d, M, d, d,
-                          self._w(p + "norm_2/g"), self._w(p + "norm_2/b"), self.xn2[l], d, st[2], st[3],
-                          bias=self._w(p + "attn/compute_output_bias/o_b"), residual=x)
-        else:
-            dh.gemm_nt(self.o[l], d, self.tview(p + "attn/o"), d, self.x1[l], d, M, d, d, dh.GEMM_BIAS | dh.GEMM_RESIDUAL,
-                       bias=self._w(p + "attn/compute_output_bias/o_b"), residual=x)
-            dh.layernorm_fwd(self.x1[l], self._w(p + "norm_2/g"), self._w(p + "norm_2/b"), self.xn2[l], st[2], st[3], M, d)
-        if self.hpre is not None:
-            dh.gemm_nt_gelu(self.xn2[l], d, self.tview(p + "mlp/mlp_linear_1/kernel"), d, self.h[l], 4 * d, M, 4 * d, d,
-                            self._w(p + "mlp/mlp_linear_1/bias"), self.hpre[l], 4 * d)
-        elif self.use_relu_bits:
-            dh.gemm_nt_relu_bits(self.xn2[l], d, self.tview(p + "mlp/mlp_linear_1/kernel"), d, self.h[l], 4 * d, M, 4 * d, d,
-                                 self._w(p + "mlp/mlp_linear_1/bias"), self.hbits[l])
-        else:
-            dh.gemm_nt(self.xn2[l], d, self.tview(p + "mlp/mlp_linear_1/kernel"), d, self.h[l], 4 * d, M, 4 * d, d,
-                       dh.GEMM_BIAS | dh.GEMM_RELU, bias=self._w(p + "mlp/mlp_linear_1/bias"))
-        if rerun:   # the re-run stops here: X[l+1] is already stored
-            return
-        W2, b2 = self.tview(p + "mlp/mlp_linear_2/kernel"), self._w(p + "mlp/mlp_linear_2/bias")
-        if drop:
-            dh.gemm_nt(self.h[l], 4 * d, W2, 4 * d, self.drop_y, d, M, d, 4 * d, dh.GEMM_BIAS, bias=b2)
-            y = mean = rstd = g_ = b_ = None          # under recompute_grad the next LayerNorm is launched on its own
-            if not self.recompute:
-                q = f"layer_{l + 1}/norm_1/" if l + 1 < L else "to_logits/layer_norm/"
-                y, mean, rstd = (self.xn1[l + 1], *self.stats[l + 1][:2]) if l + 1 < L else (self.xnf, *self.statf)
-                g_, b_ = self._w(q + "g"), self._w(q + "b")
-            dh.dropout_add_ln(self.drop_y, self.x1[l], self.X[l + 1], g_, b_, y, mean, rstd, M, d, *self.last_dropout[site_mlp(l)])
-        elif self.fuse_ln1:
-            if l + 1 < L:
-                q = f"layer_{l + 1}/norm_1/"
-                y, mean, rstd = self.xn1[l + 1], self.stats[l + 1][0], self.stats[l + 1][1]
-            else:
-                q = "to_logits/layer_norm/"
-                y, mean, rstd = self.xnf, self.statf[0], self.statf[1]
-            dh.gemm_nt_ln(self.h[l], 4 * d, W2, 4 * d, self.X[l + 1], d, M, d, 4 * d, self._w(q + "g"), self._w(q + "b"), y, d, mean, rstd,
-                          bias=b2, residual=self.x1[l])
-        else:
-            dh.gemm_nt(self.h[l], 4 * d, W2, 4 * d, self.X[l + 1], d, M, d, 4 * d, dh.GEMM_BIAS | dh.GEMM_RESIDUAL, bias=b2, residual=self.x1[l])
+        self._join_branch(l, mlp=False)
+        self._ffn1(l)
+        if not rerun:
+            self._join_branch(l, mlp=True)
 
     def logits(self) -> torch.Tensor:
         """fp32 logits [B,S,V] of the last forward(need_grad=False) ("go to full precision", models.py:395)."""
@@ -799,53 +741,20 @@ class DalleEngine:
         weights: "ema" samples from the weight average (inside ema_weights()), "raw" from the raw iterate, None from the
         average when the engine has one.  "ema" without an average raises ValueError."""
         which = resolve_weights(weights, self.ema is not None)
-        if which == "ema" and not self._in_ema:
-            with self.ema_weights():
-                return self.sample_image_tokens(text, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p,
-                                                image_prefix=image_prefix, return_logprobs=return_logprobs, kv_cache=kv_cache,
-                                                decode_graph=decode_graph, fused_sampling=fused_sampling,
-                                                guidance_scale=guidance_scale, uncond_text=uncond_text, weights="ema")
         if which == "raw" and self._in_ema:
             raise RuntimeError("sample_image_tokens(weights='raw') inside ema_weights(): the compute copies hold the average")
+        a = check_sample_args(self.B, self.T, self.S - self.T, self.text_vocab_size, self.image_vocab_size, text, top_p=top_p,
+                              guidance_scale=guidance_scale, uncond_text=uncond_text, image_prefix=image_prefix,
+                              padding_id=self.hp.get("padding_id"))
+        with self.ema_weights() if which == "ema" else contextlib.nullcontext():
+            return self._sample(text, a, temperature, top_k, seed, return_logprobs, kv_cache, decode_graph, fused_sampling)
+
+    def _sample(self, text, a, temperature, top_k, seed, return_logprobs, kv_cache, decode_graph, fused_sampling):
+        """the body of sample_image_tokens on checked arguments (a: SampleArgs), from whichever weights pb / pbt hold"""
         B, T, S, P = self.B, self.T, self.S, self.S - self.T
-        gs = float(guidance_scale)
-        if not (gs >= 0.0 and math.isfinite(gs)):
-            raise ValueError(f"sample_image_tokens: guidance_scale must be finite and >= 0 (got {guidance_scale})")
-        guided = gs != 1.0 or uncond_text is not None
-        R = B                                            # rows of text / image_prefix / the result
-        if guided:
-            if B % 2:
-                raise ValueError(f"sample_image_tokens: guidance pairs the engine's rows, so its batch must be even (B = {B})")
-            R = B // 2
-            if tuple(text.shape) != (R, T):
-                raise ValueError(f"sample_image_tokens: with guidance text must be [B / 2 = {R}, T = {T}] (got {tuple(text.shape)})")
-            if uncond_text is None:
-                pad = self.hp.get("padding_id")
-                uncond_text = torch.full((T,), self.text_vocab_size - 1 if pad is None else int(pad), dtype=torch.int32)
-            uncond_text = torch.as_tensor(uncond_text)
-            if uncond_text.dtype.is_floating_point or uncond_text.dtype == torch.bool:
-                raise ValueError("sample_image_tokens: uncond_text must hold integer token ids")
-            if tuple(uncond_text.shape) not in ((T,), (R, T)):
-                raise ValueError(f"sample_image_tokens: uncond_text must be [T = {T}] or [B / 2 = {R}, T = {T}] "
-                                 f"(got {tuple(uncond_text.shape)})")
-            if int(uncond_text.min()) < 0 or int(uncond_text.max()) >= self.text_vocab_size:
-                raise ValueError(f"sample_image_tokens: uncond_text ids must lie in [0, {self.text_vocab_size})")
-        assert text.shape == (R, T)
-        top_p = float(top_p)
-        if not (0.0 < top_p <= 1.0):
-            raise ValueError(f"sample_image_tokens: top_p must lie in (0, 1] (got {top_p})")
+        R, guided, gs, top_p, uncond_text, image_prefix, k = a
         lo, hi = self.text_vocab_size, self.text_vocab_size + self.image_vocab_size
         nv = hi - lo
-        k = 0
-        if image_prefix is not None:
-            image_prefix = torch.as_tensor(image_prefix)
-            if image_prefix.dim() != 2 or image_prefix.shape[0] != R or not (0 <= image_prefix.shape[1] < P):
-                raise ValueError(f"sample_image_tokens: image_prefix must be [B={R}, k] with 0 <= k < {P} (got {tuple(image_prefix.shape)})")
-            if image_prefix.dtype.is_floating_point or image_prefix.dtype == torch.bool:
-                raise ValueError("sample_image_tokens: image_prefix must hold integer token ids")
-            k = int(image_prefix.shape[1])
-            if k and (int(image_prefix.min()) < 0 or int(image_prefix.max()) >= nv):
-                raise ValueError(f"sample_image_tokens: image_prefix ids must lie in [0, {nv})")
         variant = Draw(nucleus=guided or top_p < 1.0 or return_logprobs, guided=guided, logp=return_logprobs)
         toks = torch.full((B, S), lo, dtype=torch.int32, device=self.dev)
         toks[:R, :T] = text.to(device=self.dev, dtype=torch.int32)
@@ -918,25 +827,20 @@ class DalleEngine:
         recompute_grad (one shared buffer) the sampler's, allocated once: L * B * S * 3d * 2 bytes"""
         if not self.recompute:
             return self.qkv
-        if getattr(self, "_kv", None) is None:
+        if self._kv is None:
             self._kv = [torch.empty(self.M, 3 * self.d, dtype=torch.bfloat16, device=self.dev) for _ in range(self.L)]
         return self._kv
 
     def _prefill(self, toks):
         """evaluation forward over toks that leaves every layer's q | k | v in the decode caches"""
-        caches = self._kv_caches()
-        if caches is self.qkv:
-            self.forward(toks, need_grad=False)
-            return
-        shared = self.qkv
-        self.qkv = caches
+        shared, self.qkv = self.qkv, self._kv_caches()      # (the same list unless recompute_grad shares one buffer)
         try:
             self.forward(toks, need_grad=False)
         finally:
             self.qkv = shared
 
     def _decode_state(self):
-        if getattr(self, "_dec", None) is None:
+        if self._dec is None:
             B, d = self.B, self.d
             b16 = dict(dtype=torch.bfloat16, device=self.dev)
             f32 = dict(dtype=torch.float32, device=self.dev)
@@ -997,7 +901,7 @@ class DalleEngine:
         B, d, L, H, S = self.B, self.d, self.L, self.H, self.S
         D = self._dec
         x, x1, xn, o, h, st, z, fresh = D["x"][0], D["x"][1], D["xn"], D["o"], D["h"], D["st"], D["z"], D["fresh"]
-        fuse_ln = B <= 32 and d <= 2048 and self.image_vocab_size % 16 == 0 and self.hp.get("decode_fuse_ln", True)
+        fuse_ln = B <= 32 and d <= 2048 and self.image_vocab_size % 16 == 0 and self.decode_fuse_ln
 
         def ln_dense(inp, ln, W, out, N, flags=0, bias=None):       # out = LN(inp) . W^T (+ bias)(ReLU / GELU)
             g, b = self._w(ln + "/g"), self._w(ln + "/b")
@@ -1017,10 +921,7 @@ class DalleEngine:
             ln_dense(x, p + "norm_1", self.tview(p + "attn/qkv"), fresh, 3 * d)
             if self.rope_cs is not None:                               # q | k of the step at table row pos, before they enter the cache
                 dh.rope_qk_decode(fresh, self.rope_cs, B, S, H, self.hd, pos_dev=D["pos_i"])
-            if self.attn_plan[l] is None:
-                dh.attention_decode(cache, o, B, H, S, 0, fresh=fresh, pos_dev=D["pos_i"], head_dim=self.hd)
-            else:                                                      # mask row of pos from the plan, pos from D[pos_i]
-                dh.attention_decode_masked(cache, o, self.attn_plan[l], B, H, S, 0, fresh=fresh, pos_dev=D["pos_i"], head_dim=self.hd)
+            self._attn_decode(l, cache, o, fresh, D["pos_i"])
             dh.gemm_nt(o, d, self.tview(p + "attn/o"), d, x1, d, B, d, d, dh.GEMM_BIAS | dh.GEMM_RESIDUAL,
                        bias=self._w(p + "attn/compute_output_bias/o_b"), residual=x)
             ln_dense(x1, p + "norm_2", self.tview(p + "mlp/mlp_linear_1/kernel"), h, 4 * d, dh.GEMM_BIAS | act,
@@ -1057,14 +958,83 @@ class DalleEngine:
     def _gv(self, name):
         return self.view(self.g, name)
 
-    def _wgrad(self, X, ldx, dY, ldy, dW, M, I, J, dbias=None, bias_weights=None, slot=None):
-        """dW = X^T dY (+ fused bias gradient).  slot 0..3: one of the block's four gradients -- its slab reduces are deferred
-        to the block's single reduce launch."""
-        if slot is None or not self.hp["defer_reduces"]:
-            dh.gemm_tn(X, ldx, dY, ldy, dW, M, I, J, self.ws, dbias=dbias, bias_weights=bias_weights)
+    # ---- weight gradients: dW = X^T dY (+ the bias gradient) as problem records in the form dh.gemm_tn_group takes
+    def _wgrad_problems(self, l, dya, dyb):
+        """block l's four weight gradients in the order of wgrad_shapes.  dya / dyb: the gradients of the FFN's and of the attention
+        branch's output.  (X is [M, I], dY [M, J], both dense: the leading dimensions are I and J.)"""
+        d, p, g = self.d, f"layer_{l}/", self._gv
+        operands = ((self.h[l], dya, "mlp/mlp_linear_2/kernel", "mlp/mlp_linear_2/bias"),
+                    (self.xn2[l], self.dh, "mlp/mlp_linear_1/kernel", "mlp/mlp_linear_1/bias"),
+                    (self.o[l], dyb, "attn/o", "attn/compute_output_bias/o_b"),
+                    (self.xn1[l], self.dqkv, "attn/qkv", None))
+        return [dict(X=X, ldx=I, dY=dY, ldy=J, dW=g(p + w), I=I, J=J, ws=ws, **({"dbias": g(p + b)} if b else {}))
+                for (X, dY, w, b), (I, J), ws in zip(operands, self.wgrad_shapes, self.ws_blk)]
+
+    def _tn_launch(self, due, deferred=None):
+        """one launch for the records in `due`: the grouped entry for several, dmi_gemm_tn for one.  deferred None: the slab
+        reduces follow at once (the head's gradient, whose prefix of the flat buffer goes to the exchange first)."""
+        if len(due) > 1:
+            dh.gemm_tn_group(due, self.M, deferred=deferred)
+        elif due:
+            q = due[0]
+            dh.gemm_tn(q["X"], q["ldx"], q["dY"], q["ldy"], q["dW"], self.M, q["I"], q["J"], q["ws"], dbias=q.get("dbias"),
+                       bias_weights=q.get("bias_weights"), deferred=deferred)
+
+    def _wgrad(self, probs, final):
+        """launches those of a block's problems that are due once the operands of problem `final` are final: all four behind the
+        last one (wgrad_group4), or the FFN's two each on its own and the attention pair (16 + 48 tiles fill the chip together)
+        behind the last.  The operands of a problem stay untouched until its launch; the slab reduces of all four wait for the
+        block's single reduce launch (self.deferred.run())."""
+        if final == 3:
+            due = probs if self.wgrad_group4 else probs[2:]
         else:
-            dh.gemm_tn(X, ldx, dY, ldy, dW, M, I, J, self.ws_blk[slot], dbias=dbias, bias_weights=bias_weights,
-                       deferred=self.deferred)
+            due = [] if self.wgrad_group4 else [probs[final]]
+        self._tn_launch(due, self.deferred)
+
+    # ---- the input gradient into a LayerNorm
+    def _d_o_chained(self):
+        """norm_2's fused backward also forms the out-projection's input gradient d_o = dxb . Wo^T in the same launch -- not under
+        residual dropout, where d_o = dyb . Wo^T reads the masked gradient"""
+        return self.fuse_lnbwd and not self._drop_resid()
+
+    def _ln_dgrad(self, idx, dres, dx):
+        """dx = the gradient into the input of LayerNorm idx (2l: norm_1 of block l, 2l + 1: its norm_2, 2L: to_logits') + dres,
+        and the LayerNorm's gain / bias gradients.  The gradient of its output is the product A . W^T of the layer that reads it
+        (FFN-1: A = self.dh; QKV: A = self.dqkv); the head's is already in self.dxn.  fuse_lnbwd: product and LayerNorm backward
+        in one pass (dmi_gemm_nt_lnbwd), chained with d_o for norm_2 (_d_o_chained); otherwise the product into self.dxn and
+        dmi_layernorm_bwd.  The gain / bias partials are summed right away, or under lnb_batch by the next _flush_ln() -- the
+        head's, which has no fused form, then joins the batch through a workspace of its own."""
+        M, d, L = self.M, self.d, self.L
+        l, second = divmod(idx, 2)
+        if idx == 2 * L:
+            ln, x, (mean, rstd), A = "to_logits/layer_norm/", self.X[L], self.statf, None
+        elif second:
+            ln, x, (mean, rstd) = f"layer_{l}/norm_2/", self.x1[l], self.stats[l][2:]
+            A, K, W = self.dh, 4 * d, self._w(f"layer_{l}/mlp/mlp_linear_1/kernel")
+        else:
+            ln, x, (mean, rstd) = f"layer_{l}/norm_1/", self.X[l], self.stats[l][:2]
+            A, K, W = self.dqkv, 3 * d, self._w(f"layer_{l}/attn/qkv")
+        g, dg, db = self._w(ln + "g"), self._gv(ln + "g"), self._gv(ln + "b")
+        if self.fuse_lnbwd and A is not None:
+            kw = dict(B2=self._w(f"layer_{l}/attn/o"), ldb2=d, C2=self.d_o) if second and self._d_o_chained() else {}
+            part = self.lnb_part[idx if self.lnb_batch else 0]
+            now = {} if self.lnb_batch else dict(dg=dg, db=db)
+            dh.gemm_nt_lnbwd(A, K, W, K, M, d, K, x, g, mean, rstd, dres, dx, part, **now, **kw)
+            if self.lnb_batch:   # (finish_batch derives the number of partial rows from a row count: 32 rows per partial row)
+                self._ln_pend.append((part, dg, db, 32 * dh.gemm_nt_lnbwd_parts(M)))
+        elif A is None and self.lnb_batch:
+            dh.layernorm_bwd(self.dxn, x, g, mean, rstd, dres, dx, None, None, self.ln_ws_final, M, d)
+            self._ln_pend.append((self.ln_ws_final, dg, db, M))
+        else:
+            if A is not None:
+                dh.gemm_nt(A, K, W, K, self.dxn, d, M, d, K)
+            dh.layernorm_bwd(self.dxn, x, g, mean, rstd, dres, dx, dg, db, self.ws, M, d)
+
+    def _flush_ln(self):
+        """sums the queued gain / bias partials, 16 LayerNorms per launch"""
+        while self._ln_pend:
+            dh.layernorm_bwd_finish_batch(self._ln_pend[:16], self.d)
+            del self._ln_pend[:16]
 
     def _launch_sort(self):
         main = torch.cuda.current_stream()
@@ -1089,30 +1059,26 @@ class DalleEngine:
             dh.set_option("reserve_cus", 0)
 
     def _backward(self, allreduce):
-        M, d, L, B, H, S, Vp = self.M, self.d, self.L, self.B, self.H, self.S, self.Vp
-        ws = self.ws
+        M, d, L, Vp = self.M, self.d, self.L, self.Vp
         E = self.z   # unnormalised dlogits: dlogits[m, :] = rowscale[m] * E[m, :]
-        rp = self.lay.ready_points
-        done = [0]
+        cuts = [0] + self.lay.ready_points
 
-        def ready(upto):   # g[done, upto) is final on this stream: hand it to the exchange
+        def ready(i):   # g[cuts[i], cuts[i + 1]) is final on this stream: hand it to the exchange
             if allreduce:
-                self.reducer.ready(done[0], upto)
-            done[0] = upto
+                self.reducer.ready(cuts[i], cuts[i + 1])
 
         if self._sort_done is None:
             self._launch_sort()
         # head: dW = (rowscale * xnf)^T E, dbias = rowscale^T E, dxn = rowscale * (E W^T)
-        self._wgrad(self.xs, d, E, Vp, self._gv("to_logits/linear_out/kernel"), M, d, Vp,
-                    dbias=self._gv("to_logits/linear_out/bias"), bias_weights=self.rowscale_bf)
-        ready(rp[0])
+        self._tn_launch([dict(X=self.xs, ldx=d, dY=E, ldy=Vp, dW=self._gv("to_logits/linear_out/kernel"), I=d, J=Vp, ws=self.ws,
+                              dbias=self._gv("to_logits/linear_out/bias"), bias_weights=self.rowscale_bf)])
+        ready(0)
         # K = vocabulary: main-loop-bound -> 256x256 tiles, one 8-wave block per CU (the library picks that kernel for long-K
         # launches that fill whole residencies of the 256 CUs).  The rows of the whole residencies run unsplit; the rows of the
         # ragged last residency run with K split so that they also fill the chip (fp32 slabs, deterministic reduce).
-        # Measured per step (profiles/r02c_*): 1.46 + 0.47 ms vs 1.81 + 0.46 ms with 128x128 tiles.
         Wk = self._w("to_logits/linear_out/kernel")
         tn8 = (d + 255) // 256
-        whole_rows = min(M, (((M + 255) // 256) * tn8 // 256) * 256 // tn8 * 256) if self.hp["dgrad_tail_split"] else M
+        whole_rows = min(M, (((M + 255) // 256) * tn8 // 256) * 256 // tn8 * 256) if self.dgrad_tail_split else M
         if whole_rows in (0, M) or Vp < 8192:
             dh.gemm_nt(E, Vp, Wk, Vp, self.dxn, d, M, d, Vp, dh.GEMM_ROWSCALE, rowscale=self.rowscale)
         else:
@@ -1123,127 +1089,43 @@ class DalleEngine:
             dh.gemm_nt_splitk(E[whole_rows:], Vp, Wk, Vp, self.dxn[whole_rows:], tail_rows, d, Vp, ns, self.ws,
                               rowscale=self.rowscale[whole_rows:])
         dxa, dxb = self.dx
-        pend = []
-
-        def ln_bwd(idx, dy, x, g, mean, rstd, dres, dx, dg, db):
-            if self.fuse_lnbwd and self.lnb_batch and idx == 2 * L:    # the head's LayerNorm joins the batched finish of the fused ones
-                dh.layernorm_bwd(dy, x, g, mean, rstd, dres, dx, None, None, self.ln_ws_final, M, d)
-                pend.append((self.ln_ws_final, dg, db, M))
-            else:
-                dh.layernorm_bwd(dy, x, g, mean, rstd, dres, dx, dg, db, ws, M, d)
-
-        def flush_ln():
-            while pend:
-                dh.layernorm_bwd_finish_batch(pend[:16], d)
-                del pend[:16]
-
-        def lnbwd(idx, A, K, Wn, x, g, mean, rstd, dres, dx, dg, db, B2=None, C2=None):
-            """product + LayerNorm backward in one pass (dmi_gemm_nt_lnbwd); the gain / bias partials are summed right away or,
-            batched, with the other LayerNorms' at the next flush_ln().  B2 / C2: the product that consumes dx, chained in the
-            same launch (C2 = dx . B2^T)."""
-            kw = dict(B2=B2, ldb2=d, C2=C2) if B2 is not None else {}
-            if self.lnb_batch:
-                part = self.lnb_part[idx]
-                dh.gemm_nt_lnbwd(A, K, Wn, K, M, d, K, x, g, mean, rstd, dres, dx, part, **kw)
-                # (finish_batch derives the number of partial rows from a row count: 32 rows per partial row)
-                pend.append((part, dg, db, 32 * dh.gemm_nt_lnbwd_parts(M)))
-            else:
-                dh.gemm_nt_lnbwd(A, K, Wn, K, M, d, K, x, g, mean, rstd, dres, dx, self.lnb_part[0], dg=dg, db=db, **kw)
-
-        ln_bwd(2 * L, self.dxn, self.X[L], self._w("to_logits/layer_norm/g"), self.statf[0], self.statf[1], None, dxa,
-               self._gv("to_logits/layer_norm/g"), self._gv("to_logits/layer_norm/b"))
+        self._ln_dgrad(2 * L, None, dxa)
+        # residual dropout: the two branch outputs' gradients are the masked stream gradients (dya: dxa masked, dyb: dxb masked
+        # after norm_2's backward); the unmasked dxa / dxb stay the residual pass-through
+        drop = self._drop_resid()
+        dya, dyb = self.dyd if drop else (dxa, dxb)
         for bi, l in enumerate(reversed(range(L))):
             p = f"layer_{l}/"
-            st = self.stats[l]
             if self.recompute:
-                self._in_backward = True
-                self._block_forward(l)
-                self._in_backward = False
-            # residual dropout: the two branch outputs' gradients are the masked stream gradients (dya below, dyb after norm_2's
-            # backward); the unmasked dxa / dxb stay the residual pass-through
-            drop = self._drop_resid()
-            dya = dxa
-            if drop:
-                dya = self.dyd[0]
-                dh.dropout_bwd(dxa, dya, M, d, *self.last_dropout[site_mlp(l)])
+                self._block_forward(l, rerun=True)
+            probs = self._wgrad_problems(l, dya, dyb)
             # FFN
-            pair = self.hp["wgrad_pair"] and self.hp["defer_reduces"]
-            group4 = pair and self.wgrad_group4    # (dxa, self.dh, dxb stay untouched until the group's launch behind the attention backward)
-            if not group4:
-                self._wgrad(self.h[l], 4 * d, dya, d, self._gv(p + "mlp/mlp_linear_2/kernel"), M, 4 * d, d,
-                            dbias=self._gv(p + "mlp/mlp_linear_2/bias"), slot=0)
-            if self.hpre is not None:
-                dh.gemm_nt_gelu_grad(dya, d, self._w(p + "mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d, self.hpre[l], 4 * d)
-            elif self.use_relu_bits:
-                dh.gemm_nt_mask_bits(dya, d, self._w(p + "mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d, self.hbits[l])
-            else:
-                dh.gemm_nt(dya, d, self._w(p + "mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d, dh.GEMM_RELU_MASK,
-                           relu_src=self.h[l])
-            if not group4:
-                self._wgrad(self.xn2[l], d, self.dh, 4 * d, self._gv(p + "mlp/mlp_linear_1/kernel"), M, d, 4 * d,
-                            dbias=self._gv(p + "mlp/mlp_linear_1/bias"), slot=1)
-            # ... and the out-projection's input gradient d_o = dxb . Wo^T in the same launch (not under residual dropout: d_o = dyb . Wo^T)
-            chain = self.fuse_lnbwd and self.hp["lnbwd_chain"] and not drop
-            if self.fuse_lnbwd:
-                lnbwd(2 * l + 1, self.dh, 4 * d, self._w(p + "mlp/mlp_linear_1/kernel"), self.x1[l], self._w(p + "norm_2/g"), st[2], st[3],
-                      dxa, dxb, self._gv(p + "norm_2/g"), self._gv(p + "norm_2/b"),
-                      B2=self._w(p + "attn/o") if chain else None, C2=self.d_o if chain else None)
-            else:
-                dh.gemm_nt(self.dh, 4 * d, self._w(p + "mlp/mlp_linear_1/kernel"), 4 * d, self.dxn, d, M, d, 4 * d)
-                ln_bwd(2 * l + 1, self.dxn, self.x1[l], self._w(p + "norm_2/g"), st[2], st[3], dxa, dxb,
-                       self._gv(p + "norm_2/g"), self._gv(p + "norm_2/b"))
-            # attention
-            dyb = dxb
             if drop:
-                dyb = self.dyd[1]
+                dh.dropout_bwd(dxa, dya, M, d, *self.last_dropout[site_mlp(l)])
+            self._wgrad(probs, 0)
+            self._ffn2_dgrad(l, dya)
+            self._wgrad(probs, 1)
+            self._ln_dgrad(2 * l + 1, dxa, dxb)
+            # attention
+            if drop:
                 dh.dropout_bwd(dxb, dyb, M, d, *self.last_dropout[site_attention(l)])
-            if not pair:
-                self._wgrad(self.o[l], d, dyb, d, self._gv(p + "attn/o"), M, d, d,
-                            dbias=self._gv(p + "attn/compute_output_bias/o_b"), slot=2)
-            if not chain:
+            if not self._d_o_chained():
                 dh.gemm_nt(dyb, d, self._w(p + "attn/o"), d, self.d_o, d, M, d, d)
-            if self.attn_plan[l] is None:
-                dh.attention_bwd(self.qkv[l], self.o[l], self.d_o, self.lse[l], self.delta, self.dqkv, B, H, S, head_dim=self.hd)
-            else:
-                dh.attention_bwd_masked(self.qkv[l], self.o[l], self.d_o, self.lse[l], self.delta, self.dqkv, self.attn_plan[l],
-                                        B, H, S, head_dim=self.hd)
+            self._attn_bwd(l)
             if self.rope_cs is not None:   # gradient w.r.t. the rotated q, k -> w.r.t. the projection's output (the rotation's transpose)
-                dh.rope_qk(self.dqkv, self.rope_cs, M, S, H, self.hd, inverse=True)
-            if pair:   # [r05] the out-projection and QKV kernels' gradients in ONE launch: 16 + 48 tiles fill the chip together
-                probs = [dict(X=self.o[l], ldx=d, dY=dyb, ldy=d, dW=self._gv(p + "attn/o"), I=d, J=d, ws=self.ws_blk[2],
-                              dbias=self._gv(p + "attn/compute_output_bias/o_b")),
-                         dict(X=self.xn1[l], ldx=d, dY=self.dqkv, ldy=3 * d, dW=self._gv(p + "attn/qkv"), I=d, J=3 * d, ws=self.ws_blk[3])]
-                if group4:   # [r06] ... and the two FFN gradients with them
-                    probs = [dict(X=self.h[l], ldx=4 * d, dY=dya, ldy=d, dW=self._gv(p + "mlp/mlp_linear_2/kernel"), I=4 * d, J=d,
-                                  ws=self.ws_blk[0], dbias=self._gv(p + "mlp/mlp_linear_2/bias")),
-                             dict(X=self.xn2[l], ldx=d, dY=self.dh, ldy=4 * d, dW=self._gv(p + "mlp/mlp_linear_1/kernel"), I=d, J=4 * d,
-                                  ws=self.ws_blk[1], dbias=self._gv(p + "mlp/mlp_linear_1/bias"))] + probs
-                dh.gemm_tn_group(probs, M, deferred=self.deferred)
-            else:
-                self._wgrad(self.xn1[l], d, self.dqkv, 3 * d, self._gv(p + "attn/qkv"), M, d, 3 * d, slot=3)
-            if self.fuse_lnbwd:
-                lnbwd(2 * l, self.dqkv, 3 * d, self._w(p + "attn/qkv"), self.X[l], self._w(p + "norm_1/g"), st[0], st[1],
-                      dxb, dxa, self._gv(p + "norm_1/g"), self._gv(p + "norm_1/b"))
-            else:
-                dh.gemm_nt(self.dqkv, 3 * d, self._w(p + "attn/qkv"), 3 * d, self.dxn, d, M, d, 3 * d)
-                ln_bwd(2 * l, self.dxn, self.X[l], self._w(p + "norm_1/g"), st[0], st[1], dxb, dxa,
-                       self._gv(p + "norm_1/g"), self._gv(p + "norm_1/b"))
+                dh.rope_qk(self.dqkv, self.rope_cs, M, self.S, self.H, self.hd, inverse=True)
+            self._wgrad(probs, 3)
+            self._ln_dgrad(2 * l, dxb, dxa)
             self.deferred.run()        # the block's seven slab reduces in one launch
             if allreduce and self.world > 1:
-                flush_ln()             # the exchange takes this block's gradients now
-            ready(rp[1 + bi])
+                self._flush_ln()       # the exchange takes this block's gradients now
+            ready(1 + bi)
         # embeddings: positions visited in token-id order (sorted on the side stream during the forward)
         if self._sort_done is not None:
             torch.cuda.current_stream().wait_event(self._sort_done)
-        if self._drop and self.embed_thresh:
-            dh.embed_bwd_dropout(self.tok_sorted, self.tok_perm, dxa, self._gv("embedding/wte"), self._gv("positional_embedding/wpe"),
-                                 B, S, d, self.V, self.embed_ws, self.last_dropout[SITE_TOKEN][0], self.last_dropout[SITE_POSITION][0],
-                                 self.embed_thresh)
-        else:
-            dh.embed_bwd(self.tok_sorted, self.tok_perm, dxa, self._gv("embedding/wte"), self._gv("positional_embedding/wpe"),
-                         B, S, d, self.V, self.embed_ws)
-        flush_ln()
-        ready(rp[L + 1])
+        self._embed_bwd(dxa)
+        self._flush_ln()
+        ready(L + 1)
 
     def wait_grads(self):
         self.reducer.finish()
@@ -1278,6 +1160,14 @@ class DalleEngine:
             return self._adafactor_step()
         return self._adam_step()
 
+    def _finish_step(self, lr):
+        """behind either optimizer's launches: the weight average, the [out, in] compute copies (the optimizer kernel has
+        written pb), the step count"""
+        self._ema_update()
+        self.refresh_compute_copies(cast=False)
+        self.global_step += 1
+        return lr
+
     def _adafactor_step(self):
         """clip_by_global_norm (src/optimizers.py:11-16, applied first, :100-103) + mtf.optimize.AdafactorOptimizer
         (src/optimizers.py:91-97) over every variable in six launches (dmi_adafactor_step); refreshes the bf16 compute copies."""
@@ -1290,10 +1180,7 @@ class DalleEngine:
         dh.adafactor_step(self.af_table, len(self.af_vars), self.af_totals, self.p, self.g, self.m, self.af_slots, self.pb,
                           self.gnorm_sq, 0.0 if clip is None else float(clip), lr, get("weight_decay", 0.0), self._af_beta1(),
                           get("epsilon_1", 1e-30), get("epsilon_2", 1e-3), self.af_ws)
-        self._ema_update()
-        self.refresh_compute_copies(cast=False)
-        self.global_step += 1
-        return lr
+        return self._finish_step(lr)
 
     def _adam_step(self):
         """clip_by_global_norm (src/optimizers.py:11-16) + AdamWeightDecayOptimizer without bias correction
@@ -1319,10 +1206,7 @@ class DalleEngine:
                 use = ("norm" not in name) and ("bias" not in name) and not name.endswith("o_b")
                 dh.adam_step(self.p[o:o + k], self.g[o:o + k], self.m[o:o + k], self.v[o:o + k], self.pb[o:o + k], k, gn, cl,
                              lr, b1, b2, eps, wd if use else 0.0)
-        self._ema_update()
-        self.refresh_compute_copies(cast=False)
-        self.global_step += 1
-        return lr
+        return self._finish_step(lr)
 
     def train_step(self, tokens: torch.Tensor) -> torch.Tensor:
         """One optimizer step.  With hparams["num_microbatches"] = n > 1, `tokens` holds n micro-batches of B rows
@@ -1337,13 +1221,13 @@ class DalleEngine:
             self.optimizer_step()
             return loss
         assert tokens.shape == (nmb * self.B, self.S), f"expected {nmb} micro-batches of {self.B} rows"
-        if getattr(self, "gacc", None) is None:
+        if self.gacc is None:
             self.gacc = torch.empty_like(self.g)
-        if getattr(self, "loss_acc", None) is None:
+        if self.loss_acc is None:         # (the model function creates the loss accumulators before the first step: its summaries hold them)
             self.loss_acc = torch.zeros_like(self.loss)
         self.loss_acc.zero_()
         if self.loss_parts is not None:
-            if getattr(self, "loss_parts_acc", None) is None:
+            if self.loss_parts_acc is None:
                 self.loss_parts_acc = torch.zeros_like(self.loss_parts)
             self.loss_parts_acc.zero_()
         for i in range(nmb):

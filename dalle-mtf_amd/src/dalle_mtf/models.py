@@ -10,6 +10,7 @@ from .activations import resolve_activation
 from .dropout import resolve_dropout
 from .ema import resolve_ema
 from .engine import DalleEngine
+from .layout import ParamLayout
 from .loss_weights import resolve_loss_weights
 from .masks import layer_masks
 from .ops import get_variable_dtype
@@ -92,18 +93,8 @@ class DALLE:
 
     def variables(self):
         """name -> shape under the reference's checkpoint names."""
-        d, V, S = self.n_embd, self.total_tokens, self.total_seq_dim
-        out = {"embedding/wte": (V, d), "positional_embedding/wpe": (S, d)}
-        for i in range(self.n_layers):
-            p = f"layer_{i}/"
-            out.update({p + "norm_1/g": (d,), p + "norm_1/b": (d,), p + "attn/q": (d, d), p + "attn/k": (d, d),
-                        p + "attn/v": (d, d), p + "attn/o": (d, d), p + "attn/compute_output_bias/o_b": (d,),
-                        p + "norm_2/g": (d,), p + "norm_2/b": (d,), p + "mlp/mlp_linear_1/kernel": (d, 4 * d),
-                        p + "mlp/mlp_linear_1/bias": (4 * d,), p + "mlp/mlp_linear_2/kernel": (4 * d, d),
-                        p + "mlp/mlp_linear_2/bias": (d,)})
-        out.update({"to_logits/layer_norm/g": (d,), "to_logits/layer_norm/b": (d,),
-                    "to_logits/linear_out/kernel": (d, V), "to_logits/linear_out/bias": (V,)})
-        return out
+        lay = ParamLayout(self.n_embd, self.n_layers, self.n_heads, self.total_tokens, self.total_seq_dim)
+        return {name: shape for name, shape, _, _ in lay.reference_variables()}
 
     def sample(self, text_tokens, vae=None, temperature=1.0, top_k=0, seed=0, top_p=1.0, image_prefix=None, return_logprobs=False,
                guidance_scale=1.0, uncond_text=None, weights=None):

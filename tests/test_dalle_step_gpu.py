@@ -175,3 +175,49 @@ def test_fused_layernorm_forms_equal_the_separate_kernels():
         assert dl <= 2e-5, (tag, dl)
         assert worst[0] <= BOUND[tag], (tag, worst)
         assert dp <= 6.5e-3, (tag, dp)      # Adam without bias correction: |step| = 3.16 lr at step 0, twice that where a near-zero gradient's sign flips
+
+
+# (n_embd, n_heads, hparams beyond compare_step's defaults, check_report bounds)
+WGRAD_SHAPE_CASES = {
+    # n_embd = 512: the fused LayerNorm backward chains the out-projection's input gradient into norm_2's launch ...
+    "d512_chained": (512, 4, {}, "d512"),
+    # ... and without it that gradient is a product of its own
+    "d512_unchained": (512, 4, dict(residual_dropout=0, fuse_lnbwd=False), "d512"),
+    # n_embd = 128: no fused form applies
+    "d128": (128, 1, {}, None),
+}
+# check_report's defaults were measured at n_embd = 256.  At n_embd = 512 (n_layers = 2, T = 64, P = 192, B = 2, vocabularies
+# 500 / 120, one step) the engine of the commit before this test, at its defaults, measured against the fp32 oracle with the same call
+# (profiles/engine_refactor_parity.json): relative loss error 2.782e-5, worst gradient tensor 0.039164 relative L2
+# (layer_1/norm_2/g), relative gradient-norm error 1.734e-4.  The bounds are those + 25 %, the margin check_report documents.
+D512_MEASURED = dict(loss_rtol=2.782e-5, grad_tol=0.039164, gn_rtol=1.734e-4)
+WGRAD_SHAPE_BOUNDS = {"d512": {k: 1.25 * v for k, v in D512_MEASURED.items()}}
+
+
+@pytest.mark.parametrize("case", sorted(WGRAD_SHAPE_CASES))
+def test_block_weight_gradient_launch_shapes_match_oracle(case, monkeypatch):
+    """The four weight gradients of a block leave as ONE grouped launch where the library plans the four on its wide tile
+    (engine.wgrad_group4), otherwise as a grouped launch of the attention pair and one launch each for the FFN's two; the head's
+    is a single launch.  One step against the fp32 oracle, with the launches counted: a silently different shape fails.
+    Measured at n_embd = 512 on the commit before (D512_MEASURED): loss 2.782e-5 relative, worst gradient tensor 0.039164, gradient
+    norm 1.734e-4; with fuse_lnbwd off the same to five digits.  n_embd = 128 (check_report's defaults): 1.12e-5, 0.0364, 8.7e-4."""
+    import dalle_hip as dh
+    from parity import check_report, compare_step
+    from src.dalle_mtf.engine import DalleEngine
+    n_embd, n_heads, extra, bounds = WGRAD_SHAPE_CASES[case]
+    L, seen, groups, singles = 2, {}, [], []
+    forward, group, single = DalleEngine.forward, dh.gemm_tn_group, dh.gemm_tn
+    monkeypatch.setattr(DalleEngine, "forward", lambda self, *a, **kw: (seen.setdefault("engine", self), forward(self, *a, **kw))[1])
+    monkeypatch.setattr(dh, "gemm_tn_group", lambda problems, *a, **kw: (groups.append(len(problems)), group(problems, *a, **kw))[1])
+    monkeypatch.setattr(dh, "gemm_tn", lambda *a, **kw: (singles.append(1), single(*a, **kw))[1])
+    hp = dict(lr=1e-3, train_steps=1000, warmup_steps=2, gradient_clipping=1.0, **extra)
+    report = compare_step(n_embd=n_embd, n_heads=n_heads, n_layers=L, text_vocab=500, image_vocab=120, T=64, P=192, B=2, steps=1, hp=hp)
+    eng = seen.pop("engine")
+    print(case, {k: report["steps"][0][k] for k in ("loss_hip", "loss_oracle_fp32", "worst_grad_rel_l2_vs_fp32_oracle", "grad_norm_hip",
+                                                    "grad_norm_oracle")}, "group4", eng.wgrad_group4, groups, len(singles), flush=True)
+    assert eng.fuse_lnbwd == (case == "d512_chained") and eng.fuse_ln == (n_embd == 512)
+    if eng.wgrad_group4:
+        assert groups == [4] * L and len(singles) == 1
+    else:
+        assert groups == [2] * L and len(singles) == 2 * L + 1
+    check_report(report, **(WGRAD_SHAPE_BOUNDS[bounds] if bounds else {}))

@@ -213,3 +213,30 @@ def test_generate_cli_rejects_malformed_caption_ids(tmp_path):
     np.save(f, np.zeros((3, 17), np.int32))
     r = _cli("--model", "dalle_example", "--caption-ids", str(f))
     assert r.returncode == 2 and "text_seq_len = 256" in r.stderr, r.stderr[-2000:]
+
+
+def test_sampler_argument_check_refuses_bad_prefixes_and_top_p_without_a_device():
+    """check_sample_args, the argument check of DalleEngine.sample_image_tokens: the image_prefix and top_p refusals of
+    test_generation_gpu.py (an engine of 3 rows, 48 image positions, 64 image tokens), same exception type and key words"""
+    import torch
+    from src.dalle_mtf.engine import check_sample_args
+    T, P, tv, iv, B = 16, 48, 60, 64, 3
+    text = torch.zeros(B, T, dtype=torch.int32)
+    for bad in (torch.zeros(3, P, dtype=torch.int32),             # a prefix leaves at least one position to draw
+                torch.zeros(2, 4, dtype=torch.int32),             # one row per row of text
+                torch.zeros(3, dtype=torch.int32)):
+        with pytest.raises(ValueError, match="image_prefix must be"):
+            check_sample_args(B, T, P, tv, iv, text, image_prefix=bad)
+    for bad in (iv, -1):
+        with pytest.raises(ValueError, match="image_prefix ids"):
+            check_sample_args(B, T, P, tv, iv, text, image_prefix=torch.full((3, 2), bad, dtype=torch.int32))
+    with pytest.raises(ValueError, match="integer"):
+        check_sample_args(B, T, P, tv, iv, text, image_prefix=torch.zeros(3, 2))
+    for bad in (0.0, -0.5, 1.5, float("nan")):
+        with pytest.raises(ValueError, match="top_p"):
+            check_sample_args(B, T, P, tv, iv, text, top_p=bad)
+    with pytest.raises(AssertionError):
+        check_sample_args(B, T, P, tv, iv, text[:2])
+    a = check_sample_args(B, T, P, tv, iv, text, image_prefix=[[1, 2], [3, 4], [5, 6]])
+    assert a.prefix_len == 2 and a.image_prefix.tolist() == [[1, 2], [3, 4], [5, 6]] and not a.guided and a.rows == B
+    assert check_sample_args(B, T, P, tv, iv, text, image_prefix=torch.zeros(3, 0, dtype=torch.int32)).prefix_len == 0

@@ -185,3 +185,40 @@ def test_caption_dropout_outside_the_unit_interval_is_refused(p):
         dalle_input_fn(_params(caption_dropout=p))
     with pytest.raises(ValueError, match="caption_dropout"):
         dalle_input_fn(_params(caption_dropout=p), eval=True)
+
+
+def test_sampler_argument_check_refuses_bad_guidance_arguments_without_a_device():
+    """check_sample_args, the argument check of DalleEngine.sample_image_tokens: the cases of
+    test_guidance_engine_gpu.py::test_guidance_refusals, same exception types and key words"""
+    import torch
+    from src.dalle_mtf.engine import check_sample_args
+    T, P, TV, IV, B = 16, 48, 60, 64, 4
+    BC = B // 2
+    text, cap = torch.zeros(B, T, dtype=torch.int32), torch.zeros(BC, T, dtype=torch.int32)
+
+    def check(text, B=B, **kw):
+        return check_sample_args(B, T, P, TV, IV, text, **kw)
+    for bad in (-1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="guidance_scale"):
+            check(cap, guidance_scale=bad)
+    with pytest.raises(ValueError, match="text must be"):
+        check(text, guidance_scale=2.0)                      # B rows of text where B / 2 are wanted
+    for bad in (torch.zeros(T + 1, dtype=torch.int32), torch.zeros(B, T, dtype=torch.int32), torch.zeros(BC, T, 1, dtype=torch.int32)):
+        with pytest.raises(ValueError, match="uncond_text must be"):
+            check(cap, guidance_scale=2.0, uncond_text=bad)
+    with pytest.raises(ValueError, match="integer"):
+        check(cap, uncond_text=torch.zeros(T))
+    for bad in (TV, -1):
+        with pytest.raises(ValueError, match="uncond_text ids"):
+            check(cap, uncond_text=torch.full((T,), bad, dtype=torch.int32))
+    with pytest.raises(ValueError, match="image_prefix"):
+        check(cap, guidance_scale=2.0, image_prefix=torch.zeros(B, 3, dtype=torch.int32))
+    with pytest.raises(ValueError, match="even"):
+        check(text[:1], B=3, guidance_scale=2.0)
+    # what it hands on: B / 2 rows, the null caption from padding_id (text_vocab_size - 1 without one), the arguments as given
+    a = check(cap, guidance_scale=2.0, top_p=0.5, image_prefix=torch.zeros(BC, 3, dtype=torch.int64))
+    assert (a.rows, a.guided, a.guidance_scale, a.top_p, a.prefix_len) == (BC, True, 2.0, 0.5, 3)
+    assert a.uncond_text.dtype == torch.int32 and a.uncond_text.tolist() == [TV - 1] * T
+    assert check(cap, guidance_scale=2.0, padding_id=TV - 2).uncond_text.tolist() == [TV - 2] * T
+    a = check(text)
+    assert (a.rows, a.guided, a.guidance_scale, a.top_p, a.uncond_text, a.image_prefix, a.prefix_len) == (B, False, 1.0, 1.0, None, None, 0)

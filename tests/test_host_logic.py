@@ -255,3 +255,24 @@ def test_sampler_uniform_is_strictly_inside_unit_interval():
             assert np.all(np.isfinite(noise)) and noise[1] < 17.0 and noise[0] > -3.0
     src = open(os.path.join(os.path.dirname(__file__), "..", "dalle-mtf_amd", "csrc", "elementwise.hip")).read()
     assert "(h >> 41) + 0.5f) * (1.0f / 8388608.0f)" in src
+
+
+def test_dalle_variables_are_the_layouts_reference_variables():
+    """DALLE.variables() is built from ParamLayout.reference_variables(): one table of the reference's names and shapes"""
+    from src.dalle_mtf.layout import ParamLayout
+    from src.dalle_mtf.models import DALLE
+    d, L, tv, iv, T, P = 128, 2, 40, 8, 8, 8
+    m = DALLE.__new__(DALLE)          # variables() reads the sizes alone: no engine, no device
+    m.n_embd, m.n_layers, m.n_heads, m.total_tokens, m.total_seq_dim = d, L, 1, tv + iv + 1, T + P
+    lay = ParamLayout(d, L, 1, tv + iv + 1, T + P)
+    assert list(m.variables().items()) == [(name, shape) for name, shape, _, _ in lay.reference_variables()]
+    v = m.variables()
+    assert len(v) == 2 + 13 * L + 4
+    assert v["embedding/wte"] == (49, d) and v["positional_embedding/wpe"] == (16, d)
+    assert v["to_logits/linear_out/kernel"] == (d, 49) and v["to_logits/linear_out/bias"] == (49,)      # V, not the padded Vp
+    assert all(v[f"layer_1/attn/{t}"] == (d, d) for t in "qkvo") and "layer_1/attn/qkv" not in v
+    assert v["layer_0/mlp/mlp_linear_1/kernel"] == (d, 4 * d) and v["layer_0/mlp/mlp_linear_2/kernel"] == (4 * d, d)
+    # the engine module keeps exporting the layout's names
+    from src.dalle_mtf import engine, layout
+    assert all(getattr(engine, n) is getattr(layout, n) for n in ("ParamLayout", "adafactor_factored_dims", "adafactor_table", "ALIGN",
+                                                                   "_round_up"))
