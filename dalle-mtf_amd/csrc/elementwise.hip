@@ -598,6 +598,117 @@ extern "C" int dmi_rope_qk_decode(uint16_t* fresh, const float* cs, int B, int S
   return DMI_OK;
 }
 
+// =====================================================================================
+// Token shift (DESIGN.md §4 "Token shift"): half of every row's channels gathered from an earlier row of its sequence
+// =====================================================================================
+// The row a 16-byte piece of sequence position s is read from, as an offset in rows; TS_ZERO: the piece is +0.  ch = the piece's
+// first channel; a quarter of d is whole pieces (d % 32 == 0).  Caption positions s < T take both shifted quarters from the previous
+// position; image token k = s - T of the G x G grid takes [0, d/4) from above (k - G) and [d/4, d/2) from the left (k - 1, not
+// across the row's start).  inverse: the transpose, again a gather, from the next position / the row below / the right.
+#define TS_ZERO 0x7fffffff
+__device__ __forceinline__ int ts_source(int s, int ch, int T, int G, int d, bool inverse) {
+  if (ch >= (d >> 1)) return 0;
+  const bool up = ch < (d >> 2);
+  if (s < T) return inverse ? (s + 1 < T ? 1 : TS_ZERO) : (s >= 1 ? -1 : TS_ZERO);
+  const int k = s - T;
+  if (up) return inverse ? (k + G < G * G ? G : TS_ZERO) : (k >= G ? -G : TS_ZERO);
+  const int c = k % G;
+  return inverse ? (c + 1 < G ? 1 : TS_ZERO) : (c >= 1 ? -1 : TS_ZERO);
+}
+
+// A flat stream of 16-byte pieces over rows * d elements, as dmi_dropout_bwd.  (row, piece in row, position in sequence) of a lane
+// are carried along the grid stride by additions: the only divisions are 32-bit and happen once per lane.
+__global__ __launch_bounds__(256) void token_shift_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, bf16_t* __restrict__ hist,
+                                                          int64_t rows, int S, int T, int G, int d, int inverse) {
+  const int vpr = d >> 3;                                   // pieces per row
+  const unsigned first = blockIdx.x * 256u + threadIdx.x;   // < 2^19: the grid is capped
+  const unsigned stride = gridDim.x * 256u;
+  int64_t row = first / (unsigned)vpr;
+  int v = (int)(first % (unsigned)vpr);
+  int s = (int)((unsigned)row % (unsigned)S);
+  const int drow = (int)(stride / (unsigned)vpr), dv = (int)(stride % (unsigned)vpr), ds = drow % S;
+  const int half = d >> 1;
+  while (row < rows) {
+    const int ch = v * 8;
+    const int off = ts_source(s, ch, T, G, d, inverse != 0);
+    u32x4 val = {0u, 0u, 0u, 0u};
+    if (off != TS_ZERO) val = *(const u32x4*)(x + (row + off) * (int64_t)d + ch);
+    *(u32x4*)(y + row * (int64_t)d + ch) = val;
+    if (hist != nullptr && ch < half) *(u32x4*)(hist + row * (int64_t)half + ch) = *(const u32x4*)(x + row * (int64_t)d + ch);
+    v += dv;
+    row += drow;
+    s += ds;
+    if (v >= vpr) { v -= vpr; ++row; ++s; }
+    if (s >= S) s -= S;
+  }
+}
+
+// The decode step: the row of position pos of B sequences (pos from device memory when pos_dev is given; outside [0, S) nothing
+// is written).  y[b] = shift of x[b] with the neighbours' halves read from hist[B, S, d/2]; hist[b, pos] <- x[b, :d/2].  One block
+// per sequence; the rows read (pos - 1, pos - G) are never the row written.
+__global__ __launch_bounds__(256) void token_shift_decode_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ hist, bf16_t* __restrict__ y,
+                                                                 int S, int T, int G, int d, int pos, const int* __restrict__ pos_dev) {
+  if (pos_dev) pos = *pos_dev;
+  if (pos < 0 || pos >= S) return;
+  const int half = d >> 1;
+  const bf16_t* xr = x + (int64_t)blockIdx.x * d;
+  bf16_t* yr = y + (int64_t)blockIdx.x * d;
+  bf16_t* hs = hist + (int64_t)blockIdx.x * S * half;
+  for (int ch = threadIdx.x * 8; ch < d; ch += 256 * 8) {
+    const u32x4 own = *(const u32x4*)(xr + ch);
+    u32x4 val = own;
+    if (ch < half) {
+      const int off = ts_source(pos, ch, T, G, d, false);
+      val = u32x4{0u, 0u, 0u, 0u};
+      if (off != TS_ZERO) val = *(const u32x4*)(hs + (int64_t)(pos + off) * half + ch);
+      *(u32x4*)(hs + (int64_t)pos * half + ch) = own;
+    }
+    *(u32x4*)(yr + ch) = val;
+  }
+}
+
+#define DMI_REQUIRE_SHIFT(name, S, T, G, d)                                                                                   \
+  do {                                                                                                                        \
+    DMI_REQUIRE((T) >= 1 && (G) >= 1, name ": T and G must be at least 1 (T=%d G=%d)", (int)(T), (int)(G));                   \
+    DMI_REQUIRE((int64_t)(S) == (int64_t)(T) + (int64_t)(G) * (G), name ": S must equal T + G * G (S=%d T=%d G=%d)", (int)(S), (int)(T), (int)(G)); \
+    DMI_REQUIRE((d) >= 32 && (d) % 32 == 0, name ": d must be a positive multiple of 32 (d=%d)", (int)(d));                   \
+  } while (0)
+
+static inline bool ts_overlap(const void* a, const void* b, int64_t bytes) {
+  const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+  return p < q + (uintptr_t)bytes && q < p + (uintptr_t)bytes;
+}
+
+extern "C" int dmi_token_shift(const uint16_t* x, uint16_t* y, uint16_t* hist, int64_t rows, int S, int T, int G, int d, int inverse,
+                               void* stream) {
+  DMI_REQUIRE(x && y, "token_shift: null pointer");
+  DMI_REQUIRE(rows > 0 && S > 0 && d > 0, "token_shift: empty shape (rows=%lld S=%d d=%d)", (long long)rows, S, d);
+  DMI_REQUIRE_SHIFT("token_shift", S, T, G, d);
+  DMI_REQUIRE(rows % S == 0, "token_shift: rows must be a multiple of S (rows=%lld S=%d)", (long long)rows, S);
+  DMI_REQUIRE(!(hist && inverse), "token_shift: hist goes with the forward only (inverse=%d)", inverse);
+  DMI_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)hist) & 15) == 0, "token_shift: buffers must be 16-byte aligned");
+  DMI_REQUIRE(!ts_overlap(x, y, rows * (int64_t)d * 2), "token_shift: x and y overlap (the shift is out of place)");
+  const int64_t n8 = rows * (int64_t)(d / 8);
+  int64_t blocks = cdiv64(n8, 256);
+  if (blocks > 256 * 8) blocks = 256 * 8;     // as dmi_dropout_bwd: 8 blocks of 4 waves per CU, the rest is the grid stride
+  token_shift_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(x, y, hist, rows, S, T, G, d, inverse);
+  DMI_CHECK_LAUNCH("token_shift");
+  return DMI_OK;
+}
+
+extern "C" int dmi_token_shift_decode(const uint16_t* x, uint16_t* hist, uint16_t* y, int B, int S, int T, int G, int d, int pos,
+                                      const int* pos_dev, void* stream) {
+  DMI_REQUIRE(x && hist && y, "token_shift_decode: null pointer");
+  DMI_REQUIRE(B > 0 && S > 0 && d > 0, "token_shift_decode: empty shape (B=%d S=%d d=%d)", B, S, d);
+  DMI_REQUIRE_SHIFT("token_shift_decode", S, T, G, d);
+  DMI_REQUIRE(pos_dev || (pos >= 0 && pos < S), "token_shift_decode: pos outside [0, S) (pos=%d S=%d)", pos, S);
+  DMI_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)hist) & 15) == 0, "token_shift_decode: buffers must be 16-byte aligned");
+  DMI_REQUIRE(!ts_overlap(x, y, (int64_t)B * d * 2), "token_shift_decode: x and y overlap (the shift is out of place)");
+  token_shift_decode_kernel<<<dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream>>>(x, hist, y, S, T, G, d, pos, pos_dev);
+  DMI_CHECK_LAUNCH("token_shift_decode");
+  return DMI_OK;
+}
+
 // ---- generic deterministic partial reduce: out[c] = sum_{p<P} part[p*ncols + c]
 __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __restrict__ part, float* __restrict__ out,
                                                               int P, int ncols) {

@@ -72,6 +72,8 @@ def _declare(L):
         "dmi_dropout_bwd": (I, [P, P, L64, I, U64, I, P]),
         "dmi_rope_qk": (I, [P, I, P, L64, I, I, I, I, P]),
         "dmi_rope_qk_decode": (I, [P, P, I, I, I, I, I, P, P]),
+        "dmi_token_shift": (I, [P, P, P, L64, I, I, I, I, I, P]),
+        "dmi_token_shift_decode": (I, [P, P, P, I, I, I, I, I, I, P, P]),
         "dmi_layernorm_bwd_workspace_bytes": (L64, [L64, I]),
         "dmi_layernorm_bwd": (I, [P, P, P, P, P, P, P, P, P, P, L64, I, P]),
         "dmi_layernorm_bwd_finish_batch": (I, [P, P, P, P, I, I, P]),
@@ -274,6 +276,25 @@ def rope_qk_decode(fresh, cs, B, S, H, head_dim, pos=0, pos_dev=None):
     assert fresh.dtype == torch.bfloat16 and fresh.numel() >= B * 3 * H * head_dim
     assert cs.dtype == torch.float32 and cs.numel() >= S * head_dim and (pos_dev is None or pos_dev.dtype == torch.int32)
     _check(lib().dmi_rope_qk_decode(_p(fresh), _p(cs), B, S, H, head_dim, int(pos), _p(pos_dev), _stream()), "rope_qk_decode")
+
+
+def token_shift(x, y, rows, S, T, G, d, inverse=False, hist=None):
+    """y = shift(x) over dense [rows, d] bf16 buffers (rows a multiple of S = T + G * G): channels [0, d/4) from the previous
+    position (image tokens: from the row above), [d/4, d/2) from the previous position (image tokens: from the left), the rest
+    unchanged; inverse: the transpose.  hist (forward only): also takes columns [0, d/2) of every input row, bf16 [rows, d/2]"""
+    _dev(x, y, hist)
+    assert x.dtype == torch.bfloat16 and y.dtype == torch.bfloat16 and x.numel() >= rows * d and y.numel() >= rows * d
+    assert hist is None or (hist.dtype == torch.bfloat16 and hist.numel() >= rows * (d // 2))
+    _check(lib().dmi_token_shift(_p(x), _p(y), _p(hist), rows, S, T, G, d, int(bool(inverse)), _stream()), "token_shift")
+
+
+def token_shift_decode(x, hist, y, B, S, T, G, d, pos=0, pos_dev=None):
+    """token_shift of the decode step's [B, d] row at position pos (pos_dev: read from device memory; outside [0, S) the launch
+    writes nothing): the neighbours' halves come from hist, bf16 [B, S, d/2], whose row pos then takes x[:, :d/2]"""
+    _dev(x, hist, y, pos_dev)
+    assert x.dtype == torch.bfloat16 and y.dtype == torch.bfloat16 and x.numel() >= B * d and y.numel() >= B * d
+    assert hist.dtype == torch.bfloat16 and hist.numel() >= B * S * (d // 2) and (pos_dev is None or pos_dev.dtype == torch.int32)
+    _check(lib().dmi_token_shift_decode(_p(x), _p(hist), _p(y), B, S, T, G, d, int(pos), _p(pos_dev), _stream()), "token_shift_decode")
 
 
 def layernorm_bwd_workspace_bytes(rows, d):

@@ -39,6 +39,7 @@ from .layout import ALIGN, ParamLayout, _round_up, adafactor_factored_dims, adaf
 from .ema import ema_decay_at, one_minus_decay, resolve_ema, resolve_weights   # noqa: F401  (ema_decay_at: part of the engine's surface)
 from .loss_weights import position_weights, resolve_loss_weights
 from .rotary import DEFAULT_BASE, resolve_rotary, rotary_table
+from .token_shift import grid_side, resolve_token_shift
 
 @contextlib.contextmanager
 def _no_gc_in_capture():
@@ -124,6 +125,8 @@ class DalleEngine:
         self.embed_thresh, self.resid_thresh, self.dropout_seed = resolve_dropout(hparams)
         # hparams["rotary_emb"] ("1d" / "axial"; None: off) and ["rotary_base"] (dalle_mtf.rotary)
         self.rotary, self.rotary_base = resolve_rotary(hparams, image_seq_len)
+        # hparams["token_shift"] (dalle_mtf.token_shift): half of every position's channels come from its neighbours, behind norm_1 and norm_2
+        self.token_shift = resolve_token_shift(hparams, n_embd, image_seq_len)
         if not torch.cuda.is_available():
             raise dh.DalleHipError("DalleEngine needs a HIP device (MI355X); there is no CPU fallback")
         dh.lib()
@@ -174,6 +177,10 @@ class DalleEngine:
         # state that comes into being on first use (None until then)
         self._t_table = None                      # refresh_compute_copies: the batched transpose's descriptor table
         self._kv = self._dec = None               # the sampler's key/value caches (under recompute_grad) and decode buffers
+        # token shift: the image grid's side, the sampler's history (hist[l][site], allocated on first use) and, inside _prefill,
+        # the history the forward's shift launches also write
+        self.G = grid_side(image_seq_len) if self.token_shift else None
+        self._shift_hist = self._shift_hist_out = None
         self.gacc = self.loss_acc = self.loss_parts_acc = None   # train_step's micro-batch accumulators
         self.event_hook = None                    # bench.py: a callable returning the list that takes the head launch's event pair
         self._ln_pend = []                        # LayerNorm gain / bias partials awaiting _flush_ln()
@@ -414,7 +421,10 @@ class DalleEngine:
         # standalone norm_1 (its statistics sum in another order; the re-run must reproduce the forward bit for bit)
         self.fuse_ln1 = self.fuse_ln and not self.recompute
         # fuse_lnbwd: LayerNorm backward inside the input-gradient product that feeds it (dmi_gemm_nt_lnbwd); dxn is never written
-        self.fuse_lnbwd = switch("fuse_lnbwd", "DALLE_FUSE_LNBWD") and ln_ok
+        # (not with token_shift: the shift's transpose stands between the product and the LayerNorm backward, and the fused form
+        # cannot carry it -- the product lands in dxn, dmi_token_shift(inverse) and dmi_layernorm_bwd follow; with fuse_lnbwd go
+        # the d_o chaining and the batched finish)
+        self.fuse_lnbwd = switch("fuse_lnbwd", "DALLE_FUSE_LNBWD") and ln_ok and not self.token_shift
         # lnbwd_batch_finish: the fused forms leave their gain / bias partials in one buffer per LayerNorm and ONE batched launch
         # sums them at the end of the backward (per block under data parallelism, where the exchange takes a block's gradients
         # as soon as it is done)
@@ -457,6 +467,10 @@ class DalleEngine:
         self.hpre = per_layer(lambda: torch.empty(M, 4 * d, **b16)) if self.ffn_form == "gelu" else None
         self.stats = per_layer(lambda: [torch.empty(M, **f32) for _ in range(4)])  # mean1, rstd1, mean2, rstd2
         self.xnf = torch.empty(M, d, **b16)
+        # token shift: xn1[l] / xn2[l] hold the SHIFTED rows -- what the QKV product, FFN-1 and their weight gradients read.  The
+        # LayerNorm that produces them (standalone, fused into a product, or dmi_dropout_add_ln) writes into this one scratch buffer
+        # and dmi_token_shift follows; the backward brings dxn back through it (_ln_dgrad).  xnf is not shifted.
+        self.shift_tmp = torch.empty(M, d, **b16) if self.token_shift else None
         self.statf = [torch.empty(M, **f32) for _ in range(2)]
         self.z = torch.empty(M, Vp, **b16)      # eval: logits; train: E = exp(logit), patched into unnormalised dlogits
         self.loss_rows = torch.empty(M, **f32)
@@ -607,10 +621,22 @@ class DalleEngine:
     def _ln_after(self, l):
         """(gain, bias, y, mean, rstd) of the LayerNorm that reads X[l + 1]: norm_1 of block l + 1, to_logits' after the last"""
         if l + 1 < self.L:
-            q, y, (mean, rstd) = f"layer_{l + 1}/norm_1/", self.xn1[l + 1], self.stats[l + 1][:2]
+            q, y, (mean, rstd) = f"layer_{l + 1}/norm_1/", self._ln_y(self.xn1[l + 1]), self.stats[l + 1][:2]
         else:
             q, y, (mean, rstd) = "to_logits/layer_norm/", self.xnf, self.statf
         return self._w(q + "g"), self._w(q + "b"), y, mean, rstd
+
+    def _ln_y(self, xn):
+        """where a block LayerNorm writes its output for xn (an xn1[l] / xn2[l]): xn itself, or with token_shift the scratch
+        buffer that _shift_ln then shifts into xn"""
+        return self.shift_tmp if self.token_shift else xn
+
+    def _shift_ln(self, l, site):
+        """token_shift: xn1[l] (site 0) / xn2[l] (site 1) = shift of the LayerNorm output in the scratch buffer; inside _prefill
+        the launch also writes the sampler's history of (l, site).  Off: nothing."""
+        if self.token_shift:
+            hist = self._shift_hist_out[l][site] if self._shift_hist_out is not None else None
+            dh.token_shift(self.shift_tmp, (self.xn2 if site else self.xn1)[l], self.M, self.S, self.T, self.G, self.d, hist=hist)
 
     def _ln1_by_prev(self):
         """norm_1 of block l + 1 (and to_logits' norm) is written by block l's FFN-2: the fused product, or under residual dropout
@@ -622,6 +648,8 @@ class DalleEngine:
         if not (self._ln1_by_prev() and l > 0):
             g, b, y, mean, rstd = self._ln_after(l - 1)
             dh.layernorm_fwd(self.X[l], g, b, y, mean, rstd, self.M, self.d)
+            if l < self.L:
+                self._shift_ln(l, 0)
 
     def _join_branch(self, l, mlp):
         """a branch of block l joins the residual stream, and the LayerNorm that reads the sum: the out-projection (x1 = X[l] + ..,
@@ -637,7 +665,7 @@ class DalleEngine:
         else:
             A, K, W, bias = self.o[l], d, self.tview(p + "attn/o"), self._w(p + "attn/compute_output_bias/o_b")
             res, out, site = self.X[l], self.x1[l], site_attention(l)
-            ln = (self._w(p + "norm_2/g"), self._w(p + "norm_2/b"), self.xn2[l], st[2], st[3])
+            ln = (self._w(p + "norm_2/g"), self._w(p + "norm_2/b"), self._ln_y(self.xn2[l]), st[2], st[3])
         if self._drop_resid():
             dh.gemm_nt(A, K, W, K, self.drop_y, d, M, d, K, dh.GEMM_BIAS, bias=bias)
             dh.dropout_add_ln(self.drop_y, res, out, *(ln or (None,) * 5), M, d, *self.last_dropout[site])
@@ -649,6 +677,10 @@ class DalleEngine:
             if ln is not None:
                 g, b, y, mean, rstd = ln
                 dh.layernorm_fwd(out, g, b, y, mean, rstd, M, d)
+        if ln is not None and not mlp:
+            self._shift_ln(l, 1)
+        elif ln is not None and l + 1 < self.L:
+            self._shift_ln(l + 1, 0)
 
     # ---- FFN-1 and the FFN-2 input gradient, one arm of self.ffn_form each
     def _ffn1(self, l):
@@ -834,10 +866,21 @@ class DalleEngine:
     def _prefill(self, toks):
         """evaluation forward over toks that leaves every layer's q | k | v in the decode caches"""
         shared, self.qkv = self.qkv, self._kv_caches()      # (the same list unless recompute_grad shares one buffer)
+        self._shift_hist_out = self._shift_history()        # token_shift: the shift launches also write the history
         try:
             self.forward(toks, need_grad=False)
         finally:
             self.qkv = shared
+            self._shift_hist_out = None
+
+    def _shift_history(self):
+        """token_shift: hist[l][site], bf16 [B, S, d/2] -- columns [0, d/2) of the output of norm_1 (site 0) / norm_2 (site 1) of
+        block l at every position the sampler has passed, what later positions' shifts read.  The sampler's own, allocated once:
+        L * B * S * d * 2 bytes, a third of the key/value caches.  Off: None."""
+        if self.token_shift and self._shift_hist is None:
+            self._shift_hist = [[torch.empty(self.B, self.S, self.d // 2, dtype=torch.bfloat16, device=self.dev) for _ in range(2)]
+                                for _ in range(self.L)]
+        return self._shift_hist
 
     def _decode_state(self):
         if self._dec is None:
@@ -852,6 +895,8 @@ class DalleEngine:
                              logits=torch.empty(B, self.image_vocab_size, **f32),
                              params=torch.zeros(6, **i32), out=torch.zeros(B, self.S - self.T, **i32), logp=torch.zeros(B, **f32),
                              graphs={}, warm=set())
+            if self.token_shift:
+                self._dec["xs"] = torch.empty(B, d, **b16)       # the shifted row
         return self._dec
 
     def decode_step(self, tokens_at_pos: torch.Tensor, pos: int, graph: bool = True) -> torch.Tensor:
@@ -897,15 +942,23 @@ class DalleEngine:
         D[logits].  sample a Draw: draws the next token (settings in D[params]) into D[tok] and column pos - (T - 1) of D[out]
         (and D[logp], see _draw), then advances the position (inside the sampling kernel).
         B <= 32: LayerNorm rides in the prologue of the product that consumes it (dmi_ln_gemm_nt) -- 5 dependent launches per
-        block instead of 7; a dependent launch costs ~7 us on this part, more than any of these kernels' work."""
+        block instead of 7; a dependent launch costs ~7 us on this part, more than any of these kernels' work.
+        token_shift: the two block LayerNorms take the unfused route with dmi_token_shift_decode between LayerNorm and product; it
+        reads the neighbours' rows from the sampler's history and writes this position's (_shift_history)."""
         B, d, L, H, S = self.B, self.d, self.L, self.H, self.S
         D = self._dec
         x, x1, xn, o, h, st, z, fresh = D["x"][0], D["x"][1], D["xn"], D["o"], D["h"], D["st"], D["z"], D["fresh"]
         fuse_ln = B <= 32 and d <= 2048 and self.image_vocab_size % 16 == 0 and self.decode_fuse_ln
 
-        def ln_dense(inp, ln, W, out, N, flags=0, bias=None):       # out = LN(inp) . W^T (+ bias)(ReLU / GELU)
+        hist = self._shift_history()
+
+        def ln_dense(inp, ln, W, out, N, flags=0, bias=None, shift=None):       # out = LN(inp) . W^T (+ bias)(ReLU / GELU)
             g, b = self._w(ln + "/g"), self._w(ln + "/b")
-            if fuse_ln:
+            if hist is not None and shift is not None:   # token_shift, shift = (layer, site): the shift stands between LayerNorm and product
+                dh.layernorm_fwd(inp, g, b, xn, st[0], st[1], B, d)
+                dh.token_shift_decode(xn, hist[shift[0]][shift[1]], D["xs"], B, S, self.T, self.G, d, pos_dev=D["pos_i"])
+                dh.gemm_nt(D["xs"], d, W, d, out, N, B, N, d, flags, bias=bias)
+            elif fuse_ln:
                 dh.ln_gemm_nt(inp, d, g, b, W, d, out, N, B, N, d, flags, bias=bias)
             else:
                 dh.layernorm_fwd(inp, g, b, xn, st[0], st[1], B, d)
@@ -918,14 +971,14 @@ class DalleEngine:
         for l in range(L):
             p = f"layer_{l}/"
             cache = caches[l]                                          # [B*S, 3d]; row b*S + pos <- q | k | v of this step
-            ln_dense(x, p + "norm_1", self.tview(p + "attn/qkv"), fresh, 3 * d)
+            ln_dense(x, p + "norm_1", self.tview(p + "attn/qkv"), fresh, 3 * d, shift=(l, 0))
             if self.rope_cs is not None:                               # q | k of the step at table row pos, before they enter the cache
                 dh.rope_qk_decode(fresh, self.rope_cs, B, S, H, self.hd, pos_dev=D["pos_i"])
             self._attn_decode(l, cache, o, fresh, D["pos_i"])
             dh.gemm_nt(o, d, self.tview(p + "attn/o"), d, x1, d, B, d, d, dh.GEMM_BIAS | dh.GEMM_RESIDUAL,
                        bias=self._w(p + "attn/compute_output_bias/o_b"), residual=x)
             ln_dense(x1, p + "norm_2", self.tview(p + "mlp/mlp_linear_1/kernel"), h, 4 * d, dh.GEMM_BIAS | act,
-                     bias=self._w(p + "mlp/mlp_linear_1/bias"))
+                     bias=self._w(p + "mlp/mlp_linear_1/bias"), shift=(l, 1))
             dh.gemm_nt(h, 4 * d, self.tview(p + "mlp/mlp_linear_2/kernel"), 4 * d, x, d, B, d, 4 * d,
                        dh.GEMM_BIAS | dh.GEMM_RESIDUAL, bias=self._w(p + "mlp/mlp_linear_2/bias"), residual=x1)
         lo, nv = self.text_vocab_size, self.image_vocab_size
@@ -1003,7 +1056,8 @@ class DalleEngine:
         (FFN-1: A = self.dh; QKV: A = self.dqkv); the head's is already in self.dxn.  fuse_lnbwd: product and LayerNorm backward
         in one pass (dmi_gemm_nt_lnbwd), chained with d_o for norm_2 (_d_o_chained); otherwise the product into self.dxn and
         dmi_layernorm_bwd.  The gain / bias partials are summed right away, or under lnb_batch by the next _flush_ln() -- the
-        head's, which has no fused form, then joins the batch through a workspace of its own."""
+        head's, which has no fused form, then joins the batch through a workspace of its own.  token_shift (never fused): the
+        block LayerNorms' output gradient is the product shifted back, dmi_token_shift(inverse), from dxn into the scratch buffer."""
         M, d, L = self.M, self.d, self.L
         l, second = divmod(idx, 2)
         if idx == 2 * L:
@@ -1026,9 +1080,13 @@ class DalleEngine:
             dh.layernorm_bwd(self.dxn, x, g, mean, rstd, dres, dx, None, None, self.ln_ws_final, M, d)
             self._ln_pend.append((self.ln_ws_final, dg, db, M))
         else:
+            dy = self.dxn
             if A is not None:
                 dh.gemm_nt(A, K, W, K, self.dxn, d, M, d, K)
-            dh.layernorm_bwd(self.dxn, x, g, mean, rstd, dres, dx, dg, db, self.ws, M, d)
+                if self.token_shift:   # gradient w.r.t. the shifted rows -> w.r.t. the LayerNorm's output (the shift's transpose)
+                    dy = self.shift_tmp
+                    dh.token_shift(self.dxn, dy, M, self.S, self.T, self.G, d, inverse=True)
+            dh.layernorm_bwd(dy, x, g, mean, rstd, dres, dx, dg, db, self.ws, M, d)
 
     def _flush_ln(self):
         """sums the queued gain / bias partials, 16 LayerNorms per launch"""
@@ -1255,6 +1313,8 @@ class DalleEngine:
         sd = {"p": self.p.detach().cpu(), "global_step": self.global_step, "optimizer": self.optimizer, "activation_fn": self.activation}
         if self.rotary is not None:    # (a checkpoint without the key is a rotary-off model)
             sd["rotary_emb"], sd["rotary_base"] = self.rotary, self.rotary_base
+        if self.token_shift:           # (a checkpoint without the key is a model without token shift)
+            sd["token_shift"] = True
         for k in ("m", "v", "af_slots"):
             if getattr(self, k) is not None:
                 sd[k] = getattr(self, k).detach().cpu()
@@ -1277,6 +1337,10 @@ class DalleEngine:
             say = lambda r: "no rotary embeddings" if r[0] is None else f"rotary_emb {r[0]!r} (rotary_base {r[1]:g})"   # noqa: E731
             raise ValueError(f"checkpoint was written by a model with {say(rot)}; this run uses {say(mine)}: "
                              "the weights of one do not compute the other")
+        if bool(sd.get("token_shift", False)) != self.token_shift:
+            say = lambda on: "token_shift on" if on else "no token shift"   # noqa: E731
+            raise ValueError(f"checkpoint was written by a model with {say(bool(sd.get('token_shift', False)))}; this run uses "
+                             f"{say(self.token_shift)}: the weights of one do not compute the other")
         self.p.copy_(sd["p"])
         for k in ("m", "v", "af_slots"):
             if getattr(self, k) is not None:

@@ -15,6 +15,7 @@ from .loss_weights import resolve_loss_weights
 from .masks import layer_masks
 from .ops import get_variable_dtype
 from .rotary import resolve_rotary
+from .token_shift import resolve_token_shift
 
 
 def _causal(S):
@@ -65,6 +66,8 @@ class DALLE:
         resolve_dropout(params)
         # "rotary_emb" / "rotary_base" (dalle_mtf.rotary): likewise; "axial" needs a square image grid
         self.rotary_emb, self.rotary_base = resolve_rotary(params, image_seq_len)
+        # "token_shift" (dalle_mtf.token_shift): likewise; needs a square image grid and n_embd % 32 == 0
+        self.token_shift = resolve_token_shift(params, n_embd, image_seq_len)
         if self.params.get("attention_dropout"):
             raise NotImplementedError("attention_dropout > 0 is not supported: embed_dropout and residual_dropout are; dropout of "
                                       "the attention weights would live inside the attention kernels (all shipped configs use 0)")

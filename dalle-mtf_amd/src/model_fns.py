@@ -166,6 +166,10 @@ def _build(params, mode_str):
         # "rotary_emb" / "rotary_base" (dalle_mtf.rotary; they reach the engine's hparams through `params`)
         logging.getLogger("dalle_mtf_amd").info("%s rotary embeddings: %s, base %g (in addition to the learned positions)",
                                                 mode_str, eng.rotary, eng.rotary_base)
+    if eng.token_shift and rank == 0:
+        # "token_shift" (dalle_mtf.token_shift; it reaches the engine's hparams through `params`)
+        logging.getLogger("dalle_mtf_amd").info("%s token shift: on (behind norm_1 and norm_2 of every block, %d x %d image grid)",
+                                                mode_str, eng.G, eng.G)
     eng.hp["num_microbatches"] = nmb   # reference model_fns.py:141-154 (1 when tokens_per_mb_per_replica is unset)
     params["num_microbatches"] = nmb
     state["local_bs"] = local_bs

@@ -102,7 +102,34 @@ int dmi_rope_qk(uint16_t* qkv, int ld, const float* cs, int64_t rows, int S, int
 int dmi_rope_qk_decode(uint16_t* fresh, const float* cs, int B, int S, int H, int head_dim, int pos, const int* pos_dev,
                        void* stream);
 
-/* ---- K2  LayerNorm eps=1e-5 biased variance   models.py:373-389, layers.py:30-33 ---- */
+/* ---- Token shift (project extension, config key "token_shift"; DESIGN.md §4 "Token shift") ----
+ * A sequence has S = T + G * G positions: p < T is a caption position, p >= T is image token k = p - T of the G x G grid at row
+ * r = k / G, column c = k % G.  y = shift(x) over rows of d bf16 channels, d % 32 == 0:
+ *   channels       caption position p < T            image position p >= T
+ *   [0, d/4)       x[p - 1] if p >= 1 else 0         from above:    x[p - G] if r >= 1 else 0
+ *   [d/4, d/2)     x[p - 1] if p >= 1 else 0         from the left: x[p - 1] if c >= 1 else 0
+ *   [d/2, d)       x[p]                              x[p]
+ * Every read is from an earlier position of the same sequence; values are copied bit for bit, zeros are +0.  The transpose
+ * (dx from dy) is again a gather:
+ *   [0, d/4)       dy[q + 1] if q + 1 < T else 0     dy[q + G] if r + 1 < G else 0
+ *   [d/4, d/2)     dy[q + 1] if q + 1 < T else 0     dy[q + 1] if c + 1 < G else 0
+ *   [d/2, d)       dy[q]                             dy[q]
+ * dmi_token_shift: out of place over dense [rows, d] buffers, rows a multiple of S (row r is position r % S of sequence r / S);
+ * row offsets are 64-bit.  inverse != 0: the transpose.  hist != NULL (forward only): columns [0, d/2) of every input row are also
+ * copied to hist[rows, d/2] -- the history the decode step reads.
+ * dmi_token_shift_decode: the row of position pos of B sequences.  y[b] = the shift of x[b] ([B, d] each) with the neighbours'
+ * halves read from rows pos - 1 and pos - G of hist[B, S, d/2]; then hist[b, pos] <- x[b, :d/2].  pos_dev != NULL: the position is
+ * read from device memory (one int32; `pos` is then ignored and a position outside [0, S) makes the launch a no-op -- the
+ * dmi_attention_decode contract, so one captured graph serves every position).
+ * Both: stream-ordered, no allocation.  A null x, y (decode: hist), an empty shape, S != T + G * G, T < 1 or G < 1, rows % S != 0,
+ * d % 32 != 0, a buffer that is not 16-byte aligned, x and y overlapping, hist together with inverse, or a by-value pos outside
+ * [0, S): DMI_ERR_INVALID -- with a message, before any launch. */
+int dmi_token_shift(const uint16_t* x, uint16_t* y, uint16_t* hist, int64_t rows, int S, int T, int G, int d, int inverse,
+                    void* stream);
+int dmi_token_shift_decode(const uint16_t* x, uint16_t* hist, uint16_t* y, int B, int S, int T, int G, int d, int pos,
+                           const int* pos_dev, void* stream);
+
+/* ---- K2  LayerNorm eps=1e-5 biased variance  models.py:373-389, layers.py:30-33 ---- */
 int dmi_layernorm_fwd(const uint16_t* x, const uint16_t* g, const uint16_t* b, uint16_t* y,
                       float* mean, float* rstd, int64_t rows, int d, float eps, void* stream);
 /* dx_out = LNbwd(dy) (+ dres if non-null); dg/db fp32 [d] written (not accumulated).
