@@ -1,13 +1,6 @@
 """numpy restatement of the stateless dropout mask (include/dalle_hip.h "Dropout"; written from the definition, not from
-dalle_mtf.dropout) and the fp32 oracle of the DALL-E step with injected per-site masks: oracle.dalle_oracle's attention / mlp /
-layer_norm / to_logits / loss_fn composed exactly as its forward_hidden does, every site's tensor multiplied by its 0 / scale mask
-where the reference calls mtf.dropout (src/dalle_mtf/models.py:198-200, 215-217, 312-314, 322-323)."""
-from collections import OrderedDict
-
+dalle_mtf.dropout); engine_masks gives the per-site masks that the fp32 step oracle (tests/dalle_step_ref.py, dropout=) injects."""
 import numpy as np
-import torch
-
-from oracle import dalle_oracle as do
 
 U = np.uint64
 
@@ -65,46 +58,3 @@ def engine_masks(last_dropout, B, S, d, n_layers):
         shape = (S, d) if site == 1 else (B, S, d)
         out[site] = mask(*last_dropout[site], shape) if site in last_dropout else np.ones(shape, np.float32)
     return out
-
-
-def loss_and_grads(params_np, tokens, cfg, masks):
-    """fp32 loss and every parameter's gradient with the per-site masks of engine_masks (None: no dropout)"""
-    P = OrderedDict((n, torch.tensor(a, dtype=torch.float32, requires_grad=True)) for n, a in params_np.items())
-    tok = torch.as_tensor(np.asarray(tokens), dtype=torch.int64)
-    B, S = tok.shape
-    one = torch.ones(())
-    m = (lambda site: one) if masks is None else (lambda site: torch.from_numpy(masks[site]))
-    x = P["embedding/wte"][tok] * m(0) + P["positional_embedding/wpe"][:S] * m(1)
-    causal = do.attn_mask(S)
-    for i in range(cfg.n_layers):
-        p = f"layer_{i}/"
-        h = do.layer_norm(x, P[p + "norm_1/g"], P[p + "norm_1/b"])
-        x = x + m(2 + 2 * i) * do.attention(h, P[p + "attn/q"], P[p + "attn/k"], P[p + "attn/v"], P[p + "attn/o"],
-                                            P[p + "attn/compute_output_bias/o_b"], cfg.n_heads, causal)
-        h = do.layer_norm(x, P[p + "norm_2/g"], P[p + "norm_2/b"])
-        x = x + m(3 + 2 * i) * do.mlp(h, P[p + "mlp/mlp_linear_1/kernel"], P[p + "mlp/mlp_linear_1/bias"],
-                                      P[p + "mlp/mlp_linear_2/kernel"], P[p + "mlp/mlp_linear_2/bias"])
-    logits = do.to_logits(P, x)
-    labels = torch.as_tensor(do.shift_labels(np.asarray(tokens), cfg.eos_token_id), dtype=torch.int64)
-    loss, _ = do.loss_fn(logits, labels)
-    loss.backward()
-    grads = OrderedDict((n, p.grad.detach().numpy().copy() if p.grad is not None else np.zeros(tuple(p.shape), np.float32))
-                        for n, p in P.items())
-    return float(loss.detach()), grads
-
-
-# ---- the engine-step setup shared by tests/test_dropout.py (CPU: the masks matter here) and tests/test_dropout_gpu.py: the small
-# model of tests/test_attn_mask_engine_gpu.py at both widths (n_embd 512 is where the fused LayerNorm products would otherwise run)
-T, P, TV, IV, NL, BATCH, RATE = 16, 256, 300, 64, 3, 2, 0.25
-WIDTHS = [(256, 2), (512, 4)]
-
-
-def step_setup(n_embd, n_heads, seed=0):
-    cfg = do.DalleConfig(n_embd, TV, IV, T, P, NL, n_heads)
-    P0 = do.init_params(cfg, seed=1234 + seed, perturb=0.05)
-    tokens = do.assemble_tokens(do.synthetic_captions(BATCH, T, TV, seed=seed + 1), do.synthetic_image_tokens(BATCH, P, IV, seed=seed + 2), TV)
-    return cfg, P0, tokens
-
-
-def rel_l2(a, b):
-    return float(np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-30))

@@ -1,6 +1,5 @@
 """float64 restatement of mtf.gelu, the tanh form [MTF-RECALL: recalled from mesh-tensorflow 0.1.18, not checked against its
-source], its derivative, and the oracle's MLP with it (oracle/dalle_oracle.py mlp with the activation swapped; the tests install it
-with monkeypatch.setattr(dalle_oracle, "mlp", gelu_mlp), which forward_hidden looks up when it runs).
+source], and its derivative; the fp32 step oracle (tests/dalle_step_ref.py, activation="gelu") puts it in the feed-forward.
   gelu(x)  = 0.5 x (1 + tanh(u)),  u = sqrt(2/pi) (x + 0.044715 x^3)
   gelu'(x) = 0.5 (1 + tanh(u)) + 0.5 x (1 - tanh(u)^2) u',  u' = sqrt(2/pi) (1 + 3 * 0.044715 x^2)"""
 import math
@@ -22,10 +21,3 @@ def gelu_grad(x):
     tanh = torch.tanh if isinstance(x, torch.Tensor) else np.tanh
     t = tanh(K0 * (x + C3 * x ** 3))
     return 0.5 * (1.0 + t) + 0.5 * x * (1.0 - t * t) * K0 * (1.0 + 3.0 * C3 * x * x)
-
-
-def gelu_mlp(x, w1, b1, w2, b2, bf16=False, force=None, site=""):
-    """oracle/dalle_oracle.py mlp with activation_fn = gelu (src/dalle_mtf/models.py:317-324): gelu(x@W1+b1)@W2+b2"""
-    from oracle import dalle_oracle as do
-    h = do._force(force, site + "h", do._rb(gelu(x @ w1 + b1), bf16))
-    return do._rb(h @ w2 + b2, bf16)

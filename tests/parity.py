@@ -48,9 +48,11 @@ def engine_sites(eng):
 
 
 def compare_step(n_embd=256, n_heads=2, n_layers=2, text_vocab=300, image_vocab=64, T=16, P=112, B=2, seed=0,
-                 steps=2, verbose=True, hp=None, perturb=0.05, bf16_oracle=True, per_tensor=False, bf16_grad_oracle=False):
+                 steps=2, verbose=True, hp=None, perturb=0.05, bf16_oracle=True, per_tensor=False, bf16_grad_oracle=False, ref_kw=None):
     """bf16_grad_oracle: also compare against the bf16 oracle with fp32 weight gradients and against the TEACHER-FORCED bf16
-    oracle (oracle/dalle_oracle.py _force: forward = the engine's stored activations, backward = the oracle's)"""
+    oracle (oracle/dalle_oracle.py _force: forward = the engine's stored activations, backward = the oracle's).
+    ref_kw: keywords of tests/dalle_step_ref.py loss_and_grads (e.g. dict(activation="gelu")); the fp32 oracle is then that one, and
+    the bf16 oracles, which know no such option, are left out"""
     from oracle import dalle_oracle as do
     from src.dalle_mtf.engine import DalleEngine
     cfg = do.DalleConfig(n_embd, text_vocab, image_vocab, T, P, n_layers, n_heads)
@@ -68,7 +70,11 @@ def compare_step(n_embd=256, n_heads=2, n_layers=2, text_vocab=300, image_vocab=
     v = {k: np.zeros_like(v) for k, v in P0.items()}
     report = {"config": dict(n_embd=n_embd, n_heads=n_heads, n_layers=n_layers, V=cfg.total_tokens, S=T + P, B=B), "steps": []}
     for step in range(steps):
-        loss_o32, g32 = do.loss_and_grads(Po, tokens, cfg, bf16=False)
+        if ref_kw:
+            import dalle_step_ref
+            loss_o32, g32 = dalle_step_ref.loss_and_grads(Po, tokens, cfg, **ref_kw)
+        else:
+            loss_o32, g32 = do.loss_and_grads(Po, tokens, cfg, bf16=False)
         loss_h = float(eng.forward(tok_d, need_grad=True).item())
         eng.backward()
         eng.wait_grads()
@@ -77,14 +83,14 @@ def compare_step(n_embd=256, n_heads=2, n_layers=2, text_vocab=300, image_vocab=
         worst32 = max(((e, k) for k, e in table32.items()), key=lambda t: t[0])
         rec = dict(step=step, loss_hip=loss_h, loss_oracle_fp32=loss_o32, worst_grad_rel_l2_vs_fp32_oracle=worst32,
                    head_fixup_flag=int(eng.head_flag.item()))
-        if bf16_oracle:
+        if bf16_oracle and not ref_kw:
             loss_o16, g16 = do.loss_and_grads(Po, tokens, cfg, bf16=True)
             rec["loss_oracle_bf16"] = loss_o16
             table16 = {k: rel_l2(gh[k], g16[k]) for k in g16}
             rec["worst_grad_rel_l2_vs_bf16_oracle"] = max(((e, k) for k, e in table16.items()), key=lambda t: t[0])
             if per_tensor:
                 rec["grad_rel_l2_vs_bf16_oracle"] = table16
-        if bf16_grad_oracle:
+        if bf16_grad_oracle and not ref_kw:
             # (a) free-running bf16 oracle whose weight gradients stay fp32 (the engine accumulates them in fp32);
             # (b), (c) TEACHER-FORCED: the oracle's forward takes the activations the engine stored for its own backward, so the
             # forward divergence of two bf16 implementations (rounding-boundary / ReLU-mask flips from different fp32

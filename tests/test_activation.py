@@ -1,6 +1,6 @@
 """GELU feed-forward on the CPU (DALLE activation_fn, DESIGN.md §4 "GELU"): the name resolution of DALLE(activation_fn=...) and the
 config key, the float64 restatement tests/gelu_ref.py against torch, the reference's own DALLE with a GELU activation_fn
-(tests/golden/ref_callsite_gelu.npz) against the oracle with its MLP swapped for the GELU one, and the argument checks of the two
+(tests/golden/ref_callsite_gelu.npz) against the fp32 step oracle with activation="gelu", and the argument checks of the two
 new C entry points."""
 import ctypes
 import json
@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(ROOT, "dalle-mtf_amd"))
-from gelu_ref import gelu, gelu_grad, gelu_mlp  # noqa: E402
+from gelu_ref import gelu, gelu_grad  # noqa: E402
 from src.dalle_mtf.activations import ACTIVATIONS, check_activation, resolve_activation  # noqa: E402
 
 GOLDEN = os.path.join(HERE, "golden", "ref_callsite_gelu.npz")
@@ -104,9 +104,10 @@ def test_fixture_is_small():
     assert os.path.getsize(GOLDEN) < 400 * 1024
 
 
-def test_reference_gelu_dalle_matches_the_gelu_oracle(monkeypatch):
+def test_reference_gelu_dalle_matches_the_gelu_oracle():
     """the reference's DALLE(activation_fn=<gelu>) over the shims, one step of a small model (tests/golden/make_gelu_golden.py),
-    against the oracle with its module-level mlp swapped for gelu_mlp: loss and every gradient (float32 on both sides)"""
+    against the fp32 step oracle (tests/dalle_step_ref.py) with activation="gelu": loss and every gradient (float32 on both sides)"""
+    import dalle_step_ref as sref
     from oracle import dalle_oracle as do
     blob, case = _fixture()
     cfg = do.DalleConfig(*[case[k] for k in ("n_embd", "text_vocab_size", "image_vocab_size", "text_seq_len", "image_seq_len",
@@ -114,8 +115,7 @@ def test_reference_gelu_dalle_matches_the_gelu_oracle(monkeypatch):
     P0 = do.init_params(cfg, seed=case["seed"], perturb=case["perturb"])
     tokens = blob["tokens"]
     _, grads_relu = do.loss_and_grads(P0, tokens, cfg)
-    monkeypatch.setattr(do, "mlp", gelu_mlp)
-    loss, grads = do.loss_and_grads(P0, tokens, cfg)
+    loss, grads = sref.loss_and_grads(P0, tokens, cfg, activation="gelu")
     ref_loss = float(blob["loss"])
     assert abs(loss - ref_loss) <= 2e-6 * abs(ref_loss), (loss, ref_loss)
     k1 = "layer_0/mlp/mlp_linear_1/kernel"      # the fixture tells GELU from ReLU

@@ -14,7 +14,7 @@ import torch
 import dalle_hip as dh  # noqa: E402  (path set up by conftest)
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gelu_ref import gelu, gelu_grad, gelu_mlp  # noqa: E402
+from gelu_ref import gelu, gelu_grad  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -149,31 +149,26 @@ def test_ln_gemm_nt_gelu_vs_layernorm_dense_gelu(M, N, K):
 
 
 # ------------------------------------------------------------------ the engine
-def _gelu_oracle(monkeypatch):
-    from oracle import dalle_oracle as do
-    monkeypatch.setattr(do, "mlp", gelu_mlp)
-
-
 @pytest.mark.parametrize("n_embd,n_heads,P,recompute", [(256, 2, 112, False), (256, 2, 112, True), (128, 2, 256, False), (256, 4, 256, True)])
-def test_engine_gelu_step_vs_gelu_oracle(monkeypatch, n_embd, n_heads, P, recompute):
-    """the compare_step pattern with the oracle's MLP swapped for the GELU one; the bounds of the ReLU tests of the same shapes
+def test_engine_gelu_step_vs_gelu_oracle(n_embd, n_heads, P, recompute):
+    """the compare_step pattern against the fp32 step oracle with activation="gelu"; the bounds of the ReLU tests of the same shapes
     (check_report's defaults: tests/parity.py smoke_step at head dim 128, test_engine_step_head_dim64_vs_oracle at 64)"""
+    from engine_case import HP
     from parity import check_report, compare_step
-    _gelu_oracle(monkeypatch)
-    hp = dict(lr=1e-3, train_steps=1000, warmup_steps=2, gradient_clipping=1.0, activation_fn="gelu", recompute_grad=recompute)
-    rep = compare_step(n_embd=n_embd, n_heads=n_heads, T=16, P=P, hp=hp)
+    hp = dict(HP, activation_fn="gelu", recompute_grad=recompute)
+    rep = compare_step(n_embd=n_embd, n_heads=n_heads, T=16, P=P, hp=hp, ref_kw=dict(activation="gelu"))
     check_report(rep)
 
 
-def test_gelu_oracle_differs_from_relu_oracle(monkeypatch):
-    """the swap is in effect: the GELU oracle's loss is not the ReLU oracle's (so the parity test above pins the activation)"""
+def test_gelu_oracle_differs_from_relu_oracle():
+    """the switch is in effect: the GELU oracle's loss is not the ReLU oracle's (so the parity test above pins the activation)"""
+    import dalle_step_ref as sref
     from oracle import dalle_oracle as do
     cfg = do.DalleConfig(128, 60, 64, 16, 112, 1, 1)
     P0 = do.init_params(cfg, seed=3, perturb=0.05)
     tokens = do.assemble_tokens(do.synthetic_captions(2, 16, 60, seed=1), do.synthetic_image_tokens(2, 112, 64, seed=2), 60)
     lr, _ = do.loss_and_grads(P0, tokens, cfg)
-    _gelu_oracle(monkeypatch)
-    lg, _ = do.loss_and_grads(P0, tokens, cfg)
+    lg, _ = sref.loss_and_grads(P0, tokens, cfg, activation="gelu")
     assert abs(lr - lg) > 1e-4 * abs(lr), (lr, lg)
 
 

@@ -1,66 +1,44 @@
 """Custom attention masks through the engine and DALLE on the GPU: the train step against a masked fp32 oracle, causal vs
 absent config key, recompute_grad, decode against the full forward, and the samplers."""
-import numpy as np
 import pytest
 import torch
 
+from engine_case import IV, P, PATTERNS, T, TV, build, step
+from parity import rel_l2
+
 pytestmark = pytest.mark.gpu
 
-T, P, TV, IV = 16, 256, 300, 64
-PATTERNS = ["row", "column", "conv:3"]
 
-
-def _setup(n_embd=256, n_heads=2, n_layers=3, B=2, seed=0, patterns=PATTERNS, hp=None):
-    from oracle import dalle_oracle as do
-    from src.dalle_mtf.models import DALLE
-    cfg = do.DalleConfig(n_embd, TV, IV, T, P, n_layers, n_heads)
-    params = dict(hp or dict(lr=1e-3, train_steps=1000, warmup_steps=2, gradient_clipping=1.0))
-    if patterns is not None:
-        params["attention_pattern"] = patterns
-    model = DALLE(n_embd=n_embd, text_vocab_size=TV, image_vocab_size=IV, text_seq_len=T, image_seq_len=P, n_layers=n_layers,
-                  n_heads=n_heads, batch_size=B, params=params)
-    P0 = do.init_params(cfg, seed=1234 + seed, perturb=0.05)
-    model.engine.load_reference_params(P0)
-    tokens = do.assemble_tokens(do.synthetic_captions(B, T, TV, seed=seed + 1), do.synthetic_image_tokens(B, P, IV, seed=seed + 2), TV)
-    return cfg, model, P0, tokens
-
-
-def _rel_l2(a, b):
-    return float(np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-30))
+def _setup(patterns=PATTERNS, **hp):
+    return build(hparams=dict(hp, attention_pattern=patterns))
 
 
 def test_engine_step_with_per_layer_masks_vs_masked_fp32_oracle():
-    import masked_attention_ref as mref
+    import dalle_step_ref as sref
     from src.dalle_mtf.masks import layer_masks
     cfg, model, P0, tokens = _setup()
     eng = model.engine
     assert all(p is not None for p in eng.attn_plan)
-    loss = float(eng.forward(torch.from_numpy(tokens).cuda(), need_grad=True).item())
-    eng.backward(allreduce=False)
-    torch.cuda.synchronize()
+    loss = float(step(eng, tokens)[0].item())
     gh = eng.export_reference(eng.g)
-    masks = layer_masks(PATTERNS, cfg.n_layers, T, P)
-    loss_o, _, go = mref.loss_and_grads(P0, tokens, cfg, masks)
+    loss_o, go = sref.loss_and_grads(P0, tokens, cfg, masks=layer_masks(PATTERNS, cfg.n_layers, T, P))
     assert abs(loss - loss_o) <= 5e-4 * abs(loss_o), (loss, loss_o)
-    worst = max((_rel_l2(gh[k], go[k]), k) for k in go)
+    worst = max((rel_l2(gh[k], go[k]), k) for k in go)
     print("masked engine vs masked fp32 oracle: loss", loss, loss_o, "worst grad", worst, flush=True)
     assert worst[0] <= 4.8e-2, worst   # the causal step's bound (tests/parity.py check_report)
     # the masks matter: the causal oracle is far from the engine
     import oracle.dalle_oracle as do
     loss_c, gc = do.loss_and_grads(P0, tokens, cfg)
-    assert max(_rel_l2(gh[k], gc[k]) for k in gc) > 0.2
+    assert max(rel_l2(gh[k], gc[k]) for k in gc) > 0.2
 
 
 def test_causal_pattern_and_absent_key_are_bit_identical():
     out = []
-    for patterns in ("causal", None, ["causal"] * 3):
-        _, model, _, tokens = _setup(patterns=patterns)
+    for patterns in ("causal", "absent", ["causal"] * 3):
+        _, model, _, tokens = _setup(patterns)
         eng = model.engine
         assert all(p is None for p in eng.attn_plan)
-        loss = eng.forward(torch.from_numpy(tokens).cuda(), need_grad=True).clone()
-        eng.backward(allreduce=False)
-        torch.cuda.synchronize()
-        out.append((loss, eng.g.clone()))
+        out.append(step(eng, tokens))
         del model, eng
         torch.cuda.empty_cache()
     for loss, g in out[1:]:
@@ -70,13 +48,9 @@ def test_causal_pattern_and_absent_key_are_bit_identical():
 def test_recompute_grad_with_masks_equals_stored_activations():
     res = []
     for rc in (False, True):
-        _, model, _, tokens = _setup(hp=dict(lr=1e-3, train_steps=1000, warmup_steps=2, gradient_clipping=1.0, recompute_grad=rc))
-        eng = model.engine
-        loss = eng.forward(torch.from_numpy(tokens).cuda(), need_grad=True).clone()
-        eng.backward(allreduce=False)
-        torch.cuda.synchronize()
-        res.append((loss, eng.g.clone()))
-        del model, eng
+        _, model, _, tokens = _setup(recompute_grad=rc)
+        res.append(step(model.engine, tokens))
+        del model
         torch.cuda.empty_cache()
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
 
@@ -84,7 +58,7 @@ def test_recompute_grad_with_masks_equals_stored_activations():
 def test_masked_decode_logits_and_samplers():
     """decode logits equal full-forward logits at every image position (the decode tolerance of test_model_fns_gpu.py); the
     graph-replayed and host-launched samplers give the same tokens; greedy cached tokens equal the plain sampler's up to near-ties"""
-    _, model, _, tokens = _setup(n_embd=256, n_heads=2)
+    _, model, _, tokens = _setup()
     eng = model.engine
     tok = torch.from_numpy(tokens).cuda()
     eng.forward(tok, need_grad=False)

@@ -221,3 +221,43 @@ def test_block_weight_gradient_launch_shapes_match_oracle(case, monkeypatch):
     else:
         assert groups == [2] * L and len(singles) == 2 * L + 1
     check_report(report, **(WGRAD_SHAPE_BOUNDS[bounds] if bounds else {}))
+
+
+def test_every_option_together_vs_the_fp32_step_oracle():
+    """The shared case (tests/engine_case.py) with every option of the step on at once: the row / column / conv:3 patterns, the axial
+    rotary table, token shift, embedding and residual dropout at 0.25, GELU and loss weights 1 / 7 -- against the one fp32 oracle
+    (tests/dalle_step_ref.py) with the engine's own dropout masks (engine.last_dropout) injected.  Bounds: the first-step bounds of
+    every single-option engine test (tests/parity.py check_report): loss 5e-4 relative, worst gradient tensor 4.8e-2 relative L2.
+    recompute_grad on gives the same bits as the default.  The per-tensor table is written out
+    (profiles/step_ref_combined.json)."""
+    import dalle_step_ref as sref
+    import dropout_ref as dref
+    from engine_case import BATCH, NL, P, PATTERNS, T, build, step
+    from parity import rel_l2, save_report
+    from src.dalle_mtf.masks import layer_masks
+    from src.dalle_mtf.rotary import rotary_table
+    on = dict(attention_pattern=PATTERNS, rotary_emb="axial", token_shift=True, embed_dropout=0.25, residual_dropout=0.25,
+              activation_fn="gelu", text_loss_weight=1, image_loss_weight=7)
+    runs = []
+    for rc in ("absent", True):
+        cfg, model, P0, tokens = build(hparams=dict(on, recompute_grad=rc))
+        eng = model.engine
+        assert eng.recompute == (rc is True) and eng.token_shift is True and eng.rotary == "axial" and eng.activation == "gelu"
+        assert all(p is not None for p in eng.attn_plan) and eng.loss_weights == (1.0, 7.0)
+        runs.append(step(eng, tokens) + (eng.export_reference(eng.g), dict(eng.last_dropout)))
+        del model, eng
+        torch.cuda.empty_cache()
+    (loss, g, gh, last), (loss_rc, g_rc, _, last_rc) = runs
+    assert torch.equal(loss, loss_rc) and torch.equal(g, g_rc) and last == last_rc
+    assert sorted(last) == list(range(2 + 2 * NL))
+    loss = float(loss.item())
+    loss_o, go = sref.loss_and_grads(P0, tokens, cfg, masks=layer_masks(PATTERNS, NL, T, P), table=rotary_table("axial", T, P, cfg.kv_dim),
+                                     token_shift=True, dropout=dref.engine_masks(last, BATCH, T + P, cfg.n_embd, NL),
+                                     activation="gelu", loss_weights=(1.0, 7.0))
+    table = {k: rel_l2(gh[k], go[k]) for k in go}
+    worst = max((e, k) for k, e in table.items())
+    save_report("step_ref_combined.json", dict(options=on, loss_hip=loss, loss_oracle_fp32=loss_o, loss_rel_err=abs(loss - loss_o) / abs(loss_o),
+                                               worst_grad_rel_l2=worst, grad_rel_l2=table))
+    print(f"every option on: loss {loss} oracle {loss_o} rel {abs(loss - loss_o) / abs(loss_o):.3g} worst grad {worst}", flush=True)
+    assert abs(loss - loss_o) <= 5e-4 * abs(loss_o), (loss, loss_o)
+    assert worst[0] <= 4.8e-2, worst

@@ -15,9 +15,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dalle-mtf_amd"))
 
 import dalle_hip as dh  # noqa: E402
+import dalle_step_ref as sref  # noqa: E402
 import dropout_ref as dref  # noqa: E402
-from dropout_ref import BATCH, NL, P, RATE, T, WIDTHS, rel_l2, step_setup  # noqa: E402
+from engine_case import BATCH, NL, P, T, inputs  # noqa: E402
+from parity import rel_l2  # noqa: E402
 from src.dalle_mtf import dropout as dr  # noqa: E402
+
+# the engine-step tests here (the masks matter) and in tests/test_dropout_gpu.py: the shared case at both widths (n_embd 512 is where the
+# fused LayerNorm products would otherwise run)
+RATE = 0.25
+WIDTHS = [(256, 2), (512, 4)]
 
 SYMBOLS = {"dmi_dropout_add_ln": 14, "dmi_dropout_bwd": 7, "dmi_embed_fwd_dropout": 12, "dmi_embed_bwd_dropout": 14}
 A, B, C, D = 0x10000, 0x20000, 0x30000, 0x40000     # fake device pointers: every refusal comes before a launch, none is dereferenced
@@ -162,12 +169,12 @@ def test_keys_are_pairwise_distinct():
 def test_masked_oracle_is_far_from_the_plain_one(n_embd, n_heads):
     """fp32 only: at rate 0.25, dropout_seed 0, step 0 the masks move some gradient tensor by more than 0.2 relative L2 -- what the
     GPU test then asserts of the engine"""
-    cfg, P0, tokens = step_setup(n_embd, n_heads)
+    cfg, P0, tokens = inputs(n_embd, n_heads)
     t = dref.threshold(RATE)
     last = {site: (dref.site_key(0, 0, 0, 0, site), t) for site in range(2 + 2 * NL)}
     masks = dref.engine_masks(last, BATCH, T + P, n_embd, NL)
-    loss_m, gm = dref.loss_and_grads(P0, tokens, cfg, masks)
-    loss_p, gp = dref.loss_and_grads(P0, tokens, cfg, None)
+    loss_m, gm = sref.loss_and_grads(P0, tokens, cfg, dropout=masks)
+    loss_p, gp = sref.loss_and_grads(P0, tokens, cfg)
     from oracle import dalle_oracle as do
     loss_o, go = do.loss_and_grads(P0, tokens, cfg)
     assert abs(loss_p - loss_o) <= 1e-6 * abs(loss_o) and max(rel_l2(gp[k], go[k]) for k in go) < 1e-5     # the composition is the oracle's

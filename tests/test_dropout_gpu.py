@@ -1,5 +1,5 @@
 """Embedding / residual dropout on the GPU: the four dropout entry points bit for bit against the numpy restatement of the mask
-(tests/dropout_ref.py), the engine's train step against the fp32 oracle with the same masks injected, and what the engine promises
+(tests/dropout_ref.py), the engine's train step against the fp32 oracle with the same masks injected (tests/dalle_step_ref.py), and what the engine promises
 around it: keys off = the parent's bits, recompute_grad, microbatches, steps, evaluation / sampling untouched, resume."""
 import numpy as np
 import pytest
@@ -9,7 +9,9 @@ pytestmark = pytest.mark.gpu
 
 import dalle_hip as dh  # noqa: E402  (path set up by conftest)
 import dropout_ref as dref  # noqa: E402
-from dropout_ref import BATCH, IV, NL, P, RATE, T, TV, WIDTHS, rel_l2, step_setup  # noqa: E402
+from engine_case import BATCH, NL, P, T, build, step  # noqa: E402
+from parity import rel_l2  # noqa: E402
+from test_dropout import RATE, WIDTHS  # noqa: E402
 
 DEV = "cuda"
 KEY = 0x0123456789ABCDEF
@@ -152,39 +154,25 @@ def test_embed_bwd_dropout(rate):
 
 
 # ------------------------------------------------------------------ engine
-HP = dict(lr=1e-3, train_steps=1000, warmup_steps=2, gradient_clipping=1.0)
-
-
 def _model(n_embd=256, n_heads=2, B=BATCH, **extra):
-    from src.dalle_mtf.models import DALLE
-    cfg, P0, tokens = step_setup(n_embd, n_heads)
-    model = DALLE(n_embd=n_embd, text_vocab_size=TV, image_vocab_size=IV, text_seq_len=T, image_seq_len=P, n_layers=NL, n_heads=n_heads,
-                  batch_size=B, params=dict(HP, **extra))
-    model.engine.load_reference_params(P0)
-    return cfg, model, P0, tokens
-
-
-def _fwd_bwd(eng, tokens):
-    loss = eng.forward(torch.from_numpy(tokens).cuda(), need_grad=True).clone()
-    eng.backward(allreduce=False)
-    torch.cuda.synchronize()
-    return loss, eng.g.clone()
+    return build(n_embd, n_heads, batch=B, hparams=extra)
 
 
 @pytest.mark.parametrize("n_embd,n_heads", WIDTHS)
 def test_engine_step_vs_masked_fp32_oracle(n_embd, n_heads):
     """loss within 5e-4 relative, worst per-tensor gradient relative L2 <= 4.8e-2 (tests/parity.py check_report) against the fp32
     oracle with the engine's own masks (engine.last_dropout) injected; and the engine is far from the plain oracle"""
+    import dalle_step_ref as sref
     from oracle import dalle_oracle as do
     cfg, model, P0, tokens = _model(n_embd, n_heads, embed_dropout=RATE, residual_dropout=RATE)
     eng = model.engine
-    loss, _ = _fwd_bwd(eng, tokens)
+    loss, _ = step(eng, tokens)
     loss = float(loss.item())
     gh = eng.export_reference(eng.g)
     t = dref.threshold(RATE)
     assert eng.last_dropout == {site: (dref.site_key(0, 0, 0, 0, site), t) for site in range(2 + 2 * NL)}
     masks = dref.engine_masks(eng.last_dropout, BATCH, T + P, n_embd, NL)
-    loss_o, go = dref.loss_and_grads(P0, tokens, cfg, masks)
+    loss_o, go = sref.loss_and_grads(P0, tokens, cfg, dropout=masks)
     worst = max((rel_l2(gh[k], go[k]), k) for k in go)
     _, gp = do.loss_and_grads(P0, tokens, cfg)
     far = max(rel_l2(gh[k], gp[k]) for k in gp)
@@ -200,7 +188,7 @@ def test_keys_zero_or_absent_are_bit_identical():
     for extra in ({}, dict(embed_dropout=0, residual_dropout=0.0, dropout_seed=5), dict(embed_dropout=None, residual_dropout=None)):
         _, model, _, tokens = _model(512, 4, **extra)
         assert model.engine.dyd is None
-        out.append(_fwd_bwd(model.engine, tokens))
+        out.append(step(model.engine, tokens))
         assert model.engine.last_dropout == {}
         del model
         torch.cuda.empty_cache()
@@ -213,7 +201,7 @@ def test_recompute_grad_with_dropout_equals_stored_activations(n_embd, n_heads):
     res = []
     for rc in (False, True):
         _, model, _, tokens = _model(n_embd, n_heads, embed_dropout=RATE, residual_dropout=RATE, recompute_grad=rc)
-        res.append(_fwd_bwd(model.engine, tokens))
+        res.append(step(model.engine, tokens))
         del model
         torch.cuda.empty_cache()
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])

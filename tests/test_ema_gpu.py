@@ -6,11 +6,11 @@ import pytest
 import torch
 
 import ema_ref
+from engine_case import P, T, build, inputs
 
 pytestmark = pytest.mark.gpu
 
-T, P, TV, IV = 16, 256, 300, 64          # the constants of tests/test_attn_mask_engine_gpu.py
-D, H, L = 128, 2, 2
+D, H, L = 128, 2, 2                      # the shared case (tests/engine_case.py) at this width and depth
 PAD = 16                                 # sentinel elements behind n
 SIZES = [1, 5, 128, 2051, 2 ** 20 + 8]
 OMDS = [0.0, 1.0, 1e-3, float(np.float32(0.9))]
@@ -94,22 +94,13 @@ def test_kernel_against_the_numpy_restatement(n):
 
 
 # ------------------------------------------------------------------------------------------------ engine
-def _engine(B=2, **hp):
-    from oracle import dalle_oracle as do
-    from src.dalle_mtf.models import DALLE
-    cfg = do.DalleConfig(D, TV, IV, T, P, L, H)
-    params = dict(dict(lr=1e-2, train_steps=1000, warmup_steps=0, gradient_clipping=1.0), **hp)
-    model = DALLE(n_embd=D, text_vocab_size=TV, image_vocab_size=IV, text_seq_len=T, image_seq_len=P, n_layers=L, n_heads=H,
-                  batch_size=B, params=params)
-    model.engine.load_reference_params(do.init_params(cfg, seed=1234, perturb=0.05))
-    return model.engine
+def _engine(**hp):
+    return build(D, H, L, hparams=dict(lr=1e-2, warmup_steps=0, **hp))[1].engine
 
 
 @pytest.fixture(scope="module")
 def batches():
-    from oracle import dalle_oracle as do
-    return [torch.from_numpy(do.assemble_tokens(do.synthetic_captions(2, T, TV, seed=s + 1), do.synthetic_image_tokens(2, P, IV, seed=s + 2),
-                                                TV)).cuda() for s in range(4)]
+    return [torch.from_numpy(inputs(D, H, L, seed=s)[2]).cuda() for s in range(4)]
 
 
 def _train(eng, batches, steps, start=0):

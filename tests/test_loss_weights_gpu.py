@@ -1,11 +1,10 @@
 """Text/image loss weights on a real MI355X (DESIGN.md §4 "Loss weights"): dmi_softmax_finish_w against dmi_softmax_finish on the
 same inputs (the weight reaches rowscale, rowscale_bf16 and Xs and nothing else, in the exact fix-up path too), dmi_loss_reduce
 against float64, and the engine / dalle_model_fn with the config keys "text_loss_weight" / "image_loss_weight" against the fp32
-oracle with the weighted loss of tests/loss_weights_ref.py applied to its loss_batch."""
+oracle (tests/dalle_step_ref.py) with the weighted loss of tests/loss_weights_ref.py applied to its loss_batch."""
 import math
 import os
 import sys
-from collections import OrderedDict
 
 import numpy as np
 import pytest
@@ -17,6 +16,8 @@ pytestmark = pytest.mark.gpu
 import dalle_hip as dh  # noqa: E402  (path set up by conftest)
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dalle_step_ref as sref  # noqa: E402
+from engine_case import HP, inputs  # noqa: E402
 from loss_weights_ref import loss_reduce_ref, weighted_loss_ref  # noqa: E402
 from parity import rel_l2, save_report  # noqa: E402
 
@@ -183,7 +184,6 @@ def test_loss_reduce_against_float64(n, period, split):
 
 # ------------------------------------------------------------------ engine
 CFG = dict(n_embd=256, n_heads=2, n_layers=2, text_vocab=300, image_vocab=64, T=16, P=112, B=2)   # tests/parity.py::compare_step
-HP = dict(lr=1e-3, train_steps=1000, warmup_steps=2, gradient_clipping=1.0)
 
 
 def _engine(B=CFG["B"], **hp):
@@ -209,25 +209,18 @@ def _step(eng, tok):
 @pytest.fixture(scope="module")
 def case():
     """weights, tokens, the fp32 oracle's loss_batch (with autograd) and the unweighted engine's step, computed once"""
-    from oracle import dalle_oracle as do
     c = CFG
-    cfg = do.DalleConfig(c["n_embd"], c["text_vocab"], c["image_vocab"], c["T"], c["P"], c["n_layers"], c["n_heads"])
-    P0 = do.init_params(cfg, seed=1234, perturb=0.05)
-    tokens = do.assemble_tokens(do.synthetic_captions(c["B"], c["T"], c["text_vocab"], seed=1),
-                                do.synthetic_image_tokens(c["B"], c["P"], c["image_vocab"], seed=2), c["text_vocab"])
-    Pt = OrderedDict((n, torch.tensor(a, dtype=torch.float32, requires_grad=True)) for n, a in P0.items())
-    _, loss_batch, _ = do.forward(Pt, tokens, cfg, bf16=False, return_logits=True)
+    cfg, P0, tokens = inputs(c["n_embd"], c["n_heads"], c["n_layers"], c["B"], T=c["T"], P=c["P"], TV=c["text_vocab"], IV=c["image_vocab"])
+    Pt = sref.leaves(P0)
+    mean, loss_batch = sref.forward_loss(Pt, tokens, cfg)
 
     def oracle(wt, wi):
         """(loss, mean_text, mean_image, gradients) of the weighted loss; wt = None: the reference's plain mean"""
         if wt is None:
-            loss, mt, mi = loss_batch.mean(), loss_batch[:, :c["T"] - 1].mean(), loss_batch[:, c["T"] - 1:].mean()
+            loss, mt, mi = mean, loss_batch[:, :c["T"] - 1].mean(), loss_batch[:, c["T"] - 1:].mean()
         else:
             loss, mt, mi = weighted_loss_ref(loss_batch, c["T"], wt, wi)
-        grads = torch.autograd.grad(loss, list(Pt.values()), retain_graph=True, allow_unused=True)
-        g = OrderedDict((n, (x.numpy().copy() if x is not None else np.zeros(tuple(p.shape), np.float32)))
-                        for (n, p), x in zip(Pt.items(), grads))
-        return float(loss.detach()), float(mt.detach()), float(mi.detach()), g
+        return float(loss.detach()), float(mt.detach()), float(mi.detach()), sref.gradients(loss, Pt, retain_graph=True)
     tok = torch.from_numpy(tokens).cuda()
     eng = _engine()
     eng.load_reference_params(P0)

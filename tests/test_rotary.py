@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import dalle_hip as dh
+import dalle_step_ref as sref
 import rotary_ref as rref
 from src.dalle_mtf import rotary as ro
 
@@ -200,13 +201,13 @@ def test_zero_angle_table_reproduces_the_plain_oracle_exactly():
     tokens = do.assemble_tokens(do.synthetic_captions(2, T, TV, seed=1), do.synthetic_image_tokens(2, P, IV, seed=2), TV)
     table = np.zeros((T + P, cfg.kv_dim // 2, 2), np.float32)
     table[..., 0] = 1.0
-    loss_r, g_r = rref.loss_and_grads(P0, tokens, cfg, table)
+    loss_r, g_r = sref.loss_and_grads(P0, tokens, cfg, table=table)
     loss_o, g_o = do.loss_and_grads(P0, tokens, cfg)
     assert loss_r == loss_o
     for k in g_o:
         assert np.array_equal(g_r[k], g_o[k]), k
     # and a real table moves the q / k gradients
-    loss_x, g_x = rref.loss_and_grads(P0, tokens, cfg, ro.rotary_table("axial", T, P, cfg.kv_dim))
+    loss_x, g_x = sref.loss_and_grads(P0, tokens, cfg, table=ro.rotary_table("axial", T, P, cfg.kv_dim))
     assert loss_x != loss_o and not np.array_equal(g_x["layer_0/attn/q"], g_o["layer_0/attn/q"])
 
 

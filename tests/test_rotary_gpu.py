@@ -1,14 +1,13 @@
 """Rotary position embeddings on the MI355X: dmi_rope_qk / dmi_rope_qk_decode against float64, the engine's train step against
-the rotated fp32 oracle (tests/rotary_ref.py), the unset key, recompute_grad, the decode step and the samplers, checkpoints."""
+the fp32 step oracle with the same table (tests/dalle_step_ref.py), the unset key, recompute_grad, the decode step and the samplers, checkpoints."""
 import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from engine_case import IV, P, PATTERNS, T, TV, build, step
+from parity import rel_l2
 
-T, P, TV, IV = 16, 256, 300, 64
-PATTERNS = ["row", "column", "conv:3"]
-HP = dict(lr=1e-3, train_steps=1000, warmup_steps=2, gradient_clipping=1.0)
+pytestmark = pytest.mark.gpu
 
 # ------------------------------------------------------------------ kernels
 KS, KH, KB = 40, 2, 2            # S = 40: no multiple of a block's four rows times anything; T = 4 caption + 6 x 6 image positions
@@ -141,36 +140,8 @@ def test_rope_qk_decode_equals_the_rows_of_the_full_kernel(hd):
 
 
 # ------------------------------------------------------------------ engine
-def _setup(n_embd=256, n_heads=2, n_layers=3, B=2, seed=0, rotary="axial", patterns=None, hp=None, base=None, qk_scale=None):
-    from oracle import dalle_oracle as do
-    from src.dalle_mtf.models import DALLE
-    cfg = do.DalleConfig(n_embd, TV, IV, T, P, n_layers, n_heads)
-    params = dict(HP, **(hp or {}))
-    if rotary != "absent":
-        params["rotary_emb"] = rotary
-    if base is not None:
-        params["rotary_base"] = base
-    if patterns is not None:
-        params["attention_pattern"] = patterns
-    model = DALLE(n_embd=n_embd, text_vocab_size=TV, image_vocab_size=IV, text_seq_len=T, image_seq_len=P, n_layers=n_layers,
-                  n_heads=n_heads, batch_size=B, params=params)
-    P0 = do.init_params(cfg, seed=1234 + seed, perturb=0.05)
-    if qk_scale is not None:
-        P0 = {k: (v * np.float32(qk_scale) if k.endswith(("attn/q", "attn/k")) else v) for k, v in P0.items()}
-    model.engine.load_reference_params(P0)
-    tokens = do.assemble_tokens(do.synthetic_captions(B, T, TV, seed=seed + 1), do.synthetic_image_tokens(B, P, IV, seed=seed + 2), TV)
-    return cfg, model, P0, tokens
-
-
-def _rel_l2(a, b):
-    return float(np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-30))
-
-
-def _step(eng, tokens):
-    loss = eng.forward(torch.from_numpy(tokens).cuda(), need_grad=True).clone()
-    eng.backward(allreduce=False)
-    torch.cuda.synchronize()
-    return loss
+def _setup(rotary="axial", hparams=None, **kw):
+    return build(hparams=dict(hparams or {}, rotary_emb=rotary), **kw)
 
 
 @pytest.mark.parametrize("n_embd,scheme,patterns", [(256, "axial", None), (128, "1d", None), (256, "axial", PATTERNS)],
@@ -178,18 +149,18 @@ def _step(eng, tokens):
 def test_engine_step_vs_rotated_fp32_oracle(n_embd, scheme, patterns):
     """the project's causal-step bounds (tests/parity.py check_report): loss 5e-4 relative, worst gradient tensor 4.8e-2 relative L2
     -- the rotation adds one bf16 rounding of q and k, the size of the rounding the QKV output already carries"""
-    import rotary_ref as rref
+    import dalle_step_ref as sref
     from src.dalle_mtf.masks import layer_masks
     from src.dalle_mtf.rotary import rotary_table
-    cfg, model, P0, tokens = _setup(n_embd=n_embd, rotary=scheme, patterns=patterns)
+    cfg, model, P0, tokens = _setup(scheme, width=n_embd, hparams=dict(attention_pattern=patterns or "absent"))
     eng = model.engine
     assert eng.rotary == scheme and eng.rope_cs is not None and tuple(eng.rope_cs.shape) == (T + P, eng.hd // 2, 2)
     assert (patterns is None) == all(p is None for p in eng.attn_plan)
-    loss = float(_step(eng, tokens).item())
+    loss = float(step(eng, tokens)[0].item())
     gh = eng.export_reference(eng.g)
     masks = layer_masks(patterns, cfg.n_layers, T, P) if patterns is not None else None
-    loss_o, go = rref.loss_and_grads(P0, tokens, cfg, rotary_table(scheme, T, P, eng.hd), masks)
-    worst = max((_rel_l2(gh[k], go[k]), k) for k in go)
+    loss_o, go = sref.loss_and_grads(P0, tokens, cfg, table=rotary_table(scheme, T, P, eng.hd), masks=masks)
+    worst = max((rel_l2(gh[k], go[k]), k) for k in go)
     print(f"rotary {scheme} n_embd {n_embd} masked {patterns is not None}: loss {loss} oracle {loss_o} worst grad {worst}", flush=True)
     assert abs(loss - loss_o) <= 5e-4 * abs(loss_o), (loss, loss_o)
     assert worst[0] <= 4.8e-2, worst
@@ -199,18 +170,20 @@ def test_the_rotation_is_live():
     """attn/q and attn/k scaled by 2 (chosen on the CPU: the rotary and the rotary-off fp32 oracles then differ by 1.34 .. 1.43
     relative L2 on those tensors, asserted > 0.2 below): the engine's q / k gradients are at least ten times farther from the
     rotary-off oracle than from the rotary one"""
-    import rotary_ref as rref
+    import dalle_step_ref as sref
     from oracle import dalle_oracle as do
     from src.dalle_mtf.rotary import rotary_table
-    cfg, model, P0, tokens = _setup(qk_scale=2.0)
+    cfg, model, P0, tokens = _setup()
     eng = model.engine
-    _step(eng, tokens)
+    P0 = {k: (v * np.float32(2.0) if k.endswith(("attn/q", "attn/k")) else v) for k, v in P0.items()}
+    eng.load_reference_params(P0)
+    step(eng, tokens)
     gh = eng.export_reference(eng.g)
-    _, g_on = rref.loss_and_grads(P0, tokens, cfg, rotary_table("axial", T, P, eng.hd))
+    _, g_on = sref.loss_and_grads(P0, tokens, cfg, table=rotary_table("axial", T, P, eng.hd))
     _, g_off = do.loss_and_grads(P0, tokens, cfg)
     for k in (k for k in g_on if k.endswith(("attn/q", "attn/k"))):
-        assert _rel_l2(g_on[k], g_off[k]) > 0.2, k
-        near, far = _rel_l2(gh[k], g_on[k]), _rel_l2(gh[k], g_off[k])
+        assert rel_l2(g_on[k], g_off[k]) > 0.2, k
+        near, far = rel_l2(gh[k], g_on[k]), rel_l2(gh[k], g_off[k])
         print(f"live {k}: vs rotary oracle {near:.4f}, vs rotary-off oracle {far:.4f}", flush=True)
         assert far >= 10 * near, (k, near, far)
 
@@ -219,26 +192,25 @@ def test_off_is_off():
     """the key absent, None and False: bit-identical loss and flat gradient, no table"""
     out = []
     for rotary in ("absent", None, False):
-        _, model, _, tokens = _setup(rotary=rotary)
+        _, model, _, tokens = _setup(rotary)
         eng = model.engine
         assert eng.rotary is None and eng.rope_cs is None
         assert "rotary_emb" not in eng.state_dict()
-        out.append((_step(eng, tokens), eng.g.clone()))
+        out.append(step(eng, tokens))
         del model, eng
         torch.cuda.empty_cache()
     for loss, g in out[1:]:
         assert torch.equal(loss, out[0][0]) and torch.equal(g, out[0][1])
-    _, model, _, tokens = _setup(rotary="axial")         # ... and on is not off
-    assert not torch.equal(_step(model.engine, tokens), out[0][0])
+    _, model, _, tokens = _setup()         # ... and on is not off
+    assert not torch.equal(step(model.engine, tokens)[0], out[0][0])
 
 
 def test_recompute_grad_with_rotary_equals_stored_activations():
     res = []
     for rc in (False, True):
-        _, model, _, tokens = _setup(hp=dict(recompute_grad=rc))
-        eng = model.engine
-        res.append((_step(eng, tokens), eng.g.clone()))
-        del model, eng
+        _, model, _, tokens = _setup(hparams=dict(recompute_grad=rc))
+        res.append(step(model.engine, tokens))
+        del model
         torch.cuda.empty_cache()
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
 
@@ -279,7 +251,7 @@ def test_checkpoint_records_and_checks_the_scheme():
     sd = eng.state_dict()
     assert sd["rotary_emb"] == "axial" and sd["rotary_base"] == 10000.0
     del model, eng
-    for kw, word in ((dict(rotary="absent"), "no rotary"), (dict(rotary="1d"), "'1d'"), (dict(base=500.0), "500")):
+    for kw, word in ((dict(rotary="absent"), "no rotary"), (dict(rotary="1d"), "'1d'"), (dict(hparams=dict(rotary_base=500.0)), "500")):
         _, other, _, _ = _setup(**kw)
         with pytest.raises(ValueError, match="rotary") as e:
             other.engine.load_state_dict(sd)

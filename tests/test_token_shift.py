@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import dalle_hip as dh
+import dalle_step_ref as sref
 import token_shift_ref as tref
 from src.dalle_mtf import token_shift as ts
 
@@ -112,12 +113,12 @@ def _small():
 
 def test_shift_off_reproduces_the_plain_oracle_exactly():
     do, cfg, P0, tokens = _small()
-    loss_r, g_r = tref.loss_and_grads(P0, tokens, cfg, token_shift=False)
+    loss_r, g_r = sref.loss_and_grads(P0, tokens, cfg, token_shift=False)
     loss_o, g_o = do.loss_and_grads(P0, tokens, cfg)
     assert loss_r == loss_o
     for k in g_o:
         assert np.array_equal(g_r[k], g_o[k]), k
-    loss_x, g_x = tref.loss_and_grads(P0, tokens, cfg)          # ... and the shift moves the loss and the gradients
+    loss_x, g_x = sref.loss_and_grads(P0, tokens, cfg, token_shift=True)          # ... and the shift moves the loss and the gradients
     assert loss_x != loss_o and not np.array_equal(g_x["layer_0/attn/q"], g_o["layer_0/attn/q"])
 
 
@@ -131,8 +132,8 @@ def test_shifted_oracle_is_causal():
     other = tokens.copy()
     other[0, 100] = TV + (other[0, 100] - TV + 1) % IV
     with torch.no_grad():
-        a = tref.forward_logits(P0, tokens, cfg).numpy()
-        b = tref.forward_logits(P0, other, cfg).numpy()
+        a = sref.forward_logits(P0, tokens, cfg, token_shift=True).numpy()
+        b = sref.forward_logits(P0, other, cfg, token_shift=True).numpy()
     assert np.array_equal(a[:, :100], b[:, :100])
     after = np.abs(a[:, 100:] - b[:, 100:]).max(axis=-1)[0]
     assert after[0] > 0 and after[1] > 0 and after[16] > 0 and after.max() > 1e-3, after[:20]

@@ -1,16 +1,14 @@
 """Token shift on the MI355X: dmi_token_shift / dmi_token_shift_decode bit for bit against the float64 reference
-(tests/token_shift_ref.py), the engine's train step against the shifted fp32 oracle, the unset key, recompute_grad, the decode
+(tests/token_shift_ref.py), the engine's train step against the shifted fp32 oracle (tests/dalle_step_ref.py), the unset key, recompute_grad, the decode
 step with its history and the samplers, checkpoints."""
-import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from engine_case import IV, P, PATTERNS, T, TV, build, inputs, step
+from parity import rel_l2
 
-T, P, TV, IV = 16, 256, 300, 64
+pytestmark = pytest.mark.gpu
 G = 16
-PATTERNS = ["row", "column", "conv:3"]
-HP = dict(lr=1e-3, train_steps=1000, warmup_steps=2, gradient_clipping=1.0)
 
 # ------------------------------------------------------------------ kernels
 KB = 3                            # sequences; T = 4 caption + 6 x 6 image positions: S = 40
@@ -147,34 +145,8 @@ def test_token_shift_decode_equals_the_rows_of_the_full_kernel(d):
 
 
 # ------------------------------------------------------------------ engine
-def _setup(n_embd=256, n_heads=2, n_layers=3, B=2, seed=0, shift=True, patterns=None, rotary=None, hp=None):
-    from oracle import dalle_oracle as do
-    from src.dalle_mtf.models import DALLE
-    cfg = do.DalleConfig(n_embd, TV, IV, T, P, n_layers, n_heads)
-    params = dict(HP, **(hp or {}))
-    if shift != "absent":
-        params["token_shift"] = shift
-    if rotary is not None:
-        params["rotary_emb"] = rotary
-    if patterns is not None:
-        params["attention_pattern"] = patterns
-    model = DALLE(n_embd=n_embd, text_vocab_size=TV, image_vocab_size=IV, text_seq_len=T, image_seq_len=P, n_layers=n_layers,
-                  n_heads=n_heads, batch_size=B, params=params)
-    P0 = do.init_params(cfg, seed=1234 + seed, perturb=0.05)
-    model.engine.load_reference_params(P0)
-    tokens = do.assemble_tokens(do.synthetic_captions(B, T, TV, seed=seed + 1), do.synthetic_image_tokens(B, P, IV, seed=seed + 2), TV)
-    return cfg, model, P0, tokens
-
-
-def _rel_l2(a, b):
-    return float(np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-30))
-
-
-def _step(eng, tokens):
-    loss = eng.forward(torch.from_numpy(tokens).cuda(), need_grad=True).clone()
-    eng.backward(allreduce=False)
-    torch.cuda.synchronize()
-    return loss
+def _setup(shift=True, hparams=None, **kw):
+    return build(hparams=dict(hparams or {}, token_shift=shift), **kw)
 
 
 _ORACLE = {}
@@ -185,12 +157,9 @@ def _oracle(n_embd, shift):
     and shared by the tests that need it"""
     key = (n_embd, shift)
     if key not in _ORACLE:
-        import token_shift_ref as tref
-        from oracle import dalle_oracle as do
-        cfg = do.DalleConfig(n_embd, TV, IV, T, P, 3, 2)
-        P0 = do.init_params(cfg, seed=1234, perturb=0.05)
-        tokens = do.assemble_tokens(do.synthetic_captions(2, T, TV, seed=1), do.synthetic_image_tokens(2, P, IV, seed=2), TV)
-        _ORACLE[key] = tref.loss_and_grads(P0, tokens, cfg, token_shift=shift)
+        import dalle_step_ref as sref
+        cfg, P0, tokens = inputs(n_embd)
+        _ORACLE[key] = sref.loss_and_grads(P0, tokens, cfg, token_shift=shift)
     return _ORACLE[key]
 
 
@@ -200,25 +169,26 @@ def _oracle(n_embd, shift):
 def test_engine_step_vs_shifted_fp32_oracle(n_embd, n_heads, n_layers, patterns, rotary):
     """the project's causal-step bounds (tests/parity.py check_report): loss 5e-4 relative, worst gradient tensor 4.8e-2 relative L2
     -- the shift copies, it adds no rounding"""
-    import token_shift_ref as tref
+    import dalle_step_ref as sref
     from src.dalle_mtf.masks import layer_masks
     from src.dalle_mtf.rotary import rotary_table
-    cfg, model, P0, tokens = _setup(n_embd=n_embd, n_heads=n_heads, n_layers=n_layers, patterns=patterns, rotary=rotary)
+    cfg, model, P0, tokens = _setup(width=n_embd, heads=n_heads, layers=n_layers,
+                                    hparams=dict(attention_pattern=patterns or "absent", rotary_emb=rotary or "absent"))
     eng = model.engine
     assert eng.token_shift is True and eng.G == G and tuple(eng.shift_tmp.shape) == (eng.M, n_embd)
     assert not eng.fuse_lnbwd and not eng.lnb_batch and not eng._d_o_chained()
     if n_embd == 512:
         print(f"n_embd 512 LayerNorm forms: fuse_ln {eng.fuse_ln} fuse_ln1 {eng.fuse_ln1} fuse_lnbwd {eng.fuse_lnbwd} "
               f"lnb_batch {eng.lnb_batch}", flush=True)
-    loss = float(_step(eng, tokens).item())
+    loss = float(step(eng, tokens)[0].item())
     gh = eng.export_reference(eng.g)
     if patterns is None and rotary is None and n_layers == 3:
         loss_o, go = _oracle(n_embd, True)
     else:
         masks = layer_masks(patterns, cfg.n_layers, T, P) if patterns is not None else None
         table = rotary_table(rotary, T, P, eng.hd) if rotary is not None else None
-        loss_o, go = tref.loss_and_grads(P0, tokens, cfg, table, masks)
-    worst = max((_rel_l2(gh[k], go[k]), k) for k in go)
+        loss_o, go = sref.loss_and_grads(P0, tokens, cfg, token_shift=True, table=table, masks=masks)
+    worst = max((rel_l2(gh[k], go[k]), k) for k in go)
     print(f"token_shift n_embd {n_embd} masked {patterns is not None} rotary {rotary}: loss {loss} oracle {loss_o} worst grad {worst}",
           flush=True)
     assert abs(loss - loss_o) <= 5e-4 * abs(loss_o), (loss, loss_o)
@@ -230,16 +200,16 @@ def test_the_shift_is_live(n_embd):
     """on the tensors the shifted rows feed (q, k, v and FFN-1's kernel) the shift-on and shift-off fp32 oracles differ by more
     than 0.2 relative L2 (0.25 .. 1.08 on the CPU at this setup), and the engine's gradient is more than 0.15 away from the
     shift-off one; the loss moves by 1.3e-3 relative only, so the gradients are what is asserted"""
-    _, model, _, tokens = _setup(n_embd=n_embd)
+    _, model, _, tokens = _setup(width=n_embd)
     eng = model.engine
-    _step(eng, tokens)
+    step(eng, tokens)
     gh = eng.export_reference(eng.g)
     _, g_on = _oracle(n_embd, True)
     _, g_off = _oracle(n_embd, False)
     keys = [k for k in g_on if k.endswith(("attn/q", "attn/k", "attn/v", "mlp/mlp_linear_1/kernel"))]
     assert len(keys) == 4 * 3
     for k in keys:
-        apart, far = _rel_l2(g_on[k], g_off[k]), _rel_l2(gh[k], g_off[k])
+        apart, far = rel_l2(g_on[k], g_off[k]), rel_l2(gh[k], g_off[k])
         print(f"live {k}: oracles apart {apart:.4f}, engine vs shift-off oracle {far:.4f}", flush=True)
         assert apart > 0.2, (k, apart)
         assert far > 0.15, (k, far)
@@ -249,10 +219,10 @@ def test_off_is_off():
     """the key absent, None and False: bit-identical loss and flat gradient, no shift buffers, nothing in the checkpoint"""
     out = []
     for shift in ("absent", None, False):
-        _, model, _, tokens = _setup(shift=shift)
+        _, model, _, tokens = _setup(shift)
         eng = model.engine
         assert eng.token_shift is False and eng.shift_tmp is None and eng.G is None
-        out.append((_step(eng, tokens), eng.g.clone()))
+        out.append(step(eng, tokens))
         eng._prefill(torch.from_numpy(tokens).cuda())
         eng.decode_step(torch.from_numpy(tokens[:, T - 1].copy()).cuda(), T - 1)
         assert eng._shift_hist is None and "xs" not in eng._dec
@@ -261,18 +231,17 @@ def test_off_is_off():
         torch.cuda.empty_cache()
     for loss, g in out[1:]:
         assert torch.equal(loss, out[0][0]) and torch.equal(g, out[0][1])
-    _, model, _, tokens = _setup(shift=True)         # ... and on is not off
-    loss = _step(model.engine, tokens)
-    assert not torch.equal(loss, out[0][0]) and not torch.equal(model.engine.g, out[0][1])
+    _, model, _, tokens = _setup()         # ... and on is not off
+    loss, g = step(model.engine, tokens)
+    assert not torch.equal(loss, out[0][0]) and not torch.equal(g, out[0][1])
 
 
 def test_recompute_grad_with_token_shift_equals_stored_activations():
     res = []
     for rc in (False, True):
-        _, model, _, tokens = _setup(hp=dict(recompute_grad=rc, residual_dropout=0.1, embed_dropout=0.1))
-        eng = model.engine
-        res.append((_step(eng, tokens), eng.g.clone()))
-        del model, eng
+        _, model, _, tokens = _setup(hparams=dict(recompute_grad=rc, residual_dropout=0.1, embed_dropout=0.1))
+        res.append(step(model.engine, tokens))
+        del model
         torch.cuda.empty_cache()
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
     assert float(res[0][1].abs().sum()) > 0
@@ -335,7 +304,7 @@ def test_checkpoint_records_and_checks_the_key():
         eng.load_state_dict(before)
     assert "no token shift" in str(e.value) and "token_shift on" in str(e.value), str(e.value)
     del model, eng
-    _, off, _, _ = _setup(shift="absent")
+    _, off, _, _ = _setup("absent")
     with pytest.raises(ValueError, match="token_shift") as e:
         off.engine.load_state_dict(sd)
     assert "no token shift" in str(e.value) and "token_shift on" in str(e.value), str(e.value)
