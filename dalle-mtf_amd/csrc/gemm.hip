@@ -2056,6 +2056,107 @@ extern "C" int dmi_gemm_nt_gelu_grad(const uint16_t* A, int lda, const uint16_t*
   return launch_nt<GEMM_GELU_GRAD>(a, 1, (hipStream_t)stream);
 }
 
+// ---- the gated FFN (DALLE "ff_glu", DESIGN.md §4 "Gated feed-forward"): FFN-1 is the plain product at N = 2 Hh into pre = [value | gate],
+// then h = value * act(gate); the backward writes d(pre) from dh and pre.  Streaming kernels beside gelu_sig / gelu_grad_f so that the
+// folded constants keep their one home: 16-byte pieces (8 bf16), fp32 arithmetic, no LDS.  A row of Hh / 8 pieces is covered by
+// 2^lsh lanes (2^lsh >= min(pieces, 256)), a block holds 256 >> lsh rows, the grid strides over rows; every address is 64-bit.
+template <int ACT>
+__global__ __launch_bounds__(256) void glu_fwd_kernel(const bf16_t* __restrict__ pre, int64_t ldpre, bf16_t* __restrict__ h, int64_t ldh,
+                                                      int64_t M, int Hh, int lsh) {
+  const int lanes = 1 << lsh, c0 = threadIdx.x & (lanes - 1), P = Hh >> 3;
+  const int64_t rows = 256 >> lsh, step = (int64_t)gridDim.x * rows;
+  for (int64_t m = (int64_t)blockIdx.x * rows + (threadIdx.x >> lsh); m < M; m += step) {
+    const bf16_t* pv = pre + m * ldpre;
+    bf16_t* ph = h + m * ldh;
+    for (int c = c0; c < P; c += lanes) {
+      float v[8], g[8];
+      unpack8(*(const u32x4*)(pv + (int64_t)c * 8), v);
+      unpack8(*(const u32x4*)(pv + Hh + (int64_t)c * 8), g);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] *= ACT == DMI_GEMM_GELU ? gelu_f(g[e]) : (g[e] > 0.f ? g[e] : 0.f);
+      *(u32x4*)(ph + (int64_t)c * 8) = pack8(v);
+    }
+  }
+}
+template <int ACT>
+__global__ __launch_bounds__(256) void glu_bwd_kernel(const bf16_t* __restrict__ dh, int64_t lddh, const bf16_t* __restrict__ pre, int64_t ldpre,
+                                                      bf16_t* __restrict__ dpre, int64_t lddpre, int64_t M, int Hh, int lsh) {
+  const int lanes = 1 << lsh, c0 = threadIdx.x & (lanes - 1), P = Hh >> 3;
+  const int64_t rows = 256 >> lsh, step = (int64_t)gridDim.x * rows;
+  for (int64_t m = (int64_t)blockIdx.x * rows + (threadIdx.x >> lsh); m < M; m += step) {
+    const bf16_t* pd = dh + m * lddh;
+    const bf16_t* pv = pre + m * ldpre;
+    bf16_t* po = dpre + m * lddpre;
+    for (int c = c0; c < P; c += lanes) {
+      float t[8], v[8], g[8], dv[8], dg[8];
+      unpack8(*(const u32x4*)(pd + (int64_t)c * 8), t);
+      unpack8(*(const u32x4*)(pv + (int64_t)c * 8), v);
+      unpack8(*(const u32x4*)(pv + Hh + (int64_t)c * 8), g);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if constexpr (ACT == DMI_GEMM_GELU) {
+          dv[e] = t[e] * gelu_f(g[e]);
+          dg[e] = t[e] * v[e] * gelu_grad_f(g[e]);
+        } else {   // relu'(0) = 0: the h > 0 convention of DMI_GEMM_RELU_MASK
+          dv[e] = t[e] * (g[e] > 0.f ? g[e] : 0.f);
+          dg[e] = g[e] > 0.f ? t[e] * v[e] : 0.f;
+        }
+      }
+      *(u32x4*)(po + (int64_t)c * 8) = pack8(dv);
+      *(u32x4*)(po + Hh + (int64_t)c * 8) = pack8(dg);
+    }
+  }
+}
+// the checks of one operand of the two entries: bf16 [M, cols] with leading dimension ld
+static int check_glu_operand(const char* who, const char* name, const void* p, int ld, int cols) {
+  DMI_REQUIRE(p, "%s: null %s", who, name);
+  DMI_REQUIRE(((uintptr_t)p & 15) == 0, "%s: %s must be 16-byte aligned", who, name);
+  DMI_REQUIRE(ld >= cols && ld % 8 == 0, "%s: need ld%s >= %d and ld%s %% 8 == 0 (ld%s=%d)", who, name, cols, name, name, ld);
+  return DMI_OK;
+}
+static int check_glu_shape(const char* who, int64_t M, int Hh, int act) {
+  DMI_REQUIRE(M > 0 && Hh > 0 && Hh % 8 == 0 && Hh <= (1 << 29), "%s: need M > 0, Hh > 0 and Hh %% 8 == 0 (M=%lld Hh=%d)", who, (long long)M, Hh);
+  DMI_REQUIRE(act == DMI_GEMM_RELU || act == DMI_GEMM_GELU, "%s: act must be DMI_GEMM_RELU or DMI_GEMM_GELU (act=%d)", who, act);
+  return DMI_OK;
+}
+// lanes per row (as a shift) and the grid: 8 blocks of 4 waves per CU hold the stream of 16-byte requests, the rest is the grid stride
+static void glu_grid(int64_t M, int Hh, int& lsh, unsigned& blocks) {
+  lsh = 0;
+  while ((1 << lsh) < Hh / 8 && lsh < 8) ++lsh;
+  int64_t b = cdiv64(M, 256 >> lsh);
+  blocks = (unsigned)(b > 256 * 8 ? 256 * 8 : b);
+}
+extern "C" int dmi_glu_fwd(const uint16_t* pre, int ldpre, uint16_t* h, int ldh, int64_t M, int Hh, int act, void* stream) {
+  int rc = check_glu_shape("glu_fwd", M, Hh, act);
+  if (rc) return rc;
+  if ((rc = check_glu_operand("glu_fwd", "pre", pre, ldpre, 2 * Hh))) return rc;
+  if ((rc = check_glu_operand("glu_fwd", "h", h, ldh, Hh))) return rc;
+  int lsh;
+  unsigned blocks;
+  glu_grid(M, Hh, lsh, blocks);
+  if (act == DMI_GEMM_GELU) glu_fwd_kernel<DMI_GEMM_GELU><<<dim3(blocks), dim3(256), 0, (hipStream_t)stream>>>(pre, ldpre, h, ldh, M, Hh, lsh);
+  else glu_fwd_kernel<DMI_GEMM_RELU><<<dim3(blocks), dim3(256), 0, (hipStream_t)stream>>>(pre, ldpre, h, ldh, M, Hh, lsh);
+  DMI_CHECK_LAUNCH("glu_fwd");
+  return DMI_OK;
+}
+extern "C" int dmi_glu_bwd(const uint16_t* dh, int lddh, const uint16_t* pre, int ldpre, uint16_t* dpre, int lddpre, int64_t M, int Hh, int act,
+                           void* stream) {
+  int rc = check_glu_shape("glu_bwd", M, Hh, act);
+  if (rc) return rc;
+  if ((rc = check_glu_operand("glu_bwd", "dh", dh, lddh, Hh))) return rc;
+  if ((rc = check_glu_operand("glu_bwd", "pre", pre, ldpre, 2 * Hh))) return rc;
+  if ((rc = check_glu_operand("glu_bwd", "dpre", dpre, lddpre, 2 * Hh))) return rc;
+  int lsh;
+  unsigned blocks;
+  glu_grid(M, Hh, lsh, blocks);
+  if (act == DMI_GEMM_GELU)
+    glu_bwd_kernel<DMI_GEMM_GELU><<<dim3(blocks), dim3(256), 0, (hipStream_t)stream>>>(dh, lddh, pre, ldpre, dpre, lddpre, M, Hh, lsh);
+  else
+    glu_bwd_kernel<DMI_GEMM_RELU><<<dim3(blocks), dim3(256), 0, (hipStream_t)stream>>>(dh, lddh, pre, ldpre, dpre, lddpre, M, Hh, lsh);
+  DMI_CHECK_LAUNCH("glu_bwd");
+  return DMI_OK;
+}
+
 // 1 where dmi_gemm_nt_ln / dmi_gemm_nt_lnbwd accept a product [M, K] x [N, K]^T with K-contiguous operands (lda = ldb = K) AND the
 // library would run it on full-row tiles itself: N = 512 (one block owns whole rows), every operand inside the 32-bit buffer offsets
 // of gemm_ntr_kernel, no CUs reserved for a concurrent exchange (launch_nt keeps the 128x128 kernel then).  Callers gate the fused

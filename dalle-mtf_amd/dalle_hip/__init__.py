@@ -124,6 +124,8 @@ def _declare(L):
         "dmi_gemm_nt_mask_bits": (I, [P, I, P, I, P, I, I, I, I, P, P]),
         "dmi_gemm_nt_gelu": (I, [P, I, P, I, P, I, I, I, I, P, P, I, P]),
         "dmi_gemm_nt_gelu_grad": (I, [P, I, P, I, P, I, I, I, I, P, I, P]),
+        "dmi_glu_fwd": (I, [P, I, P, I, L64, I, I, P]),
+        "dmi_glu_bwd": (I, [P, I, P, I, P, I, L64, I, I, P]),
         "dmi_sumsq_workspace_bytes": (L64, [L64]),
         "dmi_sumsq": (I, [P, L64, P, P, P]),
         "dmi_adam_step": (I, [P, P, P, P, P, L64, P, F, F, F, F, F, F, F, P, P]),
@@ -387,6 +389,35 @@ def gemm_nt_gelu_grad(A, lda, Bt, ldb, C, ldc, M, N, K, pre, ldpre):
     """C = bf16((A . Bt^T) * gelu'(pre)), pre as gemm_nt_gelu wrote it"""
     _dev(A, Bt, C, pre)
     _check(lib().dmi_gemm_nt_gelu_grad(_p(A), lda, _p(Bt), ldb, _p(C), ldc, M, N, K, _p(pre), ldpre, _stream()), "gemm_nt_gelu_grad")
+
+
+def _glu_act(act):
+    if act not in ("relu", "gelu"):
+        raise DalleHipError(f"glu: act must be 'relu' or 'gelu' (got {act!r})")
+    return GEMM_GELU if act == "gelu" else GEMM_RELU
+
+
+def _glu_rows(t, ld, M, cols):
+    """t holds M rows of `cols` bf16 elements at leading dimension ld (the last row need not be padded)"""
+    if not isinstance(t, int):       # (a raw device address is the caller's to size)
+        assert t.dtype == torch.bfloat16 and t.numel() >= (M - 1) * ld + cols
+
+
+def glu_fwd(pre, ldpre, h, ldh, M, Hh, act):
+    """h[m, j] = bf16(pre[m, j] * act(pre[m, Hh + j])): the gated FFN's hidden layer from pre = [value | gate]; act "relu" / "gelu" """
+    _dev(pre, h)
+    _glu_rows(pre, ldpre, M, 2 * Hh)
+    _glu_rows(h, ldh, M, Hh)
+    _check(lib().dmi_glu_fwd(_p(pre), ldpre, _p(h), ldh, M, Hh, _glu_act(act), _stream()), "glu_fwd")
+
+
+def glu_bwd(dh, lddh, pre, ldpre, dpre, lddpre, M, Hh, act):
+    """dpre[m, j] = bf16(dh * act(gate)), dpre[m, Hh + j] = bf16(dh * val * act'(gate)) from dh [M, Hh] and pre as glu_fwd read it"""
+    _dev(dh, pre, dpre)
+    _glu_rows(dh, lddh, M, Hh)
+    _glu_rows(pre, ldpre, M, 2 * Hh)
+    _glu_rows(dpre, lddpre, M, 2 * Hh)
+    _check(lib().dmi_glu_bwd(_p(dh), lddh, _p(pre), ldpre, _p(dpre), lddpre, M, Hh, _glu_act(act), _stream()), "glu_bwd")
 
 
 def ln_gemm_nt(X, ldx, gamma, beta, Bt, ldb, C, ldc, M, N, K, flags=0, bias=None, eps=1e-5):

@@ -36,6 +36,7 @@ from ..dp import GradReducer
 from .activations import check_activation
 from .dropout import SITE_POSITION, SITE_TOKEN, resolve_dropout, site_attention, site_key, site_mlp
 from .layout import ALIGN, ParamLayout, _round_up, adafactor_factored_dims, adafactor_table, reference_init   # noqa: F401  (re-exported)
+from .ff_glu import resolve_ff_glu
 from .ema import ema_decay_at, one_minus_decay, resolve_ema, resolve_weights   # noqa: F401  (ema_decay_at: part of the engine's surface)
 from .loss_weights import position_weights, resolve_loss_weights
 from .rotary import DEFAULT_BASE, resolve_rotary, rotary_table
@@ -127,6 +128,8 @@ class DalleEngine:
         self.rotary, self.rotary_base = resolve_rotary(hparams, image_seq_len)
         # hparams["token_shift"] (dalle_mtf.token_shift): half of every position's channels come from its neighbours, behind norm_1 and norm_2
         self.token_shift = resolve_token_shift(hparams, n_embd, image_seq_len)
+        # hparams["ff_glu"] (dalle_mtf.ff_glu): the gated FFN, h = value * act(gate) from an FFN-1 of width 8d
+        self.ff_glu = resolve_ff_glu(hparams)
         if not torch.cuda.is_available():
             raise dh.DalleHipError("DalleEngine needs a HIP device (MI355X); there is no CPU fallback")
         dh.lib()
@@ -149,7 +152,8 @@ class DalleEngine:
         self.hp = dict(hparams or {})
         # the FFN activation (reference src/dalle_mtf/models.py:317-324): "relu" (default) or "gelu" (dalle_mtf.activations)
         self.activation = check_activation(self.hp.get("activation_fn") or "relu")
-        self.lay = ParamLayout(n_embd, n_layers, n_heads, self.V, self.S)
+        self.lay = ParamLayout(n_embd, n_layers, n_heads, self.V, self.S, ff_glu=self.ff_glu)
+        self.F1 = self.lay.ffn1      # FFN-1's output width: 4d, gated [value | gate] = 8d
         self.Vp = self.lay.Vp
         n = self.lay.total
         f32 = dict(dtype=torch.float32, device=self.dev)
@@ -319,6 +323,9 @@ class DalleEngine:
             self.view(self.p, "to_logits/linear_out/kernel").zero_()
             self.view(self.p, "to_logits/linear_out/bias").fill_(-30000.0)   # pad logits can never win the softmax (and are masked in the CE kernel)
             for name, shp, off, ld in self.lay.reference_variables():
+                if tuple(np.shape(P[name])) != tuple(shp) and "mlp_linear_1" in name:
+                    raise ValueError(f"{name}: expected shape {tuple(shp)} with ff_glu {'on' if self.ff_glu else 'off'} "
+                                     f"(got {tuple(np.shape(P[name]))}): the gated FFN's first layer is 8 n_embd wide, the plain one's 4")
                 self._ref_view(self.p, shp, off, ld).copy_(torch.from_numpy(np.ascontiguousarray(P[name])).view(shp))
         self.refresh_compute_copies(cast=True)
         self._ema_from_p()
@@ -409,12 +416,16 @@ class DalleEngine:
         self.dp_reserve_cus = int(hp.get("dp_reserve_cus", os.environ.get("DALLE_DP_RESERVE_CUS", "0"))) if self.world > 1 else 0
         # the FFN-1 product and the FFN-2 input gradient that matches it (_ffn1 / _ffn2_dgrad): GELU keeps the pre-activation
         # (it cannot be inverted from h); ReLU hands its mask on as one bit per element where the library runs both products on
-        # the kernel that has the bit forms, and reads h back elsewhere (bit-identical)
-        self.ffn_form = "gelu" if self.activation == "gelu" else "relu_bits" if dh.relu_bits_auto(M, 4 * d, d) else "relu"
+        # the kernel that has the bit forms, and reads h back elsewhere (bit-identical).  ff_glu: FFN-1 is the plain product with its
+        # bias at N = 8d into the stored pre = [value | gate]; dmi_glu_fwd / dmi_glu_bwd stand between it and FFN-2, no bit mask
+        self.ffn_form = ("glu" if self.ff_glu else "gelu" if self.activation == "gelu" else
+                         "relu_bits" if dh.relu_bits_auto(M, 4 * d, d) else "relu")
         self.use_relu_bits = self.ffn_form == "relu_bits"
         # the fused LayerNorm forms need the library's full-row kernel (n_embd = 512, operands inside its 32-bit offsets) and
         # no CUs reserved; the two-kernel forms serve every other case
+        # (each asked with its widest product: forward FFN-2, K = 4d; backward FFN-1's input gradient, K = 4d or gated 8d)
         ln_ok = dh.gemm_nt_ln_auto(M, d, 4 * d) and self.dp_reserve_cus == 0
+        lnbwd_ok = ln_ok and dh.gemm_nt_ln_auto(M, d, self.F1)
         # fuse_ln: the products that end in the residual stream emit the LayerNorm that follows them (dmi_gemm_nt_ln)
         self.fuse_ln = switch("fuse_ln", "DALLE_FUSE_LN") and ln_ok
         # FFN-2 -> next norm_1: not under recompute_grad, whose re-run of a block starts from the stored residual stream with a
@@ -424,7 +435,7 @@ class DalleEngine:
         # (not with token_shift: the shift's transpose stands between the product and the LayerNorm backward, and the fused form
         # cannot carry it -- the product lands in dxn, dmi_token_shift(inverse) and dmi_layernorm_bwd follow; with fuse_lnbwd go
         # the d_o chaining and the batched finish)
-        self.fuse_lnbwd = switch("fuse_lnbwd", "DALLE_FUSE_LNBWD") and ln_ok and not self.token_shift
+        self.fuse_lnbwd = switch("fuse_lnbwd", "DALLE_FUSE_LNBWD") and lnbwd_ok and not self.token_shift
         # lnbwd_batch_finish: the fused forms leave their gain / bias partials in one buffer per LayerNorm and ONE batched launch
         # sums them at the end of the backward (per block under data parallelism, where the exchange takes a block's gradients
         # as soon as it is done)
@@ -437,7 +448,7 @@ class DalleEngine:
         # tile; elsewhere (n_embd = 1024 / 2048: 384+ tiles, ragged residencies in ONE launch) the attention pair shares a
         # launch and the FFN gradients keep their own
         # (wgrad_shapes: (I, J) of the four in the order of _wgrad_problems and ws_blk -- FFN-2, FFN-1, out-projection, QKV)
-        self.wgrad_shapes = [(4 * d, d), (d, 4 * d), (d, d), (d, 3 * d)]
+        self.wgrad_shapes = [(4 * d, d), (d, self.F1), (d, d), (d, 3 * d)]
         self.wgrad_group4 = dh.gemm_tn_group_plan(self.wgrad_shapes, M) > 0
 
     # ------------------------------------------------------------------ buffers
@@ -464,7 +475,9 @@ class DalleEngine:
         # what FFN-1 keeps beside h for the FFN-2 input gradient: the ReLU mask as bits (M * 4d / 8 bytes instead of a read of h,
         # 168 MB per layer at dalle_example) or GELU's pre-activation a = xn2 . W1 + b1 (bf16, 2 bytes per hidden element)
         self.hbits = per_layer(lambda: torch.empty(dh.relu_bits_bytes(M, 4 * d), **u8)) if self.ffn_form == "relu_bits" else None
-        self.hpre = per_layer(lambda: torch.empty(M, 4 * d, **b16)) if self.ffn_form == "gelu" else None
+        # or the gated FFN's [value | gate] (8d wide)
+        self.hpre = (per_layer(lambda: torch.empty(M, self.F1 if self.ffn_form == "glu" else 4 * d, **b16))
+                     if self.ffn_form in ("gelu", "glu") else None)
         self.stats = per_layer(lambda: [torch.empty(M, **f32) for _ in range(4)])  # mean1, rstd1, mean2, rstd2
         self.xnf = torch.empty(M, d, **b16)
         # token shift: xn1[l] / xn2[l] hold the SHIFTED rows -- what the QKV product, FFN-1 and their weight gradients read.  The
@@ -503,6 +516,8 @@ class DalleEngine:
         self.dx = [torch.empty(M, d, **b16) for _ in range(2)]
         self.dxn = torch.empty(M, d, **b16)
         self.dh = torch.empty(M, 4 * d, **b16)
+        # gated FFN: the gradient of pre = [value | gate], what FFN-1's input, weight and bias gradients read in place of dh
+        self.dpre = torch.empty(M, self.F1, **b16) if self.ffn_form == "glu" else None
         self.dqkv = torch.empty(M, 3 * d, **b16)
         self.d_o = torch.empty(M, d, **b16)
         # residual dropout: drop_y is where the out-projection and FFN-2 land (bias only) before dmi_dropout_add_ln, in the forward
@@ -684,11 +699,15 @@ class DalleEngine:
 
     # ---- FFN-1 and the FFN-2 input gradient, one arm of self.ffn_form each
     def _ffn1(self, l):
-        """h = act(xn2 . W1^T + b1), and what the form keeps for _ffn2_dgrad: the pre-activation, the mask bits, or nothing"""
+        """h = act(xn2 . W1^T + b1), and what the form keeps for _ffn2_dgrad: the pre-activation, the mask bits, or nothing.
+        glu: pre = xn2 . W1^T + b1 at width 8d (the plain product), then h = pre[:, :4d] * act(pre[:, 4d:])"""
         M, d, p = self.M, self.d, f"layer_{l}/"
         args = (self.xn2[l], d, self.tview(p + "mlp/mlp_linear_1/kernel"), d, self.h[l], 4 * d, M, 4 * d, d)
         b1 = self._w(p + "mlp/mlp_linear_1/bias")
-        if self.ffn_form == "gelu":
+        if self.ffn_form == "glu":
+            dh.gemm_nt(*args[:4], self.hpre[l], self.F1, M, self.F1, d, dh.GEMM_BIAS, bias=b1)
+            dh.glu_fwd(self.hpre[l], self.F1, self.h[l], 4 * d, M, 4 * d, self.activation)
+        elif self.ffn_form == "gelu":
             dh.gemm_nt_gelu(*args, b1, self.hpre[l], 4 * d)
         elif self.ffn_form == "relu_bits":
             dh.gemm_nt_relu_bits(*args, b1, self.hbits[l])
@@ -696,15 +715,23 @@ class DalleEngine:
             dh.gemm_nt(*args, dh.GEMM_BIAS | dh.GEMM_RELU, bias=b1)
 
     def _ffn2_dgrad(self, l, dy):
-        """self.dh = (dy . W2^T) * act'(..): gelu' of the stored pre-activation, the mask bits, or h > 0 read back from h"""
+        """self.dh = (dy . W2^T) * act'(..): gelu' of the stored pre-activation, the mask bits, or h > 0 read back from h.
+        glu: self.dh = dy . W2^T, the plain product, and self.dpre = its gradient w.r.t. [value | gate] (_ffn1_grad_in)"""
         M, d = self.M, self.d
         args = (dy, d, self._w(f"layer_{l}/mlp/mlp_linear_2/kernel"), d, self.dh, 4 * d, M, 4 * d, d)
-        if self.ffn_form == "gelu":
+        if self.ffn_form == "glu":
+            dh.gemm_nt(*args)
+            dh.glu_bwd(self.dh, 4 * d, self.hpre[l], self.F1, self.dpre, self.F1, M, 4 * d, self.activation)
+        elif self.ffn_form == "gelu":
             dh.gemm_nt_gelu_grad(*args, self.hpre[l], 4 * d)
         elif self.ffn_form == "relu_bits":
             dh.gemm_nt_mask_bits(*args, self.hbits[l])
         else:
             dh.gemm_nt(*args, dh.GEMM_RELU_MASK, relu_src=self.h[l])
+
+    def _ffn1_grad_in(self):
+        """the gradient of FFN-1's output, [M, F1]: what its input, weight and bias gradients read"""
+        return self.dpre if self.ffn_form == "glu" else self.dh
 
     def _block_forward(self, l, rerun=False):
         """one transformer block (src/dalle_mtf/models.py:326-335): X[l] -> X[l+1].  rerun: what backward() re-runs under
@@ -889,7 +916,7 @@ class DalleEngine:
             f32 = dict(dtype=torch.float32, device=self.dev)
             i32 = dict(dtype=torch.int32, device=self.dev)
             self._dec = dict(x=[torch.empty(B, d, **b16) for _ in range(2)], xn=torch.empty(B, d, **b16), o=torch.empty(B, d, **b16),
-                             h=torch.empty(B, 4 * d, **b16), st=[torch.empty(B, **f32) for _ in range(2)],
+                             h=torch.empty(B, 4 * d, **b16), pre=torch.empty(B, self.F1, **b16) if self.ff_glu else None, st=[torch.empty(B, **f32) for _ in range(2)],
                              z=torch.empty(B, self.image_vocab_size, **b16), fresh=torch.empty(B, 3 * d, **b16),
                              tok=torch.empty(B, **i32), pos_i=torch.zeros(2, **i32),    # [position, scratch counter of the sampler]
                              logits=torch.empty(B, self.image_vocab_size, **f32),
@@ -977,8 +1004,13 @@ class DalleEngine:
             self._attn_decode(l, cache, o, fresh, D["pos_i"])
             dh.gemm_nt(o, d, self.tview(p + "attn/o"), d, x1, d, B, d, d, dh.GEMM_BIAS | dh.GEMM_RESIDUAL,
                        bias=self._w(p + "attn/compute_output_bias/o_b"), residual=x)
-            ln_dense(x1, p + "norm_2", self.tview(p + "mlp/mlp_linear_1/kernel"), h, 4 * d, dh.GEMM_BIAS | act,
-                     bias=self._w(p + "mlp/mlp_linear_1/bias"), shift=(l, 1))
+            if self.ff_glu:    # [value | gate] into the [B, 8d] staging buffer with the bias only, then the gate: nothing depends on the position
+                ln_dense(x1, p + "norm_2", self.tview(p + "mlp/mlp_linear_1/kernel"), D["pre"], self.F1, dh.GEMM_BIAS,
+                         bias=self._w(p + "mlp/mlp_linear_1/bias"), shift=(l, 1))
+                dh.glu_fwd(D["pre"], self.F1, h, 4 * d, B, 4 * d, self.activation)
+            else:
+                ln_dense(x1, p + "norm_2", self.tview(p + "mlp/mlp_linear_1/kernel"), h, 4 * d, dh.GEMM_BIAS | act,
+                         bias=self._w(p + "mlp/mlp_linear_1/bias"), shift=(l, 1))
             dh.gemm_nt(h, 4 * d, self.tview(p + "mlp/mlp_linear_2/kernel"), 4 * d, x, d, B, d, 4 * d,
                        dh.GEMM_BIAS | dh.GEMM_RESIDUAL, bias=self._w(p + "mlp/mlp_linear_2/bias"), residual=x1)
         lo, nv = self.text_vocab_size, self.image_vocab_size
@@ -1017,7 +1049,7 @@ class DalleEngine:
         branch's output.  (X is [M, I], dY [M, J], both dense: the leading dimensions are I and J.)"""
         d, p, g = self.d, f"layer_{l}/", self._gv
         operands = ((self.h[l], dya, "mlp/mlp_linear_2/kernel", "mlp/mlp_linear_2/bias"),
-                    (self.xn2[l], self.dh, "mlp/mlp_linear_1/kernel", "mlp/mlp_linear_1/bias"),
+                    (self.xn2[l], self._ffn1_grad_in(), "mlp/mlp_linear_1/kernel", "mlp/mlp_linear_1/bias"),
                     (self.o[l], dyb, "attn/o", "attn/compute_output_bias/o_b"),
                     (self.xn1[l], self.dqkv, "attn/qkv", None))
         return [dict(X=X, ldx=I, dY=dY, ldy=J, dW=g(p + w), I=I, J=J, ws=ws, **({"dbias": g(p + b)} if b else {}))
@@ -1053,7 +1085,7 @@ class DalleEngine:
     def _ln_dgrad(self, idx, dres, dx):
         """dx = the gradient into the input of LayerNorm idx (2l: norm_1 of block l, 2l + 1: its norm_2, 2L: to_logits') + dres,
         and the LayerNorm's gain / bias gradients.  The gradient of its output is the product A . W^T of the layer that reads it
-        (FFN-1: A = self.dh; QKV: A = self.dqkv); the head's is already in self.dxn.  fuse_lnbwd: product and LayerNorm backward
+        (FFN-1: A = self.dh, gated self.dpre; QKV: A = self.dqkv); the head's is already in self.dxn.  fuse_lnbwd: product and LayerNorm backward
         in one pass (dmi_gemm_nt_lnbwd), chained with d_o for norm_2 (_d_o_chained); otherwise the product into self.dxn and
         dmi_layernorm_bwd.  The gain / bias partials are summed right away, or under lnb_batch by the next _flush_ln() -- the
         head's, which has no fused form, then joins the batch through a workspace of its own.  token_shift (never fused): the
@@ -1064,7 +1096,7 @@ class DalleEngine:
             ln, x, (mean, rstd), A = "to_logits/layer_norm/", self.X[L], self.statf, None
         elif second:
             ln, x, (mean, rstd) = f"layer_{l}/norm_2/", self.x1[l], self.stats[l][2:]
-            A, K, W = self.dh, 4 * d, self._w(f"layer_{l}/mlp/mlp_linear_1/kernel")
+            A, K, W = self._ffn1_grad_in(), self.F1, self._w(f"layer_{l}/mlp/mlp_linear_1/kernel")
         else:
             ln, x, (mean, rstd) = f"layer_{l}/norm_1/", self.X[l], self.stats[l][:2]
             A, K, W = self.dqkv, 3 * d, self._w(f"layer_{l}/attn/qkv")
@@ -1315,6 +1347,8 @@ class DalleEngine:
             sd["rotary_emb"], sd["rotary_base"] = self.rotary, self.rotary_base
         if self.token_shift:           # (a checkpoint without the key is a model without token shift)
             sd["token_shift"] = True
+        if self.ff_glu:                # (a checkpoint without the key is a model with the plain FFN)
+            sd["ff_glu"] = True
         for k in ("m", "v", "af_slots"):
             if getattr(self, k) is not None:
                 sd[k] = getattr(self, k).detach().cpu()
@@ -1341,6 +1375,10 @@ class DalleEngine:
             say = lambda on: "token_shift on" if on else "no token shift"   # noqa: E731
             raise ValueError(f"checkpoint was written by a model with {say(bool(sd.get('token_shift', False)))}; this run uses "
                              f"{say(self.token_shift)}: the weights of one do not compute the other")
+        if bool(sd.get("ff_glu", False)) != self.ff_glu:
+            say = lambda on: "ff_glu on (the gated FFN)" if on else "ff_glu off (the plain FFN)"   # noqa: E731
+            raise ValueError(f"checkpoint was written by a model with {say(bool(sd.get('ff_glu', False)))}; this run uses "
+                             f"{say(self.ff_glu)}: the weights of one do not compute the other")
         self.p.copy_(sd["p"])
         for k in ("m", "v", "af_slots"):
             if getattr(self, k) is not None:

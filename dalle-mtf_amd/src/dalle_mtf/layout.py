@@ -9,6 +9,8 @@ from typing import Dict, List, Tuple
 import numpy as np
 import torch
 
+from .ff_glu import ffn1_width
+
 ALIGN = 128  # elements
 
 
@@ -55,9 +57,13 @@ class ParamLayout:
     pad the vocabulary axis of the output projection to a multiple of 128; `export`/`load` translate
     to/from the reference's variable names and shapes."""
 
-    def __init__(self, n_embd, n_layers, n_heads, total_tokens, total_seq):
+    def __init__(self, n_embd, n_layers, n_heads, total_tokens, total_seq, ff_glu=False):
         d, L, V, S = n_embd, n_layers, total_tokens, total_seq
         self.d, self.L, self.V, self.S = d, L, V, S
+        # mlp_linear_1's output width: 4d, or with the gated FFN (config key "ff_glu") [value | gate] = 8d; everything derived from
+        # the entries -- the transposed-copy table, the reference's variable table, Adafactor's, reference_init -- follows it
+        self.ff_glu = bool(ff_glu)
+        f1 = self.ffn1 = ffn1_width(d, self.ff_glu)
         self.Vp = _round_up(V, 128)
         ent: List[Tuple[str, tuple]] = []
         ent += [("to_logits/linear_out/kernel", (d, self.Vp)), ("to_logits/linear_out/bias", (self.Vp,)),
@@ -65,7 +71,7 @@ class ParamLayout:
         for i in reversed(range(L)):
             p = f"layer_{i}/"
             ent += [(p + "mlp/mlp_linear_2/kernel", (4 * d, d)), (p + "mlp/mlp_linear_2/bias", (d,)),
-                    (p + "mlp/mlp_linear_1/kernel", (d, 4 * d)), (p + "mlp/mlp_linear_1/bias", (4 * d,)),
+                    (p + "mlp/mlp_linear_1/kernel", (d, f1)), (p + "mlp/mlp_linear_1/bias", (f1,)),
                     (p + "norm_2/g", (d,)), (p + "norm_2/b", (d,)),
                     (p + "attn/o", (d, d)), (p + "attn/compute_output_bias/o_b", (d,)),
                     (p + "attn/qkv", (d, 3 * d)),

@@ -170,6 +170,10 @@ def _build(params, mode_str):
         # "token_shift" (dalle_mtf.token_shift; it reaches the engine's hparams through `params`)
         logging.getLogger("dalle_mtf_amd").info("%s token shift: on (behind norm_1 and norm_2 of every block, %d x %d image grid)",
                                                 mode_str, eng.G, eng.G)
+    if eng.ff_glu and rank == 0:
+        # "ff_glu" (dalle_mtf.ff_glu; it reaches the engine's hparams through `params`)
+        logging.getLogger("dalle_mtf_amd").info("%s gated feed-forward: on (%s, mlp_linear_1 is [%d, %d])", mode_str,
+                                                "GEGLU" if eng.activation == "gelu" else "ReGLU", eng.d, eng.F1)
     eng.hp["num_microbatches"] = nmb   # reference model_fns.py:141-154 (1 when tokens_per_mb_per_replica is unset)
     params["num_microbatches"] = nmb
     state["local_bs"] = local_bs

@@ -312,6 +312,17 @@ int dmi_gemm_nt_gelu(const uint16_t* A, int lda, const uint16_t* Bt, int ldb, ui
                      const uint16_t* bias, uint16_t* pre, int ldpre, void* stream);
 int dmi_gemm_nt_gelu_grad(const uint16_t* A, int lda, const uint16_t* Bt, int ldb, uint16_t* C, int ldc, int M, int N, int K,
                           const uint16_t* pre, int ldpre, void* stream);
+/* The gated FFN (project extension, config key "ff_glu"; DESIGN.md §4 "Gated feed-forward"): FFN-1 is dmi_gemm_nt(BIAS) at N = 2 Hh
+ * into pre = [value | gate] (columns [0, Hh) and [Hh, 2 Hh) of a row), then
+ *   dmi_glu_fwd:  h[m, j] = bf16(val * act(gate)),  val = pre[m, j], gate = pre[m, Hh + j], read as bf16, computed in fp32;
+ *   dmi_glu_bwd:  dpre[m, j] = bf16(dh * act(gate)),  dpre[m, Hh + j] = bf16(dh * val * act'(gate)),  dh = dh[m, j].
+ * act = DMI_GEMM_RELU (relu'(0) = 0, the h > 0 convention of DMI_GEMM_RELU_MASK) or DMI_GEMM_GELU (the tanh form and its derivative
+ * as dmi_gemm_nt_gelu / _gelu_grad evaluate them).  Streaming kernels over 16-byte pieces with 64-bit addresses: M > 0, Hh % 8 == 0,
+ * every pointer 16-byte aligned, every leading dimension a multiple of 8 and at least the row (Hh for h and dh, 2 Hh for pre and
+ * dpre); nothing outside those rows and columns is touched.  DMI_ERR_INVALID, naming the argument, otherwise -- and no launch. */
+int dmi_glu_fwd(const uint16_t* pre, int ldpre, uint16_t* h, int ldh, int64_t M, int Hh, int act, void* stream);
+int dmi_glu_bwd(const uint16_t* dh, int lddh, const uint16_t* pre, int ldpre, uint16_t* dpre, int lddpre, int64_t M, int Hh, int act,
+                void* stream);
 /* An input-gradient product whose result arrives at a LayerNorm, with that LayerNorm's BACKWARD fused into the epilogue (reference:
  * the backward of src/dalle_mtf/layers.py:30-33 + models.py:387-388 behind models.py:330 / :333 -- norm_1 <- QKV, norm_2 <- FFN-1):
  *   dy = bf16(A . Bt^T) [M, N];  xh = (x - mean) * rstd;  dx[M, N] = bf16(rstd * (dy*gamma - mean_n(dy*gamma) - xh * mean_n(dy*gamma*xh)) + dres)

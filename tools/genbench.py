@@ -1,6 +1,6 @@
 """Generation throughput in one process (random weights): the KV-cached graph sampler against the plain sampler (one full
 forward per position), and the per-position cost of the draw variants (top-k, top-k + top-p, + log-likelihood).
-    python tools/genbench.py --shape example|coco --batch B [--guidance-scale S] [--rotary 1d|axial] [--token-shift] [--out FILE.json]
+    python tools/genbench.py --shape example|coco --batch B [--guidance-scale S] [--rotary 1d|axial] [--token-shift] [--ff-glu] [--activation relu|gelu] [--out FILE.json]
     python tools/genbench.py --kernels        # the two draw kernels alone (time them under rocprofv3 --kernel-trace --stats)
 The plain sampler is timed over its last --plain-positions positions (an image prefix teacher-forces the rest; each of its
 positions is one full forward, so the rate does not depend on which positions are timed).
@@ -8,7 +8,9 @@ positions is one full forward, so the rate does not depend on which positions ar
 the B / 2 generated rows, and the plain sampler is left out.
 --rotary SCHEME sets the config key "rotary_emb": one dmi_rope_qk_decode launch more per layer and position.
 --token-shift sets the config key "token_shift": the two block LayerNorms of every layer leave the fused prologue form, and one
-dmi_token_shift_decode launch follows each."""
+dmi_token_shift_decode launch follows each.
+--ff-glu sets the config key "ff_glu" (with --activation gelu: GEGLU): FFN-1 of the decode step is 8 n_embd wide with its bias only, and
+one dmi_glu_fwd launch follows it."""
 import argparse
 import json
 import os
@@ -32,12 +34,14 @@ def timed(fn, reps=1):
     return (time.perf_counter() - t0) / reps, r
 
 
-def engine_bench(shape, B, plain_positions, guidance_scale=1.0, rotary=None, token_shift=False):
+def engine_bench(shape, B, plain_positions, guidance_scale=1.0, rotary=None, token_shift=False, ff_glu=False, activation=None):
     from src.dalle_mtf.engine import DalleEngine
     c = SHAPES[shape]
     T, P, tv = 256, 1024, 50258
     eng = DalleEngine(c["d"], c["L"], c["H"], tv, c["iv"], T, P, batch_size=B, hparams=dict(lr=1e-3, train_steps=10, **c["hp"], **({"rotary_emb": rotary} if rotary else {}),
-                                                                                                **({"token_shift": True} if token_shift else {})))
+                                                                                                **({"token_shift": True} if token_shift else {}),
+                                                                                                **({"ff_glu": True} if ff_glu else {}),
+                                                                                                **({"activation_fn": activation} if activation else {})))
     eng.init_params(seed=1)
     guided = guidance_scale != 1.0
     R = B // 2 if guided else B                   # generated rows per call
@@ -49,6 +53,10 @@ def engine_bench(shape, B, plain_positions, guidance_scale=1.0, rotary=None, tok
         res["rotary_emb"] = rotary
     if token_shift:
         res["token_shift"] = True
+    if ff_glu:
+        res["ff_glu"] = True
+    if activation:
+        res["activation_fn"] = activation
     variants = (("top_k", dict(temperature=1.0, top_k=32)), ("top_k+top_p", dict(temperature=1.0, top_k=32, top_p=0.9)),
                 ("top_k+top_p+logp", dict(temperature=1.0, top_k=32, top_p=0.9, return_logprobs=True)),
                 ("top_p", dict(temperature=1.0, top_p=0.9)))
@@ -105,11 +113,13 @@ def main():
     ap.add_argument("--guidance-scale", dest="guidance_scale", type=float, default=1.0)
     ap.add_argument("--rotary", choices=("1d", "axial"), default=None)
     ap.add_argument("--token-shift", dest="token_shift", action="store_true")
+    ap.add_argument("--ff-glu", dest="ff_glu", action="store_true")
+    ap.add_argument("--activation", choices=("relu", "gelu"), default=None)
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = kernel_bench(a.reps) if a.kernels else engine_bench(a.shape, a.batch, a.plain_positions, a.guidance_scale, a.rotary, a.token_shift)
+    res = kernel_bench(a.reps) if a.kernels else engine_bench(a.shape, a.batch, a.plain_positions, a.guidance_scale, a.rotary, a.token_shift, a.ff_glu, a.activation)
     res["device"] = torch.cuda.get_device_name(0)
     line = json.dumps(res)
     print(line)
