@@ -599,6 +599,342 @@ extern "C" int dmi_rope_qk_decode(uint16_t* fresh, const float* cs, int B, int S
 }
 
 // =====================================================================================
+// QK normalisation (DESIGN.md §4 "QK norm"): q and k RMS-normalised per head with learned gains, in place in the qkv layout
+// =====================================================================================
+// As the rotation: one wave per row, lane l takes 16-byte pieces l, l + 64, ..; a head is G = head_dim / 8 adjacent pieces, so the G
+// lanes that hold it are an aligned group of the wave (64 % G == 0 and the row's piece count is a multiple of G) and the head's sum
+// is G's log2 xor-exchanges inside the wave -- no LDS, no atomics.  Every lane of the wave runs the exchanges; lanes behind the
+// row's last piece carry zeros and store nothing.  y = (x r) (g c), c = head_dim^(-1/2) for q and 1 for k.
+#define QKN_EPS 1e-6f
+template <int HD>
+__device__ __forceinline__ constexpr float qkn_scale() { return HD == 64 ? 0.125f : 0.08838834764831845f; }
+
+template <int G, typename T>
+__device__ __forceinline__ T qkn_group_sum(T x) {
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+
+// the rotation of rope_piece on eight fp32 values: t = the piece's 8 floats of the table row, sgn = +1 rotates, -1 rotates back
+template <typename T>
+__device__ __forceinline__ void qkn_rotate8(T* y, const float* __restrict__ t, T sgn) {
+  const f32x4 t0 = ((const f32x4*)t)[0], t1 = ((const f32x4*)t)[1];
+  const T c[4] = {(T)t0[0], (T)t0[2], (T)t1[0], (T)t1[2]};
+  const T s[4] = {(T)t0[1] * sgn, (T)t0[3] * sgn, (T)t1[1] * sgn, (T)t1[3] * sgn};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const T a = y[2 * j], b = y[2 * j + 1];
+    y[2 * j] = a * c[j] - b * s[j];
+    y[2 * j + 1] = a * s[j] + b * c[j];
+  }
+}
+
+// one piece of the forward; col = its first column inside [0, 2 H head_dim), Hhd = H head_dim (columns below it are q's).  pre_p
+// (nullable): where the unnormalised piece also goes.  cs_row (nullable): the table row whose rotation follows in fp32, so the
+// result is rounded once.  The full and the decode kernel share this body: the same values give the same bits.
+template <int HD>
+__device__ __forceinline__ void qkn_fwd_piece(bf16_t* __restrict__ p, bf16_t* __restrict__ pre_p, const bf16_t* __restrict__ gq,
+                                              const bf16_t* __restrict__ gk, const float* __restrict__ cs_row, int col, int Hhd,
+                                              bool active) {
+  u32x4 raw = {0u, 0u, 0u, 0u};
+  if (active) raw = *(const u32x4*)p;
+  float x[8], g[8], y[8];
+  unpack8(raw, x);
+  float ss = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ss = fmaf(x[j], x[j], ss);
+  ss = qkn_group_sum<HD / 8>(ss);
+  if (!active) return;
+  const float r = rsqrtf(ss * (1.f / HD) + QKN_EPS);
+  const bool isq = col < Hhd;
+  const int j0 = col & (HD - 1);
+  unpack8(*(const u32x4*)((isq ? gq : gk) + j0), g);
+  const float c = isq ? qkn_scale<HD>() : 1.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) y[j] = (x[j] * r) * (g[j] * c);
+  if (pre_p) *(u32x4*)pre_p = raw;
+  if (cs_row) qkn_rotate8<float>(y, cs_row + j0, 1.f);
+  *(u32x4*)p = pack8(y);
+}
+
+template <int HD>
+__global__ __launch_bounds__(256) void qk_norm_fwd_kernel(bf16_t* __restrict__ qkv, int ld, bf16_t* __restrict__ pre,
+                                                          const bf16_t* __restrict__ gq, const bf16_t* __restrict__ gk,
+                                                          const float* __restrict__ cs, int64_t rows, int S, int pieces) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  int64_t r = (int64_t)blockIdx.x * 4 + wid;
+  if (r >= rows) return;      // (a whole wave leaves: the exchanges below stay inside one wave)
+  int s = (int)(r % S);
+  const int ds = (int)(stride % S);
+  const int Hhd = pieces * 4;
+  for (; r < rows; r += stride) {
+    bf16_t* row = qkv + r * (int64_t)ld;
+    bf16_t* prow = pre ? pre + r * (int64_t)(pieces * 8) : nullptr;
+    const float* cs_row = cs ? cs + (int64_t)s * HD : nullptr;
+    for (int c0 = 0; c0 < pieces; c0 += 64) {
+      const int c = c0 + lane;
+      qkn_fwd_piece<HD>(row + c * 8, prow ? prow + c * 8 : nullptr, gq, gk, cs_row, c * 8, Hhd, c < pieces);
+    }
+    s += ds;
+    if (s >= S) s -= S;
+  }
+}
+
+// The decode step: one block per row of the [B, 3 H head_dim] staging buffer.  With a table every row sits at table row pos (from
+// device memory when pos_dev is given; outside [0, S) the launch writes nothing); without one the position is not read.
+template <int HD>
+__global__ __launch_bounds__(256) void qk_norm_decode_kernel(bf16_t* __restrict__ fresh, int ld, const bf16_t* __restrict__ gq,
+                                                             const bf16_t* __restrict__ gk, const float* __restrict__ cs, int S,
+                                                             int pieces, int pos, const int* __restrict__ pos_dev) {
+  const float* cs_row = nullptr;
+  if (cs) {
+    if (pos_dev) pos = *pos_dev;
+    if (pos < 0 || pos >= S) return;
+    cs_row = cs + (int64_t)pos * HD;
+  }
+  bf16_t* row = fresh + (int64_t)blockIdx.x * ld;
+  for (int c0 = 0; c0 < pieces; c0 += 256) {
+    const int c = c0 + threadIdx.x;
+    qkn_fwd_piece<HD>(row + c * 8, nullptr, gq, gk, cs_row, c * 8, pieces * 4, c < pieces);
+  }
+}
+
+// Backward, in place on the q | k columns of dqkv; x = the unnormalised q | k the forward kept in `pre` (packed [rows, 2 H head_dim]).
+// With a table dy is first rotated back (the transpose of the forward's rotation).  With xh = x r(x), u = g c, a = u dy:
+//   dx = r (a - xh mean_j(a_j xh_j))            fp32, rounded once to bf16
+//   dg_j = c sum_{rows, heads} dy_j xh_j        accumulated in float64 from float64 terms: the sum of squares and r are float64 (r for
+//                                               dx is that r rounded to fp32); dy_j x_j, the product of two bf16 values, is
+//                                               exact in fp32, and with a table the rotation's cos r, sin r are float64
+// 1 / sqrt(a) in float64: the hardware seed (good to about 2^-23) and two Newton steps, each squaring the error
+__device__ __forceinline__ double qkn_rsqrt64(double a) {
+  double y = __builtin_amdgcn_rsq(a);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const double e = fma(-a * y, y, 1.0);
+    y = fma(0.5 * y, e, y);
+  }
+  return y;
+}
+
+// one piece: dp = its place in dqkv, xp in pre, u = the lane's eight g c, cs_piece = its 8 floats of the table row (ROPE), acc = the
+// lane's eight float64 gain sums of this half (q or k)
+template <int HD, bool ROPE>
+__device__ __forceinline__ void qkn_bwd_piece(bf16_t* __restrict__ dp, const bf16_t* __restrict__ xp, const float* u,
+                                              const float* __restrict__ cs_piece, bool active, double* acc) {
+  constexpr int G = HD / 8;
+  u32x4 rdy = {0u, 0u, 0u, 0u}, rx = {0u, 0u, 0u, 0u};
+  if (active) {
+    rdy = *(const u32x4*)dp;
+    rx = *(const u32x4*)xp;
+  }
+  float fy[8], x[8];
+  unpack8(rdy, fy);
+  unpack8(rx, x);
+  double ss = 0.0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ss = fma((double)x[j], (double)x[j], ss);
+  ss = qkn_group_sum<G>(ss);
+  const double rd = qkn_rsqrt64(ss * (1.0 / HD) + (double)QKN_EPS);
+  const float rf = (float)rd;
+  if constexpr (ROPE) {
+    // dy rotated back is (a c + b s, b c - a s) over the pair (a, b): its terms are sums of the exact fp32 products a x, b x times
+    // c r, s r in float64; the dx path below takes the same rotation in fp32
+    const f32x4 t0 = ((const f32x4*)cs_piece)[0], t1 = ((const f32x4*)cs_piece)[1];
+    const float cc[4] = {t0[0], t0[2], t1[0], t1[2]}, sn[4] = {t0[1], t0[3], t1[1], t1[3]};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float ya = fy[2 * i], yb = fy[2 * i + 1], x0 = x[2 * i], x1 = x[2 * i + 1];
+      const double cr = (double)cc[i] * rd, sr = (double)sn[i] * rd;
+      acc[2 * i] = fma((double)(ya * x0), cr, fma((double)(yb * x0), sr, acc[2 * i]));
+      acc[2 * i + 1] = fma((double)(yb * x1), cr, fma(-(double)(ya * x1), sr, acc[2 * i + 1]));
+      fy[2 * i] = ya * cc[i] + yb * sn[i];
+      fy[2 * i + 1] = yb * cc[i] - ya * sn[i];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = fma((double)(fy[j] * x[j]), rd, acc[j]);
+  }
+  float a[8], xh[8];
+  float t = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    xh[j] = x[j] * rf;
+    a[j] = u[j] * fy[j];
+    t = fmaf(a[j], xh[j], t);
+  }
+  const float m = qkn_group_sum<G>(t) * (1.f / HD);
+  if (active) {
+    float o[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = rf * (a[j] - xh[j] * m);
+    *(u32x4*)dp = pack8(o);
+  }
+}
+
+// A lane's channel inside its head, (8 lane) mod head_dim, is the same in every pass over a row (64 pieces are a multiple of
+// head_dim, and so is the row's q half), so it keeps eight q and eight k sums in registers for all its rows; the q half and the k half
+// of a row are walked one after the other, which makes q-or-k a property of the loop, not of the lane.  The sums are then added over
+// the wave's lanes of equal channel (xor-exchanges at distances G .. 32), over the block's four waves through LDS in a fixed order,
+// and leave as one partial row [dgq | dgk] of 2 head_dim doubles per block.
+template <int HD, bool ROPE>
+__global__ __launch_bounds__(256) void qk_norm_bwd_kernel(bf16_t* __restrict__ dqkv, int ld, const bf16_t* __restrict__ pre,
+                                                          const bf16_t* __restrict__ gq, const bf16_t* __restrict__ gk,
+                                                          const float* __restrict__ cs, double* __restrict__ part, int64_t rows,
+                                                          int S, int pieces) {
+  constexpr int G = HD / 8;
+  __shared__ double sm[4][2 * HD];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  const int Q = pieces / 2;                       // the pieces of the q half; a multiple of G
+  const int j0 = (lane * 8) & (HD - 1);
+  float uq[8], uk[8];
+  unpack8(*(const u32x4*)(gq + j0), uq);
+  unpack8(*(const u32x4*)(gk + j0), uk);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) uq[j] *= qkn_scale<HD>();
+  double accq[8], acck[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) accq[j] = acck[j] = 0.0;
+  int64_t r = (int64_t)blockIdx.x * 4 + wid;
+  int s = (int)(r % S);
+  const int ds = (int)(stride % S);
+  for (; r < rows; r += stride) {
+    bf16_t* drow = dqkv + r * (int64_t)ld;
+    const bf16_t* prow = pre + r * (int64_t)(pieces * 8);
+    const float* cs_piece = ROPE ? cs + (int64_t)s * HD + j0 : nullptr;
+#pragma unroll 1
+    for (int c = lane; c - lane < Q; c += 64) qkn_bwd_piece<HD, ROPE>(drow + c * 8, prow + c * 8, uq, cs_piece, c < Q, accq);
+#pragma unroll 1
+    for (int c = lane; c - lane < Q; c += 64)
+      qkn_bwd_piece<HD, ROPE>(drow + (Q + c) * 8, prow + (Q + c) * 8, uk, cs_piece, c < Q, acck);
+    s += ds;
+    if (s >= S) s -= S;
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+#pragma unroll
+    for (int o = G; o < 64; o <<= 1) {
+      accq[j] += __shfl_xor(accq[j], o, 64);
+      acck[j] += __shfl_xor(acck[j], o, 64);
+    }
+  }
+  if (lane < G) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      sm[wid][j0 + j] = accq[j];
+      sm[wid][HD + j0 + j] = acck[j];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * HD) {
+    const int t = threadIdx.x;
+    const double sum = (sm[0][t] + sm[1][t]) + (sm[2][t] + sm[3][t]);
+    part[(int64_t)blockIdx.x * (2 * HD) + t] = t < HD ? sum * (HD == 64 ? 0.125 : 0.08838834764831845) : sum;   // c in float64
+  }
+}
+
+// dgq | dgk = the column sums of the P partial rows, in a fixed order, rounded once to fp32: 16 columns x 16 row groups per block
+__global__ __launch_bounds__(256) void qk_norm_bwd_finish_kernel(const double* __restrict__ part, float* __restrict__ dgq,
+                                                                 float* __restrict__ dgk, int P, int hd) {
+  __shared__ double sm[16][17];
+  const int cl = threadIdx.x & 15, grp = threadIdx.x >> 4;
+  const int c = blockIdx.x * 16 + cl;
+  const int nc = 2 * hd;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  if (c < nc) {
+    int p = grp;
+    for (; p + 48 < P; p += 64) {      // four independent loads in flight per thread
+      const double* q = part + (int64_t)p * nc + c;
+      a0 += q[0];
+      a1 += q[16 * nc];
+      a2 += q[32 * nc];
+      a3 += q[48 * nc];
+    }
+    for (; p < P; p += 16) a0 += part[(int64_t)p * nc + c];
+  }
+  sm[grp][cl] = (a0 + a1) + (a2 + a3);
+  __syncthreads();
+  if (grp == 0 && c < nc) {
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) s += sm[q][cl];
+    if (c < hd) dgq[c] = (float)s;
+    else dgk[c - hd] = (float)s;
+  }
+}
+
+// blocks of four rows, at most 8 per CU (as dmi_rope_qk); the backward leaves one partial row per block
+static inline int64_t qkn_blocks(int64_t rows) {
+  const int64_t blocks = cdiv64(rows, 4);
+  return blocks > 256 * 8 ? 256 * 8 : blocks;
+}
+
+#define DMI_REQUIRE_QKN(name, ld, rows, S, H, head_dim)                                                                          \
+  do {                                                                                                                           \
+    DMI_REQUIRE_ROPE(name, H, head_dim);                                                                                         \
+    DMI_REQUIRE((rows) > 0 && (S) > 0, name ": empty shape (rows=%lld S=%d)", (long long)(rows), (int)(S));                       \
+    DMI_REQUIRE((ld) >= 2 * (H) * (head_dim) && (ld) % 8 == 0, name ": ld must be a multiple of 8 and at least 2 H head_dim (ld=%d)", \
+                (int)(ld));                                                                                                      \
+  } while (0)
+
+extern "C" int dmi_qk_norm_fwd(uint16_t* qkv, int ld, uint16_t* pre, const uint16_t* gq, const uint16_t* gk, const float* cs,
+                               int64_t rows, int S, int H, int head_dim, void* stream) {
+  DMI_REQUIRE(qkv && gq && gk, "qk_norm_fwd: null pointer");
+  DMI_REQUIRE_QKN("qk_norm_fwd", ld, rows, S, H, head_dim);
+  DMI_REQUIRE((((uintptr_t)qkv | (uintptr_t)pre | (uintptr_t)gq | (uintptr_t)gk | (uintptr_t)cs) & 15) == 0,
+              "qk_norm_fwd: buffers must be 16-byte aligned");
+  const dim3 grid((unsigned)qkn_blocks(rows)), blk(256);
+  const int pieces = 2 * H * head_dim / 8;
+  if (head_dim == 64) qk_norm_fwd_kernel<64><<<grid, blk, 0, (hipStream_t)stream>>>(qkv, ld, pre, gq, gk, cs, rows, S, pieces);
+  else qk_norm_fwd_kernel<128><<<grid, blk, 0, (hipStream_t)stream>>>(qkv, ld, pre, gq, gk, cs, rows, S, pieces);
+  DMI_CHECK_LAUNCH("qk_norm_fwd");
+  return DMI_OK;
+}
+
+extern "C" int64_t dmi_qk_norm_bwd_workspace_bytes(int64_t rows, int head_dim) {
+  return rows > 0 && head_dim > 0 ? qkn_blocks(rows) * 2 * (int64_t)head_dim * 8 : 0;
+}
+
+extern "C" int dmi_qk_norm_bwd(uint16_t* dqkv, int ld, const uint16_t* pre, const uint16_t* gq, const uint16_t* gk, const float* cs,
+                               float* dgq, float* dgk, void* workspace, int64_t rows, int S, int H, int head_dim, void* stream) {
+  DMI_REQUIRE(dqkv && pre && gq && gk && dgq && dgk && workspace, "qk_norm_bwd: null pointer");
+  DMI_REQUIRE_QKN("qk_norm_bwd", ld, rows, S, H, head_dim);
+  DMI_REQUIRE((((uintptr_t)dqkv | (uintptr_t)pre | (uintptr_t)gq | (uintptr_t)gk | (uintptr_t)cs | (uintptr_t)dgq | (uintptr_t)dgk |
+                (uintptr_t)workspace) & 15) == 0, "qk_norm_bwd: buffers must be 16-byte aligned");
+  const int P = (int)qkn_blocks(rows);
+  const dim3 grid((unsigned)P), blk(256);
+  const int pieces = 2 * H * head_dim / 8;
+  double* part = (double*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  if (head_dim == 64 && cs) qk_norm_bwd_kernel<64, true><<<grid, blk, 0, st>>>(dqkv, ld, pre, gq, gk, cs, part, rows, S, pieces);
+  else if (head_dim == 64) qk_norm_bwd_kernel<64, false><<<grid, blk, 0, st>>>(dqkv, ld, pre, gq, gk, cs, part, rows, S, pieces);
+  else if (cs) qk_norm_bwd_kernel<128, true><<<grid, blk, 0, st>>>(dqkv, ld, pre, gq, gk, cs, part, rows, S, pieces);
+  else qk_norm_bwd_kernel<128, false><<<grid, blk, 0, st>>>(dqkv, ld, pre, gq, gk, cs, part, rows, S, pieces);
+  DMI_CHECK_LAUNCH("qk_norm_bwd");
+  qk_norm_bwd_finish_kernel<<<dim3((2 * head_dim + 15) / 16), blk, 0, st>>>(part, dgq, dgk, P, head_dim);
+  DMI_CHECK_LAUNCH("qk_norm_bwd_finish");
+  return DMI_OK;
+}
+
+extern "C" int dmi_qk_norm_decode(uint16_t* fresh, const uint16_t* gq, const uint16_t* gk, const float* cs, int B, int S, int H,
+                                  int head_dim, int pos, const int* pos_dev, void* stream) {
+  DMI_REQUIRE(fresh && gq && gk, "qk_norm_decode: null pointer");
+  DMI_REQUIRE_ROPE("qk_norm_decode", H, head_dim);
+  DMI_REQUIRE(B > 0 && S > 0, "qk_norm_decode: empty shape (B=%d S=%d)", B, S);
+  DMI_REQUIRE(!cs || pos_dev || (pos >= 0 && pos < S), "qk_norm_decode: pos outside [0, S) (pos=%d S=%d)", pos, S);
+  DMI_REQUIRE((((uintptr_t)fresh | (uintptr_t)gq | (uintptr_t)gk | (uintptr_t)cs) & 15) == 0,
+              "qk_norm_decode: buffers must be 16-byte aligned");
+  const dim3 grid((unsigned)B), blk(256);
+  const int ld = 3 * H * head_dim, pieces = 2 * H * head_dim / 8;
+  if (head_dim == 64) qk_norm_decode_kernel<64><<<grid, blk, 0, (hipStream_t)stream>>>(fresh, ld, gq, gk, cs, S, pieces, pos, pos_dev);
+  else qk_norm_decode_kernel<128><<<grid, blk, 0, (hipStream_t)stream>>>(fresh, ld, gq, gk, cs, S, pieces, pos, pos_dev);
+  DMI_CHECK_LAUNCH("qk_norm_decode");
+  return DMI_OK;
+}
+
+// =====================================================================================
 // Token shift (DESIGN.md §4 "Token shift"): half of every row's channels gathered from an earlier row of its sequence
 // =====================================================================================
 // The row a 16-byte piece of sequence position s is read from, as an offset in rows; TS_ZERO: the piece is +0.  ch = the piece's

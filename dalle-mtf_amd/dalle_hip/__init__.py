@@ -72,6 +72,10 @@ def _declare(L):
         "dmi_dropout_bwd": (I, [P, P, L64, I, U64, I, P]),
         "dmi_rope_qk": (I, [P, I, P, L64, I, I, I, I, P]),
         "dmi_rope_qk_decode": (I, [P, P, I, I, I, I, I, P, P]),
+        "dmi_qk_norm_fwd": (I, [P, I, P, P, P, P, L64, I, I, I, P]),
+        "dmi_qk_norm_bwd_workspace_bytes": (L64, [L64, I]),
+        "dmi_qk_norm_bwd": (I, [P, I, P, P, P, P, P, P, P, L64, I, I, I, P]),
+        "dmi_qk_norm_decode": (I, [P, P, P, P, I, I, I, I, I, P, P]),
         "dmi_token_shift": (I, [P, P, P, L64, I, I, I, I, I, P]),
         "dmi_token_shift_decode": (I, [P, P, P, I, I, I, I, I, I, P, P]),
         "dmi_layernorm_bwd_workspace_bytes": (L64, [L64, I]),
@@ -278,6 +282,50 @@ def rope_qk_decode(fresh, cs, B, S, H, head_dim, pos=0, pos_dev=None):
     assert fresh.dtype == torch.bfloat16 and fresh.numel() >= B * 3 * H * head_dim
     assert cs.dtype == torch.float32 and cs.numel() >= S * head_dim and (pos_dev is None or pos_dev.dtype == torch.int32)
     _check(lib().dmi_rope_qk_decode(_p(fresh), _p(cs), B, S, H, head_dim, int(pos), _p(pos_dev), _stream()), "rope_qk_decode")
+
+
+def qk_norm_fwd(qkv, gq, gk, rows, S, H, head_dim, pre=None, cs=None, ld=None):
+    """RMS-normalises q | k of every row of the [rows, ld] bf16 buffer in the qkv layout in place, per head, with the bf16 [head_dim]
+    gains gq, gk and head_dim^(-1/2) on q (ld defaults to 3 H head_dim).  pre: also takes the unnormalised q | k, packed bf16
+    [rows, 2 H head_dim]; cs: the rope_qk table, whose rotation of row r % S follows in the same pass (one rounding)"""
+    _dev(qkv, gq, gk, pre, cs)
+    ld = 3 * H * head_dim if ld is None else int(ld)
+    assert qkv.dtype == torch.bfloat16 and qkv.numel() >= rows * ld
+    assert gq.dtype == torch.bfloat16 and gk.dtype == torch.bfloat16 and gq.numel() >= head_dim and gk.numel() >= head_dim
+    assert pre is None or (pre.dtype == torch.bfloat16 and pre.numel() >= rows * 2 * H * head_dim)
+    assert cs is None or (cs.dtype == torch.float32 and cs.numel() >= S * head_dim)
+    _check(lib().dmi_qk_norm_fwd(_p(qkv), ld, _p(pre), _p(gq), _p(gk), _p(cs), rows, S, H, head_dim, _stream()), "qk_norm_fwd")
+
+
+def qk_norm_bwd_workspace_bytes(rows, head_dim):
+    return int(lib().dmi_qk_norm_bwd_workspace_bytes(rows, head_dim))
+
+
+def qk_norm_bwd(dqkv, pre, gq, gk, dgq, dgk, ws, rows, S, H, head_dim, cs=None, ld=None):
+    """the gradient of qk_norm_fwd, in place on q | k of dqkv (with cs: rotated back first); pre: what the forward kept; dgq, dgk:
+    fp32 [head_dim], written; ws: qk_norm_bwd_workspace_bytes(rows, head_dim) bytes"""
+    _dev(dqkv, pre, gq, gk, dgq, dgk, ws, cs)
+    ld = 3 * H * head_dim if ld is None else int(ld)
+    assert dqkv.dtype == torch.bfloat16 and dqkv.numel() >= rows * ld
+    assert pre.dtype == torch.bfloat16 and pre.numel() >= rows * 2 * H * head_dim
+    assert gq.dtype == torch.bfloat16 and gk.dtype == torch.bfloat16 and gq.numel() >= head_dim and gk.numel() >= head_dim
+    assert dgq.dtype == torch.float32 and dgk.dtype == torch.float32 and dgq.numel() >= head_dim and dgk.numel() >= head_dim
+    assert ws.numel() * ws.element_size() >= qk_norm_bwd_workspace_bytes(rows, head_dim)
+    assert cs is None or (cs.dtype == torch.float32 and cs.numel() >= S * head_dim)
+    _check(lib().dmi_qk_norm_bwd(_p(dqkv), ld, _p(pre), _p(gq), _p(gk), _p(cs), _p(dgq), _p(dgk), _p(ws), rows, S, H, head_dim,
+                                 _stream()), "qk_norm_bwd")
+
+
+def qk_norm_decode(fresh, gq, gk, B, S, H, head_dim, cs=None, pos=0, pos_dev=None):
+    """qk_norm_fwd of the decode step's [B, 3 H head_dim] staging buffer; with cs every row at position pos (pos_dev: read from
+    device memory; outside [0, S) the launch writes nothing), without it the position is not used"""
+    _dev(fresh, gq, gk, cs, pos_dev)
+    assert fresh.dtype == torch.bfloat16 and fresh.numel() >= B * 3 * H * head_dim
+    assert gq.dtype == torch.bfloat16 and gk.dtype == torch.bfloat16 and gq.numel() >= head_dim and gk.numel() >= head_dim
+    assert cs is None or (cs.dtype == torch.float32 and cs.numel() >= S * head_dim)
+    assert pos_dev is None or pos_dev.dtype == torch.int32
+    _check(lib().dmi_qk_norm_decode(_p(fresh), _p(gq), _p(gk), _p(cs), B, S, H, head_dim, int(pos), _p(pos_dev), _stream()),
+           "qk_norm_decode")
 
 
 def token_shift(x, y, rows, S, T, G, d, inverse=False, hist=None):

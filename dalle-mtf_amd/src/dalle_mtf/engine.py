@@ -37,6 +37,7 @@ from .activations import check_activation
 from .dropout import SITE_POSITION, SITE_TOKEN, resolve_dropout, site_attention, site_key, site_mlp
 from .layout import ALIGN, ParamLayout, _round_up, adafactor_factored_dims, adafactor_table, reference_init   # noqa: F401  (re-exported)
 from .ff_glu import resolve_ff_glu
+from .qk_norm import GAIN_NAMES, resolve_qk_norm
 from .ema import ema_decay_at, one_minus_decay, resolve_ema, resolve_weights   # noqa: F401  (ema_decay_at: part of the engine's surface)
 from .loss_weights import position_weights, resolve_loss_weights
 from .rotary import DEFAULT_BASE, resolve_rotary, rotary_table
@@ -130,6 +131,8 @@ class DalleEngine:
         self.token_shift = resolve_token_shift(hparams, n_embd, image_seq_len)
         # hparams["ff_glu"] (dalle_mtf.ff_glu): the gated FFN, h = value * act(gate) from an FFN-1 of width 8d
         self.ff_glu = resolve_ff_glu(hparams)
+        # hparams["qk_norm"] (dalle_mtf.qk_norm): q and k RMS-normalised per head with learned gains behind the QKV product
+        self.qk_norm = resolve_qk_norm(hparams)
         if not torch.cuda.is_available():
             raise dh.DalleHipError("DalleEngine needs a HIP device (MI355X); there is no CPU fallback")
         dh.lib()
@@ -152,7 +155,7 @@ class DalleEngine:
         self.hp = dict(hparams or {})
         # the FFN activation (reference src/dalle_mtf/models.py:317-324): "relu" (default) or "gelu" (dalle_mtf.activations)
         self.activation = check_activation(self.hp.get("activation_fn") or "relu")
-        self.lay = ParamLayout(n_embd, n_layers, n_heads, self.V, self.S, ff_glu=self.ff_glu)
+        self.lay = ParamLayout(n_embd, n_layers, n_heads, self.V, self.S, ff_glu=self.ff_glu, qk_norm=self.qk_norm)
         self.F1 = self.lay.ffn1      # FFN-1's output width: 4d, gated [value | gate] = 8d
         self.Vp = self.lay.Vp
         n = self.lay.total
@@ -178,6 +181,7 @@ class DalleEngine:
         self.last_dropout: Dict[int, Tuple[int, int]] = {}
         self._microbatch = 0
         self._drop = False
+        self._keep_pre = False      # qk_norm: the last forward was a training forward, which keeps the unnormalised q | k
         # state that comes into being on first use (None until then)
         self._t_table = None                      # refresh_compute_copies: the batched transpose's descriptor table
         self._kv = self._dec = None               # the sampler's key/value caches (under recompute_grad) and decode buffers
@@ -467,6 +471,9 @@ class DalleEngine:
             return [bufs[l % nl] for l in range(L)]
         self.xn1 = per_layer(lambda: torch.empty(M, d, **b16))
         self.qkv = per_layer(lambda: torch.empty(M, 3 * d, **b16))
+        # qk_norm: the unnormalised q | k of every row, what dmi_qk_norm_bwd recomputes the statistics from (L * M * 2d * 2 bytes, one
+        # shared buffer under recompute_grad; DESIGN.md §4 "QK norm"); off: nothing
+        self.qk_pre = per_layer(lambda: torch.empty(M, 2 * d, **b16)) if self.qk_norm else None
         self.o = per_layer(lambda: torch.empty(M, d, **b16))
         self.lse = per_layer(lambda: torch.empty(B, H, S, **f32))
         self.x1 = per_layer(lambda: torch.empty(M, d, **b16))
@@ -528,7 +535,8 @@ class DalleEngine:
         self.delta = torch.empty(3, B, H, S, **f32)   # delta | (lse, delta) pairs for the dK/dV kernel's DMA
         wsz = max(dh.gemm_tn_workspace_bytes(M, d, Vp), *(dh.gemm_tn_workspace_bytes(M, i_, j_) for i_, j_ in self.wgrad_shapes),
                   dh.layernorm_bwd_workspace_bytes(M, d), dh.sumsq_workspace_bytes(self.lay.total),
-                  dh.gemm_nt_splitk_workspace_bytes(M // 2 + 256, d, 8))
+                  dh.gemm_nt_splitk_workspace_bytes(M // 2 + 256, d, 8),
+                  dh.qk_norm_bwd_workspace_bytes(M, self.hd) if self.qk_norm else 0)
         self.ws = torch.empty(int(wsz) + 1024, **u8)
         # the four weight gradients of a block keep their split-m slabs in separate workspaces and their seven slab reduces
         # run as ONE launch at the end of the block's backward (dmi_reduce_slabs_batch)
@@ -555,6 +563,7 @@ class DalleEngine:
         B, S, L = self.B, self.S, self.L
         assert tokens.shape == (B, S) and tokens.dtype == torch.int32
         self.tokens.copy_(tokens)
+        self._keep_pre = bool(need_grad)
         self._sort_done = None
         if need_grad:   # token-id order for the embedding backward: twelve 3-5 us launches on a side stream (see dmi_sort_tokens)
             self._launch_sort()
@@ -739,13 +748,20 @@ class DalleEngine:
         M, d, p = self.M, self.d, f"layer_{l}/"
         self._ln_of_stream(l)
         dh.gemm_nt(self.xn1[l], d, self.tview(p + "attn/qkv"), d, self.qkv[l], 3 * d, M, 3 * d, d)
-        if self.rope_cs is not None:   # the attention kernels, their backward and the decode caches see rotated q and k
+        if self.qk_norm:               # normalised, and with rotary rotated in the same pass; a training forward keeps the input
+            dh.qk_norm_fwd(self.qkv[l], *self._qk_gains(l), M, self.S, self.H, self.hd,
+                           pre=self.qk_pre[l] if self._keep_pre or rerun else None, cs=self.rope_cs)
+        elif self.rope_cs is not None:   # the attention kernels, their backward and the decode caches see rotated q and k
             dh.rope_qk(self.qkv[l], self.rope_cs, M, self.S, self.H, self.hd)
         self._attn_fwd(l, self.qkv[l], self.o[l], self.lse[l])   # no transposed copies: hardware transpose reads
         self._join_branch(l, mlp=False)
         self._ffn1(l)
         if not rerun:
             self._join_branch(l, mlp=True)
+
+    def _qk_gains(self, l, buf=None):
+        """qk_norm: layer l's (q gain, k gain), [head_dim] each, in the bf16 compute copy (or in flat buffer `buf`)"""
+        return tuple(self.view(self.pb if buf is None else buf, f"layer_{l}/{g}") for g in GAIN_NAMES)
 
     def logits(self) -> torch.Tensor:
         """fp32 logits [B,S,V] of the last forward(need_grad=False) ("go to full precision", models.py:395)."""
@@ -999,7 +1015,9 @@ class DalleEngine:
             p = f"layer_{l}/"
             cache = caches[l]                                          # [B*S, 3d]; row b*S + pos <- q | k | v of this step
             ln_dense(x, p + "norm_1", self.tview(p + "attn/qkv"), fresh, 3 * d, shift=(l, 0))
-            if self.rope_cs is not None:                               # q | k of the step at table row pos, before they enter the cache
+            if self.qk_norm:                                           # normalised (and rotated at table row pos) before they enter the cache
+                dh.qk_norm_decode(fresh, *self._qk_gains(l), B, S, H, self.hd, cs=self.rope_cs, pos_dev=D["pos_i"])
+            elif self.rope_cs is not None:                             # q | k of the step at table row pos, before they enter the cache
                 dh.rope_qk_decode(fresh, self.rope_cs, B, S, H, self.hd, pos_dev=D["pos_i"])
             self._attn_decode(l, cache, o, fresh, D["pos_i"])
             dh.gemm_nt(o, d, self.tview(p + "attn/o"), d, x1, d, B, d, d, dh.GEMM_BIAS | dh.GEMM_RESIDUAL,
@@ -1202,7 +1220,10 @@ class DalleEngine:
             if not self._d_o_chained():
                 dh.gemm_nt(dyb, d, self._w(p + "attn/o"), d, self.d_o, d, M, d, d)
             self._attn_bwd(l)
-            if self.rope_cs is not None:   # gradient w.r.t. the rotated q, k -> w.r.t. the projection's output (the rotation's transpose)
+            if self.qk_norm:   # gradient w.r.t. the normalised (and rotated) q, k -> w.r.t. the projection's output, and the gains' gradients
+                dh.qk_norm_bwd(self.dqkv, self.qk_pre[l], *self._qk_gains(l), *self._qk_gains(l, self.g), self.ws, M, self.S, self.H,
+                               self.hd, cs=self.rope_cs)
+            elif self.rope_cs is not None:   # gradient w.r.t. the rotated q, k -> w.r.t. the projection's output (the rotation's transpose)
                 dh.rope_qk(self.dqkv, self.rope_cs, M, self.S, self.H, self.hd, inverse=True)
             self._wgrad(probs, 3)
             self._ln_dgrad(2 * l, dxb, dxa)
@@ -1349,6 +1370,8 @@ class DalleEngine:
             sd["token_shift"] = True
         if self.ff_glu:                # (a checkpoint without the key is a model with the plain FFN)
             sd["ff_glu"] = True
+        if self.qk_norm:               # (a checkpoint without the key is a model without QK normalisation)
+            sd["qk_norm"] = True
         for k in ("m", "v", "af_slots"):
             if getattr(self, k) is not None:
                 sd[k] = getattr(self, k).detach().cpu()
@@ -1379,6 +1402,10 @@ class DalleEngine:
             say = lambda on: "ff_glu on (the gated FFN)" if on else "ff_glu off (the plain FFN)"   # noqa: E731
             raise ValueError(f"checkpoint was written by a model with {say(bool(sd.get('ff_glu', False)))}; this run uses "
                              f"{say(self.ff_glu)}: the weights of one do not compute the other")
+        if bool(sd.get("qk_norm", False)) != self.qk_norm:
+            say = lambda on: "qk_norm on (normalised q and k with learned gains)" if on else "qk_norm off (plain q and k)"   # noqa: E731
+            raise ValueError(f"checkpoint was written by a model with {say(bool(sd.get('qk_norm', False)))}; this run uses "
+                             f"{say(self.qk_norm)}: the weights of one do not compute the other")
         self.p.copy_(sd["p"])
         for k in ("m", "v", "af_slots"):
             if getattr(self, k) is not None:

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from .ff_glu import ffn1_width
+from .qk_norm import GAIN_NAMES
 
 ALIGN = 128  # elements
 
@@ -57,13 +58,17 @@ class ParamLayout:
     pad the vocabulary axis of the output projection to a multiple of 128; `export`/`load` translate
     to/from the reference's variable names and shapes."""
 
-    def __init__(self, n_embd, n_layers, n_heads, total_tokens, total_seq, ff_glu=False):
+    def __init__(self, n_embd, n_layers, n_heads, total_tokens, total_seq, ff_glu=False, qk_norm=False):
         d, L, V, S = n_embd, n_layers, total_tokens, total_seq
         self.d, self.L, self.V, self.S = d, L, V, S
         # mlp_linear_1's output width: 4d, or with the gated FFN (config key "ff_glu") [value | gate] = 8d; everything derived from
         # the entries -- the transposed-copy table, the reference's variable table, Adafactor's, reference_init -- follows it
         self.ff_glu = bool(ff_glu)
         f1 = self.ffn1 = ffn1_width(d, self.ff_glu)
+        # QK normalisation (config key "qk_norm"): two [head_dim] gains per layer, shared by its heads, between attn/qkv and norm_1/g
+        # -- inside the layer's bucket, so bucket_ends and ready_points keep their meaning; off: the entries are exactly the plain ones
+        self.qk_norm = bool(qk_norm)
+        qkn = [(g, (d // n_heads,)) for g in GAIN_NAMES] if self.qk_norm else []
         self.Vp = _round_up(V, 128)
         ent: List[Tuple[str, tuple]] = []
         ent += [("to_logits/linear_out/kernel", (d, self.Vp)), ("to_logits/linear_out/bias", (self.Vp,)),
@@ -74,8 +79,9 @@ class ParamLayout:
                     (p + "mlp/mlp_linear_1/kernel", (d, f1)), (p + "mlp/mlp_linear_1/bias", (f1,)),
                     (p + "norm_2/g", (d,)), (p + "norm_2/b", (d,)),
                     (p + "attn/o", (d, d)), (p + "attn/compute_output_bias/o_b", (d,)),
-                    (p + "attn/qkv", (d, 3 * d)),
-                    (p + "norm_1/g", (d,)), (p + "norm_1/b", (d,))]
+                    (p + "attn/qkv", (d, 3 * d))]
+            ent += [(p + g, shp) for g, shp in qkn]
+            ent += [(p + "norm_1/g", (d,)), (p + "norm_1/b", (d,))]
         ent += [("positional_embedding/wpe", (S, d)), ("embedding/wte", (V, d))]
         self.entries = ent
         self.offset: Dict[str, int] = {}

@@ -10,6 +10,7 @@ from .activations import resolve_activation
 from .dropout import resolve_dropout
 from .ema import resolve_ema
 from .ff_glu import resolve_ff_glu
+from .qk_norm import resolve_qk_norm
 from .engine import DalleEngine
 from .layout import ParamLayout
 from .loss_weights import resolve_loss_weights
@@ -71,6 +72,8 @@ class DALLE:
         self.token_shift = resolve_token_shift(params, n_embd, image_seq_len)
         # "ff_glu" (dalle_mtf.ff_glu): likewise; the gated FFN, mlp_linear_1 is then 8 n_embd wide
         self.ff_glu = resolve_ff_glu(params)
+        # "qk_norm" (dalle_mtf.qk_norm): likewise; q and k normalised per head, two [head_dim] gains per layer
+        self.qk_norm = resolve_qk_norm(params)
         if self.params.get("attention_dropout"):
             raise NotImplementedError("attention_dropout > 0 is not supported: embed_dropout and residual_dropout are; dropout of "
                                       "the attention weights would live inside the attention kernels (all shipped configs use 0)")
@@ -100,7 +103,7 @@ class DALLE:
     def variables(self):
         """name -> shape under the reference's checkpoint names."""
         lay = ParamLayout(self.n_embd, self.n_layers, self.n_heads, self.total_tokens, self.total_seq_dim,
-                          ff_glu=getattr(self, "ff_glu", False))
+                          ff_glu=getattr(self, "ff_glu", False), qk_norm=getattr(self, "qk_norm", False))
         return {name: shape for name, shape, _, _ in lay.reference_variables()}
 
     def sample(self, text_tokens, vae=None, temperature=1.0, top_k=0, seed=0, top_p=1.0, image_prefix=None, return_logprobs=False,

@@ -251,6 +251,7 @@ def generate(argv=None):
                 rotary_emb=eng.rotary, rotary_base=eng.rotary_base if eng.rotary is not None else None,
                 token_shift=bool(eng.token_shift),
                 ff_glu=bool(eng.ff_glu),
+                qk_norm=bool(eng.qk_norm),
                 seconds=dict(load=round(t_load, 3), sample=round(t_sample, 3), decode_and_copy=round(t_decode, 3)),
                 tokens_per_s=round(nb * Bg * (P - K) / t_sample, 1) if t_sample > 0 else None)
     with open(os.path.join(args.out, "generate.json"), "w") as f:

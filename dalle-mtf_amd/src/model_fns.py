@@ -174,6 +174,10 @@ def _build(params, mode_str):
         # "ff_glu" (dalle_mtf.ff_glu; it reaches the engine's hparams through `params`)
         logging.getLogger("dalle_mtf_amd").info("%s gated feed-forward: on (%s, mlp_linear_1 is [%d, %d])", mode_str,
                                                 "GEGLU" if eng.activation == "gelu" else "ReGLU", eng.d, eng.F1)
+    if eng.qk_norm and rank == 0:
+        # "qk_norm" (dalle_mtf.qk_norm; it reaches the engine's hparams through `params`)
+        logging.getLogger("dalle_mtf_amd").info("%s QK normalisation: on (RMS per head over %d channels, eps 1e-6, gains [%d] per layer)",
+                                                mode_str, eng.hd, eng.hd)
     eng.hp["num_microbatches"] = nmb   # reference model_fns.py:141-154 (1 when tokens_per_mb_per_replica is unset)
     params["num_microbatches"] = nmb
     state["local_bs"] = local_bs

@@ -102,6 +102,35 @@ int dmi_rope_qk(uint16_t* qkv, int ld, const float* cs, int64_t rows, int S, int
 int dmi_rope_qk_decode(uint16_t* fresh, const float* cs, int B, int S, int H, int head_dim, int pos, const int* pos_dev,
                        void* stream);
 
+/* ---- QK normalisation (project extension, config key "qk_norm"; DESIGN.md §4 "QK norm") ----
+ * Every head's query and key vector is RMS-normalised over its head_dim channels, with learned gains gq, gk (bf16 [head_dim], shared
+ * by the heads, passed as the LayerNorm gains are) and the constant c = head_dim^(-1/2) for q, 1 for k.  In fp32, eps = 1e-6:
+ *   r(x) = rsqrt(mean_j(x_j^2) + eps),   y = x r(x) g c.
+ * dmi_qk_norm_fwd: in place on columns [0, 2 H head_dim) of every row of a [rows, ld] bf16 buffer in the qkv layout (ld >= 2 H head_dim,
+ * ld % 8 == 0); the v columns are neither read nor written; row offsets are 64-bit.  pre (nullable): the unnormalised q | k of every
+ * row are also written there, packed bf16 [rows, 2 H head_dim] -- what the backward reads.  cs (nullable): the table of dmi_rope_qk;
+ * the rotation of table row r % S is applied to the fp32 y in the same pass and the result rounded once to bf16 (cs == NULL: S is
+ * only checked).  An all-zero head gives zeros.
+ * dmi_qk_norm_bwd: in place on the q | k columns of dqkv, the gradient with respect to the forward's output.  With cs it is first
+ * rotated back (the transpose, as dmi_rope_qk(inverse = 1)).  With xh = x r(x) recomputed from pre, u = g c and a = u dy:
+ *   dx = r (a - xh mean_j(a_j xh_j)),    dg_j = c sum_{rows, heads} dy_j xh_j.
+ * dgq, dgk: fp32 [head_dim], written (not accumulated).  The sums are formed in float64 from float64 terms: per-block partial rows in
+ * `workspace` (dmi_qk_norm_bwd_workspace_bytes(rows, head_dim), a pure host function), then one fixed-order reduce rounded once to
+ * fp32 -- the same inputs give the same bits.
+ * dmi_qk_norm_decode: the forward for the decode step's [B, 3 H head_dim] staging buffer.  cs, pos and pos_dev as dmi_rope_qk_decode:
+ * every row at table row pos; pos_dev != NULL reads the position from device memory and a position outside [0, S) makes the launch a
+ * no-op.  cs == NULL: no rotation and the position is not used.  Bit-equal to the matching rows of dmi_qk_norm_fwd.
+ * All: stream-ordered, no allocation, no atomics.  head_dim other than 64 / 128: DMI_ERR_UNSUPPORTED; a null pointer (other than the
+ * nullable ones), an empty shape, a buffer that is not 16-byte aligned, ld < 2 H head_dim or ld % 8 != 0, or (with cs) a by-value pos
+ * outside [0, S): DMI_ERR_INVALID -- with a message, before any launch. */
+int dmi_qk_norm_fwd(uint16_t* qkv, int ld, uint16_t* pre, const uint16_t* gq, const uint16_t* gk, const float* cs, int64_t rows,
+                    int S, int H, int head_dim, void* stream);
+int64_t dmi_qk_norm_bwd_workspace_bytes(int64_t rows, int head_dim);
+int dmi_qk_norm_bwd(uint16_t* dqkv, int ld, const uint16_t* pre, const uint16_t* gq, const uint16_t* gk, const float* cs,
+                    float* dgq, float* dgk, void* workspace, int64_t rows, int S, int H, int head_dim, void* stream);
+int dmi_qk_norm_decode(uint16_t* fresh, const uint16_t* gq, const uint16_t* gk, const float* cs, int B, int S, int H, int head_dim,
+                       int pos, const int* pos_dev, void* stream);
+
 /* ---- Token shift (project extension, config key "token_shift"; DESIGN.md §4 "Token shift") ----
  * A sequence has S = T + G * G positions: p < T is a caption position, p >= T is image token k = p - T of the G x G grid at row
  * r = k / G, column c = k % G.  y = shift(x) over rows of d bf16 channels, d % 32 == 0:

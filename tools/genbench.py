@@ -1,6 +1,6 @@
 """Generation throughput in one process (random weights): the KV-cached graph sampler against the plain sampler (one full
 forward per position), and the per-position cost of the draw variants (top-k, top-k + top-p, + log-likelihood).
-    python tools/genbench.py --shape example|coco --batch B [--guidance-scale S] [--rotary 1d|axial] [--token-shift] [--ff-glu] [--activation relu|gelu] [--out FILE.json]
+    python tools/genbench.py --shape example|coco --batch B [--guidance-scale S] [--rotary 1d|axial] [--token-shift] [--ff-glu] [--qk-norm] [--activation relu|gelu] [--out FILE.json]
     python tools/genbench.py --kernels        # the two draw kernels alone (time them under rocprofv3 --kernel-trace --stats)
 The plain sampler is timed over its last --plain-positions positions (an image prefix teacher-forces the rest; each of its
 positions is one full forward, so the rate does not depend on which positions are timed).
@@ -10,7 +10,9 @@ the B / 2 generated rows, and the plain sampler is left out.
 --token-shift sets the config key "token_shift": the two block LayerNorms of every layer leave the fused prologue form, and one
 dmi_token_shift_decode launch follows each.
 --ff-glu sets the config key "ff_glu" (with --activation gelu: GEGLU): FFN-1 of the decode step is 8 n_embd wide with its bias only, and
-one dmi_glu_fwd launch follows it."""
+one dmi_glu_fwd launch follows it.
+--qk-norm sets the config key "qk_norm": one dmi_qk_norm_decode launch more per layer and position (with --rotary it takes the place
+of dmi_rope_qk_decode)."""
 import argparse
 import json
 import os
@@ -34,13 +36,14 @@ def timed(fn, reps=1):
     return (time.perf_counter() - t0) / reps, r
 
 
-def engine_bench(shape, B, plain_positions, guidance_scale=1.0, rotary=None, token_shift=False, ff_glu=False, activation=None):
+def engine_bench(shape, B, plain_positions, guidance_scale=1.0, rotary=None, token_shift=False, ff_glu=False, activation=None, qk_norm=False):
     from src.dalle_mtf.engine import DalleEngine
     c = SHAPES[shape]
     T, P, tv = 256, 1024, 50258
     eng = DalleEngine(c["d"], c["L"], c["H"], tv, c["iv"], T, P, batch_size=B, hparams=dict(lr=1e-3, train_steps=10, **c["hp"], **({"rotary_emb": rotary} if rotary else {}),
                                                                                                 **({"token_shift": True} if token_shift else {}),
                                                                                                 **({"ff_glu": True} if ff_glu else {}),
+                                                                                                **({"qk_norm": True} if qk_norm else {}),
                                                                                                 **({"activation_fn": activation} if activation else {})))
     eng.init_params(seed=1)
     guided = guidance_scale != 1.0
@@ -55,6 +58,8 @@ def engine_bench(shape, B, plain_positions, guidance_scale=1.0, rotary=None, tok
         res["token_shift"] = True
     if ff_glu:
         res["ff_glu"] = True
+    if qk_norm:
+        res["qk_norm"] = True
     if activation:
         res["activation_fn"] = activation
     variants = (("top_k", dict(temperature=1.0, top_k=32)), ("top_k+top_p", dict(temperature=1.0, top_k=32, top_p=0.9)),
@@ -114,12 +119,13 @@ def main():
     ap.add_argument("--rotary", choices=("1d", "axial"), default=None)
     ap.add_argument("--token-shift", dest="token_shift", action="store_true")
     ap.add_argument("--ff-glu", dest="ff_glu", action="store_true")
+    ap.add_argument("--qk-norm", dest="qk_norm", action="store_true")
     ap.add_argument("--activation", choices=("relu", "gelu"), default=None)
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = kernel_bench(a.reps) if a.kernels else engine_bench(a.shape, a.batch, a.plain_positions, a.guidance_scale, a.rotary, a.token_shift, a.ff_glu, a.activation)
+    res = kernel_bench(a.reps) if a.kernels else engine_bench(a.shape, a.batch, a.plain_positions, a.guidance_scale, a.rotary, a.token_shift, a.ff_glu, a.activation, a.qk_norm)
     res["device"] = torch.cuda.get_device_name(0)
     line = json.dumps(res)
     print(line)
