@@ -563,7 +563,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restri
 //   * O is normalised by the sum of the bf16-ROUNDED probabilities (v_dot2c_f32_bf16 against (1, 1) in phase B, where the VALU idles), so
 //     the weights the MFMA applies sum to exactly 1; lse keeps the unrounded sum (the backward needs the true one).  Without this the
 //     integer maximum costs accuracy: the dominant probability is no longer exactly 1, its rounding error stops cancelling and peaked
-//     rows carry one extra bf16 rounding (O at 1.47 x pure rounding against 1.02 for the round-2 kernel; 1.05 with the rounded sum);
+//     rows carry one extra bf16 rounding.  Per-row error of O over that of pure rounding bf16(float64 O), median on peaked scores, as
+//     tests/test_attention_fwd_gpu.py measures it: 1.22 .. 1.32 without (F2_LROUNDED=0, whose worst row at S = 520 also leaves that
+//     test's budget: 2.1 x the bf16 emulation's) against 1.00 .. 1.04 for the round-2 kernel; 1.00 .. 1.05 with the rounded sum;
 //   * O leaves through LDS as whole 256-byte rows (16 B per lane, 4 rows per store instruction) instead of 8-byte pieces of 32 rows
 //     per instruction; the half-row exchange of the row maximum is a v_permlane32_swap (inline asm: the builtin aliases its two results
 //     when both inputs are one value) instead of a ds_bpermute; the next item's query rows are touched two steps before an item ends.

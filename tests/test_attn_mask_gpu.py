@@ -13,6 +13,7 @@ sys.path.insert(0, os.path.join(ROOT, "dalle-mtf_amd"))
 pytestmark = pytest.mark.gpu
 
 import attention_bwd_ref as ab  # noqa: E402
+import attention_fwd_ref as af  # noqa: E402
 import dalle_hip as dh  # noqa: E402
 from src.dalle_mtf.masks import pattern_mask  # noqa: E402
 
@@ -81,6 +82,8 @@ def _check(mask_np, B=2, H=2, seed=0, xcd=None, qkv=None):
         close(got, ref, 3e-2, 2e-2 * float(ref.abs().max()), "masked " + name)
     # per-row budget against the float64 spec of the backward on the kernel's own saved forward (tests/attention_bwd_ref.py)
     ab.within_budget(dqkv, ab.make_inputs(qkv, o, lse, d_o, B, H, S, HD, mask_np), label=f"masked _check {(B, H, S)}")
+    # ... and the forward's own budget on that o and lse (tests/attention_fwd_ref.py)
+    af.within_budget_fwd(o, lse, af.make_inputs(qkv, B, H, S, HD, mask_np), label=f"masked _check forward {(B, H, S)}")
     return qkv, d_o, plan, o, lse, dqkv
 
 

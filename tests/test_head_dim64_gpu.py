@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import attention_bwd_ref as ab
+import attention_fwd_ref as af
 import dalle_hip as dh  # noqa: E402  (path set up by conftest)
 
 pytestmark = pytest.mark.gpu
@@ -64,6 +65,8 @@ def _vs_autograd(B, H, S):
         _close(got[:, i], gref[:, i], 3e-2, 2e-2 * float(gref[:, i].abs().max()), f"d{nm}")
     # per-row budget against the float64 spec of the backward on the kernel's own saved forward (tests/attention_bwd_ref.py)
     ab.within_budget(dqkv, ab.make_inputs(qkv, o, lse, d_o, B, H, S, HD), label=f"_vs_autograd {(B, H, S)}")
+    # ... and the forward's own budget on that o and lse (tests/attention_fwd_ref.py)
+    af.within_budget_fwd(o, lse, af.make_inputs(qkv, B, H, S, HD), label=f"_vs_autograd forward {(B, H, S)}")
     return o, lse, dqkv
 
 

@@ -12,6 +12,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 import attention_bwd_ref as ab  # noqa: E402
+import attention_fwd_ref as af  # noqa: E402
 import dalle_hip as dh  # noqa: E402  (path set up by conftest)
 
 DEV = "cuda"
@@ -1051,6 +1052,8 @@ def _attention_fwd_bwd(B, H, S):
         close(got[:, i], gref[:, i], 3e-2, 2e-2 * scale, f"attn bwd d{nm}")
     # per-row budget against the float64 spec of the backward on the kernel's own saved forward (tests/attention_bwd_ref.py)
     ab.within_budget(dqkv, ab.make_inputs(qkv, o, lse, d_o, B, H, S, 128), label=f"_attention_fwd_bwd {(B, H, S)}")
+    # ... and the forward's own budget on that o and lse (tests/attention_fwd_ref.py)
+    af.within_budget_fwd(o, lse, af.make_inputs(qkv, B, H, S, 128), label=f"_attention_fwd_bwd forward {(B, H, S)}")
     return dqkv
 
 
