@@ -33,15 +33,14 @@ import torch
 
 import dalle_hip as dh
 from ..dp import GradReducer
-from .activations import check_activation
-from .dropout import SITE_POSITION, SITE_TOKEN, resolve_dropout, site_attention, site_key, site_mlp
+from .dropout import SITE_POSITION, SITE_TOKEN, site_attention, site_key, site_mlp
 from .layout import ALIGN, ParamLayout, _round_up, adafactor_factored_dims, adafactor_table, reference_init   # noqa: F401  (re-exported)
-from .ff_glu import resolve_ff_glu
-from .qk_norm import GAIN_NAMES, resolve_qk_norm
-from .ema import ema_decay_at, one_minus_decay, resolve_ema, resolve_weights   # noqa: F401  (ema_decay_at: part of the engine's surface)
-from .loss_weights import position_weights, resolve_loss_weights
-from .rotary import DEFAULT_BASE, resolve_rotary, rotary_table
-from .token_shift import grid_side, resolve_token_shift
+from .qk_norm import GAIN_NAMES
+from .ema import ema_decay_at, one_minus_decay, resolve_weights   # noqa: F401  (ema_decay_at: part of the engine's surface)
+from .loss_weights import position_weights
+from .options import check_checkpoint, checkpoint_entries, resolve_options
+from .rotary import rotary_table
+from .token_shift import grid_side
 
 @contextlib.contextmanager
 def _no_gc_in_capture():
@@ -121,18 +120,12 @@ class DalleEngine:
     def __init__(self, n_embd, n_layers, n_heads, text_vocab_size, image_vocab_size, text_seq_len, image_seq_len,
                  batch_size, global_batch_size=None, eos_token_id=None, hparams: Optional[dict] = None,
                  device="cuda", process_group=None, world_size=1, comm=None, attn_masks=None):
-        self.loss_weights = resolve_loss_weights(hparams, text_seq_len)   # None: the reference's plain mean
-        self.ema_decay, self.ema_eval = resolve_ema(hparams)              # None: no weight average (dalle_mtf.ema)
-        # hparams["embed_dropout"] / ["residual_dropout"] as 16-bit thresholds (0: off) and ["dropout_seed"] (dalle_mtf.dropout)
-        self.embed_thresh, self.resid_thresh, self.dropout_seed = resolve_dropout(hparams)
-        # hparams["rotary_emb"] ("1d" / "axial"; None: off) and ["rotary_base"] (dalle_mtf.rotary)
-        self.rotary, self.rotary_base = resolve_rotary(hparams, image_seq_len)
-        # hparams["token_shift"] (dalle_mtf.token_shift): half of every position's channels come from its neighbours, behind norm_1 and norm_2
-        self.token_shift = resolve_token_shift(hparams, n_embd, image_seq_len)
-        # hparams["ff_glu"] (dalle_mtf.ff_glu): the gated FFN, h = value * act(gate) from an FFN-1 of width 8d
-        self.ff_glu = resolve_ff_glu(hparams)
-        # hparams["qk_norm"] (dalle_mtf.qk_norm): q and k RMS-normalised per head with learned gains behind the QKV product
-        self.qk_norm = resolve_qk_norm(hparams)
+        self.hp = dict(hparams or {})
+        # the options of hparams, resolved ahead of any device work (an activation_fn that is unset or empty is the reference's "relu"),
+        # and read as the engine's own attributes: dalle_mtf.options.Options names them and says what each is
+        self.options = resolve_options(self.hp, n_embd, text_seq_len, image_seq_len, activation_fn=self.hp.get("activation_fn") or "relu")
+        for name, value in self.options._asdict().items():
+            setattr(self, name, value)
         if not torch.cuda.is_available():
             raise dh.DalleHipError("DalleEngine needs a HIP device (MI355X); there is no CPU fallback")
         dh.lib()
@@ -152,9 +145,6 @@ class DalleEngine:
         self.M = self.B * self.S
         self.dev = torch.device(device)
         self.pg, self.world = process_group, world_size
-        self.hp = dict(hparams or {})
-        # the FFN activation (reference src/dalle_mtf/models.py:317-324): "relu" (default) or "gelu" (dalle_mtf.activations)
-        self.activation = check_activation(self.hp.get("activation_fn") or "relu")
         self.lay = ParamLayout(n_embd, n_layers, n_heads, self.V, self.S, ff_glu=self.ff_glu, qk_norm=self.qk_norm)
         self.F1 = self.lay.ffn1      # FFN-1's output width: 4d, gated [value | gate] = 8d
         self.Vp = self.lay.Vp
@@ -1363,15 +1353,7 @@ class DalleEngine:
 
     # ------------------------------------------------------------------ checkpoint
     def state_dict(self):
-        sd = {"p": self.p.detach().cpu(), "global_step": self.global_step, "optimizer": self.optimizer, "activation_fn": self.activation}
-        if self.rotary is not None:    # (a checkpoint without the key is a rotary-off model)
-            sd["rotary_emb"], sd["rotary_base"] = self.rotary, self.rotary_base
-        if self.token_shift:           # (a checkpoint without the key is a model without token shift)
-            sd["token_shift"] = True
-        if self.ff_glu:                # (a checkpoint without the key is a model with the plain FFN)
-            sd["ff_glu"] = True
-        if self.qk_norm:               # (a checkpoint without the key is a model without QK normalisation)
-            sd["qk_norm"] = True
+        sd = {"p": self.p.detach().cpu(), "global_step": self.global_step, "optimizer": self.optimizer, **checkpoint_entries(self.options)}
         for k in ("m", "v", "af_slots"):
             if getattr(self, k) is not None:
                 sd[k] = getattr(self, k).detach().cpu()
@@ -1384,28 +1366,7 @@ class DalleEngine:
         if written != self.optimizer:
             raise ValueError(f"checkpoint was written by the {written} optimizer; this run uses {self.optimizer}: "
                              "the optimizer state of one cannot continue the other")
-        act = sd.get("activation_fn", "relu")   # checkpoints from before the activation was recorded are ReLU models
-        if act != self.activation:
-            raise ValueError(f"checkpoint was written by a {act} model; this run uses activation_fn {self.activation!r}: "
-                             "the weights of one do not compute the other")
-        rot = (sd.get("rotary_emb"), float(sd.get("rotary_base", DEFAULT_BASE)) if sd.get("rotary_emb") is not None else None)
-        mine = (self.rotary, self.rotary_base if self.rotary is not None else None)
-        if rot != mine:
-            say = lambda r: "no rotary embeddings" if r[0] is None else f"rotary_emb {r[0]!r} (rotary_base {r[1]:g})"   # noqa: E731
-            raise ValueError(f"checkpoint was written by a model with {say(rot)}; this run uses {say(mine)}: "
-                             "the weights of one do not compute the other")
-        if bool(sd.get("token_shift", False)) != self.token_shift:
-            say = lambda on: "token_shift on" if on else "no token shift"   # noqa: E731
-            raise ValueError(f"checkpoint was written by a model with {say(bool(sd.get('token_shift', False)))}; this run uses "
-                             f"{say(self.token_shift)}: the weights of one do not compute the other")
-        if bool(sd.get("ff_glu", False)) != self.ff_glu:
-            say = lambda on: "ff_glu on (the gated FFN)" if on else "ff_glu off (the plain FFN)"   # noqa: E731
-            raise ValueError(f"checkpoint was written by a model with {say(bool(sd.get('ff_glu', False)))}; this run uses "
-                             f"{say(self.ff_glu)}: the weights of one do not compute the other")
-        if bool(sd.get("qk_norm", False)) != self.qk_norm:
-            say = lambda on: "qk_norm on (normalised q and k with learned gains)" if on else "qk_norm off (plain q and k)"   # noqa: E731
-            raise ValueError(f"checkpoint was written by a model with {say(bool(sd.get('qk_norm', False)))}; this run uses "
-                             f"{say(self.qk_norm)}: the weights of one do not compute the other")
+        check_checkpoint(self.options, sd)
         self.p.copy_(sd["p"])
         for k in ("m", "v", "af_slots"):
             if getattr(self, k) is not None:

@@ -6,18 +6,11 @@ import torch
 
 import numpy as np
 
-from .activations import resolve_activation
-from .dropout import resolve_dropout
-from .ema import resolve_ema
-from .ff_glu import resolve_ff_glu
-from .qk_norm import resolve_qk_norm
 from .engine import DalleEngine
 from .layout import ParamLayout
-from .loss_weights import resolve_loss_weights
 from .masks import layer_masks
 from .ops import get_variable_dtype
-from .rotary import resolve_rotary
-from .token_shift import resolve_token_shift
+from .options import resolve_options
 
 
 def _causal(S):
@@ -57,23 +50,11 @@ class DALLE:
             raise NotImplementedError("custom loss_fn: the kernels implement softmax cross-entropy (the reference default)")
         params = {} if params is None else params
         self.params = defaultdict(lambda: None, params)
-        # activation_fn (reference models.py:317-324, the FFN's hidden layer): "relu" | "gelu" | None -> config key "activation_fn"
-        # -> "relu" (dalle_mtf.activations)
-        self.activation_fn = resolve_activation(activation_fn, params)
-        # "text_loss_weight" / "image_loss_weight" (dalle_mtf.loss_weights): checked here, before any device work
-        resolve_loss_weights(params, text_seq_len)
-        # "ema_decay" / "ema_eval" (dalle_mtf.ema): likewise
-        resolve_ema(params)
-        # "embed_dropout" / "residual_dropout" / "dropout_seed" (dalle_mtf.dropout): likewise
-        resolve_dropout(params)
-        # "rotary_emb" / "rotary_base" (dalle_mtf.rotary): likewise; "axial" needs a square image grid
-        self.rotary_emb, self.rotary_base = resolve_rotary(params, image_seq_len)
-        # "token_shift" (dalle_mtf.token_shift): likewise; needs a square image grid and n_embd % 32 == 0
-        self.token_shift = resolve_token_shift(params, n_embd, image_seq_len)
-        # "ff_glu" (dalle_mtf.ff_glu): likewise; the gated FFN, mlp_linear_1 is then 8 n_embd wide
-        self.ff_glu = resolve_ff_glu(params)
-        # "qk_norm" (dalle_mtf.qk_norm): likewise; q and k normalised per head, two [head_dim] gains per layer
-        self.qk_norm = resolve_qk_norm(params)
+        # the options (dalle_mtf.options), checked here, before any device work.  activation_fn (reference models.py:317-324, the
+        # FFN's hidden layer): "relu" | "gelu" | None -> config key "activation_fn" -> "relu"
+        self.options = opt = resolve_options(params, n_embd, text_seq_len, image_seq_len, activation_fn=activation_fn)
+        self.activation_fn, self.rotary_emb, self.rotary_base = opt.activation, opt.rotary, opt.rotary_base
+        self.token_shift, self.ff_glu, self.qk_norm = opt.token_shift, opt.ff_glu, opt.qk_norm
         if self.params.get("attention_dropout"):
             raise NotImplementedError("attention_dropout > 0 is not supported: embed_dropout and residual_dropout are; dropout of "
                                       "the attention weights would live inside the attention kernels (all shipped configs use 0)")
@@ -103,7 +84,7 @@ class DALLE:
     def variables(self):
         """name -> shape under the reference's checkpoint names."""
         lay = ParamLayout(self.n_embd, self.n_layers, self.n_heads, self.total_tokens, self.total_seq_dim,
-                          ff_glu=getattr(self, "ff_glu", False), qk_norm=getattr(self, "qk_norm", False))
+                          ff_glu=self.options.ff_glu, qk_norm=self.options.qk_norm)
         return {name: shape for name, shape, _, _ in lay.reference_variables()}
 
     def sample(self, text_tokens, vae=None, temperature=1.0, top_k=0, seed=0, top_p=1.0, image_prefix=None, return_logprobs=False,

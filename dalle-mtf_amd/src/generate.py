@@ -183,6 +183,7 @@ def generate(argv=None):
         print("generate: no DALL-E checkpoint found (model_path / --checkpoint / tf_checkpoint): sampling from freshly "
               "initialised weights", file=sys.stderr)
     from src.dalle_mtf.ema import resolve_weights
+    from src.dalle_mtf.options import report
     try:
         which = resolve_weights(args.weights, eng.ema is not None)
     except ValueError:
@@ -248,10 +249,7 @@ def generate(argv=None):
                 temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, guidance_scale=args.guidance_scale, weights=which, image_prefix=K, image_seq_len=int(P),
                 source=next(s for s in SOURCES if getattr(args, s) is not None), images_written=len(images),
                 recompute_grad=bool(eng.recompute),
-                rotary_emb=eng.rotary, rotary_base=eng.rotary_base if eng.rotary is not None else None,
-                token_shift=bool(eng.token_shift),
-                ff_glu=bool(eng.ff_glu),
-                qk_norm=bool(eng.qk_norm),
+                **report(eng.options),
                 seconds=dict(load=round(t_load, 3), sample=round(t_sample, 3), decode_and_copy=round(t_decode, 3)),
                 tokens_per_s=round(nb * Bg * (P - K) / t_sample, 1) if t_sample > 0 else None)
     with open(os.path.join(args.out, "generate.json"), "w") as f:

@@ -14,6 +14,7 @@ import torch
 
 import dalle_hip as dh
 from .dalle_mtf import DALLE
+from .dalle_mtf.options import option_log_lines
 from .estimator import CheckpointSaverHook, EstimatorSpec, latest_checkpoint
 from .optimizers import get_optimizer
 from .utils import ModeKeys, create_host_call, get_graph_info, mode_to_str, parse_mesh_shape, scalar_summary
@@ -152,32 +153,10 @@ def _build(params, mode_str):
                   batch_size=local_bs // nmb, bf_16=params["bf_16"], mode=mode_str, params=params,
                   process_group=pg, world_size=world, global_batch_size=gbs // nmb, comm=comm)
     eng = model.engine
-    if eng.loss_weights is not None and rank == 0:
-        # "text_loss_weight" / "image_loss_weight" (dalle_mtf.loss_weights; they reach the engine's hparams through `params`)
-        logging.getLogger("dalle_mtf_amd").info(
-            "%s loss weights: text %g, image %g -> loss = (%g * mean_text + %g * mean_image) / %g over %d text and %d image positions",
-            mode_str, *eng.loss_weights, *eng.loss_weights, sum(eng.loss_weights), eng.T - 1, image_seq_len + 1)
-    if eng.ema_decay is not None and rank == 0:
-        # "ema_decay" / "ema_eval" (dalle_mtf.ema; they reach the engine's hparams through `params`)
-        logging.getLogger("dalle_mtf_amd").info(
-            "%s weight EMA: ema_decay %g (decay at step t = min(%g, (1 + t) / (10 + t))), evaluation from the %s weights",
-            mode_str, eng.ema_decay, eng.ema_decay, "averaged" if eng.ema_eval else "raw")
-    if eng.rotary is not None and rank == 0:
-        # "rotary_emb" / "rotary_base" (dalle_mtf.rotary; they reach the engine's hparams through `params`)
-        logging.getLogger("dalle_mtf_amd").info("%s rotary embeddings: %s, base %g (in addition to the learned positions)",
-                                                mode_str, eng.rotary, eng.rotary_base)
-    if eng.token_shift and rank == 0:
-        # "token_shift" (dalle_mtf.token_shift; it reaches the engine's hparams through `params`)
-        logging.getLogger("dalle_mtf_amd").info("%s token shift: on (behind norm_1 and norm_2 of every block, %d x %d image grid)",
-                                                mode_str, eng.G, eng.G)
-    if eng.ff_glu and rank == 0:
-        # "ff_glu" (dalle_mtf.ff_glu; it reaches the engine's hparams through `params`)
-        logging.getLogger("dalle_mtf_amd").info("%s gated feed-forward: on (%s, mlp_linear_1 is [%d, %d])", mode_str,
-                                                "GEGLU" if eng.activation == "gelu" else "ReGLU", eng.d, eng.F1)
-    if eng.qk_norm and rank == 0:
-        # "qk_norm" (dalle_mtf.qk_norm; it reaches the engine's hparams through `params`)
-        logging.getLogger("dalle_mtf_amd").info("%s QK normalisation: on (RMS per head over %d channels, eps 1e-6, gains [%d] per layer)",
-                                                mode_str, eng.hd, eng.hd)
+    if rank == 0:
+        # the options that are on (dalle_mtf.options; their config keys reach the engine's hparams through `params`)
+        for line in option_log_lines(eng.options, eng.d, eng.H, eng.T, image_seq_len):
+            logging.getLogger("dalle_mtf_amd").info("%s %s", mode_str, line)
     eng.hp["num_microbatches"] = nmb   # reference model_fns.py:141-154 (1 when tokens_per_mb_per_replica is unset)
     params["num_microbatches"] = nmb
     state["local_bs"] = local_bs

@@ -192,9 +192,11 @@ def test_layout_takes_the_ffn1_width_from_the_setting():
 def test_dalle_variables_follow_the_key():
     from src.dalle_mtf.models import DALLE
     m = DALLE.__new__(DALLE)          # variables() reads the sizes alone: no engine, no device
+    from src.dalle_mtf.options import resolve_options
     m.n_embd, m.n_layers, m.n_heads, m.total_tokens, m.total_seq_dim = 128, 1, 1, 77, 24
+    m.options = resolve_options({}, 128, 8, 16)
     assert m.variables()["layer_0/mlp/mlp_linear_1/kernel"] == (128, 512)
-    m.ff_glu = True
+    m.options = resolve_options({"ff_glu": True}, 128, 8, 16)
     assert m.variables()["layer_0/mlp/mlp_linear_1/kernel"] == (128, 1024) and m.variables()["layer_0/mlp/mlp_linear_1/bias"] == (1024,)
 
 

@@ -8,7 +8,7 @@ import torch
 
 import dalle_hip as dh  # noqa: E402  (path set up by conftest)
 import glu_ref
-from engine_case import HP, IV, P, PATTERNS, T, TV, inputs, step
+from engine_case import P, PATTERNS, T, build, decode_worst, inputs, step, step_pair
 from parity import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -146,14 +146,8 @@ def test_wrappers_refuse_before_a_launch():
 # ------------------------------------------------------------------ the engine
 def _build(act="gelu", width=256, heads=2, layers=3, glu=True, seed=0, hparams=None, widen_seed=5):
     """(cfg, model, P, tokens): tests/engine_case.py's small case with mlp_linear_1 widened (glu) and loaded"""
-    from src.dalle_mtf.models import DALLE
-    cfg, P0, tokens = inputs(width, heads, layers, seed=seed)
-    Pw = glu_ref.widen(P0, cfg, seed=widen_seed) if glu else P0
-    params = {k: v for k, v in dict(HP, activation_fn=act, ff_glu=glu, **(hparams or {})).items() if not (isinstance(v, str) and v == "absent")}
-    model = DALLE(n_embd=width, text_vocab_size=TV, image_vocab_size=IV, text_seq_len=T, image_seq_len=P, n_layers=layers,
-                  n_heads=heads, batch_size=tokens.shape[0], params=params)
-    model.engine.load_reference_params(Pw)
-    return cfg, model, Pw, tokens
+    return build(width, heads, layers, seed=seed, hparams=dict(activation_fn=act, ff_glu=glu, **(hparams or {})),
+                 weights=(lambda P0, cfg: glu_ref.widen(P0, cfg, seed=widen_seed)) if glu else None)
 
 
 _ORACLE = {}
@@ -257,13 +251,8 @@ def test_off_is_off():
     """the key false and the key absent: the same loss and flat gradient, bit for bit, on the plain FFN's launches"""
     out = []
     for glu in (False, "absent"):
-        from src.dalle_mtf.models import DALLE
-        cfg, P0, tokens = inputs()
-        params = dict(HP, activation_fn="gelu") if glu == "absent" else dict(HP, activation_fn="gelu", ff_glu=False)
-        model = DALLE(n_embd=256, text_vocab_size=TV, image_vocab_size=IV, text_seq_len=T, image_seq_len=P, n_layers=3, n_heads=2,
-                      batch_size=2, params=params)
+        _, model, _, tokens = build(hparams=dict(activation_fn="gelu", ff_glu=glu))
         eng = model.engine
-        eng.load_reference_params(P0)
         assert eng.ff_glu is False and eng.ffn_form == "gelu" and eng.dpre is None and eng.F1 == 4 * 256
         assert "ff_glu" not in eng.state_dict()
         out.append(step(eng, tokens))
@@ -281,12 +270,7 @@ def test_off_is_off():
 
 
 def test_recompute_grad_is_bit_identical():
-    res = []
-    for rc in (False, True):
-        _, model, _, tokens = _build("gelu", hparams=dict(recompute_grad=rc, residual_dropout=0.1, embed_dropout=0.1))
-        res.append(step(model.engine, tokens))
-        del model
-        torch.cuda.empty_cache()
+    res = step_pair(lambda rc: _build("gelu", hparams=dict(recompute_grad=rc, residual_dropout=0.1, embed_dropout=0.1))[1::2])
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
     assert float(res[0][1].abs().sum()) > 0
 
@@ -297,15 +281,8 @@ def test_decode_logits_against_the_full_forward(act):
     _, model, _, tokens = _build(act)
     eng = model.engine
     tok = torch.from_numpy(tokens).cuda()
-    eng.forward(tok, need_grad=False)
-    full = eng.logits()[:, :, TV:TV + IV].clone()
     for graph in (True, False):
-        eng._prefill(tok)
-        worst = 0.0
-        for pos in range(T - 1, T + P - 1):
-            z = eng.decode_step(tok[:, pos].contiguous(), pos, graph=graph).float()
-            ref = full[:, pos]
-            worst = max(worst, float((z - ref).abs().max() / ref.abs().max()))
+        worst = decode_worst(eng, tok, graph=graph)
         print(f"ff_glu {act} decode (graph={graph}) vs full forward logits: worst relative {worst}", flush=True)
         assert worst <= 3e-2, (graph, worst)
     assert tuple(eng._dec["pre"].shape) == (2, 8 * 256)

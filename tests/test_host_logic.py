@@ -264,6 +264,8 @@ def test_dalle_variables_are_the_layouts_reference_variables():
     d, L, tv, iv, T, P = 128, 2, 40, 8, 8, 8
     m = DALLE.__new__(DALLE)          # variables() reads the sizes alone: no engine, no device
     m.n_embd, m.n_layers, m.n_heads, m.total_tokens, m.total_seq_dim = d, L, 1, tv + iv + 1, T + P
+    from src.dalle_mtf.options import resolve_options
+    m.options = resolve_options({}, d, T, P)      # ... and the options record, all off
     lay = ParamLayout(d, L, 1, tv + iv + 1, T + P)
     assert list(m.variables().items()) == [(name, shape) for name, shape, _, _ in lay.reference_variables()]
     v = m.variables()

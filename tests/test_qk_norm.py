@@ -97,10 +97,12 @@ def test_layout_on_adds_two_gains_per_layer_between_qkv_and_norm_1(d, H):
 def test_model_variables_list_the_gains():
     from src.dalle_mtf.models import DALLE
     m = DALLE.__new__(DALLE)
-    m.n_embd, m.n_layers, m.n_heads, m.total_tokens, m.total_seq_dim, m.ff_glu, m.qk_norm = 128, 2, 2, 365, 272, False, True
+    from src.dalle_mtf.options import resolve_options
+    m.n_embd, m.n_layers, m.n_heads, m.total_tokens, m.total_seq_dim = 128, 2, 2, 365, 272
+    m.options = resolve_options({"ff_glu": False, "qk_norm": True}, 128, 16, 256)
     v = m.variables()
     assert v["layer_1/attn/q_norm/g"] == (64,) and v["layer_0/attn/k_norm/g"] == (64,)
-    m.qk_norm = False
+    m.options = m.options._replace(qk_norm=False)
     assert "layer_1/attn/q_norm/g" not in m.variables()
 
 

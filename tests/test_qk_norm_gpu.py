@@ -6,7 +6,7 @@ import pytest
 import torch
 
 import qk_norm_ref as qref
-from engine_case import HP, IV, P, PATTERNS, T, TV, inputs, step
+from engine_case import HP, IV, P, PATTERNS, T, TV, build, decode_worst, inputs, samplers_agree, step, step_pair
 from parity import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -202,14 +202,8 @@ GAIN_SEED = 5
 
 def _setup(width=256, heads=2, qk=True, hparams=None, seed=0, batch=2):
     """(cfg, model, P, tokens) on engine_case's inputs: P = the oracle's weights plus, with the key on, the perturbed gains"""
-    from src.dalle_mtf.models import DALLE
-    cfg, P0, tokens = inputs(width, heads, seed=seed, batch=batch)
-    Pg = qref.with_gains(P0, cfg, seed=GAIN_SEED) if qk is True else P0
-    params = {k: v for k, v in dict(HP, qk_norm=qk, **(hparams or {})).items() if not (isinstance(v, str) and v == "absent")}
-    model = DALLE(n_embd=width, text_vocab_size=TV, image_vocab_size=IV, text_seq_len=T, image_seq_len=P, n_layers=cfg.n_layers,
-                  n_heads=heads, batch_size=batch, params=params)
-    model.engine.load_reference_params(Pg)
-    return cfg, model, Pg, tokens
+    return build(width, heads, batch=batch, seed=seed, hparams=dict(qk_norm=qk, **(hparams or {})),
+                 weights=(lambda P0, cfg: qref.with_gains(P0, cfg, seed=GAIN_SEED)) if qk is True else None)
 
 
 @pytest.mark.parametrize("width,scheme,patterns", [(256, None, None), (128, "1d", None), (256, "axial", PATTERNS)],
@@ -279,14 +273,11 @@ def test_off_is_off():
 
 
 def test_recompute_grad_is_bit_identical():
-    res = []
-    for rc in (False, True):
+    def make(rc):
         _, model, _, tokens = _setup(hparams=dict(recompute_grad=rc, rotary_emb="axial", residual_dropout=0.1))
-        eng = model.engine
-        assert (eng.qk_pre[0].data_ptr() == eng.qk_pre[2].data_ptr()) == rc        # one shared buffer under recompute_grad
-        res.append(step(eng, tokens))
-        del model, eng
-        torch.cuda.empty_cache()
+        assert (model.engine.qk_pre[0].data_ptr() == model.engine.qk_pre[2].data_ptr()) == rc        # one shared buffer under recompute_grad
+        return model, tokens
+    res = step_pair(make)
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
     assert float(res[0][1].abs().sum()) > 0
 
@@ -345,25 +336,11 @@ def test_decode_logits_and_samplers():
     _, model, _, tokens = _setup(hparams=dict(rotary_emb="axial"))
     eng = model.engine
     tok = torch.from_numpy(tokens).cuda()
-    eng.forward(tok, need_grad=False)
-    full = eng.logits()[:, :, TV:TV + IV].clone()
     for graph in (True, False):
-        eng._prefill(tok)
-        worst = 0.0
-        for pos in range(T - 1, T + P - 1):
-            z = eng.decode_step(tok[:, pos].contiguous(), pos, graph=graph).float()
-            ref = full[:, pos]
-            worst = max(worst, float((z - ref).abs().max() / ref.abs().max()))
+        worst = decode_worst(eng, tok, graph=graph)
         print(f"qk_norm decode (graph={graph}) vs full forward logits: worst relative {worst}", flush=True)
         assert worst <= 3e-2, (graph, worst)
-    text = tok[:, :T].contiguous()
-    a = eng.sample_image_tokens(text, temperature=1.0, top_k=8, seed=3, kv_cache=True)
-    a2 = eng.sample_image_tokens(text, temperature=1.0, top_k=8, seed=3, kv_cache=True, fused_sampling=False)
-    a3 = eng.sample_image_tokens(text, temperature=1.0, top_k=8, seed=3, kv_cache=True, decode_graph=False)
-    assert torch.equal(a, a2) and torch.equal(a, a3)
-    g1 = eng.sample_image_tokens(text[:1], temperature=1.0, top_k=8, seed=5, guidance_scale=3.0)
-    g2 = eng.sample_image_tokens(text[:1], temperature=1.0, top_k=8, seed=5, guidance_scale=3.0, decode_graph=False)
-    assert tuple(g1.shape) == (1, P) and torch.equal(g1, g2)
+    samplers_agree(eng, tok[:, :T].contiguous())
 
 
 def test_checkpoint_records_and_checks_the_key():

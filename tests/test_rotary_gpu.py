@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from engine_case import IV, P, PATTERNS, T, TV, build, step
+from engine_case import P, PATTERNS, T, build, decode_worst, samplers_agree, step, step_pair
 from parity import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -206,12 +206,7 @@ def test_off_is_off():
 
 
 def test_recompute_grad_with_rotary_equals_stored_activations():
-    res = []
-    for rc in (False, True):
-        _, model, _, tokens = _setup(hparams=dict(recompute_grad=rc))
-        res.append(step(model.engine, tokens))
-        del model
-        torch.cuda.empty_cache()
+    res = step_pair(lambda rc: _setup(hparams=dict(recompute_grad=rc))[1::2])
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
 
 
@@ -221,25 +216,11 @@ def test_rotary_decode_logits_and_samplers():
     _, model, _, tokens = _setup()
     eng = model.engine
     tok = torch.from_numpy(tokens).cuda()
-    eng.forward(tok, need_grad=False)
-    full = eng.logits()[:, :, TV:TV + IV].clone()
     for graph in (True, False):
-        eng._prefill(tok)
-        worst = 0.0
-        for pos in range(T - 1, T + P - 1):
-            z = eng.decode_step(tok[:, pos].contiguous(), pos, graph=graph).float()
-            ref = full[:, pos]
-            worst = max(worst, float((z - ref).abs().max() / ref.abs().max()))
+        worst = decode_worst(eng, tok, graph=graph)
         print(f"rotary decode (graph={graph}) vs full forward logits: worst relative {worst}", flush=True)
         assert worst <= 3e-2, (graph, worst)
-    text = tok[:, :T].contiguous()
-    a = eng.sample_image_tokens(text, temperature=1.0, top_k=8, seed=3, kv_cache=True)
-    a2 = eng.sample_image_tokens(text, temperature=1.0, top_k=8, seed=3, kv_cache=True, fused_sampling=False)
-    a3 = eng.sample_image_tokens(text, temperature=1.0, top_k=8, seed=3, kv_cache=True, decode_graph=False)
-    assert torch.equal(a, a2) and torch.equal(a, a3)
-    g1 = eng.sample_image_tokens(text[:1], temperature=1.0, top_k=8, seed=5, guidance_scale=3.0)
-    g2 = eng.sample_image_tokens(text[:1], temperature=1.0, top_k=8, seed=5, guidance_scale=3.0, decode_graph=False)
-    assert tuple(g1.shape) == (1, P) and torch.equal(g1, g2)
+    samplers_agree(eng, tok[:, :T].contiguous())
 
 
 def test_checkpoint_records_and_checks_the_scheme():

@@ -4,7 +4,7 @@ step with its history and the samplers, checkpoints."""
 import pytest
 import torch
 
-from engine_case import IV, P, PATTERNS, T, TV, build, inputs, step
+from engine_case import P, PATTERNS, T, TV, build, decode_worst, inputs, samplers_agree, step, step_pair
 from parity import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -237,12 +237,7 @@ def test_off_is_off():
 
 
 def test_recompute_grad_with_token_shift_equals_stored_activations():
-    res = []
-    for rc in (False, True):
-        _, model, _, tokens = _setup(hparams=dict(recompute_grad=rc, residual_dropout=0.1, embed_dropout=0.1))
-        res.append(step(model.engine, tokens))
-        del model
-        torch.cuda.empty_cache()
+    res = step_pair(lambda rc: _setup(hparams=dict(recompute_grad=rc, residual_dropout=0.1, embed_dropout=0.1))[1::2])
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
     assert float(res[0][1].abs().sum()) > 0
 
@@ -254,18 +249,11 @@ def test_token_shift_decode_logits_against_the_full_forward():
     _, model, _, tokens = _setup()
     eng = model.engine
     tok = torch.from_numpy(tokens).cuda()
-    eng.forward(tok, need_grad=False)
-    full = eng.logits()[:, :, TV:TV + IV].clone()
     blind = tok.clone()
     blind[:, T:] = 0
     for name, fill in (("true tokens", tok), ("image part zero", blind)):
         for graph in (True, False):
-            eng._prefill(fill)
-            worst = 0.0
-            for pos in range(T - 1, T + P - 1):
-                z = eng.decode_step(tok[:, pos].contiguous(), pos, graph=graph).float()
-                ref = full[:, pos]
-                worst = max(worst, float((z - ref).abs().max() / ref.abs().max()))
+            worst = decode_worst(eng, tok, fill=fill, graph=graph)
             print(f"token_shift decode after a prefill of {name} (graph={graph}) vs full forward logits: worst relative {worst}", flush=True)
             assert worst <= 3e-2, (name, graph, worst)
     assert eng._shift_hist is not None and len(eng._shift_hist) == 3 and tuple(eng._shift_hist[0][1].shape) == (2, T + P, 128)
@@ -278,13 +266,7 @@ def test_token_shift_samplers_agree():
     eng = model.engine
     tok = torch.from_numpy(tokens).cuda()
     text = tok[:, :T].contiguous()
-    a = eng.sample_image_tokens(text, temperature=1.0, top_k=8, seed=3, kv_cache=True)
-    a2 = eng.sample_image_tokens(text, temperature=1.0, top_k=8, seed=3, kv_cache=True, fused_sampling=False)
-    a3 = eng.sample_image_tokens(text, temperature=1.0, top_k=8, seed=3, kv_cache=True, decode_graph=False)
-    assert torch.equal(a, a2) and torch.equal(a, a3)
-    g1 = eng.sample_image_tokens(text[:1], temperature=1.0, top_k=8, seed=5, guidance_scale=3.0)
-    g2 = eng.sample_image_tokens(text[:1], temperature=1.0, top_k=8, seed=5, guidance_scale=3.0, decode_graph=False)
-    assert tuple(g1.shape) == (1, P) and torch.equal(g1, g2)
+    samplers_agree(eng, text)
     prefix = (tok[:, T:T + G + 3] - TV).contiguous()
     p1 = eng.sample_image_tokens(text, temperature=1.0, top_k=8, seed=9, image_prefix=prefix)
     p2 = eng.sample_image_tokens(text, temperature=1.0, top_k=8, seed=9, image_prefix=prefix, decode_graph=False)

@@ -36,32 +36,28 @@ def timed(fn, reps=1):
     return (time.perf_counter() - t0) / reps, r
 
 
-def engine_bench(shape, B, plain_positions, guidance_scale=1.0, rotary=None, token_shift=False, ff_glu=False, activation=None, qk_norm=False):
+# command-line option -> (the argparse arguments of its flag, the config key it sets); the keys that are set also go into the result
+OPTIONS = {"rotary": (dict(choices=("1d", "axial"), default=None), "rotary_emb"),
+           "token_shift": (dict(action="store_true"), "token_shift"),
+           "ff_glu": (dict(action="store_true"), "ff_glu"),
+           "qk_norm": (dict(action="store_true"), "qk_norm"),
+           "activation": (dict(choices=("relu", "gelu"), default=None), "activation_fn")}
+
+
+def engine_bench(shape, B, plain_positions, guidance_scale=1.0, **options):
+    """options: the values of OPTIONS' command-line options; one that is unset or false sets no key"""
     from src.dalle_mtf.engine import DalleEngine
     c = SHAPES[shape]
     T, P, tv = 256, 1024, 50258
-    eng = DalleEngine(c["d"], c["L"], c["H"], tv, c["iv"], T, P, batch_size=B, hparams=dict(lr=1e-3, train_steps=10, **c["hp"], **({"rotary_emb": rotary} if rotary else {}),
-                                                                                                **({"token_shift": True} if token_shift else {}),
-                                                                                                **({"ff_glu": True} if ff_glu else {}),
-                                                                                                **({"qk_norm": True} if qk_norm else {}),
-                                                                                                **({"activation_fn": activation} if activation else {})))
+    keys = {OPTIONS[name][1]: value for name, value in options.items() if value}
+    eng = DalleEngine(c["d"], c["L"], c["H"], tv, c["iv"], T, P, batch_size=B, hparams=dict(lr=1e-3, train_steps=10, **c["hp"], **keys))
     eng.init_params(seed=1)
     guided = guidance_scale != 1.0
     R = B // 2 if guided else B                   # generated rows per call
     gkw = dict(guidance_scale=guidance_scale) if guided else {}
     text = torch.randint(0, tv - 1, (R, T), dtype=torch.int32, device="cuda")
     res = dict(shape=shape, batch=B, guidance_scale=guidance_scale, rows_generated=R, n_embd=c["d"], n_layers=c["L"], n_heads=c["H"], seq=T + P, image_vocab=c["iv"],
-               recompute_grad=bool(eng.recompute))
-    if rotary:
-        res["rotary_emb"] = rotary
-    if token_shift:
-        res["token_shift"] = True
-    if ff_glu:
-        res["ff_glu"] = True
-    if qk_norm:
-        res["qk_norm"] = True
-    if activation:
-        res["activation_fn"] = activation
+               recompute_grad=bool(eng.recompute), **keys)
     variants = (("top_k", dict(temperature=1.0, top_k=32)), ("top_k+top_p", dict(temperature=1.0, top_k=32, top_p=0.9)),
                 ("top_k+top_p+logp", dict(temperature=1.0, top_k=32, top_p=0.9, return_logprobs=True)),
                 ("top_p", dict(temperature=1.0, top_p=0.9)))
@@ -116,16 +112,14 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--plain-positions", type=int, default=16)
     ap.add_argument("--guidance-scale", dest="guidance_scale", type=float, default=1.0)
-    ap.add_argument("--rotary", choices=("1d", "axial"), default=None)
-    ap.add_argument("--token-shift", dest="token_shift", action="store_true")
-    ap.add_argument("--ff-glu", dest="ff_glu", action="store_true")
-    ap.add_argument("--qk-norm", dest="qk_norm", action="store_true")
-    ap.add_argument("--activation", choices=("relu", "gelu"), default=None)
+    for name, (kw, _) in OPTIONS.items():
+        ap.add_argument("--" + name.replace("_", "-"), dest=name, **kw)
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = kernel_bench(a.reps) if a.kernels else engine_bench(a.shape, a.batch, a.plain_positions, a.guidance_scale, a.rotary, a.token_shift, a.ff_glu, a.activation, a.qk_norm)
+    res = kernel_bench(a.reps) if a.kernels else engine_bench(a.shape, a.batch, a.plain_positions, a.guidance_scale,
+                                                                     **{name: getattr(a, name) for name in OPTIONS})
     res["device"] = torch.cuda.get_device_name(0)
     line = json.dumps(res)
     print(line)

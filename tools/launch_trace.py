@@ -63,6 +63,15 @@ def configurations():
                          ("rotary_1d", dict(rotary_emb="1d"), {})):
         c["sample/" + name] = dict(SAMPLER, hp=hp, sample=kw)
     c["sample/mask"] = dict(SAMPLER, hp={}, sample={}, masks=["causal", "local:8"])
+    # token shift, the gated FFN and QK normalisation, on P = 64: token shift and the axial scheme need a square image grid
+    shift, glu, qk_axial = dict(token_shift=True), dict(ff_glu=True), dict(qk_norm=True, rotary_emb="axial")
+    for name, hp in (("token_shift", shift), ("ff_glu_relu", glu), ("ff_glu_gelu", dict(glu, activation_fn="gelu")),
+                     ("qk_norm", dict(qk_norm=True)), ("qk_norm_axial", qk_axial),
+                     ("all_options", dict(shift, **glu, **qk_axial, activation_fn="gelu", embed_dropout=0.1, residual_dropout=0.1,
+                                          text_loss_weight=1, image_loss_weight=7))):
+        c["small/" + name] = dict(SMALL, P=64, hp=hp)
+    for name, hp in (("token_shift", shift), ("ff_glu", glu), ("qk_norm_axial", qk_axial)):
+        c["sample/" + name] = dict(SAMPLER, P=64, hp=hp, sample={})
     return c
 
 
