@@ -284,6 +284,302 @@ extern "C" int dmi_gumbel_softmax_bwd(const uint16_t* dy, const uint16_t* y_soft
 }
 
 // =====================================================================================
+// KL(q(z|x) || uniform) of the codebook posterior and codebook usage (DESIGN.md §4 "VAE: KL term and codebook statistics").
+// Per row m of the fp32 logits [M, T], no noise, no temperature:
+//   lse = logsumexp_k l_k,  q_k = exp(l_k - lse),  e = sum_k q_k ln q_k,  KL_m = e + ln T,  KL = mean_m KL_m
+//   d loss / d l_j gains (beta_t / M) q_j (ln q_j - e)
+// No float atomics anywhere: every sum has a fixed order (lane-serial, wave butterfly, block order), so two runs give equal bits.
+// =====================================================================================
+#define KL_MAX_T 4096
+// One wave per row, the row in registers (as gumbel_fwd_kernel<NC>).  With d_k = l_k - max, t_k = exp(d_k), s = sum t_k:
+// lse = max + ln s and e = (sum_k t_k d_k) / s - ln s: both sums have terms of one sign, and d_k is taken against the row's own
+// maximum, so a common shift of the logits (normal + 1000) costs nothing but the final rounding of lse.  t_k = 0 (underflow)
+// contributes 0 * d_k = 0 (d_k is finite).  exp is __expf (exp2 of d log2 e, as in gumbel_fwd_kernel); the error model
+// of tests/vae_kl_ref.py counts the product's rounding.  part[block] = the block's four KL_m in the order (0 + 1) + (2 + 3).
+template <int NC>
+__global__ __launch_bounds__(256) void codebook_kl_fwd_kernel(const float* __restrict__ logits, float* __restrict__ rowstat,
+                                                              float* __restrict__ part, int64_t M, int T, float ln_t) {
+  __shared__ float sm[4];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + wid;
+  const bool live = row < M;
+  const int nch = T / 8;
+  float klm = 0.f;
+  if (live) {
+    float v[NC][8];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+      const int c = lane + 64 * i;
+      if (c < nch) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const f32x4 l = *(const f32x4*)(logits + row * T + c * 8 + 4 * q);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            v[i][4 * q + e] = l[e];
+            mx = fmaxf(mx, l[e]);
+          }
+        }
+      }
+    }
+    mx = wave_max(mx);
+    float s = 0.f, a = 0.f;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+      const int c = lane + 64 * i;
+      if (c < nch) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float d = v[i][e] - mx;
+          const float t = __expf(d);
+          s += t;
+          a += t * d;
+        }
+      }
+    }
+    s = wave_sum(s);
+    a = wave_sum(a);
+    const float ls = logf(s);
+    const float en = a / s - ls;
+    klm = en + ln_t;
+    if (lane == 0) {
+      rowstat[row * 2] = mx + ls;
+      rowstat[row * 2 + 1] = en;
+    }
+  }
+  if (lane == 0) sm[wid] = klm;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+#define USAGE_MAX_BLOCKS 512   // row slabs of dmi_codebook_usage
+#define USAGE_MIN_ROWS 32      // ... of at least this many rows each
+static inline int64_t usage_blocks(int64_t M) {
+  const int64_t nb = cdiv64(M, USAGE_MIN_ROWS);
+  return nb > USAGE_MAX_BLOCKS ? USAGE_MAX_BLOCKS : nb;
+}
+// the larger of: one KL partial per four rows; [blocks][T] fp32 + [blocks][T] int32 usage partials
+extern "C" int64_t dmi_codebook_kl_workspace_bytes(int64_t M, int T) {
+  if (M <= 0 || T <= 0) return 0;
+  const int64_t kl = cdiv64(M, 4) * 4, us = usage_blocks(M) * (int64_t)T * 8;
+  return kl > us ? kl : us;
+}
+extern "C" int dmi_codebook_kl_fwd(const float* logits, float* rowstat, float* kl, int64_t M, int T, void* workspace, void* stream) {
+  DMI_REQUIRE(logits && rowstat && kl && workspace, "codebook_kl_fwd: null pointer");
+  DMI_REQUIRE(M > 0, "codebook_kl_fwd: M must be positive (M=%lld)", (long long)M);
+  DMI_REQUIRE(T > 0 && T % 8 == 0 && T <= KL_MAX_T, "codebook_kl_fwd: T must be a multiple of 8 and at most %d (T=%d)", KL_MAX_T, T);
+  DMI_REQUIRE(cdiv64(M, 4) <= 0x7fffffffLL, "codebook_kl_fwd: M too large (M=%lld)", (long long)M);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t nb = cdiv64(M, 4);
+  dim3 grid((unsigned)nb), blk(256);
+  const float ln_t = (float)log((double)T);
+  float* part = (float*)workspace;
+  if (T <= 512) codebook_kl_fwd_kernel<1><<<grid, blk, 0, st>>>(logits, rowstat, part, M, T, ln_t);
+  else if (T <= 1024) codebook_kl_fwd_kernel<2><<<grid, blk, 0, st>>>(logits, rowstat, part, M, T, ln_t);
+  else if (T <= 2048) codebook_kl_fwd_kernel<4><<<grid, blk, 0, st>>>(logits, rowstat, part, M, T, ln_t);
+  else codebook_kl_fwd_kernel<8><<<grid, blk, 0, st>>>(logits, rowstat, part, M, T, ln_t);
+  DMI_CHECK_LAUNCH("codebook_kl_fwd");
+  return dmi_sum_f32(part, nb, 1.f / (float)M, kl, stream);
+}
+
+// gumbel_bwd_kernel with the KL gradient added before the one bf16 rounding:
+//   dlogits = bf16( (1/tau) y_soft (dy - sum_j dy_j y_soft_j) + (beta_t / M) q (ln q - e) ),  ln q = l - lse, q = exp(ln q)
+// The Gumbel term is the expression of gumbel_bwd_kernel, formed first and on its own; with beta_t == 0 nothing is added to it
+// (adding 0 would turn a -0 into +0), so that case gives gumbel_bwd_kernel's bits.
+__global__ __launch_bounds__(256) void gumbel_bwd_kl_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ y_soft,
+                                                            const float* __restrict__ logits, const float* __restrict__ rowstat,
+                                                            bf16_t* __restrict__ dlogits, int64_t M, int T, float inv_temp,
+                                                            const float* __restrict__ temp_dev, float klw,
+                                                            const float* __restrict__ klw_dev) {
+  if (temp_dev) inv_temp = 1.f / temp_dev[0];
+  if (klw_dev) klw = klw_dev[0];
+  const float cw = klw / (float)M;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + wid;
+  if (row >= M) return;
+  const int nch = T / 8;
+  float dot = 0.f;
+  for (int c = lane; c < nch; c += 64) {
+    float a[8], p[8];
+    unpack8(*(const u32x4*)(dy + row * T + c * 8), a);
+    unpack8(*(const u32x4*)(y_soft + row * T + c * 8), p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dot += a[e] * p[e];
+  }
+  dot = wave_sum(dot);
+  const float lse = rowstat[row * 2], en = rowstat[row * 2 + 1];
+  for (int c = lane; c < nch; c += 64) {
+    float a[8], p[8], o[8];
+    unpack8(*(const u32x4*)(dy + row * T + c * 8), a);
+    unpack8(*(const u32x4*)(y_soft + row * T + c * 8), p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = inv_temp * p[e] * (a[e] - dot);
+    if (cw != 0.f) {
+      const f32x4 l0 = *(const f32x4*)(logits + row * T + c * 8), l1 = *(const f32x4*)(logits + row * T + c * 8 + 4);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float lq = (e < 4 ? l0[e & 3] : l1[e & 3]) - lse;
+        o[e] += cw * __expf(lq) * (lq - en);
+      }
+    }
+    *(u32x4*)(dlogits + row * T + c * 8) = pack8(o);
+  }
+}
+extern "C" int dmi_gumbel_softmax_bwd_kl(const uint16_t* dy, const uint16_t* y_soft, const float* logits, const float* rowstat,
+                                         uint16_t* dlogits, int64_t M, int T, float temperature, const float* temperature_dev,
+                                         float kl_weight, const float* kl_weight_dev, void* stream) {
+  DMI_REQUIRE(dy && y_soft && logits && rowstat && dlogits, "gumbel_bwd_kl: null pointer");
+  DMI_REQUIRE(M > 0, "gumbel_bwd_kl: M must be positive (M=%lld)", (long long)M);
+  DMI_REQUIRE(T > 0 && T % 8 == 0 && T <= KL_MAX_T, "gumbel_bwd_kl: T must be a multiple of 8 and at most %d (T=%d)", KL_MAX_T, T);
+  DMI_REQUIRE(cdiv64(M, 4) <= 0x7fffffffLL, "gumbel_bwd_kl: M too large (M=%lld)", (long long)M);
+  DMI_REQUIRE(temperature > 0.f || temperature_dev, "gumbel_bwd_kl: temperature must be positive (or given on the device)");
+  DMI_REQUIRE(kl_weight_dev || (kl_weight >= 0.f && kl_weight <= 3.0e38f), "gumbel_bwd_kl: kl_weight must be finite and >= 0");
+  gumbel_bwd_kl_kernel<<<dim3((unsigned)cdiv64(M, 4)), dim3(256), 0, (hipStream_t)stream>>>(
+      dy, y_soft, logits, rowstat, dlogits, M, T, temperature_dev ? 0.f : 1.f / temperature, temperature_dev,
+      kl_weight_dev ? 0.f : kl_weight, kl_weight_dev);
+  DMI_CHECK_LAUNCH("gumbel_bwd_kl");
+  return DMI_OK;
+}
+
+// loss[0] = recon[0] + beta_t * kl[0], one rounding (fused multiply-add); beta_t by value or from device memory
+__global__ void elbo_loss_kernel(const float* __restrict__ recon, const float* __restrict__ kl, float klw,
+                                 const float* __restrict__ klw_dev, float* __restrict__ loss) {
+  if (klw_dev) klw = klw_dev[0];
+  loss[0] = __fmaf_rn(klw, kl[0], recon[0]);
+}
+extern "C" int dmi_elbo_loss(const float* recon, const float* kl, float kl_weight, const float* kl_weight_dev, float* loss,
+                             void* stream) {
+  DMI_REQUIRE(recon && kl && loss, "elbo_loss: null pointer");
+  DMI_REQUIRE(kl_weight_dev || (kl_weight >= 0.f && kl_weight <= 3.0e38f), "elbo_loss: kl_weight must be finite and >= 0");
+  elbo_loss_kernel<<<dim3(1), dim3(1), 0, (hipStream_t)stream>>>(recon, kl, kl_weight_dev ? 0.f : kl_weight, kl_weight_dev, loss);
+  DMI_CHECK_LAUNCH("elbo_loss");
+  return DMI_OK;
+}
+
+// Codebook usage.  Stage 1: block b owns rows [b*rpb, min(M, (b+1)*rpb)).  Its 1024 threads are four row groups of 256: group g takes
+// rows r0 + g, r0 + g + 4, ...; a thread owns the 8-column chunks t and t + 256 and adds q = exp(l - lse) of its columns row by row in
+// registers; groups 1..3 hand their sums over in LDS and group 0 adds the four as (0 + 1) + (2 + 3) -> qpart[b][T].  The block's
+// picks index[m] are then counted in an LDS histogram over the same storage (integer adds: exact in any order) -> cpart[b][T].
+// Stage 2: 16 columns per block, 64 groups of threads each add a 64th of the slabs in block order, then group 0 adds the 64 in
+// order (T / 16 blocks: 128 at T = 2048, enough to spread the 8 MB of partials over the device).
+__global__ __launch_bounds__(1024) void codebook_usage_part_kernel(const float* __restrict__ logits, const float* __restrict__ rowstat,
+                                                                   const int* __restrict__ index, float* __restrict__ qpart,
+                                                                   int* __restrict__ cpart, int64_t M, int T, int64_t rpb) {
+  __shared__ float red[3 * KL_MAX_T];
+  const int tid = threadIdx.x, ct = tid & 255, grp = tid >> 8;
+  const int64_t r0 = (int64_t)blockIdx.x * rpb;
+  const int64_t r1 = r0 + rpb < M ? r0 + rpb : M;
+  const int nch = T / 8;
+  if (qpart) {
+    float acc[2][8];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[i][e] = 0.f;
+#pragma unroll 4
+    for (int64_t r = r0 + grp; r < r1; r += 4) {
+      const float lse = rowstat[r * 2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int c = ct + 256 * i;
+        if (c < nch) {
+          const f32x4 l0 = *(const f32x4*)(logits + r * T + c * 8), l1 = *(const f32x4*)(logits + r * T + c * 8 + 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            acc[i][e] += __expf(l0[e] - lse);
+            acc[i][4 + e] += __expf(l1[e] - lse);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = ct + 256 * i;
+      if (grp > 0 && c < nch) {
+        float* dst = red + (grp - 1) * T + c * 8;
+        *(f32x4*)dst = f32x4{acc[i][0], acc[i][1], acc[i][2], acc[i][3]};
+        *(f32x4*)(dst + 4) = f32x4{acc[i][4], acc[i][5], acc[i][6], acc[i][7]};
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = ct + 256 * i;
+      if (grp == 0 && c < nch) {
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (acc[i][e] + red[c * 8 + e]) + (red[T + c * 8 + e] + red[2 * T + c * 8 + e]);
+        float* dst = qpart + (int64_t)blockIdx.x * T + c * 8;
+        *(f32x4*)dst = f32x4{o[0], o[1], o[2], o[3]};
+        *(f32x4*)(dst + 4) = f32x4{o[4], o[5], o[6], o[7]};
+      }
+    }
+    __syncthreads();     // red is the histogram from here on
+  }
+  if (cpart) {
+    int* hist = (int*)red;
+    for (int k = tid; k < T; k += 1024) hist[k] = 0;
+    __syncthreads();
+    for (int64_t r = r0 + tid; r < r1; r += 1024) {
+      const int k = index[r];
+      if (k >= 0 && k < T) atomicAdd(&hist[k], 1);
+    }
+    __syncthreads();
+    for (int k = tid; k < T; k += 1024) cpart[(int64_t)blockIdx.x * T + k] = hist[k];
+  }
+}
+__global__ __launch_bounds__(1024) void codebook_usage_sum_kernel(const float* __restrict__ qpart, const int* __restrict__ cpart,
+                                                                  float* __restrict__ qsum, int* __restrict__ counts, int T, int nb) {
+  __shared__ float fq[64][16];
+  __shared__ int fc[64][16];
+  const int j = threadIdx.x & 15, grp = threadIdx.x >> 4;
+  const int col = blockIdx.x * 16 + j;
+  const int per = (nb + 63) / 64;
+  const int b0 = grp * per, b1 = (b0 + per < nb) ? b0 + per : nb;
+  float a = 0.f;
+  int n = 0;
+  if (col < T) {
+    if (qpart)
+      for (int b = b0; b < b1; ++b) a += qpart[(int64_t)b * T + col];
+    if (cpart)
+      for (int b = b0; b < b1; ++b) n += cpart[(int64_t)b * T + col];
+  }
+  fq[grp][j] = a;
+  fc[grp][j] = n;
+  __syncthreads();
+  if (grp == 0 && col < T) {
+    float q = fq[0][j];
+    int c = fc[0][j];
+#pragma unroll 8
+    for (int g = 1; g < 64; ++g) {
+      q += fq[g][j];
+      c += fc[g][j];
+    }
+    if (qsum) qsum[col] = q;
+    if (counts) counts[col] = c;
+  }
+}
+extern "C" int dmi_codebook_usage(const float* logits, const float* rowstat, const int32_t* index, float* qsum, int32_t* counts,
+                                  int64_t M, int T, void* workspace, void* stream) {
+  DMI_REQUIRE(workspace && (qsum || counts), "codebook_usage: null pointer (workspace, or both qsum and counts)");
+  DMI_REQUIRE(!qsum || (logits && rowstat), "codebook_usage: null pointer (qsum needs logits and rowstat)");
+  DMI_REQUIRE(!counts || index, "codebook_usage: null pointer (counts needs index)");
+  DMI_REQUIRE(M > 0, "codebook_usage: M must be positive (M=%lld)", (long long)M);
+  DMI_REQUIRE(T > 0 && T % 8 == 0 && T <= KL_MAX_T, "codebook_usage: T must be a multiple of 8 and at most %d (T=%d)", KL_MAX_T, T);
+  const int64_t nb = usage_blocks(M);
+  const int64_t rpb = cdiv64(M, nb);
+  const int64_t nbu = cdiv64(M, rpb);       // slabs that hold a row (<= nb)
+  float* qpart = qsum ? (float*)workspace : nullptr;
+  int* cpart = counts ? (int*)((float*)workspace + nb * T) : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  codebook_usage_part_kernel<<<dim3((unsigned)nbu), dim3(1024), 0, st>>>(logits, rowstat, index, qpart, cpart, M, T, rpb);
+  DMI_CHECK_LAUNCH("codebook_usage");
+  codebook_usage_sum_kernel<<<dim3((unsigned)((T + 15) / 16)), dim3(1024), 0, st>>>(qpart, cpart, qsum, counts, T, (int)nbu);
+  DMI_CHECK_LAUNCH("codebook_usage_sum");
+  return DMI_OK;
+}
+
+// =====================================================================================
 // MSE (src/vae_tf/layers.py:24-25): loss = mean((img - out)^2) over N*Cin values; out bf16 [N, Cp] (Cp >= Cin padded);
 // d_out = 2 (out - img) * grad_scale / (N*Cin), pad channels 0.  partial sums -> dmi_sum_f32.
 // =====================================================================================

@@ -153,6 +153,11 @@ def _declare(L):
         "dmi_mse_workspace_bytes": (L64, []),
         "dmi_mse_loss": (I, [P, P, P, P, L64, I, I, F, P, P]),
         "dmi_add_f32": (I, [P, P, L64, P]),
+        "dmi_codebook_kl_workspace_bytes": (L64, [L64, I]),
+        "dmi_codebook_kl_fwd": (I, [P, P, P, L64, I, P, P]),
+        "dmi_gumbel_softmax_bwd_kl": (I, [P, P, P, P, P, L64, I, F, P, F, P, P]),
+        "dmi_elbo_loss": (I, [P, P, F, P, P, P]),
+        "dmi_codebook_usage": (I, [P, P, P, P, P, L64, I, P, P]),
         "dmi_comm_load": (I, [c_char_p]),
         "dmi_comm_unique_id_bytes": (I, []),
         "dmi_comm_unique_id": (I, [P]),
@@ -951,6 +956,34 @@ def gumbel_softmax_bwd(dy, y_soft, dlogits, M, T, temperature, temperature_dev=N
     _dev(dy, y_soft, dlogits)
     _check(lib().dmi_gumbel_softmax_bwd(_p(dy), _p(y_soft), _p(dlogits), M, T, float(temperature), _p(temperature_dev), _stream()),
            "gumbel_softmax_bwd")
+
+
+def codebook_kl_workspace_bytes(M, T):
+    return lib().dmi_codebook_kl_workspace_bytes(M, T)
+
+
+def codebook_kl_fwd(logits, rowstat, kl, M, T, ws):
+    _dev(logits, rowstat, kl, ws)
+    _check(lib().dmi_codebook_kl_fwd(_p(logits), _p(rowstat), _p(kl), M, T, _p(ws), _stream()), "codebook_kl_fwd")
+
+
+def gumbel_softmax_bwd_kl(dy, y_soft, logits, rowstat, dlogits, M, T, temperature, kl_weight, temperature_dev=None,
+                          kl_weight_dev=None):
+    _dev(dy, y_soft, logits, rowstat, dlogits, temperature_dev, kl_weight_dev)
+    _check(lib().dmi_gumbel_softmax_bwd_kl(_p(dy), _p(y_soft), _p(logits), _p(rowstat), _p(dlogits), M, T, float(temperature),
+                                           _p(temperature_dev), float(kl_weight), _p(kl_weight_dev), _stream()),
+           "gumbel_softmax_bwd_kl")
+
+
+def elbo_loss(recon, kl, loss, kl_weight, kl_weight_dev=None):
+    _dev(recon, kl, loss, kl_weight_dev)
+    _check(lib().dmi_elbo_loss(_p(recon), _p(kl), float(kl_weight), _p(kl_weight_dev), _p(loss), _stream()), "elbo_loss")
+
+
+def codebook_usage(logits, rowstat, index, qsum, counts, M, T, ws):
+    _dev(logits, rowstat, index, qsum, counts, ws)
+    _check(lib().dmi_codebook_usage(_p(logits), _p(rowstat), _p(index), _p(qsum), _p(counts), M, T, _p(ws), _stream()),
+           "codebook_usage")
 
 
 def mse_workspace_bytes():

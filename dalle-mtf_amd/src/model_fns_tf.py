@@ -2,11 +2,14 @@
 builds the DiscreteVAE, anneals the Gumbel temperature (:40-45), forward with reconstruction loss (:48-56),
 tf.train.AdamOptimizer(lr) semantics + mean over replicas (CrossShardOptimizer, :58-66), loss/image summaries
 (:68-107).  predict raises NotImplementedError as upstream (:30-31)."""
+import logging
+
 import torch
 
 from .estimator import CheckpointSaverHook, EstimatorSpec, latest_checkpoint
 from .utils import ModeKeys, SummaryWriter, mode_to_str
 from .vae_tf import DiscreteVAE
+from .vae_tf.kl import kl_log_lines, resolve_kl_options
 
 
 def _dist_info():
@@ -23,7 +26,18 @@ def temperature_schedule(step, params):
     return 1.0 if t is None else t
 
 
+def _stat_scalars(model, loss):
+    """loss_recon, loss_kl, kl_weight (beta_t of the forward just run) and the codebook statistics, as floats: what the train
+    summaries and eval_metrics carry with "codebook_stats" on or kl_loss_weight > 0 (one DiscreteVAE.codebook_stats() call)"""
+    st = model.codebook_stats()
+    on = model.kl_weight > 0
+    return dict(loss_recon=float(model.loss_recon[0]) if on else float(loss), loss_kl=st["kl"],
+                kl_weight=float(model.kl_weight_t) if on else 0.0, perplexity_soft=st["perplexity_soft"],
+                perplexity_hard=st["perplexity_hard"], codes_used_frac=st["codes_used_frac"])
+
+
 def _build(params, mode_str):
+    kl = resolve_kl_options(params)       # ValueError naming the key, before any device work
     world, rank, pg, comm = _dist_info()
     H = params["dataset"]["image_size"]
     gbs = params[f"{mode_str}_batch_size"]
@@ -38,7 +52,10 @@ def _build(params, mode_str):
         recompute_grad=params.get("recompute_grad") or False,
         use_bf16=params.get("use_bf16") or False,
         stack_factor=params.get("stack_factor") or 1,
-        dimensions=H, batch_size=gbs // world, mode=mode_str, process_group=pg, world_size=world, comm=comm)
+        dimensions=H, batch_size=gbs // world, mode=mode_str, process_group=pg, world_size=world, comm=comm,
+        kl_loss_weight=kl.kl_loss_weight, kl_anneal_steps=kl.kl_anneal_steps)
+    for line in kl_log_lines(kl, model.num_tokens, model.grid):
+        logging.getLogger("dalle_mtf_amd").info("%s %s", mode_str, line)
     ck = latest_checkpoint(params["model_path"]) if params.get("model_path") else None
     if ck is not None:
         model.load_state_dict(torch.load(ck, map_location="cpu"))
@@ -63,6 +80,8 @@ def vae_model_fn(features, labels, mode, params):
     if mode == ModeKeys.PREDICT:
         raise NotImplementedError
     assert mode in (ModeKeys.TRAIN, ModeKeys.EVAL)
+    kl = resolve_kl_options(params)
+    stats_on = kl.codebook_stats or kl.kl_loss_weight > 0
     key = f"_vae_state_{mode_str}"
     if params.get(key) is None:
         if mode == ModeKeys.EVAL and params.get("_vae_state_train") is not None and \
@@ -99,7 +118,10 @@ def vae_model_fn(features, labels, mode, params):
         if st["writer"] is not None and float(loss) < 1e-9:      # the reference's record_if(loss < 1e-9) gate (:88)
             st["writer"].images(model.global_step, "eval/input_image", denormalize(imgs))
             st["writer"].images(model.global_step, "eval/reconstruction_image", denormalize(reconstruction))
-        return EstimatorSpec(mode=mode, loss=loss, eval_metrics={"_loss": loss})
+        metrics = {"_loss": loss}
+        if stats_on:
+            metrics.update(_stat_scalars(model, loss))
+        return EstimatorSpec(mode=mode, loss=loss, eval_metrics=metrics)
 
     # TRAIN: forward + backward + optimizer run inside train_op as ONE step (DiscreteVAE.train_step: a replayed HIP graph on a
     # single GPU); spec.loss is the device scalar that step fills in -- the loss of this batch before the update, as upstream.
@@ -110,7 +132,8 @@ def vae_model_fn(features, labels, mode, params):
     host_call = None
     if st["writer"] is not None:      # rank 0 only: loss (+ temperature), input and reconstruction images (reference :68-78)
         def host_call_fn(step, loss, temperature, input):
-            st["writer"].scalars(step, loss=loss, temperature=temperature)
+            extra = _stat_scalars(model, loss) if stats_on else {}      # outside the captured step, only where something is logged
+            st["writer"].scalars(step, loss=loss, temperature=temperature, **extra)
             st["writer"].images(step, "input_image", denormalize(input))
             st["writer"].images(step, "reconstruction_image", denormalize(model.reconstruction()))   # of the step just run
         host_call = (host_call_fn, {"loss": model.loss[0], "temperature": temp, "input": imgs})

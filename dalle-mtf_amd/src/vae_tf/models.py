@@ -25,6 +25,7 @@ import torch
 
 import dalle_hip as dh
 from ..dp import GradReducer
+from .kl import kl_weight_at, resolve_kl_options, usage_stats
 
 IMG_CP = 8     # padded image channels
 OUT_CP = 64    # padded reconstruction channels
@@ -69,7 +70,8 @@ class _Conv:
 class DiscreteVAE:
     def __init__(self, num_tokens, dimensions, convblocks, dim=512, hidden_dim=64, input_channels=3, recompute_grad=False,
                  use_bf16=False, stack_factor=1, batch_size=32, mode="train", device="cuda", process_group=None, world_size=1,
-                 comm=None):
+                 comm=None, kl_loss_weight=0.0, kl_anneal_steps=None):
+        kl = resolve_kl_options(dict(kl_loss_weight=kl_loss_weight, kl_anneal_steps=kl_anneal_steps))   # ValueError before any device work
         if num_tokens > GUMBEL_MAX_TOKENS:
             raise ValueError(f"num_tokens = {num_tokens}: the Gumbel-softmax kernel (dmi_gumbel_softmax_fwd, one wave per row) "
                              f"handles codebooks of at most {GUMBEL_MAX_TOKENS} tokens")
@@ -103,10 +105,15 @@ class DiscreteVAE:
         self.n_hid = self.convblocks[-1][1]
         self.grid = self.Hs // (2 ** len(self.convblocks))
         self.global_step = 0
+        # loss = recon + beta_t KL(q || uniform), beta_t = beta min(1, step / kl_anneal_steps) (vae_tf/kl.py; 0 = the reference's loss)
+        self.kl_weight, self.kl_anneal_steps = kl.kl_loss_weight, kl.kl_anneal_steps
+        self.kl_weight_t = self.kl_weight if kl.kl_anneal_steps is None else 0.0
+        self.rowstat = self.loss_recon = self.loss_kl = self.ws_kl = self._usage = None
+        self._kl_fresh = False       # rowstat / loss_kl describe the logits buffer as it stands
         self._graphs, self._graph_warm, self._dyn_on, self._img_static = {}, False, False, None
         self._build_graph()
         self._alloc()
-        self._dyn = torch.zeros(2, dtype=torch.float32, device=self.dev)   # [lr_t, temperature] read by graph-replayed kernels
+        self._dyn = torch.zeros(3, dtype=torch.float32, device=self.dev)   # [lr_t, temperature, beta_t] read by graph-replayed kernels
         # gradient exchange (mean over replicas = SUM here x grad_scale 1/world in the Adam kernel), overlapped with backward
         self.reducer = GradReducer(self.g, world_size, comm=comm, pg=process_group)
 
@@ -250,6 +257,8 @@ class DiscreteVAE:
             wsz = max(wsz, dh.gemm_tn_workspace_bytes(max(M_out, M_in), c.kk * max(c.cin, c.cout), max(c.cin, c.cout)),
                       dh.colsum_workspace_bytes(max(M_out, M_in), max(c.cout, c.cin)))
         wsz = max(wsz, dh.gemm_tn_workspace_bytes(Mg, self.n_hid, self.num_tokens), dh.mse_workspace_bytes())
+        if self.kl_weight > 0:
+            self._kl_buffers()
         self.ws = torch.empty(int(wsz) + 1024, dtype=torch.uint8, device=dev)
         # backward(): the split-m slab reduces of the weight gradients are DEFERRED and run a few layers at a time in one launch
         # (the small configurations spent a fifth of their step in ~60 reduce launches of a few microseconds); every pending
@@ -259,6 +268,16 @@ class DiscreteVAE:
         self.ws_pool = [torch.empty_like(self.ws) for _ in range(WS_POOL)]     # (self.ws stays free for the immediate calls)
         self._ws_next = 0
         self.deferred = dh.DeferredReduces()
+
+    def _kl_buffers(self):
+        """(lse, e) per row, the two loss terms as device scalars and the workspace of dmi_codebook_kl_fwd / dmi_codebook_usage (sized by
+        dmi_codebook_kl_workspace_bytes, as the header asks): with the model when kl_loss_weight > 0, else at the first
+        codebook_stats()"""
+        if self.rowstat is None:
+            f32 = dict(dtype=torch.float32, device=self.dev)
+            self.rowstat = torch.empty(self.Mg, 2, **f32)
+            self.loss_recon, self.loss_kl = torch.zeros(1, **f32), torch.zeros(1, **f32)
+            self.ws_kl = torch.empty(int(dh.codebook_kl_workspace_bytes(self.Mg, self.num_tokens)) + 1024, dtype=torch.uint8, device=self.dev)
 
     # ------------------------------------------------------------------ parameters
     def view(self, buf, name):
@@ -463,8 +482,13 @@ class DiscreteVAE:
         self.x_enc = x
         dh.gemm_nt(x, self.n_hid, self.codebook_t, self.n_hid, self.logits, self.num_tokens, self.Mg, self.num_tokens, self.n_hid,
                    dh.GEMM_OUT_F32)
+        self._kl_fresh = False
         if return_logits:
             return self.logits.view(B, self.grid, self.grid, self.num_tokens)
+        kl_on = self.kl_weight > 0 and return_recon_loss
+        if kl_on:
+            dh.codebook_kl_fwd(self.logits, self.rowstat, self.loss_kl, self.Mg, self.num_tokens, self.ws_kl)
+            self._kl_fresh = True
         if noise is None:
             self.u.uniform_(1e-9, 1.0)
         elif not (isinstance(noise, str) and noise == "preset"):   # "preset": self.u was filled by the caller (graph replay)
@@ -477,7 +501,12 @@ class DiscreteVAE:
             return self.reconstruction()
         need_grad = (self.mode == "train") if need_grad is None else need_grad
         # d(out) of mean((img-out)^2); 1/world folds the CrossShardOptimizer mean (src/model_fns_tf.py:61) into the gradient
-        dh.mse_loss(self.img_net, x, self.ga if need_grad else None, self.loss, B * self.Hs * self.Hs, self.c_st, OUT_CP, 1.0, self.ws)
+        dh.mse_loss(self.img_net, x, self.ga if need_grad else None, self.loss_recon if kl_on else self.loss, B * self.Hs * self.Hs,
+                    self.c_st, OUT_CP, 1.0, self.ws)
+        if kl_on:       # loss = recon + beta_t KL on the device; beta_t by value, or from _dyn on the graph path
+            if not self._dyn_on:
+                self.kl_weight_t = kl_weight_at(self.global_step, self.kl_weight, self.kl_anneal_steps)
+            dh.elbo_loss(self.loss_recon, self.loss_kl, self.loss, self.kl_weight_t, kl_weight_dev=self._kl_dev())
         return self.loss[0], self.reconstruction()
 
     def _decoder_from_y(self):
@@ -561,6 +590,7 @@ class DiscreteVAE:
                 i += 2
         dh.conv2d_f32(x, self.Mg, 1, 1, self.n_hid, 1, 1, 1, [(0, 0)], self.view(self.p, "codebook/codebook"), None, None,
                       self.logits, self.num_tokens)
+        self._kl_fresh = False
         return self.logits.view(B, self.grid, self.grid, self.num_tokens)
 
     # ------------------------------------------------------------------ backward
@@ -706,7 +736,11 @@ class DiscreteVAE:
                 T, nh, Mg = self.num_tokens, self.n_hid, self.Mg
                 dh.gemm_tn(d, nh, self.y, T, self.gc2, Mg, nh, T, self.ws)                               # dC from x_dec = y C^T
                 dh.gemm_nt(d, nh, self.codebook_t, nh, self.dy, T, Mg, T, nh)                            # dy = dxdec . C
-                dh.gumbel_softmax_bwd(self.dy, self.y_soft, self.dlogits, Mg, T, self.temperature, temperature_dev=self._temp_dev())
+                if self.kl_weight > 0:     # the KL gradient (beta_t / M) q (ln q - e) joins before the one bf16 rounding
+                    dh.gumbel_softmax_bwd_kl(self.dy, self.y_soft, self.logits, self.rowstat, self.dlogits, Mg, T, self.temperature,
+                                             self.kl_weight_t, temperature_dev=self._temp_dev(), kl_weight_dev=self._kl_dev())
+                else:
+                    dh.gumbel_softmax_bwd(self.dy, self.y_soft, self.dlogits, Mg, T, self.temperature, temperature_dev=self._temp_dev())
                 dh.gemm_tn(self.x_enc, nh, self.dlogits, T, self._gv("codebook/codebook"), Mg, nh, T, self.ws)  # dC from logits = x C
                 dh.add_f32(self._gv("codebook/codebook"), self.gc2, nh * T)
                 nd = spare[0]
@@ -735,14 +769,18 @@ class DiscreteVAE:
     def _temp_dev(self):
         return self._dyn[1:2] if self._dyn_on else None
 
+    def _kl_dev(self):
+        return self._dyn[2:3] if self._dyn_on else None
+
     def train_step(self, features, lr, hard_gumbel=True, temperature=1.0, noise=None, graph=None):
         """forward + backward + optimizer_step.  The small configurations are launch-bound (vae_example: ~170 launches of a
         few microseconds each; 3.2 ms per step from Python against ~1 ms of kernel time, profiles/r02_bench_vae_example.json),
         so the step is captured ONCE as a HIP graph and replayed: per step the host then issues the image copy, the Gumbel
         uniforms (drawn eagerly), two scalar fills and one graph launch.  The learning rate lr_t
         (tf.train.AdamOptimizer's bias-corrected rate, src/model_fns_tf.py:58) and the annealed temperature (:40-45) live in
-        a 2-float device buffer the kernels read (dmi_adam_step lr_dev / dmi_gumbel_softmax_* temperature_dev), so one graph
-        serves the whole schedule.  Eager when: data-parallel (the exchange runs on its own stream and communicator), a
+        a small device buffer the kernels read (dmi_adam_step lr_dev / dmi_gumbel_softmax_* temperature_dev), and with
+        kl_loss_weight > 0 so does the ramped KL weight beta_t (dmi_gumbel_softmax_bwd_kl / dmi_elbo_loss kl_weight_dev), so one
+        graph serves the whole schedule.  Eager when: data-parallel (the exchange runs on its own stream and communicator), a
         bench event hook is set, DALLE_VAE_GRAPH=0, or graph=False.  Same kernels, same order: results are bit-identical to
         the eager step (tested).  Returns the device scalar loss."""
         want = (os.environ.get("DALLE_VAE_GRAPH", "1") != "0") if graph is None else bool(graph)
@@ -761,6 +799,9 @@ class DiscreteVAE:
             self.u.copy_(noise.to(self.dev).reshape(self.Mg, self.num_tokens))
         self._dyn[0:1].fill_(self.lr_t(lr))          # by-value kernel arguments: no host buffer whose lifetime could race a replay
         self._dyn[1:2].fill_(float(temperature))
+        if self.kl_weight > 0:
+            self.kl_weight_t = kl_weight_at(self.global_step, self.kl_weight, self.kl_anneal_steps)
+            self._dyn[2:3].fill_(self.kl_weight_t)
         self.temperature = float(temperature)
         key = bool(hard_gumbel)
         g = self._graphs.get(key)
@@ -772,7 +813,7 @@ class DiscreteVAE:
                     # outside the capture
                     self._step_body(key)
                     self._graph_warm = True
-                    return self.loss[0]
+                    return self.loss[0]      # (forward() ran in Python: _kl_fresh is as it left it)
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 step0 = self.global_step
@@ -784,12 +825,34 @@ class DiscreteVAE:
                 self._dyn_on = False
         g.replay()
         self.global_step += 1
+        self._kl_fresh = self.kl_weight > 0     # the replay rewrote logits; it ran dmi_codebook_kl_fwd on them only with a KL weight
         return self.loss[0]
 
     def _step_body(self, hard_gumbel):
         self.forward(self._img_static, return_recon_loss=True, hard_gumbel=hard_gumbel, temperature=1.0, noise="preset", need_grad=True)
         self.backward()
         self.optimizer_step(1.0)      # lr / temperature arguments are ignored on the device-scalar path
+
+    # ------------------------------------------------------------------ codebook statistics
+    def codebook_stats(self):
+        """Codebook health on the last forward's logits / index (outside the captured step; call it where something is logged):
+        kl = mean over positions of KL(q || uniform) in nats, perplexity_soft = exp(H(mean_m q[m, :])), perplexity_hard =
+        exp(H(counts / M)) of the codes the Gumbel arg-max picked, codes_used = #{counts > 0} and codes_used_frac = codes_used /
+        num_tokens.  dmi_codebook_kl_fwd (unless the forward ran it) and dmi_codebook_usage; the two entropies over [num_tokens]
+        are taken on the host in float64.  One device-to-host copy."""
+        T, Mg = self.num_tokens, self.Mg
+        self._kl_buffers()
+        if self._usage is None:
+            self._usage = dict(qsum=torch.empty(T, dtype=torch.float32, device=self.dev),
+                               counts=torch.empty(T, dtype=torch.int32, device=self.dev))
+        u = self._usage
+        if not self._kl_fresh:
+            dh.codebook_kl_fwd(self.logits, self.rowstat, self.loss_kl, Mg, T, self.ws_kl)
+            self._kl_fresh = True
+        dh.codebook_usage(self.logits, self.rowstat, self.index, u["qsum"], u["counts"], Mg, T, self.ws_kl)
+        out = dict(kl=float(self.loss_kl[0]))
+        out.update(usage_stats(u["qsum"].cpu().numpy(), u["counts"].cpu().numpy(), Mg))
+        return out
 
     def state_dict(self):
         # reference-named variables as plain tensors in a plain dict: loadable with torch.load(weights_only=True)

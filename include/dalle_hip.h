@@ -610,6 +610,28 @@ int64_t dmi_mse_workspace_bytes(void);
 int dmi_mse_loss(const float* img, const uint16_t* outp, uint16_t* dout, float* loss, int64_t N, int Cin, int Cp,
                  float grad_scale, void* workspace, void* stream);
 int dmi_add_f32(float* dst, const float* src, int64_t n, void* stream);
+/* KL(q(z|x) || uniform) of the codebook posterior and codebook usage (project extension; DESIGN.md §4 "VAE: KL term and codebook
+ * statistics").  Per row m of the fp32 logits [M, T] (no noise, no temperature): lse = logsumexp_k l_k, q_k = exp(l_k - lse),
+ * e = sum_k q_k ln q_k (a term with q = 0 contributes 0), KL_m = e + ln T, KL = mean_m KL_m (nats per position).
+ * All: stream-ordered, no allocation, no float atomics (every sum has a fixed order: two runs give equal bits), rows indexed in
+ * 64 bits.  DMI_ERR_INVALID with a message, before any launch: a null pointer, M <= 0, T % 8 != 0, T > 4096.
+ *   dmi_codebook_kl_fwd        rowstat fp32 [M, 2] = (lse_m, e_m); kl[0] = KL.  workspace: dmi_codebook_kl_workspace_bytes(M, T)
+ *                              bytes (covers dmi_codebook_usage too), 16-byte aligned.
+ *   dmi_gumbel_softmax_bwd_kl  dmi_gumbel_softmax_bwd with the KL gradient added before the one bf16 rounding:
+ *                              dlogits = bf16((1/tau) y_soft (dy - sum_j dy_j y_soft_j) + (beta_t / M) q (ln q - e)), q and ln q
+ *                              recomputed from logits and rowstat.  kl_weight_dev (nullable): beta_t is read from device memory,
+ *                              as temperature_dev is.  beta_t = 0 gives dmi_gumbel_softmax_bwd's bits.  By value: finite, >= 0.
+ *   dmi_elbo_loss              loss[0] = recon[0] + beta_t * kl[0] in one rounding (device scalars; beta_t as above).
+ *   dmi_codebook_usage         qsum fp32 [T] = sum_m q[m, k] (needs logits, rowstat); counts int32 [T] = #{m : index[m] == k}, exact
+ *                              (needs index; values outside [0, T) are not counted).  Either pair may be null, not both. */
+int64_t dmi_codebook_kl_workspace_bytes(int64_t M, int T);
+int dmi_codebook_kl_fwd(const float* logits, float* rowstat, float* kl, int64_t M, int T, void* workspace, void* stream);
+int dmi_gumbel_softmax_bwd_kl(const uint16_t* dy, const uint16_t* y_soft, const float* logits, const float* rowstat,
+                              uint16_t* dlogits, int64_t M, int T, float temperature, const float* temperature_dev,
+                              float kl_weight, const float* kl_weight_dev, void* stream);
+int dmi_elbo_loss(const float* recon, const float* kl, float kl_weight, const float* kl_weight_dev, float* loss, void* stream);
+int dmi_codebook_usage(const float* logits, const float* rowstat, const int32_t* index, float* qsum, int32_t* counts,
+                       int64_t M, int T, void* workspace, void* stream);
 
 
 /* ---- input format (host only): CRC-32C (Castagnoli) of a TFRecord length header / payload, as tf.data.TFRecordDataset
