@@ -991,12 +991,8 @@ extern "C" int dmi_attention_fwd(const uint16_t* qkv, uint16_t* o, float* lse, i
   DMI_REQUIRE(qkv && o && lse, "attention_fwd: null pointer");
   DMI_REQUIRE(B > 0 && H > 0 && S > 0 && S % 8 == 0, "attention_fwd: S must be a multiple of 8 (S=%d)", S);
   DMI_REQUIRE((int64_t)S * 3 * H * HD * 2 < 0x7fffffff, "attention_fwd: sequence too long for 32-bit buffer offsets");
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
-    (void)hipFuncSetAttribute((const void*)attn_fwd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
-    attr_done = true;
-  }
+  raise_lds_once<attn_fwd_kernel<false>>(2 * QK_STAGE);
+  raise_lds_once<attn_fwd2_kernel>(2 * QK_STAGE);
   {
     const int items = ((S + 127) / 128) * B * H;
     const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();   // two persistent blocks per CU
@@ -1607,15 +1603,11 @@ extern "C" int dmi_attention_bwd(const uint16_t* qkv, const uint16_t* o, const u
   DMI_REQUIRE((int64_t)S * 3 * H * HD * 2 < 0x7fffffff, "attention_bwd: sequence too long for 32-bit buffer offsets");
   hipStream_t st = (hipStream_t)stream;
   float* stats = delta + (int64_t)B * H * S;  // delta scratch is [3][B,H,S]: delta | (lse, delta) pairs
-  static bool attr_done = false;
   const int shm = 32768 + DKV_NSTAGE * DKV_STAGE;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
-    attr_done = true;
-  }
+  raise_lds_once<attn_bwd_dq_kernel<0, false>>(2 * QK_STAGE);
+  raise_lds_once<attn_bwd_dq_kernel<1, false>>(2 * QK_STAGE);
+  raise_lds_once<attn_bwd_dkv_kernel<0>>(shm);
+  raise_lds_once<attn_bwd_dkv_kernel<1>>(shm);
   const int items = ((S + 127) / 128) * B * H;
   {
     const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();   // two persistent blocks per CU
@@ -2787,11 +2779,7 @@ extern "C" int dmi_attention_fwd_masked(const uint16_t* qkv, uint16_t* o, float*
   if (rt == 1) return dmi_attention_fwd_hd(qkv, o, lse, B, H, S, head_dim, stream);
   DMI_REQUIRE(B > 0 && H > 0 && S > 0 && S % 8 == 0, "attention_fwd_masked: S must be a multiple of 8 (S=%d)", S);
   DMI_REQUIRE((int64_t)S * 3 * H * HD * 2 < 0x7fffffff, "attention_fwd_masked: sequence too long for 32-bit buffer offsets");
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<true, const int*>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
-    attr_done = true;
-  }
+  raise_lds_once<attn_fwd_kernel<true, const int*>>(2 * QK_STAGE);
   const int items = ((S + 127) / 128) * B * H;
   const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();   // two persistent blocks per CU
   const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
@@ -2813,12 +2801,8 @@ extern "C" int dmi_attention_bwd_masked(const uint16_t* qkv, const uint16_t* o, 
   hipStream_t st = (hipStream_t)stream;
   float* stats = delta + (int64_t)B * H * S;
   const int shm = 32768 + DKV_NSTAGE * DKV_STAGE;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<1, true, const int*>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * QK_STAGE);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
-    attr_done = true;
-  }
+  raise_lds_once<attn_bwd_dq_kernel<1, true, const int*>>(2 * QK_STAGE);
+  raise_lds_once<attn_bwd_dkv_masked_kernel>(shm);
   const int items = ((S + 127) / 128) * B * H;
   {
     const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();

@@ -114,3 +114,11 @@ void dmi_set_error(const char* fmt, ...);
   } while (0)
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// One-time host setup, safe from any host thread: a function-local static is initialised once, under the compiler's guard.
+// raise_lds_once<kernel>(bytes): lift the kernel's dynamic LDS limit before its first launch (the same bytes at every call site).
+template <auto KERNEL>
+static inline void raise_lds_once(int bytes) {
+  static const hipError_t once = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  (void)once;
+}

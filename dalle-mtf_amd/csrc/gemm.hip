@@ -20,91 +20,32 @@
 // The measured-slower generations of these kernels (register-staged v1, persistent v3, hand-scheduled 3-stage v5,
 // grouped / stream-K weight gradients) live on the git branch `r01-kernel-variants`, not in the product library.
 #include "common.h"
-#include <string.h>
+#include "gemm_plan.h"
+#include <atomic>
 #include <type_traits>
 
-static int g_opt_nt4 = 1;        // 256x128 NT tile: 0 never, 1 auto (>= 3 residencies and K <= 1024), 2 always (tests)
-static int g_opt_nt8 = 1;        // 256x256 NT tile (8 waves): 0 never, 1 auto (K >= nt8_min_k, whole residencies), 2 always (tests)
-int g_opt_reserve_cus = 0;       // CUs the persistent kernels (256x256 NT, attention) leave free, and which switch the one-tile-per-CU
-                                 // full-row kernel off: a block of those kernels whose CU is held by a concurrent kernel (the RCCL channels
-                                 // of the gradient exchange) starts late and stretches the whole launch -- measured with the token sort as
-                                 // the intruder (layer 0's forward 687 us instead of 410 us).  The engine sets 16 when world_size > 1.
+static GemmOptions g_opt;        // every dispatch option but the attention kernels' (gemm_plan.h says what each one does)
+int g_opt_reserve_cus = 0;       // = g_opt.reserve_cus, for attention.hip's persistent grids
 int g_opt_attn_fwd = 1;          // attention forward kernel: 0 round-2 form, 1 software-pipelined (round 6)
 int g_opt_attn_bwd = 1;          // attention backward: bit 0 = whole-row epilogue stores through LDS (round 6)
 int g_opt_attn_mask_force = 0;   // 1: a causal mask plan runs the masked attention kernels too (tests, tools/attn_mask_bench.py)
 int g_opt_attn_xcd = 8;          // attention block order: 0 plain grid; G >= 1: per-XCD ranges, groups of G (batch, head) pairs tile-major
-static int g_opt_tn8 = 0;        // 256x256 weight-gradient tile (8 waves, still on 32x32x16 MFMAs): 0 never (default since the 128x128 kernel
-                                 // moved to 16x16x32: 45 / 76 us vs 60 / 86 us on the 512x512 / 512x1536 gradients), 1 auto (few tiles), 2 always (tests)
-static int g_opt_tn8_max_tiles = 16;   // auto mode: use the 256x256 weight-gradient kernel below this many tiles (A/B hook)
-static int g_opt_nt8_min_k = 2048;   // auto mode of the 256x256 NT tile: minimum K.  2048 (was 4096): the 1.3B dimensions' K = 2048 products
-                                     // run 354 -> 339 ms/step (profiles/r03_ab_nt8_min_k.log); K = 1024 measured equal, K = 512 slower
-static int g_opt_skinny = 1;     // M <= 32 products (the decode step) on the weight-streaming kernel: 0 never, 1 auto
-static int g_opt_tn_wide = 1;    // [r06] unsplit weight gradients with many column stripes (the head) as a gang stream-K on 128 x 256 tiles: 0 never, 1 auto
-static int g_opt_tn_tail = 1;    // weight gradients: row-split the tiles of a ragged last residency (see gemm_tn_tail_kernel)
-static int g_opt_cstream = 1;    // bf16 outputs stored write-through (sc1; + non-temporal from cstream_nt_min_mb MiB): 0 never, 1 auto (outputs >=
-                                 // cstream_min_mb MiB: they cannot be re-read from L2 anyway, and as plain stores they evict the operands the concurrent
-                                 // tiles share), 2 always sc1, 3 always sc1 nt, 4 auto with sc1 only (A/B)
-static int g_opt_cstream_min_mb = 256;
-static int g_opt_cstream_nt_min_mb = 1024;
-static int g_opt_res16 = 1;      // register epilogue: the residual as 16-byte pieces through the row swap (1) or 8-byte pieces in the accumulator layout (0)
-static int g_opt_ntr = 1;        // full-row 160x512 tiles for N = 512 products (gemm_ntr_kernel): 0 never, 1 auto, 2 whenever the shape allows
-static int g_opt_nt8p = 1;       // persistent 256x256 NT kernel with the register epilogue (gemm_nt8p_kernel): 0 never, 1 auto (short K, >= 2
-                                 // tiles per CU), 2 whenever the shape allows it (tests, tools/kbench.py)
-static int g_opt_relu_bits = 1;   // FFN ReLU mask as one bit per element (dmi_gemm_nt_relu_bits / _mask_bits) where the persistent kernel runs: 0 never, 1 auto
-static int g_opt_nt8p_max_k = 1024;   // auto mode: K above this keeps the one-tile-per-block kernels (the main loop then dominates a tile)
-static int g_opt_nt4_lds = 49152;   // dynamic LDS requested by the 256x128 NT kernel: 49152 = what it uses (3 blocks / CU); 65536 / 98304
-                                    // cap the residency at 2 / 1 blocks per CU (tools/phases.py: a block's phases without co-resident blocks)
 unsigned long long* g_dbg_buf = nullptr;   // (also read by the ATTN_STAMP experiment build of attention.hip)
 extern "C" int dmi_set_debug_buffer(void* p) { g_dbg_buf = (unsigned long long*)p; return 0; }
-extern "C" int dmi_get_option(const char* name) {
-  if (!strcmp(name, "nt4")) return g_opt_nt4;
-  if (!strcmp(name, "nt8")) return g_opt_nt8;
-  if (!strcmp(name, "tn_tail")) return g_opt_tn_tail;
-  if (!strcmp(name, "tn_wide")) return g_opt_tn_wide;
-  if (!strcmp(name, "nt4_lds")) return g_opt_nt4_lds;
-  if (!strcmp(name, "nt8p")) return g_opt_nt8p;
-  if (!strcmp(name, "ntr")) return g_opt_ntr;
-  if (!strcmp(name, "cstream")) return g_opt_cstream;
-  if (!strcmp(name, "cstream_min_mb")) return g_opt_cstream_min_mb;
-  if (!strcmp(name, "cstream_nt_min_mb")) return g_opt_cstream_nt_min_mb;
-  if (!strcmp(name, "nt8p_max_k")) return g_opt_nt8p_max_k;
-  if (!strcmp(name, "relu_bits")) return g_opt_relu_bits;
-  if (!strcmp(name, "res16")) return g_opt_res16;
-  if (!strcmp(name, "skinny")) return g_opt_skinny;
-  if (!strcmp(name, "nt8_min_k")) return g_opt_nt8_min_k;
-  if (!strcmp(name, "tn8")) return g_opt_tn8;
-  if (!strcmp(name, "tn8_max_tiles")) return g_opt_tn8_max_tiles;
-  if (!strcmp(name, "attn_xcd")) return g_opt_attn_xcd;
-  if (!strcmp(name, "attn_mask_force")) return g_opt_attn_mask_force;
-  if (!strcmp(name, "attn_fwd")) return g_opt_attn_fwd;
-  if (!strcmp(name, "attn_bwd")) return g_opt_attn_bwd;
-  if (!strcmp(name, "reserve_cus")) return g_opt_reserve_cus;
-  return -1;
-}
+
+static const OptionSlot g_option_table[] = {
+    {"nt4", &g_opt.nt4}, {"nt8", &g_opt.nt8}, {"nt8_min_k", &g_opt.nt8_min_k}, {"nt8p", &g_opt.nt8p}, {"nt8p_max_k", &g_opt.nt8p_max_k},
+    {"ntr", &g_opt.ntr}, {"nt4_lds", &g_opt.nt4_lds, 49152, 163840}, {"skinny", &g_opt.skinny}, {"res16", &g_opt.res16},
+    {"relu_bits", &g_opt.relu_bits}, {"cstream", &g_opt.cstream}, {"cstream_min_mb", &g_opt.cstream_min_mb},
+    {"cstream_nt_min_mb", &g_opt.cstream_nt_min_mb}, {"tn8", &g_opt.tn8}, {"tn8_max_tiles", &g_opt.tn8_max_tiles},
+    {"tn_wide", &g_opt.tn_wide}, {"tn_tail", &g_opt.tn_tail}, {"reserve_cus", &g_opt.reserve_cus, 0, INT32_MAX},
+    {"attn_xcd", &g_opt_attn_xcd}, {"attn_mask_force", &g_opt_attn_mask_force, INT32_MIN, INT32_MAX, true},
+    {"attn_fwd", &g_opt_attn_fwd}, {"attn_bwd", &g_opt_attn_bwd}};
+extern "C" int dmi_get_option(const char* name) { return option_get(g_option_table, name); }
 extern "C" int dmi_set_option(const char* name, int value) {
-  if (!strcmp(name, "nt4")) { g_opt_nt4 = value; return 0; }
-  if (!strcmp(name, "nt8")) { g_opt_nt8 = value; return 0; }
-  if (!strcmp(name, "tn_tail")) { g_opt_tn_tail = value; return 0; }
-  if (!strcmp(name, "tn_wide")) { g_opt_tn_wide = value; return 0; }
-  if (!strcmp(name, "nt4_lds")) { if (value < 49152 || value > 163840) return -1; g_opt_nt4_lds = value; return 0; }
-  if (!strcmp(name, "nt8p")) { g_opt_nt8p = value; return 0; }
-  if (!strcmp(name, "ntr")) { g_opt_ntr = value; return 0; }
-  if (!strcmp(name, "cstream")) { g_opt_cstream = value; return 0; }
-  if (!strcmp(name, "cstream_min_mb")) { g_opt_cstream_min_mb = value; return 0; }
-  if (!strcmp(name, "cstream_nt_min_mb")) { g_opt_cstream_nt_min_mb = value; return 0; }
-  if (!strcmp(name, "nt8p_max_k")) { g_opt_nt8p_max_k = value; return 0; }
-  if (!strcmp(name, "relu_bits")) { g_opt_relu_bits = value; return 0; }
-  if (!strcmp(name, "res16")) { g_opt_res16 = value; return 0; }
-  if (!strcmp(name, "skinny")) { g_opt_skinny = value; return 0; }
-  if (!strcmp(name, "nt8_min_k")) { g_opt_nt8_min_k = value; return 0; }
-  if (!strcmp(name, "tn8")) { g_opt_tn8 = value; return 0; }
-  if (!strcmp(name, "tn8_max_tiles")) { g_opt_tn8_max_tiles = value; return 0; }
-  if (!strcmp(name, "attn_xcd")) { g_opt_attn_xcd = value; return 0; }
-  if (!strcmp(name, "attn_mask_force")) { g_opt_attn_mask_force = value ? 1 : 0; return 0; }
-  if (!strcmp(name, "attn_fwd")) { g_opt_attn_fwd = value; return 0; }
-  if (!strcmp(name, "attn_bwd")) { g_opt_attn_bwd = value; return 0; }
-  if (!strcmp(name, "reserve_cus")) { if (value < 0) return -1; g_opt_reserve_cus = value; return 0; }
-  return -1;
+  const int rc = option_set(g_option_table, name, value);
+  g_opt_reserve_cus = g_opt.reserve_cus;
+  return rc;
 }
 
 #define BM 128
@@ -1827,109 +1768,72 @@ __global__ __launch_bounds__(64 * SK_WAVES) void gemm_ln_nt_skinny_kernel(const 
   }
 }
 
-static int num_cus() {
-  static int n = 0;
-  if (!n) {
+// the tile geometry gemm_plan.h plans with is the kernels'
+static_assert(BM == NT2_TILE && BN == NT2_TILE && BK == NT_BK && BM4 == NT4_TILE_M && BM8 == NT8_TILE && BN8 == NT8_TILE && GROUP_M == TN_GROUP_ORDER);
+
+static int num_cus() {    // CUs of the current device (256, the MI355X's count, where no device answers)
+  static const int n = [] {
     int dev = 0;
     hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n < 8) n = 256;
-  }
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
+    return prop.multiProcessorCount >= 8 ? prop.multiProcessorCount : 256;
+  }();
   return n;
 }
 
-static int persistent_grid() {    // blocks of a one-per-CU persistent kernel: a multiple of 8 (block id % 8 = XCD)
-  int n = (num_cus() - g_opt_reserve_cus) & ~7;
-  return n < 8 ? 8 : n;
-}
-
-// persistent 256x256 tiles (gemm_nt8p_kernel): what a launch needs, and whether the automatic choice takes it (short K, at
-// least two tiles per CU)
-static bool nt8p_can(const GemmArgs& a) {
-  return a.k_per_split == a.K && a.K % 128 == 0 && (int64_t)a.M * a.lda < (1 << 30) && (int64_t)a.N * a.ldb < (1 << 30);
-}
-static bool nt8p_auto(int M, int N, int K) {
-  return K <= g_opt_nt8p_max_k && ((M + BM8 - 1) / BM8) * ((N + BN8 - 1) / BN8) >= 2 * num_cus();
-}
+// the kernels of an epilogue: which arms of nt_plan exist for FLAGS (launch_nt instantiates exactly these)
 template <int FLAGS>
-static int launch_nt8p(const GemmArgs& a, hipStream_t st) {
-  static bool attr8p = false;
-  if (!attr8p) { (void)hipFuncSetAttribute((const void*)gemm_nt8p_kernel<FLAGS>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072); attr8p = true; }
-  GemmArgs b = a;
-  b.tiles_m = (a.M + BM8 - 1) / BM8; b.tiles_n = (a.N + BN8 - 1) / BN8;
-  gemm_nt8p_kernel<FLAGS><<<dim3(persistent_grid()), dim3(512), 131072, st>>>(b);
-  DMI_CHECK_LAUNCH("gemm_nt8p");
+constexpr NtTraits nt_traits = {
+    FLAGS == 0 || FLAGS == DMI_GEMM_BIAS || FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_RELU) || FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_RESIDUAL) ||
+        FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_GELU) || FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_GELU | GEMM_GELU_PRE) || FLAGS == GEMM_GELU_GRAD,
+    // (the GELU epilogues are not compiled into the full-row kernel: with 4 d = 512 those products run on the other tiles)
+    epi_regs_ok<FLAGS> && !(FLAGS & (GEMM_SOFTMAX | DMI_GEMM_GELU | GEMM_GELU_GRAD)),
+    epi_regs_ok<FLAGS>, !(FLAGS & DMI_GEMM_OUT_F32), (FLAGS & GEMM_SOFTMAX) != 0};
+
+// KERNEL on the plan's grid, its tile counts and `pf` in the arguments, its dynamic LDS limit raised once
+template <auto KERNEL>
+static int launch_planned(GemmArgs a, const NtPlan& p, const char* name, hipStream_t st) {
+  raise_lds_once<KERNEL>(p.lds);
+  a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.pf = p.pf;
+  KERNEL<<<dim3(p.grid_x, p.grid_y), dim3(p.block), p.lds, st>>>(a);
+  DMI_CHECK_LAUNCH(name);
   return DMI_OK;
 }
-
+// Plan, then launch.  Each arm sits behind its trait, so a kernel that is not built for FLAGS is never instantiated.
 template <int FLAGS>
-static int launch_nt(const GemmArgs& a, int nsplit, hipStream_t st) {
-  const dim3 grid(a.tiles_m * a.tiles_n, nsplit), blk(256);
-  if constexpr (FLAGS == 0 || FLAGS == DMI_GEMM_BIAS || FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_RELU) || FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_RESIDUAL) ||
-                FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_GELU) || FLAGS == (DMI_GEMM_BIAS | DMI_GEMM_GELU | GEMM_GELU_PRE) || FLAGS == GEMM_GELU_GRAD) {
-    if (g_opt_skinny && a.M <= 32 && nsplit == 1 && a.N % 16 == 0) {
-      gemm_nt_skinny_kernel<FLAGS><<<dim3(a.N / 16), dim3(64 * SK_WAVES), 0, st>>>(a);
-      DMI_CHECK_LAUNCH("gemm_nt_skinny");
-      return DMI_OK;
-    }
+static int launch_nt(GemmArgs a, int nsplit, hipStream_t st) {
+  constexpr NtTraits T = nt_traits<FLAGS>;
+  const NtPlan p = nt_plan(T, a.M, a.N, a.K, a.lda, a.ldb, a.k_per_split, nsplit, g_opt, num_cus());
+  switch (p.kernel) {
+    case NtKernel::SKINNY:
+      if constexpr (T.skinny) {
+        gemm_nt_skinny_kernel<FLAGS><<<dim3(p.grid_x), dim3(p.block), 0, st>>>(a);
+        DMI_CHECK_LAUNCH("gemm_nt_skinny");
+        return DMI_OK;
+      }
+      break;
+    case NtKernel::NTR:
+      if constexpr (T.ntr) return launch_planned<gemm_ntr_kernel<FLAGS, NTR_ROWS / 32>>(a, p, "gemm_ntr", st);
+      break;
+    case NtKernel::NT8P:
+      if constexpr (T.regs) return launch_planned<gemm_nt8p_kernel<FLAGS>>(a, p, "gemm_nt8p", st);
+      break;
+    case NtKernel::NT8: return launch_planned<gemm_nt8_kernel<FLAGS>>(a, p, "gemm_nt8", st);
+    case NtKernel::NT4:
+      if constexpr (T.nt4) {
+        // the one limit that follows a run-time option: set again when the value changed (not on every launch: a host call each)
+        static std::atomic<int> set4{0};
+        if (set4.exchange(p.lds) != p.lds) (void)hipFuncSetAttribute((const void*)gemm_nt4_kernel<FLAGS>, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
+        a.tiles_m = p.tiles_m;
+        gemm_nt4_kernel<FLAGS><<<dim3(p.grid_x), dim3(p.block), p.lds, st>>>(a);
+        DMI_CHECK_LAUNCH("gemm_nt4");
+        return DMI_OK;
+      }
+      break;
+    case NtKernel::NT2: return launch_planned<gemm_nt2_kernel<FLAGS>>(a, p, "gemm_nt", st);
   }
-  // (the GELU epilogues are not compiled into the full-row kernel: with 4 d = 512 those products run on the tiles below)
-  if constexpr (epi_regs_ok<FLAGS> && !(FLAGS & (GEMM_SOFTMAX | DMI_GEMM_GELU | GEMM_GELU_GRAD))) {
-    // full-row tiles: N = 512 exactly, one 160-row tile per block
-    if (g_opt_ntr && a.N == 512 && nsplit == 1 && a.k_per_split == a.K && a.K % 32 == 0 && (int64_t)a.N * a.ldb < (1 << 30) &&
-        (g_opt_ntr == 2 || (a.M >= 160 * (num_cus() / 2) && a.K <= 4096 && g_opt_reserve_cus == 0))) {   // (the head's input gradient, K = 50816: 1.83 ms here vs 1.32 ms on 256x256 tiles)
-      constexpr int RT = 5;
-      constexpr int LDSB = 3 * (32 * RT * 64 + 32768);
-      static bool attrr = false;
-      if (!attrr) { (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<FLAGS, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB); attrr = true; }
-      GemmArgs b = a;
-      b.pf = g_opt_res16 ? 2 : 0;     // residual rows as 16-byte pieces (A/B switch)
-      gemm_ntr_kernel<FLAGS, RT><<<dim3((a.M + 32 * RT - 1) / (32 * RT)), dim3(512), LDSB, st>>>(b);
-      DMI_CHECK_LAUNCH("gemm_ntr");
-      return DMI_OK;
-    }
-  }
-  if constexpr (epi_regs_ok<FLAGS>) {
-    // persistent 256x256 tiles: short-K products with at least two tiles per CU (see gemm_nt8p_kernel)
-    const bool can = nsplit == 1 && nt8p_can(a);
-    const bool auto_ok = nt8p_auto(a.M, a.N, a.K);
-    // 3 = auto for the softmax head only (tests: its register epilogue adds the row-sum partials in its own fixed order, so a
-    // step that is to be compared bit for bit with the 128x128 kernels keeps the head where it is)
-    if (can && ((g_opt_nt8p == 1 && auto_ok) || g_opt_nt8p == 2 || (g_opt_nt8p == 3 && (FLAGS & GEMM_SOFTMAX) && auto_ok)))
-      return launch_nt8p<FLAGS>(a, st);
-  }
-  {
-    const int t8m = (a.M + BM8 - 1) / BM8, t8n = (a.N + BN8 - 1) / BN8;
-    // 256x256 tiles (one 8-wave block per CU): main-loop-bound shapes only -- long K and whole residencies of 256 blocks
-    const bool auto8 = g_opt_nt8 == 1 && a.k_per_split >= g_opt_nt8_min_k && (t8m * t8n * nsplit) % 256 == 0;
-    if (auto8 || g_opt_nt8 == 2) {
-      static bool attr8 = false;
-      if (!attr8) { (void)hipFuncSetAttribute((const void*)gemm_nt8_kernel<FLAGS>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072); attr8 = true; }
-      GemmArgs b = a;
-      b.tiles_m = t8m; b.tiles_n = t8n;
-      gemm_nt8_kernel<FLAGS><<<dim3(t8m * t8n, nsplit), dim3(512), 131072, st>>>(b);
-      DMI_CHECK_LAUNCH("gemm_nt8");
-      return DMI_OK;
-    }
-  }
-  if constexpr (!(FLAGS & DMI_GEMM_OUT_F32)) {
-    const int tiles4 = ((a.M + BM4 - 1) / BM4) * a.tiles_n;
-    // 256x128 tiles when the grid still covers >= 3 residencies; long-K shapes prefer the BK = 64 kernel.  2 = force (tests)
-    if (g_opt_nt4 && nsplit == 1 && a.k_per_split == a.K && ((tiles4 >= 1536 && a.K <= 1024) || g_opt_nt4 == 2)) {
-      static int attr4 = 0;
-      if (attr4 != g_opt_nt4_lds) { (void)hipFuncSetAttribute((const void*)gemm_nt4_kernel<FLAGS>, hipFuncAttributeMaxDynamicSharedMemorySize, g_opt_nt4_lds); attr4 = g_opt_nt4_lds; }
-      GemmArgs b = a;
-      b.tiles_m = (a.M + BM4 - 1) / BM4;
-      gemm_nt4_kernel<FLAGS><<<dim3(tiles4), blk, g_opt_nt4_lds, st>>>(b);
-      DMI_CHECK_LAUNCH("gemm_nt4");
-      return DMI_OK;
-    }
-  }
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)gemm_nt2_kernel<FLAGS>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); attr_done = true; }
-  gemm_nt2_kernel<FLAGS><<<grid, blk, 65536, st>>>(a);
-  DMI_CHECK_LAUNCH("gemm_nt");
-  return DMI_OK;
+  dmi_set_error("gemm_nt: the plan names a kernel that is not built for epilogue %d", FLAGS);    // (nt_plan honours the traits: not reached)
+  return DMI_ERR_UNSUPPORTED;
 }
 
 static int check_nt(const void* A, int lda, const void* B, int ldb, const void* C, int ldc, int M, int N, int K) {
@@ -1948,13 +1852,7 @@ static void fill_nt_args(GemmArgs& a, const uint16_t* A, int lda, const uint16_t
   a.k_per_split = K; a.slab_stride = 0; a.dbg = nullptr; a.pf = 0;
   a.ln_gamma = nullptr; a.ln_beta = nullptr; a.ln_y = nullptr; a.ln_mean = nullptr; a.ln_rstd = nullptr; a.ln_eps = 0.f; a.ln_ldy = 0;
   a.ln_x = nullptr; a.ln_part = nullptr; a.B2 = nullptr; a.C2 = nullptr; a.ldb2 = 0;
-  const int64_t cbytes = ((int64_t)(M - 1) * ldc + N) * 2;     // bf16 outputs (the fp32 forms do not use the policy)
-  // 1 (default): auto by size -- sc1 from cstream_min_mb, sc1 nt from cstream_nt_min_mb (a stream far larger than the 256-MB
-  // Infinity Cache: the 4-GB softmax numerators; outputs of a few hundred MB that the next kernel re-reads were measured with
-  // sc1 only and keep it); 2: always sc1; 3: always sc1 nt; 4: auto by size, sc1 only (A/B)
-  const bool big = cbytes >= ((int64_t)g_opt_cstream_min_mb << 20), huge = cbytes >= ((int64_t)g_opt_cstream_nt_min_mb << 20);
-  const int pol = (g_opt_cstream == 1 && big) ? (huge ? 2 : 1) : (g_opt_cstream == 2) ? 1 : (g_opt_cstream == 3) ? 2 : (g_opt_cstream == 4 && big) ? 1 : 0;
-  a.cpol = cbytes < (int64_t)0xffffffff ? pol : 0;
+  a.cpol = nt_cpol(M, N, ldc, g_opt);
 }
 
 extern "C" int dmi_gemm_nt(const uint16_t* A, int lda, const uint16_t* Bt, int ldb, void* C, int ldc, int M, int N,
@@ -1993,11 +1891,11 @@ extern "C" int64_t dmi_relu_bits_bytes(int M, int N) { return (int64_t)((N + 63)
 // 1 if the automatic dispatch runs these shapes on the kernel that has the bit forms (the engine then uses them; otherwise it keeps
 // dmi_gemm_nt with DMI_GEMM_RELU / DMI_GEMM_RELU_MASK, which every tile size serves)
 extern "C" int dmi_relu_bits_auto(int M, int N, int K) {
-  return (g_opt_relu_bits && g_opt_nt8p == 1 && N % 64 == 0 && K % 128 == 0 && nt8p_auto(M, N, K)) ? 1 : 0;
+  return relu_bits_auto(M, N, K, g_opt, num_cus()) ? 1 : 0;
 }
 static int check_bits(const char* who, const GemmArgs& a, const void* bits) {
   DMI_REQUIRE(bits && ((uintptr_t)bits & 7) == 0, "%s: null / unaligned bit buffer", who);
-  if (a.N % 64 != 0 || !nt8p_can(a)) {
+  if (!relu_bits_can(a.M, a.N, a.K, a.lda, a.ldb)) {
     dmi_set_error("%s: needs N %% 64 == 0, K %% 128 == 0 and operands below 2 GiB (M=%d N=%d K=%d)", who, a.M, a.N, a.K);
     return DMI_ERR_UNSUPPORTED;
   }
@@ -2012,7 +1910,7 @@ extern "C" int dmi_gemm_nt_relu_bits(const uint16_t* A, int lda, const uint16_t*
   fill_nt_args(a, A, lda, Bt, ldb, C, ldc, M, N, K);
   a.bias = bias; a.relu_bits = (unsigned short*)bits; a.dbg = g_dbg_buf;
   if ((rc = check_bits("gemm_nt_relu_bits", a, bits))) return rc;
-  return launch_nt8p<DMI_GEMM_BIAS | DMI_GEMM_RELU | GEMM_RELU_BITS>(a, (hipStream_t)stream);
+  return launch_planned<gemm_nt8p_kernel<DMI_GEMM_BIAS | DMI_GEMM_RELU | GEMM_RELU_BITS>>(a, nt8p_plan(M, N, g_opt, num_cus()), "gemm_nt8p", (hipStream_t)stream);
 }
 extern "C" int dmi_gemm_nt_mask_bits(const uint16_t* A, int lda, const uint16_t* Bt, int ldb, uint16_t* C, int ldc, int M, int N, int K,
                                      const void* bits, void* stream) {
@@ -2022,7 +1920,7 @@ extern "C" int dmi_gemm_nt_mask_bits(const uint16_t* A, int lda, const uint16_t*
   fill_nt_args(a, A, lda, Bt, ldb, C, ldc, M, N, K);
   a.relu_bits = (unsigned short*)bits; a.dbg = g_dbg_buf;
   if ((rc = check_bits("gemm_nt_mask_bits", a, bits))) return rc;
-  return launch_nt8p<GEMM_MASK_BITS>(a, (hipStream_t)stream);
+  return launch_planned<gemm_nt8p_kernel<GEMM_MASK_BITS>>(a, nt8p_plan(M, N, g_opt, num_cus()), "gemm_nt8p", (hipStream_t)stream);
 }
 
 // ---- the GELU FFN (DALLE activation_fn "gelu", see gelu_sig above): FFN-1 forward keeps the pre-activation for the FFN-2 input
@@ -2161,10 +2059,13 @@ extern "C" int dmi_glu_bwd(const uint16_t* dh, int lddh, const uint16_t* pre, in
 // library would run it on full-row tiles itself: N = 512 (one block owns whole rows), every operand inside the 32-bit buffer offsets
 // of gemm_ntr_kernel, no CUs reserved for a concurrent exchange (launch_nt keeps the 128x128 kernel then).  Callers gate the fused
 // forms on it when they size their buffers and keep the two-kernel path otherwise (advisor finding, round 5).
-extern "C" int dmi_gemm_nt_ln_auto(int M, int N, int K) {
-  if (M <= 0 || N != 512 || K <= 0 || K % BK != 0) return 0;
-  if ((int64_t)N * K >= (1 << 30) || (int64_t)M * K >= ((int64_t)1 << 31) || (int64_t)M * N * 2 >= ((int64_t)1 << 31)) return 0;
-  return g_opt_reserve_cus == 0 ? 1 : 0;
+extern "C" int dmi_gemm_nt_ln_auto(int M, int N, int K) { return nt_ln_auto(M, N, K, g_opt) ? 1 : 0; }
+
+// the two fused full-row forms run `a` on gemm_ntr_kernel<0, 5, LN>
+template <int LN>
+static int launch_ntr_ln(const GemmArgs& a, const char* name, hipStream_t st) {
+  // (pf 0: option res16 belongs to the plain register epilogue; the fused epilogues do not read it)
+  return launch_planned<gemm_ntr_kernel<0, NTR_ROWS / 32, LN>>(a, ntr_plan(a.M, 0), name, st);
 }
 
 // Product with N = 512 outputs + bias + residual, and the LayerNorm of the result in the same pass (full-row tiles, see
@@ -2177,7 +2078,7 @@ extern "C" int dmi_gemm_nt_ln(const uint16_t* A, int lda, const uint16_t* Bt, in
   DMI_REQUIRE(gamma && beta && Y && mean && rstd, "gemm_nt_ln: null pointer");
   DMI_REQUIRE((((uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)Y | (uintptr_t)bias | (uintptr_t)residual) & 15) == 0 && ldy % 8 == 0 && ldy >= N,
               "gemm_nt_ln: operands must be 16-byte aligned");
-  if (N != 512 || (int64_t)N * ldb >= (1 << 30) || (int64_t)M * lda >= ((int64_t)1 << 31)) {
+  if (!nt_ln_can(M, N, lda, ldb)) {
     dmi_set_error("gemm_nt_ln: the fused form needs N = 512 (one block owns whole rows); got N=%d", N);
     return DMI_ERR_UNSUPPORTED;
   }
@@ -2185,13 +2086,7 @@ extern "C" int dmi_gemm_nt_ln(const uint16_t* A, int lda, const uint16_t* Bt, in
   fill_nt_args(a, A, lda, Bt, ldb, C, ldc, M, N, K);
   a.bias = bias; a.residual = residual;
   a.ln_gamma = gamma; a.ln_beta = beta; a.ln_y = Y; a.ln_ldy = ldy; a.ln_mean = mean; a.ln_rstd = rstd; a.ln_eps = eps;
-  constexpr int RT = 5;
-  constexpr int LDSB = 3 * (32 * RT * 64 + 32768);
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<0, RT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB); attr = true; }
-  gemm_ntr_kernel<0, RT, 1><<<dim3((M + 32 * RT - 1) / (32 * RT)), dim3(512), LDSB, (hipStream_t)stream>>>(a);
-  DMI_CHECK_LAUNCH("gemm_nt_ln");
-  return DMI_OK;
+  return launch_ntr_ln<1>(a, "gemm_nt_ln", (hipStream_t)stream);
 }
 
 // Product with N = 512 outputs whose result is the gradient arriving at a LayerNorm, and that LayerNorm's backward in the same pass
@@ -2205,30 +2100,20 @@ extern "C" int dmi_gemm_nt_lnbwd(const uint16_t* A, int lda, const uint16_t* Bt,
   if (rc) return rc;
   DMI_REQUIRE(x && gamma && mean && rstd && part, "gemm_nt_lnbwd: null pointer");
   DMI_REQUIRE((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)dres | (uintptr_t)part) & 15) == 0, "gemm_nt_lnbwd: operands must be 16-byte aligned");
-  if (N != 512 || (int64_t)N * ldb >= (1 << 30) || (int64_t)M * lda >= ((int64_t)1 << 31) || (int64_t)M * N * 2 >= ((int64_t)1 << 31)) {
+  if (!nt_lnbwd_can(M, N, lda, ldb)) {
     dmi_set_error("gemm_nt_lnbwd: the fused form needs N = 512 (one block owns whole rows) and operands below 2 GiB; got M=%d N=%d", M, N);
     return DMI_ERR_UNSUPPORTED;
   }
   GemmArgs a;
   fill_nt_args(a, A, lda, Bt, ldb, dx, N, M, N, K);
   a.residual = dres; a.ln_x = x; a.ln_gamma = gamma; a.ln_mean = (float*)mean; a.ln_rstd = (float*)rstd; a.ln_y = dx; a.ln_ldy = N; a.ln_part = part;
-  constexpr int RT = 5;
-  constexpr int LDSB = 3 * (32 * RT * 64 + 32768);
   if (B2 || C2) {     // chained: C2[M, N] = dx . B2^T in the same launch (B2 [N, ldb2] bf16, K-contiguous like Bt; C2 row pitch N)
     DMI_REQUIRE(B2 && C2 && ldb2 >= N && ldb2 % 8 == 0 && (((uintptr_t)B2 | (uintptr_t)C2) & 15) == 0 && (const void*)C2 != (const void*)dx,
                 "gemm_nt_lnbwd: bad chained product (B2 / ldb2 / C2)");
     a.B2 = B2; a.ldb2 = ldb2; a.C2 = C2;
-    static bool attr3 = false;
-    if (!attr3) { (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<0, RT, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB); attr3 = true; }
-    gemm_ntr_kernel<0, RT, 3><<<dim3((M + 32 * RT - 1) / (32 * RT)), dim3(512), LDSB, (hipStream_t)stream>>>(a);
-    DMI_CHECK_LAUNCH("gemm_nt_lnbwd (chained)");
-    return DMI_OK;
+    return launch_ntr_ln<3>(a, "gemm_nt_lnbwd (chained)", (hipStream_t)stream);
   }
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_ntr_kernel<0, RT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB); attr = true; }
-  gemm_ntr_kernel<0, RT, 2><<<dim3((M + 32 * RT - 1) / (32 * RT)), dim3(512), LDSB, (hipStream_t)stream>>>(a);
-  DMI_CHECK_LAUNCH("gemm_nt_lnbwd");
-  return DMI_OK;
+  return launch_ntr_ln<2>(a, "gemm_nt_lnbwd", (hipStream_t)stream);
 }
 
 extern "C" int dmi_ln_gemm_nt(const uint16_t* X, int ldx, const uint16_t* gamma, const uint16_t* beta, float eps, const uint16_t* Bt, int ldb,
@@ -2331,60 +2216,7 @@ extern "C" int dmi_gemm_nt_splitk(const uint16_t* A, int lda, const uint16_t* Bt
 // =====================================================================================
 #define TN_BKM 64      // rows of m per step
 
-static int tn_splits(int M, int I, int J) {
-  // 2 blocks of 256 threads are resident per CU (64 KiB LDS each): 512 slots.  Pick the split count that fills
-  // whole multiples of the residency (a 1.5x grid leaves a quarter of the chip idle in the tail) and keeps at
-  // least 4 k-steps per block; fewer splits also means fewer fp32 slabs to write and reduce.
-  const int tiles = ((I + 127) / 128) * ((J + 127) / 128);
-  const int max_s = (M + 4 * TN_BKM - 1) / (4 * TN_BKM);
-  if (tiles >= 384) return 1;
-  int s = 512 / tiles;
-  if (s < 1) s = 1;
-  if (s > max_s) s = max_s;
-  if (s < 1) s = 1;
-  return s;
-}
-static int64_t round_up64(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-// 256x256-tile weight-gradient kernel (8 waves, one block per CU): used when both dimensions fill 256-wide tiles
-// (measured in the dalle_example step, profiles/r02c_*: it wins where the 128x128 plan needs many row splits -- 512x512: 64 -> 57 us,
-// 512x1536: 88 -> 79 us incl. the slab reduce -- and ties or loses from 16 tiles up, where its 64-row steps give the LDS-DMA
-// no more cover than the two co-resident blocks of the 128x128 kernel have)
-static bool tn8_eligible(int M, int I, int J) {
-  if (g_opt_tn8 == 2) return true;
-  const int tiles = ((I + 255) / 256) * ((J + 255) / 256);
-  return g_opt_tn8 == 1 && I >= 256 && J >= 256 && M >= 2048 && tiles < g_opt_tn8_max_tiles;
-}
-static int tn8_splits(int M, int I, int J) {
-  const int tiles = ((I + 255) / 256) * ((J + 255) / 256);
-  const int max_s = (M + 8 * TN_BKM - 1) / (8 * TN_BKM);   // at least 8 k-steps per block
-  int best = 1;
-  double best_cost = 1e30;
-  for (int s2 = 1; s2 <= 64 && s2 <= max_s; ++s2) {
-    // makespan in units of one unsplit block: rounds of 256 resident blocks, each 1/s long, + the fp32 slab round trip
-    // (write + read of s x I x J x 4 bytes at ~4 TB/s vs the block's 2 x 256 x 256 x M flops at ~4.5 TFLOP/s per CU)
-    const double rounds = (double)(((int64_t)tiles * s2 + 255) / 256) / s2;
-    const double slab = (s2 > 1) ? (double)s2 * I * J * 8.0 / 4.0e12 / (2.0 * 256 * 256 * (double)M / 4.5e12) : 0.0;
-    const double cost = rounds + slab;
-    if (cost < best_cost - 1e-9) { best_cost = cost; best = s2; }
-  }
-  return best;
-}
-
-extern "C" int64_t dmi_gemm_tn_workspace_bytes(int M, int I, int J) {
-  const int s = tn_splits(M, I, J);
-  const int64_t slabs = (s > 1) ? (int64_t)s * I * J * 4 : 0;
-  const int64_t cs = (int64_t)s * J * 4;  // bias partials
-  // unsplit shapes with a ragged last residency: row-split slabs of the tail stripe, < 512 tiles x 64 KiB (+ bias rows)
-  const int64_t tiles = (int64_t)((I + 127) / 128) * ((J + 127) / 128);
-  const int64_t tail = (s == 1 && tiles > 512) ? (512 * 65536 + 512 * 128 * 4 * (int64_t)((I + 127) / 128)) : 0;
-  int64_t base = round_up64(slabs, 256) + round_up64(cs, 256) + 256;
-  if (I >= 256 && J >= 256) {   // the 256x256-tile kernel's split plan (whatever the option says now)
-    const int s8 = tn8_splits(M, I, J);
-    const int64_t b8 = round_up64((s8 > 1) ? (int64_t)s8 * I * J * 4 : 0, 256) + round_up64((int64_t)s8 * J * 4, 256) + 256;
-    if (b8 > base) base = b8;
-  }
-  return base > tail + 256 ? base : tail + 256;
-}
+extern "C" int64_t dmi_gemm_tn_workspace_bytes(int M, int I, int J) { return tn_workspace_bytes(M, I, J); }
 
 #define CONV_MAX_TAPS 16
 struct ConvGeom {   // convolution geometry of the implicit-im2col kernels (dmi_conv_gemm_nt, dmi_conv_wgrad_tn)
@@ -3356,200 +3188,144 @@ extern "C" int dmi_reduce_slabs_batch(const dmi_reduce_item* items, int n, void*
   return DMI_OK;
 }
 
-// Weight gradients that share M in one launch (see gemm_tn_group_kernel).  Every problem's workspace holds its own slabs
-// (dmi_gemm_tn_workspace_bytes(M, I, J) bytes suffice: the group never splits finer than the single launch would); the slab
-// reduces are appended to `deferred` (2 per problem at most) or, with deferred == NULL, run here as one batched launch.
-// row splits of the group's plan on 128 x 256 tiles, or 0 where the group stays on 128 x 128 tiles: the union of the wide tiles must
-// fill (>= 448 of) the 512 block slots with a split count >= 2 that every problem's own workspace has slabs for
-static int tn_group_wide_splits(const int* I, const int* J, int n, int M) {
-  if (!g_opt_tn_wide) return 0;
-  int Tw = 0, smin = 1 << 30;
-  for (int k = 0; k < n; ++k) {
-    Tw += ((I[k] + TNW_TI - 1) / TNW_TI) * ((J[k] + TNW_TJ - 1) / TNW_TJ);
-    const int sk = tn_splits(M, I[k], J[k]);
-    if (sk < smin) smin = sk;
-  }
-  const int max_s = (M + 4 * TN_BKM - 1) / (4 * TN_BKM);
-  int Sw = Tw >= 384 ? 1 : 512 / Tw;
-  if (Sw > max_s) Sw = max_s;
-  return (Sw >= 2 && Sw <= smin && Tw * Sw >= 448) ? Sw : 0;
+static_assert(TN_BKM == TN_STEP && TNW_TI == TNW_TILE_I && TNW_TJ == TNW_TILE_J && TNW_BKM == TNW_STEP && TN_GROUP_MAX == TN_GROUP_N);
+
+// the argument checks of one weight gradient: dmi_gemm_tn's (k < 0), or problem k's of dmi_gemm_tn_group
+static int check_tn(int k, const dmi_tn_problem& q, int M) {
+  const char* who = k < 0 ? "gemm_tn" : "gemm_tn_group";
+  char in_k[32] = "";
+  if (k >= 0) snprintf(in_k, sizeof(in_k), " in problem %d", k);
+  DMI_REQUIRE(q.X && q.dY && q.dW && q.workspace, "%s: null pointer%s", who, in_k);
+  const bool shape_ok = M > 0 && q.I % 8 == 0 && q.J % 8 == 0 && q.ldx % 8 == 0 && q.ldy % 8 == 0 && q.ldx >= q.I && q.ldy >= q.J;
+  if (k < 0) DMI_REQUIRE(shape_ok, "gemm_tn: I, J, ldx, ldy must be multiples of 8 (M=%d I=%d J=%d)", M, q.I, q.J);
+  else DMI_REQUIRE(shape_ok, "gemm_tn_group: I, J, ldx, ldy must be multiples of 8 (problem %d: I=%d J=%d)", k, q.I, q.J);
+  DMI_REQUIRE((((uintptr_t)q.X | (uintptr_t)q.dY | (uintptr_t)q.dW | (uintptr_t)q.workspace) & 15) == 0, "%s: 16-byte alignment required", who);
+  DMI_REQUIRE(!q.bias_weights || (q.dbias && ((uintptr_t)q.bias_weights & 3) == 0 && M % 2 == 0), "%s: bias_weights needs dbias, 4-byte alignment and an even M%s",
+              who, k < 0 ? " (the weights travel as dwords: the last weight of an odd M would be range-checked away)" : "");
+  DMI_REQUIRE(tn_ld_fits(q.ldx, q.ldy), "%s: leading dimension too large", who);
+  return DMI_OK;
 }
-extern "C" int dmi_gemm_tn_group_plan(const int* I, const int* J, int n, int M) {
-  if (!I || !J || n < 1 || n > TN_GROUP_MAX || M <= 0) return 0;
-  return tn_group_wide_splits(I, J, n, M);
+
+// the reduces a gradient split `nsplit` ways owes (bias partials first), appended to items; returns how many: none when unsplit
+static int tn_reduce_items(dmi_reduce_item* items, float* slabs, float* bpart, float* dW, float* dbias, int nsplit, int I, int J) {
+  if (nsplit == 1) return 0;
+  int n = 0;
+  if (dbias) items[n++] = {bpart, dbias, nsplit, J / 4};
+  items[n++] = {slabs, dW, nsplit, (int64_t)I * J / 4};
+  return n;
 }
-extern "C" int dmi_gemm_tn_group(const dmi_tn_problem* probs, int n, int M, dmi_reduce_item* deferred, int* n_deferred, void* stream) {
-  DMI_REQUIRE(probs && n >= 1 && n <= TN_GROUP_MAX && M > 0, "gemm_tn_group: 1..%d problems", TN_GROUP_MAX);
-  TnGroup g;
-  g.n = n;
-  int T = 0;
-  for (int k = 0; k < n; ++k) {
-    const dmi_tn_problem& q = probs[k];
-    DMI_REQUIRE(q.X && q.dY && q.dW && q.workspace, "gemm_tn_group: null pointer in problem %d", k);
-    DMI_REQUIRE(q.I % 8 == 0 && q.J % 8 == 0 && q.ldx % 8 == 0 && q.ldy % 8 == 0 && q.ldx >= q.I && q.ldy >= q.J,
-                "gemm_tn_group: I, J, ldx, ldy must be multiples of 8 (problem %d: I=%d J=%d)", k, q.I, q.J);
-    DMI_REQUIRE((((uintptr_t)q.X | (uintptr_t)q.dY | (uintptr_t)q.dW | (uintptr_t)q.workspace) & 15) == 0, "gemm_tn_group: 16-byte alignment required");
-    DMI_REQUIRE(!q.bias_weights || (q.dbias && ((uintptr_t)q.bias_weights & 3) == 0 && M % 2 == 0), "gemm_tn_group: bias_weights needs dbias, 4-byte alignment and an even M");
-    DMI_REQUIRE((int64_t)TN_BKM * (q.ldx > q.ldy ? q.ldx : q.ldy) * 2 < 0x7fffffff, "gemm_tn_group: leading dimension too large");
-    g.first_tile[k] = T;
-    T += ((q.I + 127) / 128) * ((q.J + 127) / 128);
-  }
-  g.first_tile[n] = T;
-  for (int k = n + 1; k <= TN_GROUP_MAX; ++k) g.first_tile[k] = T;
-  const int max_s = (M + 4 * TN_BKM - 1) / (4 * TN_BKM);
-  int S = T >= 384 ? 1 : 512 / T;
-  if (S > max_s) S = max_s;
-  if (S < 1) S = 1;
-  // [r06] the wide tile, if its plan fills the slots with splits every problem's workspace has slabs for
-  bool wide = false;
-  {
-    int Is[TN_GROUP_MAX], Js[TN_GROUP_MAX];
-    for (int k = 0; k < n; ++k) { Is[k] = probs[k].I; Js[k] = probs[k].J; }
-    const int Sw = tn_group_wide_splits(Is, Js, n, M);
-    if (Sw) {
-      wide = true; S = Sw; T = 0;
-      for (int k = 0; k < n; ++k) {
-        g.first_tile[k] = T;
-        T += ((probs[k].I + TNW_TI - 1) / TNW_TI) * ((probs[k].J + TNW_TJ - 1) / TNW_TJ);
-      }
-      for (int k = n; k <= TN_GROUP_MAX; ++k) g.first_tile[k] = T;
-    }
-  }
-  dmi_reduce_item items[2 * TN_GROUP_MAX];
-  int ni = 0;
-  for (int k = 0; k < n; ++k) {
-    const dmi_tn_problem& q = probs[k];
-    TnArgs& a = g.p[k];
-    a.X = q.X; a.Y = q.dY; a.M = M; a.I = q.I; a.J = q.J; a.ldx = q.ldx; a.ldy = q.ldy;
-    a.tiles_i = (q.I + 127) / 128; a.tiles_j = wide ? (q.J + TNW_TJ - 1) / TNW_TJ : (q.J + 127) / 128;
-    a.m_per_split = (int)round_up64((M + S - 1) / S, TN_BKM);
-    float* slabs = (float*)q.workspace;
-    const int64_t slab_bytes = (S > 1) ? round_up64((int64_t)S * q.I * q.J * 4, 256) : 0;
-    float* bpart = (float*)((char*)q.workspace + slab_bytes);
-    a.C = (S > 1) ? slabs : q.dW;
-    a.slab_stride = (S > 1) ? (int64_t)q.I * q.J : 0;
-    a.bias_w = q.bias_weights;
-    a.bias_part = q.dbias ? ((S > 1) ? bpart : q.dbias) : nullptr;
-    a.dbg = nullptr;
-    if (S > 1) {
-      if (q.dbias) { items[ni].slabs = bpart; items[ni].out = q.dbias; items[ni].nsplit = S; items[ni].n4 = q.J / 4; ++ni; }
-      items[ni].slabs = slabs; items[ni].out = q.dW; items[ni].nsplit = S; items[ni].n4 = (int64_t)q.I * q.J / 4; ++ni;
-    }
-  }
-  for (int k = n; k < TN_GROUP_MAX; ++k) g.p[k] = g.p[0];
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES);
-    (void)hipFuncSetAttribute((const void*)gemm_tn_group_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TNW_LDS_BYTES);
-    attr_done = true;
-  }
-  if (wide) gemm_tn_group_wide_kernel<<<dim3(T * S), dim3(256), TNW_LDS_BYTES, (hipStream_t)stream>>>(g);
-  else gemm_tn_group_kernel<<<dim3(T * S), dim3(256), TN_LDS_BYTES, (hipStream_t)stream>>>(g);
-  DMI_CHECK_LAUNCH("gemm_tn_group");
+// One gradient's kernel arguments on `nsplit` row splits: into its workspace (tn_layout) when split, else straight into dW / dbias.
+static int tn_fill_args(TnArgs& a, dmi_reduce_item* items, const dmi_tn_problem& q, int M, int nsplit, int tiles_i, int tiles_j, int m_per_split) {
+  float* slabs = (float*)q.workspace;
+  float* bpart = (float*)((char*)q.workspace + tn_layout(nsplit, q.I, q.J).slab_bytes);
+  a.X = q.X; a.Y = q.dY; a.M = M; a.I = q.I; a.J = q.J; a.ldx = q.ldx; a.ldy = q.ldy;
+  a.tiles_i = tiles_i; a.tiles_j = tiles_j; a.m_per_split = m_per_split;
+  a.C = (nsplit > 1) ? slabs : q.dW;
+  a.slab_stride = (nsplit > 1) ? (int64_t)q.I * q.J : 0;
+  a.bias_w = q.bias_weights;
+  a.bias_part = q.dbias ? ((nsplit > 1) ? bpart : q.dbias) : nullptr;
+  a.dbg = nullptr;
+  return tn_reduce_items(items, slabs, bpart, q.dW, q.dbias, nsplit, q.I, q.J);
+}
+// the reduces of a launch: handed to the caller (who runs dmi_reduce_slabs_batch later; the workspaces must stay untouched until
+// then), or run here -- as one batched launch, or (`each`: the launch's name) one launch per item; same summation order either way
+static int tn_finish(const dmi_reduce_item* items, int ni, dmi_reduce_item* deferred, int* n_deferred, const char* each, void* stream) {
   if (n_deferred) *n_deferred = 0;
   if (deferred && n_deferred) {
     for (int i = 0; i < ni; ++i) deferred[i] = items[i];
     *n_deferred = ni;
     return DMI_OK;
   }
-  return dmi_reduce_slabs_batch(items, ni, stream);
+  if (!each) return dmi_reduce_slabs_batch(items, ni, stream);
+  for (int i = 0; i < ni; ++i) {
+    const int64_t n4 = items[i].n4, blocks = cdiv64(n4, 256);
+    reduce_slabs_kernel<<<dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, (hipStream_t)stream>>>(items[i].slabs, items[i].out, items[i].nsplit, n4, n4);
+    DMI_CHECK_LAUNCH(each);
+  }
+  return DMI_OK;
+}
+
+// Weight gradients that share M in one launch (see gemm_tn_group_kernel; the plan: tn_group_plan).  The slab reduces are appended
+// to `deferred` (2 per problem at most) or, with deferred == NULL, run here as one batched launch.
+extern "C" int dmi_gemm_tn_group_plan(const int* I, const int* J, int n, int M) {
+  if (!I || !J || n < 1 || n > TN_GROUP_MAX || M <= 0) return 0;
+  const TnGroupPlan g = tn_group_plan(I, J, n, M, g_opt);
+  return g.wide ? g.S : 0;
+}
+extern "C" int dmi_gemm_tn_group(const dmi_tn_problem* probs, int n, int M, dmi_reduce_item* deferred, int* n_deferred, void* stream) {
+  DMI_REQUIRE(probs && n >= 1 && n <= TN_GROUP_MAX && M > 0, "gemm_tn_group: 1..%d problems", TN_GROUP_MAX);
+  int Is[TN_GROUP_MAX], Js[TN_GROUP_MAX];
+  for (int k = 0; k < n; ++k) {
+    const int rc = check_tn(k, probs[k], M);
+    if (rc) return rc;
+    Is[k] = probs[k].I; Js[k] = probs[k].J;
+  }
+  const TnGroupPlan gp = tn_group_plan(Is, Js, n, M, g_opt);
+  TnGroup g;
+  g.n = n;
+  for (int k = 0; k <= TN_GROUP_MAX; ++k) g.first_tile[k] = gp.first_tile[k];
+  dmi_reduce_item items[2 * TN_GROUP_MAX];
+  int ni = 0;
+  for (int k = 0; k < n; ++k) ni += tn_fill_args(g.p[k], items + ni, probs[k], M, gp.S, gp.tiles_i[k], gp.tiles_j[k], gp.m_per_split);
+  for (int k = n; k < TN_GROUP_MAX; ++k) g.p[k] = g.p[0];
+  if (gp.wide) {
+    raise_lds_once<gemm_tn_group_wide_kernel>(TNW_LDS_BYTES);
+    gemm_tn_group_wide_kernel<<<dim3(gp.T * gp.S), dim3(256), TNW_LDS_BYTES, (hipStream_t)stream>>>(g);
+  } else {
+    raise_lds_once<gemm_tn_group_kernel>(TN_LDS_BYTES);
+    gemm_tn_group_kernel<<<dim3(gp.T * gp.S), dim3(256), TN_LDS_BYTES, (hipStream_t)stream>>>(g);
+  }
+  DMI_CHECK_LAUNCH("gemm_tn_group");
+  return tn_finish(items, ni, deferred, n_deferred, nullptr, stream);
 }
 
 extern "C" int dmi_gemm_tn(const uint16_t* X, int ldx, const uint16_t* dY, int ldy, float* dW, float* dbias,
                            const uint16_t* bias_weights, int M, int I, int J, void* workspace, dmi_reduce_item* deferred,
                            int* n_deferred, void* stream) {
-  DMI_REQUIRE(X && dY && dW && workspace, "gemm_tn: null pointer");
-  DMI_REQUIRE(M > 0 && I % 8 == 0 && J % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && ldx >= I && ldy >= J,
-              "gemm_tn: I, J, ldx, ldy must be multiples of 8 (M=%d I=%d J=%d)", M, I, J);
-  DMI_REQUIRE((((uintptr_t)X | (uintptr_t)dY | (uintptr_t)dW | (uintptr_t)workspace) & 15) == 0, "gemm_tn: 16-byte alignment required");
-  DMI_REQUIRE(!bias_weights || (dbias && ((uintptr_t)bias_weights & 3) == 0 && M % 2 == 0),
-              "gemm_tn: bias_weights needs dbias, 4-byte alignment and an even M (the weights travel as dwords: the last weight of an odd M would be range-checked away)");
-  DMI_REQUIRE((int64_t)TN_BKM * (ldx > ldy ? ldx : ldy) * 2 < 0x7fffffff, "gemm_tn: leading dimension too large");
+  const dmi_tn_problem q = {X, ldx, dY, ldy, dW, dbias, bias_weights, I, J, workspace};
+  const int rc = check_tn(-1, q, M);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const bool use8 = tn8_eligible(M, I, J);
-  const int nsplit = use8 ? tn8_splits(M, I, J) : tn_splits(M, I, J);
-  float* slabs = (float*)workspace;
-  const int64_t slab_bytes = (nsplit > 1) ? round_up64((int64_t)nsplit * I * J * 4, 256) : 0;
+  const TnPlan p = tn_plan(M, I, J, g_opt, num_cus());
   TnArgs a;
-  a.X = X; a.Y = dY; a.M = M; a.I = I; a.J = J; a.ldx = ldx; a.ldy = ldy;
-  a.tiles_i = use8 ? (I + 255) / 256 : (I + 127) / 128; a.tiles_j = use8 ? (J + 255) / 256 : (J + 127) / 128;
-  a.m_per_split = (int)round_up64((M + nsplit - 1) / nsplit, TN_BKM);
-  a.C = (nsplit > 1) ? slabs : dW;
-  a.slab_stride = (nsplit > 1) ? (int64_t)I * J : 0;
+  dmi_reduce_item items[2];
+  const int ni = tn_fill_args(a, items, q, M, p.nsplit, p.tiles_i, p.tiles_j, p.m_per_split);
   a.dbg = g_dbg_buf;
-  a.bias_w = bias_weights;
-  float* bpart = (float*)((char*)workspace + slab_bytes);   // [nsplit][J] bias partials behind the slabs
-  a.bias_part = dbias ? ((nsplit > 1) ? bpart : dbias) : nullptr;
-  static bool attr_done = false;
-  const int shm = TN_LDS_BYTES;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
-    (void)hipFuncSetAttribute((const void*)gemm_tn_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, shm);
-    attr_done = true;
-  }
-  const int tiles = a.tiles_i * a.tiles_j;
-  const int tail_tiles = tiles % 512, n_whole = tiles - tail_tiles;
-  const int S = tail_tiles ? 512 / tail_tiles : 1;
-  if (!use8 && g_opt_tn_wide && nsplit == 1) {   // [r06] gang stream-K on the 128 x 256 tile (gemm_tn_wide_sk_kernel): unsplit gradients with many stripes
-    const int wti = (I + TNW_TI - 1) / TNW_TI, wtj = (J + TNW_TJ - 1) / TNW_TJ, nsteps = (M + TNW_BKM - 1) / TNW_BKM;
-    const int gangs = (2 * persistent_grid() / wti) & ~7;   // two blocks per CU, the reserved CUs left free; whole gangs per XCD
-    if (gangs >= 8 && wtj >= gangs && (int64_t)(wtj + 1) * nsteps < 0x7fffffff) {
-      a.tiles_i = wti; a.tiles_j = wtj;
-      a.C = dW; a.slab_stride = 0; a.bias_part = dbias;
-      static bool attrs = false;
-      if (!attrs) { (void)hipFuncSetAttribute((const void*)gemm_tn_wide_sk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TNW_LDS_BYTES); attrs = true; }
-      tn_wide_zero_kernel<<<dim3(wtj), dim3(256), 0, st>>>(dW, dbias, I, J, wtj, gangs, nsteps);
+  const dim3 grid(p.grid), blk(p.block);
+  switch (p.kernel) {
+    case TnKernel::WIDE_SK:
+      raise_lds_once<gemm_tn_wide_sk_kernel>(TNW_LDS_BYTES);
+      tn_wide_zero_kernel<<<dim3(p.tiles_j), dim3(256), 0, st>>>(dW, dbias, I, J, p.tiles_j, p.gangs, p.nsteps);
       DMI_CHECK_LAUNCH("gemm_tn_wide_zero");
-      gemm_tn_wide_sk_kernel<<<dim3(gangs * wti), dim3(256), TNW_LDS_BYTES, st>>>(a, gangs, nsteps);
+      gemm_tn_wide_sk_kernel<<<grid, blk, TNW_LDS_BYTES, st>>>(a, p.gangs, p.nsteps);
       DMI_CHECK_LAUNCH("gemm_tn_wide_sk");
-      if (n_deferred) *n_deferred = 0;
-      return DMI_OK;
+      break;
+    case TnKernel::TN8:
+      raise_lds_once<gemm_tn8_kernel>(TN8_LDS_BYTES);
+      gemm_tn8_kernel<<<grid, blk, TN8_LDS_BYTES, st>>>(a);
+      DMI_CHECK_LAUNCH("gemm_tn8");
+      break;
+    case TnKernel::TAIL: {
+      float* tslab = (float*)workspace;                         // [S][I][W]
+      float* tbias = tslab + (int64_t)p.S * I * p.W;            // [S][W]
+      raise_lds_once<gemm_tn_tail_kernel>(TN_LDS_BYTES);
+      gemm_tn_tail_kernel<<<grid, blk, TN_LDS_BYTES, st>>>(a, p.n_whole, p.S, p.mps, tslab, tbias, p.c0, p.W);
+      DMI_CHECK_LAUNCH("gemm_tn_tail");
+      reduce_slabs_2d_kernel<<<dim3(512), dim3(256), 0, st>>>(tslab, dW + p.c0, p.S, I, p.W, J);
+      DMI_CHECK_LAUNCH("gemm_tn_tail_reduce");
+      if (dbias) {
+        reduce_slabs_2d_kernel<<<dim3(8), dim3(256), 0, st>>>(tbias, dbias + p.c0, p.S, 1, p.W, J);
+        DMI_CHECK_LAUNCH("gemm_tn_tail_bias_reduce");
+      }
+      break;
     }
+    case TnKernel::TN:
+      raise_lds_once<gemm_tn_kernel>(TN_LDS_BYTES);
+      gemm_tn_kernel<<<grid, blk, TN_LDS_BYTES, st>>>(a);
+      DMI_CHECK_LAUNCH("gemm_tn");
+      break;
   }
-  if (use8) {
-    static bool attr8 = false;
-    if (!attr8) { (void)hipFuncSetAttribute((const void*)gemm_tn8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN8_LDS_BYTES); attr8 = true; }
-    gemm_tn8_kernel<<<dim3(tiles * nsplit), dim3(512), TN8_LDS_BYTES, st>>>(a);
-    DMI_CHECK_LAUNCH("gemm_tn8");
-  } else
-  // tiles are numbered ti-fastest: with tiles_i | n_whole the tail is the column stripe [c0, J) of dW
-  if (g_opt_tn_tail && nsplit == 1 && tiles > 512 && S >= 2 && a.tiles_i <= GROUP_M && n_whole % a.tiles_i == 0 && J % 4 == 0) {
-    const int c0 = (n_whole / a.tiles_i) * 128, W = J - c0;
-    const int mps = (int)round_up64((M + S - 1) / S, TN_BKM);
-    float* tslab = (float*)workspace;                       // [S][I][W]
-    float* tbias = tslab + (int64_t)S * I * W;              // [S][W]
-    gemm_tn_tail_kernel<<<dim3(n_whole + tail_tiles * S), dim3(256), shm, st>>>(a, n_whole, S, mps, tslab, tbias, c0, W);
-    DMI_CHECK_LAUNCH("gemm_tn_tail");
-    reduce_slabs_2d_kernel<<<dim3(512), dim3(256), 0, st>>>(tslab, dW + c0, S, I, W, J);
-    DMI_CHECK_LAUNCH("gemm_tn_tail_reduce");
-    if (dbias) {
-      reduce_slabs_2d_kernel<<<dim3(8), dim3(256), 0, st>>>(tbias, dbias + c0, S, 1, W, J);
-      DMI_CHECK_LAUNCH("gemm_tn_tail_bias_reduce");
-    }
-  } else {
-    gemm_tn_kernel<<<dim3(tiles * nsplit), dim3(256), shm, st>>>(a);
-    DMI_CHECK_LAUNCH("gemm_tn");
-  }
-  if (n_deferred) *n_deferred = 0;
-  if (nsplit > 1) {
-    const int64_t n4 = (int64_t)I * J / 4;
-    if (deferred && n_deferred) {   // the caller reduces later (dmi_reduce_slabs_batch); the workspace must stay untouched until then
-      int k = 0;
-      if (dbias) { deferred[k].slabs = bpart; deferred[k].out = dbias; deferred[k].nsplit = nsplit; deferred[k].n4 = J / 4; ++k; }
-      deferred[k].slabs = slabs; deferred[k].out = dW; deferred[k].nsplit = nsplit; deferred[k].n4 = n4; ++k;
-      *n_deferred = k;
-      return DMI_OK;
-    }
-    if (dbias) {
-      reduce_slabs_kernel<<<dim3((unsigned)cdiv64(J / 4, 256)), dim3(256), 0, st>>>(bpart, dbias, nsplit, J / 4, J / 4);
-      DMI_CHECK_LAUNCH("gemm_tn_bias_reduce");
-    }
-    int64_t blocks = cdiv64(n4, 256);
-    if (blocks > 2048) blocks = 2048;
-    reduce_slabs_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(slabs, dW, nsplit, n4, n4);
-    DMI_CHECK_LAUNCH("gemm_tn_reduce");
-  }
-  return DMI_OK;
+  return tn_finish(items, ni, deferred, n_deferred, "gemm_tn_reduce", stream);
 }
 
 // =====================================================================================
@@ -3670,8 +3446,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_nt_kernel(GemmArgs a, ConvGe
 
 template <int FLAGS>
 static int launch_conv(const GemmArgs& a, const ConvGeom& g, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)conv_gemm_nt_kernel<FLAGS>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); attr_done = true; }
+  raise_lds_once<conv_gemm_nt_kernel<FLAGS>>(65536);
   conv_gemm_nt_kernel<FLAGS><<<dim3(a.tiles_m * a.tiles_n), dim3(256), 65536, st>>>(a, g);
   DMI_CHECK_LAUNCH("conv_gemm_nt");
   return DMI_OK;
@@ -3761,7 +3536,7 @@ extern "C" int dmi_conv_wgrad_tn(const uint16_t* x, int B, int H, int W, int C, 
   const int64_t img_bytes = (int64_t)H * W * C * 2, img_rows = (int64_t)Ho * Wo, Ml = (int64_t)B * img_rows;
   DMI_REQUIRE(img_bytes < 0x7ffffff0 && Ml < 0x7fffffff, "conv_wgrad_tn: activation tensor too large for 32-bit buffer offsets");
   DMI_REQUIRE((((uintptr_t)x | (uintptr_t)dY | (uintptr_t)dW | (uintptr_t)workspace) & 15) == 0, "conv_wgrad_tn: 16-byte alignment required");
-  DMI_REQUIRE((int64_t)TN_BKM * ldy * 2 < 0x7fffffff, "conv_wgrad_tn: leading dimension too large");
+  DMI_REQUIRE(tn_ld_fits(0, ldy), "conv_wgrad_tn: leading dimension too large");
   hipStream_t st = (hipStream_t)stream;
   const int M = (int)Ml, I = ntaps * C, J = N;
   const int per = (int)((B < (0x7ffffff0 - 1) / img_bytes) ? B : (0x7ffffff0 - 1) / img_bytes);   // images per launch
@@ -3773,13 +3548,11 @@ extern "C" int dmi_conv_wgrad_tn(const uint16_t* x, int B, int H, int W, int C, 
   DMI_REQUIRE(sc >= 1, "conv_wgrad_tn: %d image chunks but a workspace of %d slabs (I=%d J=%d)", nchunk, splits_all, I, J);
   const int nsplit = sc * nchunk;
   float* slabs = (float*)workspace;
-  const int64_t slab_bytes = (nsplit > 1) ? round_up64((int64_t)nsplit * I * J * 4, 256) : 0;
-  float* bpart = (float*)((char*)workspace + slab_bytes);
+  float* bpart = (float*)((char*)workspace + tn_layout(nsplit, I, J).slab_bytes);
   ConvGeom g;
   g.H = H; g.W = W; g.C = C; g.Ho = Ho; g.Wo = Wo; g.stride = stride; g.ntaps = ntaps; g.lw = lw; g.lh = lh;
   for (int i = 0; i < CONV_MAX_TAPS; ++i) { g.dy[i] = i < ntaps ? dy[i] : 0; g.dx[i] = i < ntaps ? dx[i] : 0; }
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute((const void*)conv_wgrad_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES); attr_done = true; }
+  raise_lds_once<conv_wgrad_tn_kernel>(TN_LDS_BYTES);
   for (int c = 0; c < nchunk; ++c) {
     const int b0 = c * per, nb = (B - b0 < per) ? B - b0 : per;
     const int Mc = (int)(nb * img_rows);
@@ -3795,23 +3568,7 @@ extern "C" int dmi_conv_wgrad_tn(const uint16_t* x, int B, int H, int W, int C, 
     conv_wgrad_tn_kernel<<<dim3(a.tiles_i * a.tiles_j * sc), dim3(256), TN_LDS_BYTES, st>>>(a, g);
     DMI_CHECK_LAUNCH("conv_wgrad_tn");
   }
-  if (nsplit > 1) {
-    const int64_t n4 = (int64_t)I * J / 4;
-    if (deferred && n_deferred) {   // the caller reduces later (dmi_reduce_slabs_batch); the workspace must stay untouched until then
-      int k = 0;
-      if (dbias) { deferred[k].slabs = bpart; deferred[k].out = dbias; deferred[k].nsplit = nsplit; deferred[k].n4 = J / 4; ++k; }
-      deferred[k].slabs = slabs; deferred[k].out = dW; deferred[k].nsplit = nsplit; deferred[k].n4 = n4; ++k;
-      *n_deferred = k;
-      return DMI_OK;
-    }
-    if (dbias) {
-      reduce_slabs_kernel<<<dim3((unsigned)cdiv64(J / 4, 256)), dim3(256), 0, st>>>(bpart, dbias, nsplit, J / 4, J / 4);
-      DMI_CHECK_LAUNCH("conv_wgrad_tn_bias_reduce");
-    }
-    int64_t blocks = cdiv64(n4, 256);
-    if (blocks > 2048) blocks = 2048;
-    reduce_slabs_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(slabs, dW, nsplit, n4, n4);
-    DMI_CHECK_LAUNCH("conv_wgrad_tn_reduce");
-  }
-  return DMI_OK;
+  dmi_reduce_item items[2];
+  const int ni = tn_reduce_items(items, slabs, bpart, dW, dbias, nsplit, I, J);
+  return tn_finish(items, ni, deferred, n_deferred, "conv_wgrad_tn_reduce", stream);
 }
