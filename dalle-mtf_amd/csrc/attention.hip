@@ -2829,3 +2829,303 @@ extern "C" int dmi_attention_decode_masked(uint16_t* qkv, const uint16_t* fresh,
   if (rt == 1) return dmi_attention_decode_hd(qkv, fresh, o, B, H, S, pos, pos_dev, head_dim, stream);
   return attn_decode_launch("attention_decode_masked", qkv, fresh, o, (const int*)plan, B, H, S, pos, pos_dev, head_dim, stream);
 }
+
+// =====================================================================================
+// FP8 key/value cache ("kv8"; DESIGN.md §4 "Generation: FP8 key/value cache")
+// =====================================================================================
+// Per layer: data uint8 [B, S, 2, H, head_dim] (K then V, OCP E4M3FN) and scale fp32 [B, S, 2, H], one power of two per (position,
+// head): for a head's row x (bf16, after QK-norm and rotary), e = clamp(floor(log2(max |x_j|)) - 7, -119, 120) (0 for an all-zero
+// row), scale = 2^e, data_j = e4m3(x_j 2^-e) to nearest even.  x_j 2^-e is exact in fp32 and below 256, so nothing saturates, and the
+// dequantised data_j 2^e is exact in fp32 and in bf16.  Conversions are gfx950's packed ones (v_cvt_pk_fp8_f32 / v_cvt_pk_f32_fp8).
+__device__ __forceinline__ int kv8_exponent(float amax) {     // amax >= 0, finite; a subnormal maximum clamps as its logarithm does
+  const unsigned bits = __float_as_uint(amax);
+  if (bits == 0u) return 0;
+  const int e = (int)(bits >> 23) - 134;
+  return e < -119 ? -119 : (e > 120 ? 120 : e);
+}
+__device__ __forceinline__ float kv8_pow2(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }   // -126 <= e <= 127
+__device__ __forceinline__ unsigned kv8_pack4(const float* f, float inv) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, w, true);
+  return (unsigned)w;
+}
+__device__ __forceinline__ void kv8_unpack16(const u32x4& v, float* f) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const pk_f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], true);
+    f[4 * i] = lo[0], f[4 * i + 1] = lo[1], f[4 * i + 2] = hi[0], f[4 * i + 3] = hi[1];
+  }
+}
+// the maximum over the GL adjacent lanes (an aligned group of the wave) that hold one head's row
+template <int GL>
+__device__ __forceinline__ float kv8_group_max(float x) {
+#pragma unroll
+  for (int o = GL / 2; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
+  return x;
+}
+
+// Streaming quantiser: thread t takes 16-byte piece t % pieces (8 bf16 of the k | v columns, pieces = 2 H head_dim / 8) of row
+// t / pieces of the [B, s1 - s0] rows; a head is head_dim / 8 adjacent pieces, an aligned lane group (as in qk_norm_fwd_kernel), so
+// its maximum is log2 of that many xor-exchanges inside the wave.  Every lane runs the exchanges; lanes past the end carry zeros
+// and store nothing.  8-byte data stores, the group's first lane stores the scale.  Offsets are 64-bit.
+template <int HEAD_DIM>
+__global__ __launch_bounds__(256) void kv8_quantize_kernel(const bf16_t* __restrict__ qkv, int ld, uint8_t* __restrict__ data,
+                                                           float* __restrict__ scale, int S, int s0, int ns, int pieces, int64_t total) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool active = t < total;
+  const int64_t r = active ? t / pieces : 0;
+  const int col = active ? (int)(t % pieces) : 0;
+  const int64_t row = (r / ns) * S + s0 + r % ns;
+  u32x4 raw = {0u, 0u, 0u, 0u};
+  if (active) raw = *(const u32x4*)(qkv + row * ld + pieces * 4 + col * 8);
+  float x[8];
+  unpack8(raw, x);
+  float amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(x[j]));
+  amax = kv8_group_max<HEAD_DIM / 8>(amax);
+  if (!active) return;
+  const int e = kv8_exponent(amax);
+  const float inv = kv8_pow2(-e);
+  const u32x2 out = {kv8_pack4(x, inv), kv8_pack4(x + 4, inv)};
+  *(u32x2*)(data + row * (pieces * 8) + col * 8) = out;
+  if (col % (HEAD_DIM / 8) == 0) scale[row * (pieces / (HEAD_DIM / 8)) + col / (HEAD_DIM / 8)] = kv8_pow2(e);
+}
+
+extern "C" int dmi_kv8_quantize(const uint16_t* qkv, int ld, uint8_t* data, float* scale, int B, int S, int H, int head_dim, int s0, int s1,
+                                void* stream) {
+  DMI_REQUIRE(qkv && data && scale, "kv8_quantize: null pointer");
+  A64_HEAD_DIM_CHECK("kv8_quantize");
+  DMI_REQUIRE(B > 0 && S > 0 && H > 0, "kv8_quantize: empty shape (B=%d S=%d H=%d)", B, S, H);
+  DMI_REQUIRE(0 <= s0 && s0 < s1 && s1 <= S, "kv8_quantize: need 0 <= s0 < s1 <= S (s0=%d, s1=%d, S=%d)", s0, s1, S);
+  DMI_REQUIRE(ld >= 3 * H * head_dim && ld % 8 == 0, "kv8_quantize: ld must be a multiple of 8 and at least 3 H head_dim (ld=%d)", ld);
+  DMI_REQUIRE((((uintptr_t)qkv | (uintptr_t)data) & 15) == 0 && ((uintptr_t)scale & 3) == 0,
+              "kv8_quantize: qkv and data must be 16-byte aligned, scale 4-byte aligned");
+  const int pieces = 2 * H * head_dim / 8, ns = s1 - s0;
+  const int64_t total = (int64_t)B * ns * pieces, blocks = cdiv64(total, 256);
+  DMI_REQUIRE(blocks < 0x7fffffff, "kv8_quantize: too many rows for one launch");
+  const dim3 grid((unsigned)blocks), blk(256);
+  if (head_dim == 64) kv8_quantize_kernel<64><<<grid, blk, 0, (hipStream_t)stream>>>(qkv, ld, data, scale, S, s0, ns, pieces, total);
+  else kv8_quantize_kernel<128><<<grid, blk, 0, (hipStream_t)stream>>>(qkv, ld, data, scale, S, s0, ns, pieces, total);
+  DMI_CHECK_LAUNCH("kv8_quantize");
+  return DMI_OK;
+}
+
+// Decode over the FP8 cache: attn_decode_kernel's block (one per (batch, head), sixteen waves, a wave per 64-key chunk, online
+// softmax per wave, fixed-order merge through LDS) and its roundings (fp32 scores, P to bf16 before P.V, the row sum over the
+// unrounded P).  A key row is HEAD_DIM bytes: LPR = HEAD_DIM / 16 lanes of 16 B.  Lane (c = lane % LPR, g = lane / LPR) owns head
+// dims [16c, 16c + 16) and, per chunk, keys G i + g (i = 0..LPR-1), G = 64 / LPR: every load instruction of the wave still fetches
+// G whole rows (head dim 128: eight 128-B rows, 8 in flight per lane; 64: sixteen 64-B rows, 4 in flight).  After the reduce-scatter
+// butterfly lane (c, g) holds the score of key G c + g over the raw FP8 values; the scales are powers of two, so the key's scale
+// multiplies that score, and the value's scale the rounded probability, exactly as if every element had been scaled.
+// The step's own row: `fresh` [B, 3d] is required (the cache holds no queries).  The chunk loop walks the cache rows BELOW pos; the
+// last wave -- the one with the fewest chunks -- opens its online softmax with key pos instead: it quantises the head's fresh k and
+// v in registers (the bits of kv8_quantize_kernel), stores them into cache row pos and attends to their dequantised values.  So
+// the result does not depend on what cache row pos held, nor on the block seeing its own stores.
+// A row's byte offset inside the (batch, head) slice is 32-bit (the host checks S 2d < 2^31) on a block-uniform 64-bit base.
+template <int HEAD_DIM, bool MASKED, typename... PLAN>
+__global__ __launch_bounds__(64 * DEC_WAVES) void attn_decode_kv8_kernel(uint8_t* data, float* scale, const bf16_t* __restrict__ fresh,
+                                                                         bf16_t* __restrict__ o, PLAN __restrict__... plan_, int H, int S,
+                                                                         int pos_arg, const int* __restrict__ pos_dev) {
+  static_assert(sizeof...(PLAN) == (MASKED ? 1 : 0) && (HEAD_DIM == 128 || (HEAD_DIM == 64 && !MASKED)), "attn_decode_kv8_kernel instance");
+  constexpr int LPR = HEAD_DIM / 16;  // lanes per key row = rows in flight per lane = values a lane brings to the butterfly
+  constexpr int G = 64 / LPR;         // lane groups = keys per load instruction
+  __shared__ float ps[DEC_WAVES][64];
+  __shared__ float red_m[DEC_WAVES], red_l[DEC_WAVES];
+  __shared__ float oacc[DEC_WAVES][HEAD_DIM];
+  const int bh = blockIdx.x, b = bh / H, hh = bh % H;
+  const int d = H * HEAD_DIM;
+  const unsigned rowb = 2u * (unsigned)d;              // bytes per position: K [H, head_dim] then V
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int c = lane & (LPR - 1), g = lane / LPR;
+  const int pos = pos_dev ? *pos_dev : pos_arg;
+  if (pos < 0 || pos >= S) return;                     // (block-uniform; the host checks the by-value form)
+  int W = 0;                                           // MASKED: row `pos` of the row bitmap, W words
+  const unsigned* __restrict__ mrow = nullptr;
+  if constexpr (MASKED) {
+    const int* __restrict__ plan = (plan_, ...);
+    W = plan[AMP_W];
+    mrow = (const unsigned*)(plan + plan[AMP_ROWBITS]) + (int64_t)pos * W;
+  }
+  uint8_t* base = data + (int64_t)b * S * rowb + hh * HEAD_DIM;   // K of position s, head hh: base + s rowb; V: + d
+  float* sbase = scale + (int64_t)b * S * 2 * H + hh;              // K scale of position s: sbase[2 H s]; V: [2 H s + H]
+  const bf16_t* fr = fresh + (int64_t)b * 3 * d + hh * HEAD_DIM + 16 * c;
+  float q[16];
+  unpack8(*(const u32x4*)fr, q);
+  unpack8(*(const u32x4*)(fr + 8), q + 8);
+  float m = -1e30f, l = 0.f;
+  float oa[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) oa[j] = 0.f;
+  if (wid == DEC_WAVES - 1) {                          // key pos: every lane group holds the whole fresh row, group 0 / 1 store k / v
+    u32x4 fq[2];
+    float fs[2];
+#pragma unroll
+    for (int which = 0; which < 2; ++which) {
+      float x[16];
+      unpack8(*(const u32x4*)(fr + (1 + which) * d), x);
+      unpack8(*(const u32x4*)(fr + (1 + which) * d + 8), x + 8);
+      float amax = 0.f;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) amax = fmaxf(amax, fabsf(x[j]));
+      const int e = kv8_exponent(kv8_group_max<LPR>(amax));
+      const float inv = kv8_pow2(-e);
+      fs[which] = kv8_pow2(e);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) fq[which][i] = kv8_pack4(x + 4 * i, inv);
+    }
+    if (g < 2) {
+      *(u32x4*)(base + (int64_t)pos * rowb + g * d + 16 * c) = g == 0 ? fq[0] : fq[1];
+      if (c == 0) sbase[(int64_t)pos * 2 * H + g * H] = g == 0 ? fs[0] : fs[1];
+    }
+    bool attend = true;
+    if constexpr (MASKED) attend = (mrow[pos >> 5] >> (pos & 31)) & 1u;
+    if (attend) {                                      // (wave-uniform) the first key of this wave: p = exp(0) = 1, exact in bf16
+      float f[16];
+      kv8_unpack16(fq[0], f);
+      float t = 0.f;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) t = __builtin_fmaf(f[j], q[j], t);
+#pragma unroll
+      for (int w = LPR / 2; w >= 1; w >>= 1) t += __shfl_xor(t, w, 64);
+      m = t * fs[0];
+      l = 1.f;
+      kv8_unpack16(fq[1], f);
+      const float pj = g == 0 ? fs[1] : 0.f;           // the lane groups' accumulators are summed at the end: group 0 alone adds it
+#pragma unroll
+      for (int j = 0; j < 16; ++j) oa[j] = pj * f[j];
+    }
+  }
+  for (int ch0 = wid; ch0 * 64 < pos; ch0 += DEC_WAVES) {
+    unsigned w0 = 0u, w1 = 0u;                           // MASKED: the chunk's 64 bits of the row (words past the row read as 0)
+    if constexpr (MASKED) {
+      w0 = mrow[2 * ch0];
+      w1 = 2 * ch0 + 1 < W ? mrow[2 * ch0 + 1] : 0u;
+      if ((w0 | w1) == 0u) continue;                     // (wave-uniform) nothing of this chunk is attended to
+    }
+    const int k0 = ch0 * 64;
+    const int kb = G * c + g;                            // after the butterfly this lane holds key k0 + kb: its two scales
+    const int mykey = k0 + kb < pos ? k0 + kb : pos - 1;
+    const float ks = sbase[(int64_t)mykey * 2 * H], vs = sbase[(int64_t)mykey * 2 * H + H];
+    auto row_of = [&](int i, int which) -> u32x4 {       // key k0 + G i + g, clamped below pos
+      int key = k0 + G * i + g;
+      key = key < pos ? key : pos - 1;
+      return *(const u32x4*)(base + ((unsigned)key * rowb + (unsigned)(which * d + 16 * c)));
+    };
+    u32x4 raw[LPR];
+#pragma unroll
+    for (int i = 0; i < LPR; ++i) raw[i] = row_of(i, 0);
+    float p[LPR];
+#pragma unroll
+    for (int i = 0; i < LPR; ++i) {
+      float f[16];
+      kv8_unpack16(raw[i], f);
+      float t = 0.f;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) t = __builtin_fmaf(f[j], q[j], t);
+      p[i] = t;
+      __builtin_amdgcn_sched_barrier(0);               // a row at a time: 16 converted values live, not 16 LPR
+    }
+    // reduce-scatter over the LPR lanes of a group (attn_decode_kernel)
+#pragma unroll
+    for (int w = LPR / 2; w >= 1; w >>= 1) {
+      const bool up = (c & w) != 0;
+#pragma unroll
+      for (int j = 0; j < w; ++j) {
+        const float send = up ? p[j] : p[j + w];
+        const float keep = up ? p[j + w] : p[j];
+        p[j] = keep + __shfl_xor(send, w, 64);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < LPR; ++i) raw[i] = row_of(i, 1);      // value rows requested before the softmax' wave reductions
+    bool valid = k0 + kb < pos;
+    if constexpr (MASKED) valid = valid && (((kb < 32 ? w0 : w1) >> (kb & 31)) & 1u);
+    const float sc = valid ? p[0] * ks : -1e30f;
+    const float mn = fmaxf(m, wave_max(sc));
+    const float alpha = __expf(m - mn);
+    const float pe = valid ? __expf(sc - mn) : 0.f;
+    l = l * alpha + wave_sum(pe);
+    m = mn;
+    ps[wid][kb] = bf2f(f2bf(pe)) * vs;
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // wave-private strip: in-order LDS, no block barrier needed
+#pragma unroll
+    for (int j = 0; j < 16; ++j) oa[j] *= alpha;
+#pragma unroll
+    for (int i = 0; i < LPR; ++i) {
+      float f[16];
+      kv8_unpack16(raw[i], f);
+      const float pj = ps[wid][G * i + g];               // 0 for masked keys and keys from pos on (their rows were clamped below pos)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) oa[j] = __builtin_fmaf(pj, f[j], oa[j]);
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) oa[j] = lane_groups_sum<LPR>(oa[j]);   // the G lane groups hold disjoint key subsets of the same dims
+  if (lane == 0) { red_m[wid] = m; red_l[wid] = l; }
+  if (g == 0) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) oacc[wid][16 * c + j] = oa[j];
+  }
+  __syncthreads();
+  if (wid == 0) {
+    float M = red_m[0];
+#pragma unroll
+    for (int w = 1; w < DEC_WAVES; ++w) M = fmaxf(M, red_m[w]);
+    float L = 0.f, a0 = 0.f, a1 = 0.f;         // head dim 128: lane owns dims 2 lane, 2 lane + 1; head dim 64: dim lane (a0 alone)
+#pragma unroll
+    for (int w = 0; w < DEC_WAVES; ++w) {      // fixed order: deterministic
+      const float sc = __expf(red_m[w] - M);
+      L += red_l[w] * sc;
+      if constexpr (HEAD_DIM == 128) {
+        a0 += oacc[w][2 * lane] * sc;
+        a1 += oacc[w][2 * lane + 1] * sc;
+      } else {
+        a0 += oacc[w][lane] * sc;
+      }
+    }
+    if constexpr (HEAD_DIM == 128) {
+      const float inv = 1.f / L;
+      *(unsigned*)(o + (int64_t)b * d + hh * HEAD_DIM + 2 * lane) = pack2bf(a0 * inv, a1 * inv);
+    } else {
+      o[(int64_t)b * d + hh * HEAD_DIM + lane] = f2bf(a0 / L);
+    }
+  }
+}
+
+// both kv8 decode entry points: one set of checks, one launch (plan != nullptr: the masked instance, head dim 128 only -- amp_route)
+static int attn_decode_kv8_launch(const char* name, uint8_t* data, float* scale, const uint16_t* fresh, uint16_t* o, const int* plan, int B,
+                                  int H, int S, int pos, const int* pos_dev, int head_dim, void* stream) {
+  DMI_REQUIRE(data && scale && o, "%s: null pointer", name);
+  DMI_REQUIRE(fresh, "%s: fresh is required (the FP8 cache holds no queries)", name);
+  DMI_REQUIRE(B > 0 && H > 0 && S > 0, "%s: bad shape", name);
+  DMI_REQUIRE((int64_t)S * 2 * H * head_dim < 0x7fffffff, "%s: sequence too long for 32-bit row offsets", name);
+  DMI_REQUIRE(pos_dev || (pos >= 0 && pos < S), "%s: need 0 <= pos < S (pos=%d, S=%d)", name, pos, S);
+  DMI_REQUIRE((((uintptr_t)data | (uintptr_t)fresh) & 15) == 0 && (((uintptr_t)scale | (uintptr_t)o) & 3) == 0,
+              "%s: data and fresh must be 16-byte aligned, scale and o 4-byte aligned", name);
+  const dim3 grid((unsigned)(B * H)), block(64 * DEC_WAVES);
+  hipStream_t st = (hipStream_t)stream;
+  if (plan) attn_decode_kv8_kernel<128, true, const int*><<<grid, block, 0, st>>>(data, scale, fresh, o, plan, H, S, pos, pos_dev);
+  else if (head_dim == 64) attn_decode_kv8_kernel<64, false><<<grid, block, 0, st>>>(data, scale, fresh, o, H, S, pos, pos_dev);
+  else attn_decode_kv8_kernel<128, false><<<grid, block, 0, st>>>(data, scale, fresh, o, H, S, pos, pos_dev);
+  DMI_CHECK_LAUNCH(name);
+  return DMI_OK;
+}
+
+extern "C" int dmi_attention_decode_kv8(uint8_t* data, float* scale, const uint16_t* fresh, uint16_t* o, int B, int H, int S, int pos,
+                                        const int* pos_dev, int head_dim, void* stream) {
+  A64_HEAD_DIM_CHECK("attention_decode_kv8");
+  return attn_decode_kv8_launch("attention_decode_kv8", data, scale, fresh, o, nullptr, B, H, S, pos, pos_dev, head_dim, stream);
+}
+
+extern "C" int dmi_attention_decode_kv8_masked(uint8_t* data, float* scale, const uint16_t* fresh, uint16_t* o, const int32_t* plan,
+                                               const int32_t* plan_host, int B, int H, int S, int pos, const int* pos_dev, int head_dim,
+                                               void* stream) {
+  const int rt = amp_route(plan, plan_host, S, head_dim, "attention_decode_kv8_masked");
+  if (rt < 0) return rt;
+  if (rt == 1) return dmi_attention_decode_kv8(data, scale, fresh, o, B, H, S, pos, pos_dev, head_dim, stream);
+  return attn_decode_kv8_launch("attention_decode_kv8_masked", data, scale, fresh, o, (const int*)plan, B, H, S, pos, pos_dev, head_dim,
+                                stream);
+}

@@ -102,6 +102,9 @@ def _declare(L):
         "dmi_attention_fwd_masked": (I, [P, P, P, P, P, I, I, I, I, P]),
         "dmi_attention_bwd_masked": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P]),
         "dmi_attention_decode_masked": (I, [P, P, P, P, P, I, I, I, I, P, I, P]),
+        "dmi_kv8_quantize": (I, [P, I, P, P, I, I, I, I, I, I, P]),
+        "dmi_attention_decode_kv8": (I, [P, P, P, P, I, I, I, I, P, I, P]),
+        "dmi_attention_decode_kv8_masked": (I, [P, P, P, P, P, P, I, I, I, I, P, I, P]),
         "dmi_label_logit": (I, [P, I, P, I, P, P, P, P, L64, I, I, P]),
         "dmi_gemm_nt_softmax_partials": (L64, [I]),
         "dmi_gemm_nt_softmax": (I, [P, I, P, I, P, P, P, I, P, I, I, I, P]),
@@ -492,6 +495,36 @@ def attention_decode(qkv, o, B, H, S, pos, fresh=None, pos_dev=None, head_dim=12
         assert pos_dev.dtype == torch.int32
     _check(lib().dmi_attention_decode_hd(_p(qkv), _p(fresh), _p(o), B, H, S, int(pos), _p(pos_dev), int(head_dim), _stream()),
            "attention_decode")
+
+
+def _kv8_check(data, scale, B, S, H, head_dim):
+    _dev(data, scale)
+    assert data.dtype == torch.uint8 and data.numel() >= B * S * 2 * H * head_dim
+    assert scale.dtype == torch.float32 and scale.numel() >= B * S * 2 * H
+
+
+def kv8_quantize(qkv, data, scale, B, S, H, head_dim, s0, s1, ld=None):
+    """rows s0 <= s < s1 of every sequence of the bf16 [B*S, ld] q | k | v buffer (ld defaults to 3 H head_dim) into the FP8 cache:
+    data uint8 [B, S, 2, H, head_dim] (E4M3FN) and scale fp32 [B, S, 2, H], one power of two per (position, head)"""
+    _dev(qkv)
+    _kv8_check(data, scale, B, S, H, head_dim)
+    ld = 3 * H * head_dim if ld is None else int(ld)
+    assert qkv.dtype == torch.bfloat16 and qkv.numel() >= B * S * ld
+    _check(lib().dmi_kv8_quantize(_p(qkv), ld, _p(data), _p(scale), B, S, H, int(head_dim), int(s0), int(s1), _stream()), "kv8_quantize")
+
+
+def attention_decode_kv8(data, scale, fresh, o, B, H, S, pos, pos_dev=None, head_dim=128, plan=None):
+    """attention_decode over the FP8 cache (data, scale) of kv8_quantize: q from the [B, 3d] staging buffer `fresh`, whose k and v
+    are quantised into cache row pos; every key and value attended to is a dequantised one.  plan: an AttnMaskPlan (row pos of it)"""
+    _dev(fresh, o, pos_dev)
+    _kv8_check(data, scale, B, S, H, head_dim)
+    assert fresh.dtype == torch.bfloat16 and fresh.numel() >= B * 3 * H * head_dim and (pos_dev is None or pos_dev.dtype == torch.int32)
+    if plan is None:
+        _check(lib().dmi_attention_decode_kv8(_p(data), _p(scale), _p(fresh), _p(o), B, H, S, int(pos), _p(pos_dev), int(head_dim),
+                                              _stream()), "attention_decode_kv8")
+    else:
+        _check(lib().dmi_attention_decode_kv8_masked(_p(data), _p(scale), _p(fresh), _p(o), _p(plan.dev), plan.host.ctypes.data, B, H, S,
+                                                     int(pos), _p(pos_dev), int(head_dim), _stream()), "attention_decode_kv8_masked")
 
 
 def gemm_nt_splitk_workspace_bytes(M, N, nsplit):

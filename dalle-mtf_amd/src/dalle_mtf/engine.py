@@ -36,6 +36,7 @@ from ..dp import GradReducer
 from .dropout import SITE_POSITION, SITE_TOKEN, site_attention, site_key, site_mlp
 from .layout import ALIGN, ParamLayout, _round_up, adafactor_factored_dims, adafactor_table, reference_init   # noqa: F401  (re-exported)
 from .qk_norm import GAIN_NAMES
+from .kv_cache import DEFAULT as KV_DEFAULT, resolve_kv_cache_dtype
 from .ema import ema_decay_at, one_minus_decay, resolve_weights   # noqa: F401  (ema_decay_at: part of the engine's surface)
 from .loss_weights import position_weights
 from .options import check_checkpoint, checkpoint_entries, resolve_options
@@ -175,6 +176,11 @@ class DalleEngine:
         # state that comes into being on first use (None until then)
         self._t_table = None                      # refresh_compute_copies: the batched transpose's descriptor table
         self._kv = self._dec = None               # the sampler's key/value caches (under recompute_grad) and decode buffers
+        # the engine's cache type -- what _prefill, the decode step and a sampling call without kv_cache_dtype use (kv_cache_as sets
+        # it for a span) --, the FP8 caches (allocated on first use) and, inside an fp8 _prefill, the caches the forward quantises
+        # every layer's k | v into
+        self.kv_cache_dtype = KV_DEFAULT
+        self._kv8 = self._kv8_out = None
         # token shift: the image grid's side, the sampler's history (hist[l][site], allocated on first use) and, inside _prefill,
         # the history the forward's shift launches also write
         self.G = grid_side(image_seq_len) if self.token_shift else None
@@ -234,8 +240,12 @@ class DalleEngine:
 
     def _attn_decode(self, l, cache, o, fresh, pos_dev):
         """one query row per sequence at the position in pos_dev against cache rows 0 .. pos; `fresh` (q | k | v of the step)
-        enters the cache first.  Masked: the mask row of pos comes from the plan."""
-        if self.attn_plan[l] is None:
+        enters the cache first.  Masked: the mask row of pos comes from the plan.  cache: the layer's bf16 [B*S, 3d] buffer, or the
+        (data, scale) pair of its FP8 cache -- the one place that picks the decode entry point."""
+        if isinstance(cache, tuple):
+            dh.attention_decode_kv8(*cache, fresh, o, self.B, self.H, self.S, 0, pos_dev=pos_dev, head_dim=self.hd,
+                                    plan=self.attn_plan[l])
+        elif self.attn_plan[l] is None:
             dh.attention_decode(cache, o, self.B, self.H, self.S, 0, fresh=fresh, pos_dev=pos_dev, head_dim=self.hd)
         else:
             dh.attention_decode_masked(cache, o, self.attn_plan[l], self.B, self.H, self.S, 0, fresh=fresh, pos_dev=pos_dev,
@@ -743,6 +753,8 @@ class DalleEngine:
                            pre=self.qk_pre[l] if self._keep_pre or rerun else None, cs=self.rope_cs)
         elif self.rope_cs is not None:   # the attention kernels, their backward and the decode caches see rotated q and k
             dh.rope_qk(self.qkv[l], self.rope_cs, M, self.S, self.H, self.hd)
+        if self._kv8_out is not None:    # an fp8 prefill: the layer's q | k | v are final, its k | v rows enter the FP8 cache
+            dh.kv8_quantize(self.qkv[l], *self._kv8_out[l], self.B, self.S, self.H, self.hd, 0, self.S)
         self._attn_fwd(l, self.qkv[l], self.o[l], self.lse[l])   # no transposed copies: hardware transpose reads
         self._join_branch(l, mlp=False)
         self._ffn1(l)
@@ -762,7 +774,8 @@ class DalleEngine:
     def sample_image_tokens(self, text: torch.Tensor, temperature: float = 1.0, top_k: int = 0, seed: int = 0,
                             top_p: float = 1.0, image_prefix: Optional[torch.Tensor] = None, return_logprobs: bool = False,
                             kv_cache: bool = True, decode_graph: bool = True, fused_sampling: bool = True,
-                            guidance_scale: float = 1.0, uncond_text: Optional[torch.Tensor] = None, weights: Optional[str] = None):
+                            guidance_scale: float = 1.0, uncond_text: Optional[torch.Tensor] = None, weights: Optional[str] = None,
+                            kv_cache_dtype: Optional[str] = None):
         """Autoregressive image-token sampling: text int32 [B, T] -> image-token ids [B, P] in [0, image_vocab_size).
         The reference scaffolds this (is_incremental_inference, models.py:246-254,281-285) but its predict path raises
         NotImplementedError (model_fns.py:135-136).  Logits are restricted to the image vocabulary; temperature / top-k /
@@ -804,14 +817,22 @@ class DalleEngine:
         the drawn tokens, unguided, temperature 1).
 
         weights: "ema" samples from the weight average (inside ema_weights()), "raw" from the raw iterate, None from the
-        average when the engine has one.  "ema" without an average raises ValueError."""
+        average when the engine has one.  "ema" without an average raises ValueError.
+
+        kv_cache_dtype: "bf16" or "fp8" (None: the engine's, self.kv_cache_dtype, "bf16" unless set).  "fp8": K and V of every
+        layer in OCP E4M3 with one power-of-two scale per (position, head) (include/dalle_hip.h "kv8"; DESIGN.md §4 "Generation: FP8 key/value cache"): the prefill's forward
+        quantises each layer's rows behind its QKV product (dmi_kv8_quantize), the decode step attends with
+        dmi_attention_decode_kv8, and every key and value the attention sees is a dequantised one.  L * B * S * (2d + 8H) bytes,
+        allocated once; under recompute_grad the bf16 caches above are never allocated.  Every other argument composes unchanged;
+        logp is then the likelihood under the fp8-cache computation.  Anything else, or "fp8" with kv_cache=False: ValueError."""
+        kv_dtype = resolve_kv_cache_dtype(self.kv_cache_dtype if kv_cache_dtype is None else kv_cache_dtype, kv_cache)
         which = resolve_weights(weights, self.ema is not None)
         if which == "raw" and self._in_ema:
             raise RuntimeError("sample_image_tokens(weights='raw') inside ema_weights(): the compute copies hold the average")
         a = check_sample_args(self.B, self.T, self.S - self.T, self.text_vocab_size, self.image_vocab_size, text, top_p=top_p,
                               guidance_scale=guidance_scale, uncond_text=uncond_text, image_prefix=image_prefix,
                               padding_id=self.hp.get("padding_id"))
-        with self.ema_weights() if which == "ema" else contextlib.nullcontext():
+        with self.ema_weights() if which == "ema" else contextlib.nullcontext(), self.kv_cache_as(kv_dtype):
             return self._sample(text, a, temperature, top_k, seed, return_logprobs, kv_cache, decode_graph, fused_sampling)
 
     def _sample(self, text, a, temperature, top_k, seed, return_logprobs, kv_cache, decode_graph, fused_sampling):
@@ -887,9 +908,25 @@ class DalleEngine:
             toks[:, T + pos] = tok
         return result((toks[:R, T:] - lo).contiguous())
 
+    @contextlib.contextmanager
+    def kv_cache_as(self, kv_cache_dtype):
+        """inside: the engine's cache type is kv_cache_dtype ("bf16", "fp8"; None: the default)"""
+        prev, self.kv_cache_dtype = self.kv_cache_dtype, resolve_kv_cache_dtype(kv_cache_dtype)
+        try:
+            yield
+        finally:
+            self.kv_cache_dtype = prev
+
     def _kv_caches(self):
-        """the per-layer [B*S, 3d] key/value caches the decode step reads: the forward's own projection buffers, or under
-        recompute_grad (one shared buffer) the sampler's, allocated once: L * B * S * 3d * 2 bytes"""
+        """the per-layer key/value caches the decode step reads.  bf16: the [B*S, 3d] buffers -- the forward's own projection
+        buffers, or under recompute_grad (one shared buffer) the sampler's, allocated once: L * B * S * 3d * 2 bytes.  fp8: per layer
+        (data uint8 [B, S, 2, H, head_dim], scale fp32 [B, S, 2, H]), the sampler's, allocated once: L * B * S * (2d + 8H) bytes"""
+        if self.kv_cache_dtype == "fp8":
+            if self._kv8 is None:
+                B, S, H = self.B, self.S, self.H
+                self._kv8 = [(torch.empty(B, S, 2, H, self.hd, dtype=torch.uint8, device=self.dev),
+                              torch.empty(B, S, 2, H, dtype=torch.float32, device=self.dev)) for _ in range(self.L)]
+            return self._kv8
         if not self.recompute:
             return self.qkv
         if self._kv is None:
@@ -897,14 +934,19 @@ class DalleEngine:
         return self._kv
 
     def _prefill(self, toks):
-        """evaluation forward over toks that leaves every layer's q | k | v in the decode caches"""
-        shared, self.qkv = self.qkv, self._kv_caches()      # (the same list unless recompute_grad shares one buffer)
+        """evaluation forward over toks that leaves every layer's q | k | v in the decode caches (fp8: the forward keeps its own
+        projection buffers -- one shared buffer under recompute_grad -- and quantises every layer's k | v out of them)"""
+        shared = self.qkv
+        if self.kv_cache_dtype == "fp8":
+            self._kv8_out = self._kv_caches()
+        else:
+            self.qkv = self._kv_caches()                    # (the same list unless recompute_grad shares one buffer)
         self._shift_hist_out = self._shift_history()        # token_shift: the shift launches also write the history
         try:
             self.forward(toks, need_grad=False)
         finally:
             self.qkv = shared
-            self._shift_hist_out = None
+            self._shift_hist_out = self._kv8_out = None
 
     def _shift_history(self):
         """token_shift: hist[l][site], bf16 [B, S, d/2] -- columns [0, d/2) of the output of norm_1 (site 0) / norm_2 (site 1) of
@@ -952,23 +994,24 @@ class DalleEngine:
         return D["logits"]
 
     def _run_decode(self, sample, graph: bool):
-        """sample: False (the decode_step body) or the draw variant (a Draw) -- one captured graph per variant, the draw node
-        differs"""
+        """sample: False (the decode_step body) or the draw variant (a Draw) -- one captured graph per variant and cache type: the
+        draw node and the attention nodes differ.  The bf16 graphs are keyed by the variant alone, the fp8 ones by ("fp8", variant)."""
         D = self._dec
+        key = sample if self.kv_cache_dtype == KV_DEFAULT else (self.kv_cache_dtype, sample)
         if not graph:
             self._decode_body(sample)
-        elif sample not in D["graphs"] and sample not in D["warm"]:
+        elif key not in D["graphs"] and key not in D["warm"]:
             self._decode_body(sample)      # first step eager: lazily created views / copies come into being outside the capture
-            D["warm"].add(sample)
+            D["warm"].add(key)
         else:
-            if sample not in D["graphs"]:
+            if key not in D["graphs"]:
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 # other host threads (input producer) stay free to call HIP; no finaliser runs inside the capture
                 with _no_gc_in_capture(), torch.cuda.graph(g, capture_error_mode="thread_local"):
                     self._decode_body(sample)
-                D["graphs"][sample] = g    # (capture records, it does not execute: the replay below is the step)
-            D["graphs"][sample].replay()
+                D["graphs"][key] = g       # (capture records, it does not execute: the replay below is the step)
+            D["graphs"][key].replay()
 
     def _decode_body(self, sample=False):
         """the launches of one decode step; reads D[tok] and the position D[pos_i][0] from device memory.  sample=False: writes
@@ -1003,7 +1046,7 @@ class DalleEngine:
                      pos_dev=D["pos_i"])                                  # every row takes wpe[pos]
         for l in range(L):
             p = f"layer_{l}/"
-            cache = caches[l]                                          # [B*S, 3d]; row b*S + pos <- q | k | v of this step
+            cache = caches[l]                                          # bf16: [B*S, 3d], row b*S + pos <- q | k | v of this step
             ln_dense(x, p + "norm_1", self.tview(p + "attn/qkv"), fresh, 3 * d, shift=(l, 0))
             if self.qk_norm:                                           # normalised (and rotated at table row pos) before they enter the cache
                 dh.qk_norm_decode(fresh, *self._qk_gains(l), B, S, H, self.hd, cs=self.rope_cs, pos_dev=D["pos_i"])

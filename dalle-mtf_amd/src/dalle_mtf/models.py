@@ -88,7 +88,7 @@ class DALLE:
         return {name: shape for name, shape, _, _ in lay.reference_variables()}
 
     def sample(self, text_tokens, vae=None, temperature=1.0, top_k=0, seed=0, top_p=1.0, image_prefix=None, return_logprobs=False,
-               guidance_scale=1.0, uncond_text=None, weights=None):
+               guidance_scale=1.0, uncond_text=None, weights=None, kv_cache_dtype=None):
         """text ids [B, text_seq_len] -> image-token ids [B, image_seq_len] (and the decoded images when a DiscreteVAE is
         given): the generation path the reference leaves unfinished (model_fns.py:135-136).  top_p < 1: nucleus filter after
         top-k; image_prefix int [B, k]: complete images from their first k tokens; return_logprobs: also the model's
@@ -96,11 +96,13 @@ class DALLE:
         classifier-free guidance -- text_tokens (and image_prefix) are [B / 2, ...], the other half of the batch carries
         uncond_text (default: the null caption), and B / 2 rows come back.  weights: "ema" samples from the weight average
         (config key "ema_decay"), "raw" from the raw iterate, None from the average when the engine has one; "ema" without an
-        average raises ValueError.  Returns toks, (toks, images), (toks, logp) or
+        average raises ValueError.  kv_cache_dtype: "bf16" (None: the default) or "fp8", the sampler's key/value cache type
+        (dalle_mtf.kv_cache); anything else raises ValueError.  Returns toks, (toks, images), (toks, logp) or
         (toks, images, logp)."""
         res = self.engine.sample_image_tokens(text_tokens, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p,
                                               image_prefix=image_prefix, return_logprobs=return_logprobs,
-                                              guidance_scale=guidance_scale, uncond_text=uncond_text, weights=weights)
+                                              guidance_scale=guidance_scale, uncond_text=uncond_text, weights=weights,
+                                              kv_cache_dtype=kv_cache_dtype)
         toks, logp = res if return_logprobs else (res, None)
         out = (toks, vae.decode_tokens(toks)) if vae is not None else (toks,)
         if return_logprobs:

@@ -16,6 +16,8 @@ guidance) pairs every row with a null-caption row in the same batch, so a batch 
 output rows; the files keep their shapes per caption and per sample, and logprob.npy stays the conditional model's own score.
 --weights ema | raw samples from the run's weight average (config key "ema_decay") or from the raw iterate; auto (default)
 takes the average when the checkpoint or the config has one.  generate.json records the resolved choice.
+--kv-cache-dtype bf16 | fp8 (else the config key "kv_cache_dtype", else bf16) picks the sampler's key/value cache; with fp8
+logprob.npy is the likelihood under the fp8-cache computation.  generate.json records the resolved type.
 Every argument is checked before the GPU is touched."""
 import argparse
 import json
@@ -30,6 +32,7 @@ SOURCES = ("caption_ids", "captions", "from_eval")
 
 
 def build_parser():
+    from src.dalle_mtf.kv_cache import KV_CACHE_DTYPES
     p = argparse.ArgumentParser(prog="generate_dalle.py", description="Generate images from captions with a trained DALL-E run.")
     p.add_argument("--model", required=True, help="DALL-E config: a name under configs/ or a path to a .json file")
     p.add_argument("--out", default="generated", help="output directory (default: %(default)s)")
@@ -53,6 +56,10 @@ def build_parser():
     p.add_argument("--weights", choices=("auto", "ema", "raw"), default="auto",
                    help="sample from the weight average (ema), the raw iterate (raw), or the average when the run has one (auto, "
                         "default)")
+    p.add_argument("--kv-cache-dtype", dest="kv_cache_dtype", choices=KV_CACHE_DTYPES, default=None,
+                   help="the sampler's key/value cache: bf16, or fp8 (E4M3 with a power-of-two scale per position and head: a third "
+                        "of the memory, about half the bytes read per position; logprob.npy is then the likelihood under the "
+                        "fp8-cache computation).  Default: the config's kv_cache_dtype, else bf16")
     p.add_argument("--seed", type=int, default=0, help="batch j draws with seed + j")
     p.add_argument("--no-images", dest="no_images", action="store_true", help="write tokens and scores only")
     return p
@@ -73,6 +80,7 @@ def load_config(model):
 def check_args(parser, args, params):
     """everything that can be refused without a GPU"""
     from src.model_fns import image_seq_len_of
+    from src.dalle_mtf.kv_cache import resolve_kv_cache_dtype
     P = image_seq_len_of(params)
     if not (0.0 < args.top_p <= 1.0):
         _fail(parser, f"--top-p must lie in (0, 1] (got {args.top_p})")
@@ -84,6 +92,10 @@ def check_args(parser, args, params):
         _fail(parser, f"--samples-per-caption must be >= 1 (got {args.samples})")
     if args.batch is not None and args.batch < 1:
         _fail(parser, f"--batch must be >= 1 (got {args.batch})")
+    try:       # the flag goes before the config key
+        args.kv_cache_dtype = resolve_kv_cache_dtype(args.kv_cache_dtype if args.kv_cache_dtype is not None else params.get("kv_cache_dtype"))
+    except ValueError as e:
+        _fail(parser, f"config key {e}")
     if args.batch is None and not params["predict_batch_size"]:
         _fail(parser, "--batch is needed: the config has no predict_batch_size")
     if not (args.guidance_scale >= 0.0 and math.isfinite(args.guidance_scale)):
@@ -221,7 +233,8 @@ def generate(argv=None):
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         toks, lp = model.sample(cap, temperature=args.temperature, top_k=args.top_k, seed=args.seed + j, top_p=args.top_p,
-                                image_prefix=pre, return_logprobs=True, guidance_scale=args.guidance_scale, weights=which)
+                                image_prefix=pre, return_logprobs=True, guidance_scale=args.guidance_scale, weights=which,
+                                kv_cache_dtype=args.kv_cache_dtype)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         m = min(Bg, rows - j * Bg)
@@ -251,7 +264,8 @@ def generate(argv=None):
                 recompute_grad=bool(eng.recompute),
                 **report(eng.options),
                 seconds=dict(load=round(t_load, 3), sample=round(t_sample, 3), decode_and_copy=round(t_decode, 3)),
-                tokens_per_s=round(nb * Bg * (P - K) / t_sample, 1) if t_sample > 0 else None)
+                tokens_per_s=round(nb * Bg * (P - K) / t_sample, 1) if t_sample > 0 else None,
+                kv_cache_dtype=args.kv_cache_dtype)
     with open(os.path.join(args.out, "generate.json"), "w") as f:
         json.dump(info, f, indent=1)
     print(json.dumps(info))

@@ -287,6 +287,32 @@ int dmi_attention_bwd_masked(const uint16_t* qkv, const uint16_t* o, const uint1
 int dmi_attention_decode_masked(uint16_t* qkv, const uint16_t* fresh, uint16_t* o, const int32_t* plan, const int32_t* plan_host,
                                 int B, int H, int S, int pos, const int* pos_dev, int head_dim, void* stream);
 
+/* ---- FP8 key/value cache for generation ("kv8", project extension; DESIGN.md §4 "Generation: FP8 key/value cache") ----
+ * Per layer two buffers: data uint8 [B, S, 2, H, head_dim] (K then V, OCP E4M3FN bytes) and scale fp32 [B, S, 2, H].  For one head's
+ * row x of head_dim bf16 values:  amax = max |x_j|,  e = clamp(floor(log2(amax)) - 7, -119, 120) (e = 0 when amax = 0),
+ * scale = 2^e,  data_j = e4m3fn(x_j 2^-e) rounded to nearest even -- the byte torch.float8_e4m3fn gives for that fp32 value.  The
+ * product is exact in fp32 and below 256 (nothing saturates); data_j 2^e is exact in fp32 and in bf16.
+ * dmi_kv8_quantize: rows s0 <= s < s1 of every sequence of a bf16 [B*S, ld] buffer in the qkv layout (its k | v columns, ld >= 3 H
+ * head_dim, ld % 8 == 0) go into data / scale; other rows are not touched; offsets are 64-bit.
+ * dmi_attention_decode_kv8: the graph-replayable contract of dmi_attention_decode over that cache.  fresh (required: the cache holds
+ * no queries) = the step's [B, 3 H head_dim] staging row; the kernel takes q from it, quantises the head's fresh k and v, stores them
+ * into cache row pos and attends over the DEQUANTISED keys and values 0 .. pos -- row pos included, so the result does not depend
+ * on what the cache row held before.  pos_dev != NULL: the position is read from device memory (`pos` is then ignored and a position
+ * outside [0, S) makes the launch a no-op).  o bf16 [B, H head_dim].  Roundings as dmi_attention_decode (fp32 scores, P rounded to
+ * bf16 before P V, the row sum over the unrounded P), waves merged in a fixed order: the same inputs give the same bits.
+ * dmi_attention_decode_kv8_masked: row pos of a mask plan (plan / plan_host as dmi_attention_decode_masked: a causal plan runs the
+ * call above, any other plan needs head_dim 128).
+ * All: stream-ordered, no allocation, no atomics.  head_dim other than 64 / 128: DMI_ERR_UNSUPPORTED; a null pointer, an empty
+ * shape, data / qkv / fresh not 16-byte aligned, a bad ld, s0 / s1 outside 0 <= s0 < s1 <= S, or a by-value pos outside [0, S):
+ * DMI_ERR_INVALID -- with a message, before any launch. */
+int dmi_kv8_quantize(const uint16_t* qkv, int ld, uint8_t* data, float* scale, int B, int S, int H, int head_dim, int s0, int s1,
+                     void* stream);
+int dmi_attention_decode_kv8(uint8_t* data, float* scale, const uint16_t* fresh, uint16_t* o, int B, int H, int S, int pos,
+                             const int* pos_dev, int head_dim, void* stream);
+int dmi_attention_decode_kv8_masked(uint8_t* data, float* scale, const uint16_t* fresh, uint16_t* o, const int32_t* plan,
+                                    const int32_t* plan_host, int B, int H, int S, int pos, const int* pos_dev, int head_dim,
+                                    void* stream);
+
 /* ---- K7/K8  to_logits + cross entropy, labels = shift(tokens)   models.py:391-395,348-359,407-410
  * labels[t] = tokens[t+1], last = eos (bit-exact int path). */
 int dmi_shift_labels(const int32_t* tokens, int32_t* labels, int B, int S, int eos, void* stream);
