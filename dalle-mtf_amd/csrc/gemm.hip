@@ -1836,9 +1836,11 @@ static int launch_nt(GemmArgs a, int nsplit, hipStream_t st) {
   return DMI_ERR_UNSUPPORTED;
 }
 
-static int check_nt(const void* A, int lda, const void* B, int ldb, const void* C, int ldc, int M, int N, int K) {
+// kstep: the k-step of the kernel behind the entry point (64 everywhere but the two fused full-row forms, which run on gemm_ntr_kernel
+// alone: k-steps of 32)
+static int check_nt(const void* A, int lda, const void* B, int ldb, const void* C, int ldc, int M, int N, int K, int kstep = BK) {
   DMI_REQUIRE(A && B && C, "gemm_nt: null pointer");
-  DMI_REQUIRE(M > 0 && N > 0 && K > 0 && K % BK == 0 && N % 8 == 0, "gemm_nt: need K%%64==0 and N%%8==0 (M=%d N=%d K=%d)", M, N, K);
+  DMI_REQUIRE(M > 0 && N > 0 && K > 0 && K % kstep == 0 && N % 8 == 0, "gemm_nt: need K%%%d==0 and N%%8==0 (M=%d N=%d K=%d)", kstep, M, N, K);
   DMI_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 && lda >= K && ldb >= K && ldc >= N, "gemm_nt: bad leading dimensions");
   DMI_REQUIRE((((uintptr_t)A | (uintptr_t)B) & 15) == 0 && ((uintptr_t)C & 15) == 0, "gemm_nt: operands must be 16-byte aligned");
   return DMI_OK;
@@ -2073,7 +2075,7 @@ static int launch_ntr_ln(const GemmArgs& a, const char* name, hipStream_t st) {
 extern "C" int dmi_gemm_nt_ln(const uint16_t* A, int lda, const uint16_t* Bt, int ldb, uint16_t* C, int ldc, int M, int N, int K,
                               const uint16_t* bias, const uint16_t* residual, const uint16_t* gamma, const uint16_t* beta, float eps,
                               uint16_t* Y, int ldy, float* mean, float* rstd, void* stream) {
-  int rc = check_nt(A, lda, Bt, ldb, C, ldc, M, N, K);
+  int rc = check_nt(A, lda, Bt, ldb, C, ldc, M, N, K, 32);
   if (rc) return rc;
   DMI_REQUIRE(gamma && beta && Y && mean && rstd, "gemm_nt_ln: null pointer");
   DMI_REQUIRE((((uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)Y | (uintptr_t)bias | (uintptr_t)residual) & 15) == 0 && ldy % 8 == 0 && ldy >= N,
@@ -2096,7 +2098,7 @@ extern "C" int dmi_gemm_nt_lnbwd_parts(int M) { return 2 * ((M + 159) / 160); }
 extern "C" int dmi_gemm_nt_lnbwd(const uint16_t* A, int lda, const uint16_t* Bt, int ldb, int M, int N, int K, const uint16_t* x,
                                  const uint16_t* gamma, const float* mean, const float* rstd, const uint16_t* dres, uint16_t* dx,
                                  float* part, const uint16_t* B2, int ldb2, uint16_t* C2, void* stream) {
-  int rc = check_nt(A, lda, Bt, ldb, dx, N, M, N, K);
+  int rc = check_nt(A, lda, Bt, ldb, dx, N, M, N, K, 32);
   if (rc) return rc;
   DMI_REQUIRE(x && gamma && mean && rstd && part, "gemm_nt_lnbwd: null pointer");
   DMI_REQUIRE((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)dres | (uintptr_t)part) & 15) == 0, "gemm_nt_lnbwd: operands must be 16-byte aligned");

@@ -340,7 +340,8 @@ int64_t dmi_gemm_nt_softmax_partials(int N);
  * feeding :333,373-389 -- out-projection + residual -> norm_2; :321-324 feeding the next block's :330 / to_logits' :392 -- FFN-2 +
  * residual -> norm_1 / final norm):  C[M, N] = bf16(A . Bt^T + bias + residual)  (bias, residual nullable),
  * Y[M, N] = bf16((C - mean) * rstd * gamma + beta), mean / rstd fp32 [M] over the ROUNDED row (biased variance, eps inside the
- * rsqrt: what dmi_layernorm_fwd computes from the stored C).  N = 512 only (a block owns whole rows): DMI_ERR_UNSUPPORTED otherwise. */
+ * rsqrt: what dmi_layernorm_fwd computes from the stored C).  N = 512 only (a block owns whole rows): DMI_ERR_UNSUPPORTED otherwise.
+ * K % 32 == 0 (the full-row kernel's k-step; dmi_gemm_nt_lnbwd the same). */
 int dmi_gemm_nt_ln(const uint16_t* A, int lda, const uint16_t* Bt, int ldb, uint16_t* C, int ldc, int M, int N, int K,
                    const uint16_t* bias, const uint16_t* residual, const uint16_t* gamma, const uint16_t* beta, float eps,
                    uint16_t* Y, int ldy, float* mean, float* rstd, void* stream);

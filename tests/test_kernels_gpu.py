@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 import attention_bwd_ref as ab  # noqa: E402
 import attention_fwd_ref as af  # noqa: E402
 import dalle_hip as dh  # noqa: E402  (path set up by conftest)
+import layernorm_ref as lr  # noqa: E402
 
 DEV = "cuda"
 
@@ -119,6 +120,8 @@ def test_layernorm_fwd_bwd(rows, d):
     ref = F.layer_norm(xf, (d,), gf, bff, 1e-5)
     close(y, ref.detach(), 1e-2, 1e-2, "ln_fwd")
     close(mean, x.float().mean(-1), 1e-5, 1e-5, "ln mean")
+    r64 = lr.ln_fwd64(x, g, b, 1e-5)[2]       # the backward consumes rstd: held to its derived bound (tests/layernorm_ref.py)
+    assert bool(((rstd.cpu().double() - r64).abs() <= lr.rstd_bound(x, 1e-5) * r64).all()), "ln rstd"
     dy = rnd(rows, d, seed=5)
     dres = rnd(rows, d, seed=6)
     ref.backward(dy.float())
