@@ -1999,6 +1999,103 @@ extern "C" int dmi_loss_reduce(const float* loss_rows, int64_t M, const float* p
   return DMI_OK;
 }
 
+// Padded caption positions ("loss_ignore_padding", a project extension): the weight of a row depends on its label.  Row m is a text
+// row when m % period < split; a text row whose label is pad_id is ignored (keep = 0), every other row is kept.
+//   counts[0] = n_t = the kept text rows, counts[1] = n_i = the image rows (exact, int32);
+//   plain:    row_w[m] = keep / (n_t + n_i);   else: keep * ct / max(n_t, 1) on text rows, ci / n_i on image rows
+// (the numerator in fp32, one correctly rounded division by the count converted to float; an ignored row is exactly 0).
+// One block: every thread counts its rows m = t, t + 1024, ... (position advanced without a division, as in loss_reduce_kernel),
+// the block adds the integer counts -- any order gives the same integers --, then every thread writes its rows.
+__device__ __forceinline__ int wave_sum_i32(int x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+__global__ __launch_bounds__(1024) void loss_mask_kernel(const int* __restrict__ labels, int64_t M, int period, int split, int pad_id,
+                                                         float ct, float ci, int plain, int* __restrict__ counts,
+                                                         float* __restrict__ row_w) {
+  __shared__ int sm[2][16];
+  const int tid = threadIdx.x;
+  const int step = 1024 % period, pos0 = tid % period;
+  int pos = pos0, nt = 0, ni = 0;
+  for (int64_t m = tid; m < M; m += 1024) {
+    if (pos < split) nt += labels[m] != pad_id; else ++ni;
+    pos += step;
+    if (pos >= period) pos -= period;
+  }
+  nt = wave_sum_i32(nt); ni = wave_sum_i32(ni);
+  if ((tid & 63) == 0) { sm[0][tid >> 6] = nt; sm[1][tid >> 6] = ni; }
+  __syncthreads();
+  nt = ni = 0;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) { nt += sm[0][w]; ni += sm[1][w]; }
+  if (tid == 0) { counts[0] = nt; counts[1] = ni; }
+  const float wt = plain ? 1.f / (float)(nt + ni > 1 ? nt + ni : 1) : ct / (float)(nt > 1 ? nt : 1);
+  const float wi = plain ? wt : (ni ? ci / (float)ni : 0.f);
+  pos = pos0;
+  for (int64_t m = tid; m < M; m += 1024) {
+    row_w[m] = pos < split ? (labels[m] != pad_id ? wt : 0.f) : wi;
+    pos += step;
+    if (pos >= period) pos -= period;
+  }
+}
+extern "C" int dmi_loss_mask(const int32_t* labels, int64_t M, int period, int split, int pad_id, float ct, float ci, int plain,
+                             int32_t* counts, float* row_w, void* stream) {
+  DMI_REQUIRE(labels && counts && row_w, "loss_mask: null pointer");
+  DMI_REQUIRE(M > 0 && M < (1ll << 31), "loss_mask: M must lie in [1, 2^31) (the counts are int32)");
+  DMI_REQUIRE(period > 0 && split >= 0 && split <= period, "loss_mask: bad sizes (period > 0, 0 <= split <= period: period=%d split=%d)",
+              period, split);
+  loss_mask_kernel<<<dim3(1), dim3(1024), 0, (hipStream_t)stream>>>(labels, M, period, split, pad_id, ct, ci, plain, counts, row_w);
+  DMI_CHECK_LAUNCH("loss_mask");
+  return DMI_OK;
+}
+
+// The masked loss and what is reported beside it, on loss_reduce_kernel's tree (one block, fixed order, no atomics):
+//   out4[0] = scale * sum_m row_w[m] * loss_rows[m];  out4[1] = L_t = sum over kept text rows / max(n_t, 1);
+//   out4[2] = L_i = mean over the image rows;  out4[3] = n_t / the number of text rows;  a mean over no rows is 0.
+// n_t = counts[0] and n_i = counts[1] are dmi_loss_mask's (read from the device: no host sync).
+__global__ __launch_bounds__(1024) void loss_reduce_masked_kernel(const float* __restrict__ loss_rows, const float* __restrict__ row_w,
+                                                                  const int* __restrict__ labels, int64_t M, int period, int split,
+                                                                  int pad_id, const int* __restrict__ counts, float scale,
+                                                                  float ntext, float* __restrict__ out4) {
+  __shared__ float sm[3][16];
+  const int tid = threadIdx.x;
+  const int step = 1024 % period;
+  int pos = tid % period;
+  float aw = 0.f, at = 0.f, ai = 0.f;
+  for (int64_t m = tid; m < M; m += 1024) {
+    const float l = loss_rows[m];
+    aw = __builtin_fmaf(row_w[m], l, aw);
+    if (pos < split) at += labels[m] != pad_id ? l : 0.f; else ai += l;
+    pos += step;
+    if (pos >= period) pos -= period;
+  }
+  aw = wave_sum(aw); at = wave_sum(at); ai = wave_sum(ai);
+  if ((tid & 63) == 0) { sm[0][tid >> 6] = aw; sm[1][tid >> 6] = at; sm[2][tid >> 6] = ai; }
+  __syncthreads();
+  if (tid < 3) {
+    const float* s = sm[tid];
+    const float r = (((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]))) +
+                    (((s[8] + s[9]) + (s[10] + s[11])) + ((s[12] + s[13]) + (s[14] + s[15])));
+    const int n = counts[tid == 1 ? 0 : 1];
+    out4[tid] = tid == 0 ? r * scale : (n > 0 ? r / (float)n : 0.f);
+  } else if (tid == 3) {
+    out4[3] = ntext > 0.f ? (float)counts[0] / ntext : 0.f;
+  }
+}
+extern "C" int dmi_loss_reduce_masked(const float* loss_rows, const float* row_w, const int32_t* labels, int64_t M, int period,
+                                      int split, int pad_id, const int32_t* counts, float scale, float* out4, void* stream) {
+  DMI_REQUIRE(loss_rows && row_w && labels && counts && out4, "loss_reduce_masked: null pointer");
+  DMI_REQUIRE(M > 0 && M < (1ll << 31) && period > 0 && split >= 0 && split <= period,
+              "loss_reduce_masked: bad sizes (0 < M < 2^31, period > 0, 0 <= split <= period)");
+  const int64_t full = M / period, rem = M % period;
+  const int64_t ntext = full * split + (rem < split ? rem : split);
+  loss_reduce_masked_kernel<<<dim3(1), dim3(1024), 0, (hipStream_t)stream>>>(loss_rows, row_w, labels, M, period, split, pad_id, counts,
+                                                                             scale, (float)ntext, out4);
+  DMI_CHECK_LAUNCH("loss_reduce_masked");
+  return DMI_OK;
+}
+
 #define SUMSQ_BLOCKS 2048
 extern "C" int64_t dmi_sumsq_workspace_bytes(int64_t n) { (void)n; return SUMSQ_BLOCKS * 4; }
 // (A sweep from the END of the buffer -- the flat gradient buffer is laid out in backward's completion order, so its tail is what the 256-MB

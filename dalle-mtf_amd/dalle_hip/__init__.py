@@ -111,6 +111,8 @@ def _declare(L):
         "dmi_softmax_finish": (I, [P, I, P, P, P, P, I, P, I, P, P, I, I, P, P, P, P, P, L64, I, I, F, P]),
         "dmi_softmax_finish_w": (I, [P, I, P, P, P, P, I, P, I, P, P, I, I, P, P, P, P, P, L64, I, I, F, P, I, P]),
         "dmi_loss_reduce": (I, [P, L64, P, I, I, F, P, P]),
+        "dmi_loss_mask": (I, [P, L64, I, I, I, F, F, I, P, P, P]),
+        "dmi_loss_reduce_masked": (I, [P, P, P, L64, I, I, I, P, F, P, P]),
         "dmi_shift_labels": (I, [P, P, I, I, I, P]),
         "dmi_cross_entropy": (I, [P, I, P, P, P, L64, I, F, P]),
         "dmi_sum_f32": (I, [P, L64, F, P, P]),
@@ -759,6 +761,22 @@ def loss_reduce(loss_rows, n, pos_weight, period, split, scale, out3):
     _dev(loss_rows, pos_weight, out3)
     _check(lib().dmi_loss_reduce(_p(loss_rows), n, _p(pos_weight), int(period), int(split), float(scale), _p(out3), _stream()),
            "loss_reduce")
+
+
+def loss_mask(labels, M, period, split, pad_id, ct, ci, plain, counts, row_w):
+    """counts int32 [2] = (kept text rows, image rows), row_w fp32 [M] = every row's loss weight with the text rows whose label is
+    pad_id ignored (include/dalle_hip.h); text rows: m % period < split"""
+    _dev(labels, counts, row_w)
+    _check(lib().dmi_loss_mask(_p(labels), M, int(period), int(split), int(pad_id), float(ct), float(ci), int(bool(plain)), _p(counts),
+                               _p(row_w), _stream()), "loss_mask")
+
+
+def loss_reduce_masked(loss_rows, row_w, labels, M, period, split, pad_id, counts, scale, out4):
+    """out4 fp32 [4] = (scale * sum_m row_w[m] * loss_rows[m], mean over the kept text rows, mean over the image rows, kept text rows /
+    text rows); counts: loss_mask's"""
+    _dev(loss_rows, row_w, labels, counts, out4)
+    _check(lib().dmi_loss_reduce_masked(_p(loss_rows), _p(row_w), _p(labels), M, int(period), int(split), int(pad_id), _p(counts),
+                                        float(scale), _p(out4), _stream()), "loss_reduce_masked")
 
 
 def assemble_tokens(text, vae_logits, tokens_out, B, T, P, C, text_vocab):

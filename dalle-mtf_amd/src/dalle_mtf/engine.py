@@ -38,6 +38,7 @@ from .layout import ALIGN, ParamLayout, _round_up, adafactor_factored_dims, adaf
 from .qk_norm import GAIN_NAMES
 from .kv_cache import DEFAULT as KV_DEFAULT, resolve_kv_cache_dtype
 from .ema import ema_decay_at, one_minus_decay, resolve_weights   # noqa: F401  (ema_decay_at: part of the engine's surface)
+from .loss_mask import mask_coefficients, resolve_loss_ignore_padding
 from .loss_weights import position_weights
 from .options import check_checkpoint, checkpoint_entries, resolve_options
 from .rotary import rotary_table
@@ -127,6 +128,8 @@ class DalleEngine:
         self.options = resolve_options(self.hp, n_embd, text_seq_len, image_seq_len, activation_fn=self.hp.get("activation_fn") or "relu")
         for name, value in self.options._asdict().items():
             setattr(self, name, value)
+        # hparams["loss_ignore_padding"] (dalle_mtf.loss_mask): a training setting beside the options, like the sampler's cache type
+        self.loss_ignore_padding, self.loss_pad_id = resolve_loss_ignore_padding(self.hp, text_seq_len, text_vocab_size)
         if not torch.cuda.is_available():
             raise dh.DalleHipError("DalleEngine needs a HIP device (MI355X); there is no CPU fallback")
         dh.lib()
@@ -185,7 +188,7 @@ class DalleEngine:
         # the history the forward's shift launches also write
         self.G = grid_side(image_seq_len) if self.token_shift else None
         self._shift_hist = self._shift_hist_out = None
-        self.gacc = self.loss_acc = self.loss_parts_acc = None   # train_step's micro-batch accumulators
+        self.gacc = self.loss_acc = self.loss_parts_acc = self.text_kept_frac_acc = None   # train_step's micro-batch accumulators
         self.event_hook = None                    # bench.py: a callable returning the list that takes the head launch's event pair
         self._ln_pend = []                        # LayerNorm gain / bias partials awaiting _flush_ln()
         self._build_attn_plans(attn_masks)
@@ -498,11 +501,22 @@ class DalleEngine:
         # hparams["text_loss_weight"] / ["image_loss_weight"] (dalle_mtf.loss_weights): the static weight of every position, computed
         # in float64 and uploaded once; loss3 = (weighted loss | text mean, image mean), written by dmi_loss_reduce
         self.pos_weight = self.loss_parts = None
-        if self.loss_weights is not None:
+        if self.loss_weights is not None and not self.loss_ignore_padding:
             w = position_weights(self.T, S - self.T, *self.loss_weights)
             self.pos_weight = torch.from_numpy(w.astype(np.float32)).to(self.dev)
             self.loss3 = torch.zeros(3, **f32)
             self.loss, self.loss_parts = self.loss3[0:1], self.loss3[1:3]
+        # hparams["loss_ignore_padding"] (dalle_mtf.loss_mask): the weight of a row depends on its label, so dmi_loss_mask writes
+        # row_w [M] and counts = (kept text rows, image rows) behind shift_labels in every forward, the weighted finish reads row_w
+        # with period M, and dmi_loss_reduce_masked writes loss4 = (loss | kept-text mean, image mean | kept fraction of the text
+        # labels).  The counts stay on the device.  Off: none of these buffers, none of these launches
+        self.row_w = self.mask_counts = self.text_kept_frac = None
+        if self.loss_ignore_padding:
+            self.mask_coef = mask_coefficients(self.loss_weights)
+            self.row_w = torch.zeros(M, **f32)
+            self.mask_counts = torch.zeros(2, dtype=torch.int32, device=self.dev)
+            self.loss4 = torch.zeros(4, **f32)
+            self.loss, self.loss_parts, self.text_kept_frac = self.loss4[0:1], self.loss4[1:3], self.loss4[3:4]
         self.gnorm_sq = torch.zeros(1, **f32)
         # fused softmax head (training path, include/dalle_hip.h K7/K8 (b))
         self.nparts = dh.gemm_nt_softmax_partials(Vp)
@@ -556,6 +570,9 @@ class DalleEngine:
         -log softmax(logits)[label] (src/dalle_mtf/models.py:348-359), labels = shift(tokens) (:407-410).
         With loss weights set (self.pos_weight): the weighted loss sum_{b,p} w[p] NLL[b,p] / B instead, self.loss_parts = the
         unweighted (text mean, image mean), and rowscale carries w[p]; self.loss_rows stays the unweighted NLL.
+        With "loss_ignore_padding" on (self.row_w): the masked loss sum_{b,p} c[b,p] NLL[b,p] of dalle_mtf.loss_mask, with or without
+        loss weights; self.loss_parts = (mean over the kept caption labels, image mean), self.text_kept_frac the kept fraction of the
+        caption labels, rowscale carries c[b,p] (0 on ignored rows); self.loss_rows stays the unmasked NLL of every position.
         need_grad=True (training): the softmax is fused into the vocabulary projection -- self.z then holds the
         unnormalised dlogits E, self.rowscale their per-row factor (already scaled by 1/(global B*S*microbatches)).
         need_grad=False (evaluation): self.z holds the bf16 logits (see logits()); the loss is the plain mean
@@ -568,6 +585,9 @@ class DalleEngine:
         if need_grad:   # token-id order for the embedding backward: twelve 3-5 us launches on a side stream (see dmi_sort_tokens)
             self._launch_sort()
         dh.shift_labels(self.tokens, self.labels, B, S, self.eos)
+        if self.row_w is not None:   # this batch's row weights and counts (text rows: p < T - 1)
+            ct, ci, plain = self.mask_coef
+            dh.loss_mask(self.labels, self.M, S, self.T - 1, self.loss_pad_id, ct, ci, plain, self.mask_counts, self.row_w)
         self._draw_dropout(need_grad)
         self._embed_fwd()
         for l in range(L):
@@ -580,7 +600,7 @@ class DalleEngine:
         M, d, S, Vp = self.M, self.d, self.S, self.Vp
         Wt, bias = self.tview("to_logits/linear_out/kernel"), self._w("to_logits/linear_out/bias")
         nmb = (self.hp.get("num_microbatches", 1) or 1) if need_grad else 1
-        weighted = self.pos_weight is not None
+        weighted, masked = self.pos_weight is not None, self.row_w is not None
         if need_grad:
             dh.label_logit(self.xnf, d, Wt, d, bias, self.labels, self.zl, self.head_flag, M, d, self.V)
         hook = self.event_hook       # bench.py: HIP events around the largest single launch
@@ -596,13 +616,19 @@ class DalleEngine:
             e1.record()
             hook().append((e0, e1))
         if need_grad:   # the weighted finish scales row (b, p) by w[p] / (global B), the plain one every row by 1 / (global B * S)
-            finish, scale = ((dh.softmax_finish_w, (1.0 / (self.B_global * nmb), self.pos_weight, S)) if weighted else
-                             (dh.softmax_finish, (1.0 / (self.B_global * S * nmb),)))
+            if masked:  # row_w is normalised by this forward's own counts: what is left is the mean over micro-batches and ranks
+                finish, scale = dh.softmax_finish_w, (1.0 / (nmb * self.world), self.row_w, M)
+            else:
+                finish, scale = ((dh.softmax_finish_w, (1.0 / (self.B_global * nmb), self.pos_weight, S)) if weighted else
+                                 (dh.softmax_finish, (1.0 / (self.B_global * S * nmb),)))
             finish(self.rowsum_part, self.nparts, self.zl, None, self.labels, self.xnf, d, Wt, d, bias, self.z, Vp, Vp,
                    self.loss_rows, self.rowscale, self.rowscale_bf, self.xs, self.head_flag, M, d, self.V, *scale)
         else:
             dh.cross_entropy(self.z, Vp, self.labels, self.loss_rows, None, M, self.V, 0.0)
-        if weighted:
+        if masked:
+            dh.loss_reduce_masked(self.loss_rows, self.row_w, self.labels, M, S, self.T - 1, self.loss_pad_id, self.mask_counts,
+                                  1.0 / nmb, self.loss4)
+        elif weighted:
             dh.loss_reduce(self.loss_rows, M, self.pos_weight, S, self.T - 1, 1.0 / (self.B * nmb), self.loss3)
         else:
             dh.sum_f32(self.loss_rows, M, 1.0 / (M * nmb), self.loss)
@@ -1356,7 +1382,9 @@ class DalleEngine:
         """One optimizer step.  With hparams["num_microbatches"] = n > 1, `tokens` holds n micro-batches of B rows
         ([n*B, S]): gradients are accumulated locally and reduced once, and the loss is the sum of the micro-batch
         means / n (mtf.serialize_training_step as used at src/model_fns.py:156-166; src/dalle_mtf/models.py:356).  With loss
-        weights set, self.loss_parts_acc accumulates the micro-batches' (text mean, image mean) / n the same way."""
+        weights set, self.loss_parts_acc accumulates the micro-batches' (text mean, image mean) / n the same way, and with
+        "loss_ignore_padding" on self.text_kept_frac_acc their kept fractions / n (every micro-batch is normalised by its own
+        counts: the step's loss is the mean of the masked means)."""
         self._not_in_ema("train_step")
         nmb = self.hp.get("num_microbatches", 1) or 1
         if nmb == 1:
@@ -1374,12 +1402,18 @@ class DalleEngine:
             if self.loss_parts_acc is None:
                 self.loss_parts_acc = torch.zeros_like(self.loss_parts)
             self.loss_parts_acc.zero_()
+        if self.text_kept_frac is not None:
+            if self.text_kept_frac_acc is None:
+                self.text_kept_frac_acc = torch.zeros_like(self.text_kept_frac)
+            self.text_kept_frac_acc.zero_()
         for i in range(nmb):
             self._microbatch = i          # (keys the dropout masks: every micro-batch draws its own)
             loss = self.forward(tokens[i * self.B:(i + 1) * self.B], need_grad=True)
             self.loss_acc += loss
             if self.loss_parts is not None:
                 self.loss_parts_acc.add_(self.loss_parts, alpha=1.0 / nmb)
+            if self.text_kept_frac is not None:
+                self.text_kept_frac_acc.add_(self.text_kept_frac, alpha=1.0 / nmb)
             self.backward(allreduce=False)
             if i == 0:
                 self.gacc.copy_(self.g)

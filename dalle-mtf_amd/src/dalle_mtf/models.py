@@ -8,6 +8,7 @@ import numpy as np
 
 from .engine import DalleEngine
 from .layout import ParamLayout
+from .loss_mask import resolve_loss_ignore_padding
 from .masks import layer_masks
 from .ops import get_variable_dtype
 from .options import resolve_options
@@ -55,6 +56,8 @@ class DALLE:
         self.options = opt = resolve_options(params, n_embd, text_seq_len, image_seq_len, activation_fn=activation_fn)
         self.activation_fn, self.rotary_emb, self.rotary_base = opt.activation, opt.rotary, opt.rotary_base
         self.token_shift, self.ff_glu, self.qk_norm = opt.token_shift, opt.ff_glu, opt.qk_norm
+        # "loss_ignore_padding" (dalle_mtf.loss_mask): a training setting kept beside the options, checked here too
+        self.loss_ignore_padding, self.loss_pad_id = resolve_loss_ignore_padding(params, text_seq_len, text_vocab_size)
         if self.params.get("attention_dropout"):
             raise NotImplementedError("attention_dropout > 0 is not supported: embed_dropout and residual_dropout are; dropout of "
                                       "the attention weights would live inside the attention kernels (all shipped configs use 0)")

@@ -14,6 +14,7 @@ import torch
 
 import dalle_hip as dh
 from .dalle_mtf import DALLE
+from .dalle_mtf.loss_mask import log_line as loss_mask_log_line
 from .dalle_mtf.options import option_log_lines
 from .estimator import CheckpointSaverHook, EstimatorSpec, latest_checkpoint
 from .optimizers import get_optimizer
@@ -157,6 +158,8 @@ def _build(params, mode_str):
         # the options that are on (dalle_mtf.options; their config keys reach the engine's hparams through `params`)
         for line in option_log_lines(eng.options, eng.d, eng.H, eng.T, image_seq_len):
             logging.getLogger("dalle_mtf_amd").info("%s %s", mode_str, line)
+        if eng.loss_ignore_padding:    # a training setting kept beside the options (dalle_mtf.loss_mask)
+            logging.getLogger("dalle_mtf_amd").info("%s %s", mode_str, loss_mask_log_line(eng.loss_pad_id, eng.loss_weights))
     eng.hp["num_microbatches"] = nmb   # reference model_fns.py:141-154 (1 when tokens_per_mb_per_replica is unset)
     params["num_microbatches"] = nmb
     state["local_bs"] = local_bs
@@ -251,6 +254,10 @@ def dalle_model_fn(features, labels, mode, params):
                 eng.loss_parts_acc = torch.zeros_like(eng.loss_parts)
             scalar_summary("loss_text", eng.loss_parts_acc[0])
             scalar_summary("loss_image", eng.loss_parts_acc[1])
+        if eng.text_kept_frac is not None:
+            if getattr(eng, "text_kept_frac_acc", None) is None:
+                eng.text_kept_frac_acc = torch.zeros_like(eng.text_kept_frac)
+            scalar_summary("text_kept_frac", eng.text_kept_frac_acc[0])
         scalar_summary("lr", st["lr_fn"]())
         return EstimatorSpec(mode=mode, loss=eng.loss_acc[0], train_op=train_op_mb,
                              host_call=create_host_call(params["model_path"]) if (params.get("model_path") and st["rank"] == 0) else None,
@@ -259,22 +266,29 @@ def dalle_model_fn(features, labels, mode, params):
         # the engine may have been sized for one training micro-batch: evaluate the batch in engine-sized chunks (equal
         # sizes, so the mean of the chunk means is the batch mean, src/dalle_mtf/models.py:354)
         # "ema_eval": the losses of the averaged weights (DalleEngine.ema_weights)
-        total = parts = None
+        total = parts = kept = metrics = None
         with eng.ema_weights() if eng.ema_eval else contextlib.nullcontext():
             for c in range(B // eng.B):
                 l, _ = model.forward({"tokens": tokens[c * eng.B:(c + 1) * eng.B]}, return_loss=True)
                 total = l.clone() if total is None else total + l
                 if eng.loss_parts is not None:
                     parts = eng.loss_parts.clone() if parts is None else parts + eng.loss_parts
+                if eng.text_kept_frac is not None:
+                    kept = eng.text_kept_frac.clone() if kept is None else kept + eng.text_kept_frac
         if parts is not None:
             scalar_summary("loss_text", parts[0] / (B // eng.B))
             scalar_summary("loss_image", parts[1] / (B // eng.B))
-        return EstimatorSpec(mode=mode, loss=total / (B // eng.B))
+        if kept is not None:   # "loss_ignore_padding": every chunk is normalised by its own counts, the chunks averaged
+            scalar_summary("text_kept_frac", kept[0] / (B // eng.B))
+            metrics = {"text_kept_frac": kept[0] / (B // eng.B)}
+        return EstimatorSpec(mode=mode, loss=total / (B // eng.B), eval_metrics=metrics)
     loss, _loss_batch = model.forward({"tokens": tokens}, return_loss=True)
     scalar_summary("loss", loss)
     if eng.loss_parts is not None:
         scalar_summary("loss_text", eng.loss_parts[0])
         scalar_summary("loss_image", eng.loss_parts[1])
+    if eng.text_kept_frac is not None:
+        scalar_summary("text_kept_frac", eng.text_kept_frac[0])
     scalar_summary("lr", st["lr_fn"]())
 
     def train_op():

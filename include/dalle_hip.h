@@ -429,6 +429,26 @@ int dmi_softmax_finish_w(const float* rowsum_part, int nparts, const float* labe
                          int64_t M, int K, int V, float dz_scale, const float* pos_weight, int period, void* stream);
 int dmi_loss_reduce(const float* loss_rows, int64_t M, const float* pos_weight, int period, int split, float scale,
                     float* out3, void* stream);
+/* Padded caption positions (config key "loss_ignore_padding", a project extension): the weight of a row depends on its label.
+ * Row m is a text row when m % period < split (period = the sequence length, split = T - 1) and an image row otherwise; a text row
+ * whose label is pad_id is ignored (keep = 0), image rows are always kept.  n_t = the kept text rows, n_i = the image rows.
+ *   dmi_loss_mask           counts int32 [2] = (n_t, n_i), exact; row_w fp32 [M] = the weight of every row:
+ *                             plain != 0:  keep / (n_t + n_i)
+ *                             plain == 0:  keep * ct / max(n_t, 1) on text rows, ci / n_i on image rows
+ *                           with ct = wt / (wt + wi), ci = wi / (wt + wi) computed by the host in float64: the numerator in fp32,
+ *                           one correctly rounded division by the count converted to float, ignored rows exactly 0.  One launch,
+ *                           one block, integer counts (no float atomics): two runs give equal bits.  0 < M < 2^31, period > 0,
+ *                           0 <= split <= period.  The gradient path is dmi_softmax_finish_w with pos_weight = row_w, period = M.
+ *   dmi_loss_reduce_masked  out4[0] = scale * sum_m row_w[m] * loss_rows[m]  (the masked loss),
+ *                           out4[1] = L_t = sum of loss_rows over the kept text rows / max(n_t, 1),
+ *                           out4[2] = L_i = mean of loss_rows over the image rows,
+ *                           out4[3] = n_t / the number of text rows;  a mean over no rows is 0.
+ *                           counts = dmi_loss_mask's, read on the device.  dmi_loss_reduce's single-block tree (fixed order, no
+ *                           atomics).  Sizes as dmi_loss_mask. */
+int dmi_loss_mask(const int32_t* labels, int64_t M, int period, int split, int pad_id, float ct, float ci, int plain,
+                  int32_t* counts, float* row_w, void* stream);
+int dmi_loss_reduce_masked(const float* loss_rows, const float* row_w, const int32_t* labels, int64_t M, int period, int split,
+                           int pad_id, const int32_t* counts, float scale, float* out4, void* stream);
 
 /* ---- K10  image-token indexing   src/model_fns.py:76-77,118-119 (bit-exact)
  * tokens_out[b, 0:T] = text[b]; tokens_out[b, T + p] = argmax_c logits[b, p, c] (first max) + text_vocab */
