@@ -780,3 +780,445 @@ extern "C" int dmi_depth_to_space_f32(const float* stacked, float* img, int B, i
   DMI_CHECK_LAUNCH("depth_to_space");
   return DMI_OK;
 }
+
+// =====================================================================================
+// Vector-quantised bottleneck (project extension; DESIGN.md §4 "VAE: vector quantisation").  X = x_enc bf16 [M, D], Cb the bf16
+// codebook, codebook_t [T, D] its transpose (code k = row k), h[k] = 1/2 sum_j Cb[j,k]^2:
+//   s[m,k] = sum_j X[m,j] Cb[j,k] - h[k]     idx[m] = lowest k among the maxima of s[m,:]     xq[m,:] = Cb[:, idx[m]]
+//   Lq = (1/(M D)) sum_m ||X[m] - xq[m]||^2   dX = bf16(d + (2 beta/(M D)) (X - xq))   dC[:,k] = (2/(M D)) sum_{m: idx[m]=k} (Cb[:,k] - X[m,:])
+// Every sum has a fixed order (no float atomics): two runs give equal bits.
+// =====================================================================================
+#define VQ_MAX_T 4096
+#define VQ_MAX_D 512
+#define VQ_ROWS 64
+
+// h[k] from the bf16 transpose: one wave per code, a lane squares one 16-byte piece (D <= 512: at most 64 pieces), wave_sum.
+__global__ __launch_bounds__(256) void vq_half_norms_bf16_kernel(const bf16_t* __restrict__ cbt, int ldc, float* __restrict__ h, int T, int D) {
+  const int lane = threadIdx.x & 63;
+  const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (k >= T) return;
+  float a = 0.f;
+  if (lane < D / 8) {
+    float f[8];
+    unpack8(*(const u32x4*)(cbt + (int64_t)k * ldc + lane * 8), f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a += f[e] * f[e];
+  }
+  a = wave_sum(a);
+  if (lane == 0) h[k] = 0.5f * a;
+}
+// h[k] from the fp32 masters [D, T]: one thread per code, rows top to bottom
+__global__ __launch_bounds__(256) void vq_half_norms_f32_kernel(const float* __restrict__ cb, float* __restrict__ h, int T, int D) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= T) return;
+  float a = 0.f;
+  for (int j = 0; j < D; ++j) {
+    const float v = cb[(int64_t)j * T + k];
+    a += v * v;
+  }
+  h[k] = 0.5f * a;
+}
+extern "C" int dmi_vq_half_norms(const uint16_t* codebook_t, int ldc, const float* codebook_f32, float* h, int T, int D, void* stream) {
+  DMI_REQUIRE(h, "vq_half_norms: null pointer (h)");
+  DMI_REQUIRE((codebook_t != nullptr) != (codebook_f32 != nullptr), "vq_half_norms: give exactly one of codebook_t (bf16 [T, ldc]) and codebook_f32 (fp32 [D, T])");
+  DMI_REQUIRE(T > 0 && D > 0, "vq_half_norms: T and D must be positive (T=%d D=%d)", T, D);
+  if (codebook_t) {
+    DMI_REQUIRE(D % 8 == 0 && ldc % 8 == 0 && ldc >= D && (((uintptr_t)codebook_t) & 15) == 0, "vq_half_norms: codebook_t needs D%%8==0, ldc%%8==0, ldc>=D, 16-byte alignment (D=%d ldc=%d)", D, ldc);
+    if (D > VQ_MAX_D) {
+      dmi_set_error("vq_half_norms: D = %d is above %d (one 16-byte piece per lane)", D, VQ_MAX_D);
+      return DMI_ERR_UNSUPPORTED;
+    }
+    vq_half_norms_bf16_kernel<<<dim3((unsigned)((T + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(codebook_t, ldc, h, T, D);
+  } else {
+    vq_half_norms_f32_kernel<<<dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(codebook_f32, h, T, D);
+  }
+  DMI_CHECK_LAUNCH("vq_half_norms");
+  return DMI_OK;
+}
+
+// scores[m,k] -= h[k]  (fp32 [M, T]; behind the logits product when DALL-E tokenises)
+__global__ __launch_bounds__(256) void vq_scores_bias_kernel(float* __restrict__ s, const float* __restrict__ h, int64_t M, int T) {
+  const int t4 = T / 4;
+  const int64_t total = M * t4;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i % t4);
+    f32x4 v = *(f32x4*)(s + i * 4);
+    const f32x4 hv = *(const f32x4*)(h + c * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] -= hv[e];
+    *(f32x4*)(s + i * 4) = v;
+  }
+}
+extern "C" int dmi_vq_scores_bias(float* scores, const float* h, int64_t M, int T, void* stream) {
+  DMI_REQUIRE(scores && h, "vq_scores_bias: null pointer");
+  DMI_REQUIRE(M > 0, "vq_scores_bias: M must be positive (M=%lld)", (long long)M);
+  DMI_REQUIRE(T > 0 && T % 4 == 0, "vq_scores_bias: T must be a positive multiple of 4 (T=%d)", T);
+  DMI_REQUIRE(((((uintptr_t)scores) | ((uintptr_t)h)) & 15) == 0, "vq_scores_bias: scores and h must be 16-byte aligned");
+  int64_t blocks = cdiv64(M * (T / 4), 256);
+  if (blocks > 16384) blocks = 16384;
+  vq_scores_bias_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(scores, h, M, T);
+  DMI_CHECK_LAUNCH("vq_scores_bias");
+  return DMI_OK;
+}
+
+// (value descending, index ascending)
+__device__ __forceinline__ void vq_take(float& bv, int& bi, float ov, int oi) {
+  if (ov > bv || (ov == bv && oi < bi)) {
+    bv = ov;
+    bi = oi;
+  }
+}
+
+// The assignment: a block owns 64 rows of X, staged once in LDS ([64][D] bf16, 16-byte pieces XOR-swizzled by row & 7), and sweeps
+// the codebook in tiles of 256 codes, 64 per wave, read straight from global memory (each wave reads its own codes: no LDS round
+// trip, no barrier in the sweep).  MFMA A = codes, B = rows of X, so a lane holds D[code 4g + r][row c] (c = lane & 15,
+// g = lane >> 4): four codes of ONE row per accumulator, and the running (best, index) stays per lane.  A 64-wide k-chunk is two
+// MFMAs; a load instruction of a wave takes 64 contiguous bytes from each of 16 code rows (lane group g the 16 bytes at 16g).
+// The accumulation order of a score depends on D alone, never on the tile: equal columns give equal bits.
+// The code fragments of the next k-chunk are fetched under the current chunk's 32 MFMAs.
+__global__ __launch_bounds__(256) void vq_assign_kernel(const bf16_t* __restrict__ x, int ldx, const bf16_t* __restrict__ cbt, int ldc,
+                                                        const float* __restrict__ h, int* __restrict__ idx, bf16_t* __restrict__ xq,
+                                                        int ldq, float* __restrict__ score, int64_t M, int T, int D) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char vq_smem[];
+  u32x4* xs = (u32x4*)vq_smem;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  constexpr int RB = 4, ROWS = VQ_ROWS;      // RB row blocks of 16
+  const int64_t m0 = (int64_t)blockIdx.x * ROWS;
+  const int cpr = D / 8;       // 16-byte pieces per row (a multiple of 8)
+  for (int i = tid; i < ROWS * cpr; i += 256) {
+    const int r = i / cpr, p = i % cpr;
+    u32x4 v = {0, 0, 0, 0};
+    if (m0 + r < M) v = *(const u32x4*)(x + (m0 + r) * ldx + p * 8);
+    xs[r * cpr + (p ^ (r & 7))] = v;
+  }
+  __syncthreads();
+  float best[RB];
+  int bidx[RB];
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb) {
+    best[rb] = -INFINITY;
+    bidx[rb] = 0x7fffffff;
+  }
+  const int nk = D / 64;
+  for (int t0 = wid * 64; t0 < T; t0 += 256) {
+    f32x4 acc[RB][4];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const bf16_t* bp = cbt + (int64_t)(t0 + c) * ldc + g * 8;
+    u32x4 bcur[4][2], bnxt[4][2];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+      bcur[cb][0] = *(const u32x4*)(bp + (int64_t)cb * 16 * ldc);
+      bcur[cb][1] = *(const u32x4*)(bp + (int64_t)cb * 16 * ldc + 32);
+    }
+    for (int kc = 0; kc < nk; ++kc) {
+      if (kc + 1 < nk) {
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+          bnxt[cb][0] = *(const u32x4*)(bp + (int64_t)cb * 16 * ldc + (kc + 1) * 64);
+          bnxt[cb][1] = *(const u32x4*)(bp + (int64_t)cb * 16 * ldc + (kc + 1) * 64 + 32);
+        }
+      }
+      u32x4 a[RB][2];
+      const int p0 = kc * 8 + g;
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) {
+        const int r = rb * 16 + c;
+        a[rb][0] = xs[r * cpr + (p0 ^ (r & 7))];
+        a[rb][1] = xs[r * cpr + ((p0 + 4) ^ (r & 7))];
+      }
+      MFMA_PRIO(1);
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+          for (int cb = 0; cb < 4; ++cb)
+            acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bcur[cb][j]), __builtin_bit_cast(bf16x8, a[rb][j]),
+                                                                  acc[rb][cb], 0, 0, 0);
+      MFMA_PRIO(0);
+      if (kc + 1 < nk) {
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+          bcur[cb][0] = bnxt[cb][0];
+          bcur[cb][1] = bnxt[cb][1];
+        }
+      }
+    }
+    // ascending codes within the lane: cb, then the accumulator register; strict > keeps the first maximum
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+      const int k0 = t0 + cb * 16 + g * 4;
+      const f32x4 hv = *(const f32x4*)(h + k0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) {
+          const float sc = acc[rb][cb][e] - hv[e];
+          if (sc > best[rb]) {
+            best[rb] = sc;
+            bidx[rb] = k0 + e;
+          }
+        }
+    }
+  }
+  // the four lane groups of a row, then the four waves
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+    for (int o = 16; o <= 32; o <<= 1) {
+      const float ov = __shfl_xor(best[rb], o, 64);
+      const int oi = __shfl_xor(bidx[rb], o, 64);
+      vq_take(best[rb], bidx[rb], ov, oi);
+    }
+  __syncthreads();             // every wave has left the X tile: its storage carries the reduction from here on
+  float* redv = (float*)vq_smem;          // [4][ROWS]
+  int* redi = (int*)(redv + 4 * ROWS);    // [4][ROWS]
+  int* sidx = redi + 4 * ROWS;            // [ROWS]   (36 ROWS bytes in all: under the smallest tile, ROWS x 64 x 2)
+  if (g == 0) {
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) {
+      redv[wid * ROWS + rb * 16 + c] = best[rb];
+      redi[wid * ROWS + rb * 16 + c] = bidx[rb];
+    }
+  }
+  __syncthreads();
+  if (tid < ROWS) {
+    float bv = redv[tid];
+    int bi = redi[tid];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) vq_take(bv, bi, redv[w * ROWS + tid], redi[w * ROWS + tid]);
+    if (bi < 0 || bi >= T) bi = 0;        // no score compared above -inf (NaN rows): a valid code all the same
+    sidx[tid] = bi;
+    if (m0 + tid < M) {
+      idx[m0 + tid] = bi;
+      if (score) score[m0 + tid] = bv;
+    }
+  }
+  if (!xq) return;
+  __syncthreads();
+  for (int i = tid; i < ROWS * cpr; i += 256) {
+    const int r = i / cpr, p = i % cpr;
+    if (m0 + r < M) *(u32x4*)(xq + (m0 + r) * ldq + p * 8) = *(const u32x4*)(cbt + (int64_t)sidx[r] * ldc + p * 8);
+  }
+}
+extern "C" int dmi_vq_assign(const uint16_t* x, int ldx, const uint16_t* codebook_t, int ldc, const float* h, int32_t* idx, uint16_t* xq,
+                             int ldq, float* score, int64_t M, int T, int D, void* stream) {
+  DMI_REQUIRE(x && codebook_t && h && idx, "vq_assign: null pointer (x, codebook_t, h or idx)");
+  DMI_REQUIRE(M > 0, "vq_assign: M must be positive (M=%lld)", (long long)M);
+  DMI_REQUIRE(T > 0 && D > 0, "vq_assign: T and D must be positive (T=%d D=%d)", T, D);
+  DMI_REQUIRE(ldx >= D && ldx % 8 == 0, "vq_assign: ldx must be a multiple of 8 and at least D (ldx=%d D=%d)", ldx, D);
+  DMI_REQUIRE(ldc >= D && ldc % 8 == 0, "vq_assign: ldc must be a multiple of 8 and at least D (ldc=%d D=%d)", ldc, D);
+  DMI_REQUIRE(!xq || (ldq >= D && ldq % 8 == 0), "vq_assign: ldq must be a multiple of 8 and at least D (ldq=%d D=%d)", ldq, D);
+  DMI_REQUIRE(((((uintptr_t)x) | ((uintptr_t)codebook_t) | ((uintptr_t)h) | ((uintptr_t)xq)) & 15) == 0,
+              "vq_assign: x, codebook_t, h and xq must be 16-byte aligned");
+  if (D % 64 != 0 || D > VQ_MAX_D || T % 64 != 0 || T > VQ_MAX_T) {
+    dmi_set_error("vq_assign: needs D %% 64 == 0, D <= %d, T %% 64 == 0, T <= %d (D=%d T=%d)", VQ_MAX_D, VQ_MAX_T, D, T);
+    return DMI_ERR_UNSUPPORTED;
+  }
+  vq_assign_kernel<<<dim3((unsigned)cdiv64(M, VQ_ROWS)), dim3(256), VQ_ROWS * D * 2, (hipStream_t)stream>>>(x, ldx, codebook_t, ldc, h, idx,
+                                                                                                      xq, ldq, score, M, T, D);
+  DMI_CHECK_LAUNCH("vq_assign");
+  return DMI_OK;
+}
+
+// xq rows by index (decode_tokens); an id outside [0, T) gives a zero row and reads nothing
+__global__ __launch_bounds__(256) void vq_gather_kernel(const bf16_t* __restrict__ cbt, int ldc, const int* __restrict__ idx,
+                                                        bf16_t* __restrict__ out, int ldo, int64_t M, int T, int D) {
+  const int cpr = D / 8;
+  const int64_t total = M * cpr;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int p = (int)(i % cpr);
+    const int64_t m = i / cpr;
+    const int k = idx[m];
+    u32x4 v = {0, 0, 0, 0};
+    if (k >= 0 && k < T) v = *(const u32x4*)(cbt + (int64_t)k * ldc + p * 8);
+    *(u32x4*)(out + m * ldo + p * 8) = v;
+  }
+}
+extern "C" int dmi_vq_gather(const uint16_t* codebook_t, int ldc, const int32_t* idx, uint16_t* out, int ldo, int64_t M, int T, int D,
+                             void* stream) {
+  DMI_REQUIRE(codebook_t && idx && out, "vq_gather: null pointer");
+  DMI_REQUIRE(M > 0, "vq_gather: M must be positive (M=%lld)", (long long)M);
+  DMI_REQUIRE(T > 0 && D > 0 && D % 8 == 0, "vq_gather: T must be positive and D a positive multiple of 8 (T=%d D=%d)", T, D);
+  DMI_REQUIRE(ldc >= D && ldc % 8 == 0 && ldo >= D && ldo % 8 == 0, "vq_gather: ldc and ldo must be multiples of 8 and at least D (ldc=%d ldo=%d D=%d)", ldc, ldo, D);
+  DMI_REQUIRE(((((uintptr_t)codebook_t) | ((uintptr_t)out)) & 15) == 0, "vq_gather: codebook_t and out must be 16-byte aligned");
+  int64_t blocks = cdiv64(M * (D / 8), 256);
+  if (blocks > 16384) blocks = 16384;
+  vq_gather_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(codebook_t, ldc, idx, out, ldo, M, T, D);
+  DMI_CHECK_LAUNCH("vq_gather");
+  return DMI_OK;
+}
+
+// Lq: a thread sums the squares of its 16-byte pieces in order, wave_sum, four waves, then dmi_sum_f32 over the block partials
+#define VQ_LOSS_BLOCKS 1024
+__global__ __launch_bounds__(256) void vq_loss_kernel(const bf16_t* __restrict__ x, int ldx, const bf16_t* __restrict__ xq, int ldq,
+                                                      float* __restrict__ part, int64_t M, int D) {
+  __shared__ float sm[4];
+  const int cpr = D / 8;
+  const int64_t total = M * cpr;
+  float acc = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int p = (int)(i % cpr);
+    const int64_t m = i / cpr;
+    float a[8], b[8];
+    unpack8(*(const u32x4*)(x + m * ldx + p * 8), a);
+    unpack8(*(const u32x4*)(xq + m * ldq + p * 8), b);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float d = a[e] - b[e];
+      acc += d * d;
+    }
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+extern "C" int64_t dmi_vq_loss_workspace_bytes(void) { return VQ_LOSS_BLOCKS * 4; }
+extern "C" int dmi_vq_loss(const uint16_t* x, int ldx, const uint16_t* xq, int ldq, float* loss, int64_t M, int D, void* workspace,
+                           void* stream) {
+  DMI_REQUIRE(x && xq && loss && workspace, "vq_loss: null pointer");
+  DMI_REQUIRE(M > 0, "vq_loss: M must be positive (M=%lld)", (long long)M);
+  DMI_REQUIRE(D > 0 && D % 8 == 0, "vq_loss: D must be a positive multiple of 8 (D=%d)", D);
+  DMI_REQUIRE(ldx >= D && ldx % 8 == 0 && ldq >= D && ldq % 8 == 0, "vq_loss: ldx and ldq must be multiples of 8 and at least D (ldx=%d ldq=%d D=%d)", ldx, ldq, D);
+  DMI_REQUIRE(((((uintptr_t)x) | ((uintptr_t)xq) | ((uintptr_t)workspace)) & 15) == 0, "vq_loss: x, xq and workspace must be 16-byte aligned");
+  vq_loss_kernel<<<dim3(VQ_LOSS_BLOCKS), dim3(256), 0, (hipStream_t)stream>>>(x, ldx, xq, ldq, (float*)workspace, M, D);
+  DMI_CHECK_LAUNCH("vq_loss");
+  return dmi_sum_f32((const float*)workspace, VQ_LOSS_BLOCKS, (float)(1.0 / ((double)M * (double)D)), loss, stream);
+}
+
+// dX = bf16(d + a (X - xq)), a = 2 beta / (M D); a == 0 copies d (so that -0 stays -0)
+__global__ __launch_bounds__(256) void vq_bwd_x_kernel(const bf16_t* __restrict__ d, int ldd, const bf16_t* __restrict__ x, int ldx,
+                                                       const bf16_t* __restrict__ xq, int ldq, bf16_t* __restrict__ dx, int lddx,
+                                                       int64_t M, int D, float a) {
+  const int cpr = D / 8;
+  const int64_t total = M * cpr;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int p = (int)(i % cpr);
+    const int64_t m = i / cpr;
+    u32x4 dv = *(const u32x4*)(d + m * ldd + p * 8);
+    if (a != 0.f) {
+      float fd[8], fx[8], fq[8];
+      unpack8(dv, fd);
+      unpack8(*(const u32x4*)(x + m * ldx + p * 8), fx);
+      unpack8(*(const u32x4*)(xq + m * ldq + p * 8), fq);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) fd[e] = fd[e] + a * (fx[e] - fq[e]);
+      dv = pack8(fd);
+    }
+    *(u32x4*)(dx + m * lddx + p * 8) = dv;
+  }
+}
+extern "C" int dmi_vq_bwd_x(const uint16_t* d, int ldd, const uint16_t* x, int ldx, const uint16_t* xq, int ldq, uint16_t* dx, int lddx,
+                            int64_t M, int D, float beta, void* stream) {
+  DMI_REQUIRE(d && x && xq && dx, "vq_bwd_x: null pointer");
+  DMI_REQUIRE(M > 0, "vq_bwd_x: M must be positive (M=%lld)", (long long)M);
+  DMI_REQUIRE(D > 0 && D % 8 == 0, "vq_bwd_x: D must be a positive multiple of 8 (D=%d)", D);
+  DMI_REQUIRE(beta >= 0.f && beta <= 3.0e38f, "vq_bwd_x: beta must be finite and >= 0 (beta=%g)", (double)beta);
+  DMI_REQUIRE(ldd >= D && ldd % 8 == 0 && ldx >= D && ldx % 8 == 0 && ldq >= D && ldq % 8 == 0 && lddx >= D && lddx % 8 == 0,
+              "vq_bwd_x: ldd, ldx, ldq and lddx must be multiples of 8 and at least D (D=%d)", D);
+  DMI_REQUIRE(((((uintptr_t)d) | ((uintptr_t)x) | ((uintptr_t)xq) | ((uintptr_t)dx)) & 15) == 0, "vq_bwd_x: operands must be 16-byte aligned");
+  const float a = (float)(2.0 * (double)beta / ((double)M * (double)D));
+  int64_t blocks = cdiv64(M * (D / 8), 256);
+  if (blocks > 16384) blocks = 16384;
+  vq_bwd_x_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(d, ldd, x, ldx, xq, ldq, dx, lddx, M, D, a);
+  DMI_CHECK_LAUNCH("vq_bwd_x");
+  return DMI_OK;
+}
+
+// dC: no sort and no workspace.  A block owns eight codes, one per wave; every wave walks idx (512 rows per round, eight per lane,
+// the same lines for the eight waves of the block), ballots its code's rows and adds Cb[:,k] - X[m,:] for them in a fixed order
+// (element slot 0..7 of the round, then lane): lane p keeps the eight channels of piece p in registers.  A code nobody picked
+// keeps its zeros.  The eight columns go through LDS ([code][channel], conflict-free both ways) so that a row of the [D, T] gradient
+// is written 32 bytes at a time.
+__global__ __launch_bounds__(512) void vq_codebook_grad_kernel(const bf16_t* __restrict__ x, int ldx, const int* __restrict__ idx,
+                                                               const bf16_t* __restrict__ cbt, int ldc, float* __restrict__ dC,
+                                                               int64_t M, int T, int D, float scale) {
+  __shared__ float sm[8][VQ_MAX_D];      // [code of the block][channel]: a lane writes its 32 bytes, a thread reads one float per code
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int k = blockIdx.x * 8 + wid;           // T % 8 == 0
+  const bool active = lane < D / 8;
+  float cb[8], acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) cb[e] = acc[e] = 0.f;
+  if (active) unpack8(*(const u32x4*)(cbt + (int64_t)k * ldc + lane * 8), cb);
+  for (int64_t base = 0; base < M; base += 512) {
+    int v[8];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int64_t m4 = base + q * 256 + lane * 4;
+      if (m4 + 3 < M) {
+        const u32x4 t = *(const u32x4*)(idx + m4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[q * 4 + e] = (int)t[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[q * 4 + e] = (m4 + e < M) ? idx[m4 + e] : -1;
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      unsigned long long mask = __ballot(v[s] == k);
+      const int64_t row0 = base + (s >> 2) * 256 + (s & 3);
+      while (mask) {
+        const int b0 = __ffsll(mask) - 1;
+        mask &= mask - 1;
+        int b1 = -1;
+        if (mask) {
+          b1 = __ffsll(mask) - 1;
+          mask &= mask - 1;
+        }
+        if (active) {
+          float f0[8], f1[8];
+          const u32x4 r0 = *(const u32x4*)(x + (row0 + 4 * b0) * ldx + lane * 8);
+          u32x4 r1 = {0, 0, 0, 0};
+          if (b1 >= 0) r1 = *(const u32x4*)(x + (row0 + 4 * b1) * ldx + lane * 8);
+          unpack8(r0, f0);
+          unpack8(r1, f1);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[e] += cb[e] - f0[e];
+          if (b1 >= 0) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] += cb[e] - f1[e];
+          }
+        }
+      }
+    }
+  }
+  if (active) {
+    *(f32x4*)&sm[wid][lane * 8] = f32x4{acc[0] * scale, acc[1] * scale, acc[2] * scale, acc[3] * scale};
+    *(f32x4*)&sm[wid][lane * 8 + 4] = f32x4{acc[4] * scale, acc[5] * scale, acc[6] * scale, acc[7] * scale};
+  }
+  __syncthreads();
+  if (tid < D) {
+    float* dst = dC + (int64_t)tid * T + blockIdx.x * 8;
+    *(f32x4*)dst = f32x4{sm[0][tid], sm[1][tid], sm[2][tid], sm[3][tid]};
+    *(f32x4*)(dst + 4) = f32x4{sm[4][tid], sm[5][tid], sm[6][tid], sm[7][tid]};
+  }
+}
+extern "C" int64_t dmi_vq_codebook_grad_workspace_bytes(int64_t M, int T, int D) {
+  (void)M; (void)T; (void)D;
+  return 0;       // the ballot walk needs none; the query stays so that another method can have one
+}
+extern "C" int dmi_vq_codebook_grad(const uint16_t* x, int ldx, const int32_t* idx, const uint16_t* codebook_t, int ldc, float* dC,
+                                    int64_t M, int T, int D, void* workspace, void* stream) {
+  (void)workspace;
+  DMI_REQUIRE(x && idx && codebook_t && dC, "vq_codebook_grad: null pointer (x, idx, codebook_t or dC)");
+  DMI_REQUIRE(M > 0, "vq_codebook_grad: M must be positive (M=%lld)", (long long)M);
+  DMI_REQUIRE(T > 0 && D > 0, "vq_codebook_grad: T and D must be positive (T=%d D=%d)", T, D);
+  DMI_REQUIRE(ldx >= D && ldx % 8 == 0 && ldc >= D && ldc % 8 == 0, "vq_codebook_grad: ldx and ldc must be multiples of 8 and at least D (ldx=%d ldc=%d D=%d)", ldx, ldc, D);
+  DMI_REQUIRE(((((uintptr_t)x) | ((uintptr_t)idx) | ((uintptr_t)codebook_t) | ((uintptr_t)dC)) & 15) == 0,
+              "vq_codebook_grad: x, idx, codebook_t and dC must be 16-byte aligned");
+  if (D % 8 != 0 || D > VQ_MAX_D || T % 8 != 0 || T > VQ_MAX_T) {
+    dmi_set_error("vq_codebook_grad: needs D %% 8 == 0, D <= %d, T %% 8 == 0, T <= %d (D=%d T=%d)", VQ_MAX_D, VQ_MAX_T, D, T);
+    return DMI_ERR_UNSUPPORTED;
+  }
+  const float scale = (float)(2.0 / ((double)M * (double)D));
+  vq_codebook_grad_kernel<<<dim3((unsigned)(T / 8)), dim3(512), 0, (hipStream_t)stream>>>(x, ldx, idx, codebook_t, ldc, dC, M, T, D, scale);
+  DMI_CHECK_LAUNCH("vq_codebook_grad");
+  return DMI_OK;
+}

@@ -163,6 +163,15 @@ def _declare(L):
         "dmi_gumbel_softmax_bwd_kl": (I, [P, P, P, P, P, L64, I, F, P, F, P, P]),
         "dmi_elbo_loss": (I, [P, P, F, P, P, P]),
         "dmi_codebook_usage": (I, [P, P, P, P, P, L64, I, P, P]),
+        "dmi_vq_half_norms": (I, [P, I, P, P, I, I, P]),
+        "dmi_vq_assign": (I, [P, I, P, I, P, P, P, I, P, L64, I, I, P]),
+        "dmi_vq_scores_bias": (I, [P, P, L64, I, P]),
+        "dmi_vq_loss_workspace_bytes": (L64, []),
+        "dmi_vq_loss": (I, [P, I, P, I, P, L64, I, P, P]),
+        "dmi_vq_bwd_x": (I, [P, I, P, I, P, I, P, I, L64, I, F, P]),
+        "dmi_vq_codebook_grad_workspace_bytes": (L64, [L64, I, I]),
+        "dmi_vq_codebook_grad": (I, [P, I, P, P, I, P, L64, I, I, P, P]),
+        "dmi_vq_gather": (I, [P, I, P, P, I, L64, I, I, P]),
         "dmi_comm_load": (I, [c_char_p]),
         "dmi_comm_unique_id_bytes": (I, []),
         "dmi_comm_unique_id": (I, [P]),
@@ -1035,6 +1044,50 @@ def codebook_usage(logits, rowstat, index, qsum, counts, M, T, ws):
     _dev(logits, rowstat, index, qsum, counts, ws)
     _check(lib().dmi_codebook_usage(_p(logits), _p(rowstat), _p(index), _p(qsum), _p(counts), M, T, _p(ws), _stream()),
            "codebook_usage")
+
+
+def vq_half_norms(h, T, D, codebook_t=None, ldc=0, codebook_f32=None):
+    """h[k] = 1/2 sum_j c[j,k]^2 from the bf16 transpose [T, ldc] or from the fp32 masters [D, T] (exactly one)"""
+    _dev(h, codebook_t, codebook_f32)
+    _check(lib().dmi_vq_half_norms(_p(codebook_t), ldc, _p(codebook_f32), _p(h), T, D, _stream()), "vq_half_norms")
+
+
+def vq_assign(x, ldx, codebook_t, ldc, h, idx, xq, ldq, score, M, T, D):
+    _dev(x, codebook_t, h, idx, xq, score)
+    _check(lib().dmi_vq_assign(_p(x), ldx, _p(codebook_t), ldc, _p(h), _p(idx), _p(xq), ldq, _p(score), M, T, D, _stream()), "vq_assign")
+
+
+def vq_scores_bias(scores, h, M, T):
+    _dev(scores, h)
+    _check(lib().dmi_vq_scores_bias(_p(scores), _p(h), M, T, _stream()), "vq_scores_bias")
+
+
+def vq_loss_workspace_bytes():
+    return lib().dmi_vq_loss_workspace_bytes()
+
+
+def vq_loss(x, ldx, xq, ldq, loss, M, D, ws):
+    _dev(x, xq, loss, ws)
+    _check(lib().dmi_vq_loss(_p(x), ldx, _p(xq), ldq, _p(loss), M, D, _p(ws), _stream()), "vq_loss")
+
+
+def vq_bwd_x(d, ldd, x, ldx, xq, ldq, dx, lddx, M, D, beta):
+    _dev(d, x, xq, dx)
+    _check(lib().dmi_vq_bwd_x(_p(d), ldd, _p(x), ldx, _p(xq), ldq, _p(dx), lddx, M, D, float(beta), _stream()), "vq_bwd_x")
+
+
+def vq_codebook_grad_workspace_bytes(M, T, D):
+    return lib().dmi_vq_codebook_grad_workspace_bytes(M, T, D)
+
+
+def vq_codebook_grad(x, ldx, idx, codebook_t, ldc, dC, M, T, D, ws=None):
+    _dev(x, idx, codebook_t, dC, ws)
+    _check(lib().dmi_vq_codebook_grad(_p(x), ldx, _p(idx), _p(codebook_t), ldc, _p(dC), M, T, D, _p(ws), _stream()), "vq_codebook_grad")
+
+
+def vq_gather(codebook_t, ldc, idx, out, ldo, M, T, D):
+    _dev(codebook_t, idx, out)
+    _check(lib().dmi_vq_gather(_p(codebook_t), ldc, _p(idx), _p(out), ldo, M, T, D, _stream()), "vq_gather")
 
 
 def mse_workspace_bytes():

@@ -10,6 +10,7 @@ from .estimator import CheckpointSaverHook, EstimatorSpec, latest_checkpoint
 from .utils import ModeKeys, SummaryWriter, mode_to_str
 from .vae_tf import DiscreteVAE
 from .vae_tf.kl import kl_log_lines, resolve_kl_options
+from .vae_tf.vq import resolve_vq_options, vq_log_lines
 
 
 def _dist_info():
@@ -30,6 +31,9 @@ def _stat_scalars(model, loss):
     """loss_recon, loss_kl, kl_weight (beta_t of the forward just run) and the codebook statistics, as floats: what the train
     summaries and eval_metrics carry with "codebook_stats" on or kl_loss_weight > 0 (one DiscreteVAE.codebook_stats() call)"""
     st = model.codebook_stats()
+    if model.vq_on:      # vae_tf/vq.py STAT_SCALARS: no posterior, so no kl and no perplexity_soft
+        return dict(loss_recon=float(model.loss_recon[0]), loss_vq=float(model.loss_vq[0]), perplexity_hard=st["perplexity_hard"],
+                    codes_used_frac=st["codes_used_frac"])
     on = model.kl_weight > 0
     return dict(loss_recon=float(model.loss_recon[0]) if on else float(loss), loss_kl=st["kl"],
                 kl_weight=float(model.kl_weight_t) if on else 0.0, perplexity_soft=st["perplexity_soft"],
@@ -38,6 +42,7 @@ def _stat_scalars(model, loss):
 
 def _build(params, mode_str):
     kl = resolve_kl_options(params)       # ValueError naming the key, before any device work
+    vq = resolve_vq_options(params)
     world, rank, pg, comm = _dist_info()
     H = params["dataset"]["image_size"]
     gbs = params[f"{mode_str}_batch_size"]
@@ -53,8 +58,8 @@ def _build(params, mode_str):
         use_bf16=params.get("use_bf16") or False,
         stack_factor=params.get("stack_factor") or 1,
         dimensions=H, batch_size=gbs // world, mode=mode_str, process_group=pg, world_size=world, comm=comm,
-        kl_loss_weight=kl.kl_loss_weight, kl_anneal_steps=kl.kl_anneal_steps)
-    for line in kl_log_lines(kl, model.num_tokens, model.grid):
+        kl_loss_weight=kl.kl_loss_weight, kl_anneal_steps=kl.kl_anneal_steps, quantizer=vq.quantizer, vq_commitment=vq.vq_commitment)
+    for line in vq_log_lines(vq, model.num_tokens, model.grid, model.n_hid) or kl_log_lines(kl, model.num_tokens, model.grid):
         logging.getLogger("dalle_mtf_amd").info("%s %s", mode_str, line)
     ck = latest_checkpoint(params["model_path"]) if params.get("model_path") else None
     if ck is not None:
@@ -81,7 +86,7 @@ def vae_model_fn(features, labels, mode, params):
         raise NotImplementedError
     assert mode in (ModeKeys.TRAIN, ModeKeys.EVAL)
     kl = resolve_kl_options(params)
-    stats_on = kl.codebook_stats or kl.kl_loss_weight > 0
+    stats_on = kl.codebook_stats or kl.kl_loss_weight > 0 or resolve_vq_options(params).quantizer == "vq"
     key = f"_vae_state_{mode_str}"
     if params.get(key) is None:
         if mode == ModeKeys.EVAL and params.get("_vae_state_train") is not None and \

@@ -25,10 +25,12 @@ import torch
 
 import dalle_hip as dh
 from ..dp import GradReducer
-from .kl import kl_weight_at, resolve_kl_options, usage_stats
+from .kl import _perplexity, kl_weight_at, resolve_kl_options, usage_stats
+from .vq import check_checkpoint, resolve_vq_options
 
 IMG_CP = 8     # padded image channels
 OUT_CP = 64    # padded reconstruction channels
+VQ_MAX_WIDTH = 512           # widest code of dmi_vq_assign / dmi_vq_codebook_grad
 GUMBEL_MAX_TOKENS = 4096    # largest codebook of dmi_gumbel_softmax_fwd (eight 8-column chunks per lane)
 ALIGN = 128
 WS_POOL = 7    # weight gradients in flight before their slab reduces are flushed (2 reduce items each, 16 per batched launch)
@@ -70,11 +72,17 @@ class _Conv:
 class DiscreteVAE:
     def __init__(self, num_tokens, dimensions, convblocks, dim=512, hidden_dim=64, input_channels=3, recompute_grad=False,
                  use_bf16=False, stack_factor=1, batch_size=32, mode="train", device="cuda", process_group=None, world_size=1,
-                 comm=None, kl_loss_weight=0.0, kl_anneal_steps=None):
+                 comm=None, kl_loss_weight=0.0, kl_anneal_steps=None, quantizer=None, vq_commitment=None):
         kl = resolve_kl_options(dict(kl_loss_weight=kl_loss_weight, kl_anneal_steps=kl_anneal_steps))   # ValueError before any device work
+        vq = resolve_vq_options(dict(quantizer=quantizer, vq_commitment=vq_commitment, kl_loss_weight=kl_loss_weight,
+                                     kl_anneal_steps=kl_anneal_steps))
         if num_tokens > GUMBEL_MAX_TOKENS:
             raise ValueError(f"num_tokens = {num_tokens}: the Gumbel-softmax kernel (dmi_gumbel_softmax_fwd, one wave per row) "
                              f"handles codebooks of at most {GUMBEL_MAX_TOKENS} tokens")
+        n_hid = tuple(convblocks[-1])[1]
+        if vq.quantizer == "vq" and (n_hid % 64 != 0 or not 64 <= n_hid <= VQ_MAX_WIDTH):
+            raise ValueError(f"quantizer = 'vq': the code width n_hid = {n_hid} (the last convblock's channels) must be a multiple of 64 "
+                             f"between 64 and {VQ_MAX_WIDTH} (dmi_vq_assign keeps 64 rows of that width in LDS)")
         if not torch.cuda.is_available():
             raise dh.DalleHipError("DiscreteVAE needs a HIP device (MI355X); there is no CPU fallback")
         dh.lib()
@@ -109,6 +117,8 @@ class DiscreteVAE:
         self.kl_weight, self.kl_anneal_steps = kl.kl_loss_weight, kl.kl_anneal_steps
         self.kl_weight_t = self.kl_weight if kl.kl_anneal_steps is None else 0.0
         self.rowstat = self.loss_recon = self.loss_kl = self.ws_kl = self._usage = None
+        # "vq": nearest-code bottleneck, loss = recon + (1 + beta) Lq (vae_tf/vq.py); "gumbel" = the reference's, unchanged
+        self.quantizer, self.vq_on, self.vq_beta = vq.quantizer, vq.quantizer == "vq", vq.vq_commitment
         self._kl_fresh = False       # rowstat / loss_kl describe the logits buffer as it stands
         self._graphs, self._graph_warm, self._dyn_on, self._img_static = {}, False, False, None
         self._build_graph()
@@ -170,7 +180,8 @@ class DiscreteVAE:
         self.p, self.g = torch.zeros(n, **f32), torch.zeros(n, **f32)
         self.m, self.v = torch.zeros(n, **f32), torch.zeros(n, **f32)
         self.pb = torch.zeros(n, **b16)
-        self.gc2 = torch.zeros(self.n_hid * self.num_tokens, **f32)  # second contribution to the tied codebook gradient
+        # second contribution to the tied codebook gradient (the VQ codebook gradient has one source)
+        self.gc2 = None if self.vq_on else torch.zeros(self.n_hid * self.num_tokens, **f32)
         # derived weight copies: views of ONE flat buffer, so that the per-step refresh is two batched launches
         # (dmi_transpose_bf16_batch + dmi_weight_gather_batch) instead of one launch per copy
         self.wf, self.wd, self.wp = {}, {}, {}
@@ -235,10 +246,18 @@ class DiscreteVAE:
                 self.act_out.append(torch.empty(B * c.Ho * c.Wo, c.cout, **b16))
         Mg = B * self.grid * self.grid
         self.Mg = Mg
-        self.logits = torch.empty(Mg, self.num_tokens, **f32)
-        self.u = torch.empty(Mg, self.num_tokens, **f32)
-        self.y = torch.empty(Mg, self.num_tokens, **b16)
-        self.y_soft = torch.empty(Mg, self.num_tokens, **b16)
+        if self.vq_on:      # nothing of size [M, T] in the training step; logits come into being with the first return_logits call
+            self.logits = self.u = self.y = self.y_soft = None
+            self.h = torch.zeros(self.num_tokens, **f32)              # half-norms of the bf16 codebook (refresh_compute_copies)
+            self.h32 = None                                           # ... of the fp32 masters (encode_logits_fp32)
+            self.loss_recon, self.loss_vq = torch.zeros(1, **f32), torch.zeros(1, **f32)
+            self.ws_vq = torch.empty(int(max(dh.vq_loss_workspace_bytes(), dh.vq_codebook_grad_workspace_bytes(Mg, self.num_tokens, self.n_hid)))
+                                     + 1024, dtype=torch.uint8, device=dev)
+        else:
+            self.logits = torch.empty(Mg, self.num_tokens, **f32)
+            self.u = torch.empty(Mg, self.num_tokens, **f32)
+            self.y = torch.empty(Mg, self.num_tokens, **b16)
+            self.y_soft = torch.empty(Mg, self.num_tokens, **b16)
         self.index = torch.empty(Mg, dtype=torch.int32, device=dev)
         self.xdec = torch.empty(Mg, self.n_hid, **b16)
         self.loss = torch.zeros(1, **f32)
@@ -248,8 +267,8 @@ class DiscreteVAE:
         self.ga = torch.empty(max_act, **b16)
         self.gb = torch.empty(max_act, **b16)
         self.gc = torch.empty(max_act, **b16)
-        self.dy = torch.empty(Mg, self.num_tokens, **b16)
-        self.dlogits = torch.empty(Mg, self.num_tokens, **b16)
+        self.dy = None if self.vq_on else torch.empty(Mg, self.num_tokens, **b16)
+        self.dlogits = None if self.vq_on else torch.empty(Mg, self.num_tokens, **b16)
         wsz = 1 << 20
         for c in self.convs:
             M_out = B * c.Ho * c.Wo
@@ -388,6 +407,8 @@ class DiscreteVAE:
             dh.weight_gather_batch(self.pb, self.wcopies, T["ga"], T["ga"].shape[0], T["blocks"])
         for name, kind, R, Rp, C in T["padded"]:
             dh.transpose_padded(self.view(self.pb, name + "/kernel"), getattr(self, kind)[name], R, Rp, C)
+        if self.vq_on:
+            dh.vq_half_norms(self.h, self.num_tokens, self.n_hid, codebook_t=self.codebook_t, ldc=self.n_hid)
 
     # ------------------------------------------------------------------ conv building blocks
     def _w(self, name):
@@ -480,6 +501,8 @@ class DiscreteVAE:
                 x = self.act_out[i + 1]
                 i += 2
         self.x_enc = x
+        if self.vq_on:
+            return self._forward_vq(return_recon_loss, return_logits, need_grad)
         dh.gemm_nt(x, self.n_hid, self.codebook_t, self.n_hid, self.logits, self.num_tokens, self.Mg, self.num_tokens, self.n_hid,
                    dh.GEMM_OUT_F32)
         self._kl_fresh = False
@@ -509,12 +532,41 @@ class DiscreteVAE:
             dh.elbo_loss(self.loss_recon, self.loss_kl, self.loss, self.kl_weight_t, kl_weight_dev=self._kl_dev())
         return self.loss[0], self.reconstruction()
 
+    def _forward_vq(self, return_recon_loss, return_logits, need_grad):
+        """the rest of forward() under "quantizer": "vq": dmi_vq_assign (index, and xq straight into the decoder's input), decoder,
+        dmi_mse_loss, dmi_vq_loss, loss = recon + (1 + beta) Lq.  return_logits: the scores s = x . C - h as [B, g, g, T] fp32, whose
+        arg-max is the code (the logits product, then dmi_vq_scores_bias)"""
+        B, T, nh, Mg = self.B, self.num_tokens, self.n_hid, self.Mg
+        if return_logits:
+            self._logits_buffer()
+            dh.gemm_nt(self.x_enc, nh, self.codebook_t, nh, self.logits, T, Mg, T, nh, dh.GEMM_OUT_F32)
+            dh.vq_scores_bias(self.logits, self.h, Mg, T)
+            return self.logits.view(B, self.grid, self.grid, T)
+        dh.vq_assign(self.x_enc, nh, self.codebook_t, nh, self.h, self.index, self.xdec, nh, None, Mg, T, nh)
+        x = self._decoder_from_xdec()
+        if not return_recon_loss:
+            return self.reconstruction()
+        need_grad = (self.mode == "train") if need_grad is None else need_grad
+        dh.mse_loss(self.img_net, x, self.ga if need_grad else None, self.loss_recon, B * self.Hs * self.Hs, self.c_st, OUT_CP, 1.0, self.ws)
+        dh.vq_loss(self.x_enc, nh, self.xdec, nh, self.loss_vq, Mg, nh, self.ws_vq)
+        dh.elbo_loss(self.loss_recon, self.loss_vq, self.loss, 1.0 + self.vq_beta)
+        return self.loss[0], self.reconstruction()
+
+    def _logits_buffer(self):
+        if self.logits is None:
+            self.logits = torch.empty(self.Mg, self.num_tokens, dtype=torch.float32, device=self.dev)
+
     def _decoder_from_y(self):
         """decoder (vae_tf/models.py:123-163) on self.y [Mg, num_tokens] (soft / hard one-hot): y @ codebook^T, then per reversed
         block a 4x4 s2 conv-transpose and the residual stacks, final 1x1 conv -> self.out_pad"""
         convs = self.convs
         dh.gemm_nt(self.y, self.num_tokens, self._w("codebook/codebook"), self.num_tokens, self.xdec, self.n_hid, self.Mg, self.n_hid,
                    self.num_tokens)
+        return self._decoder_from_xdec()
+
+    def _decoder_from_xdec(self):
+        """the decoder's convolutions on self.xdec [Mg, n_hid] -> self.out_pad"""
+        convs = self.convs
         x = self.xdec
         i = self.n_enc
         while i < len(convs):
@@ -538,6 +590,10 @@ class DiscreteVAE:
         The sampling half the reference leaves unfinished (predict raises upstream, src/model_fns.py:135-136)."""
         tok = tokens.to(device=self.dev, dtype=torch.int64).reshape(self.Mg)
         assert int(tok.min()) >= 0 and int(tok.max()) < self.num_tokens
+        if self.vq_on:       # the code itself: rows of codebook_t by index
+            dh.vq_gather(self.codebook_t, self.n_hid, tok.to(torch.int32), self.xdec, self.n_hid, self.Mg, self.num_tokens, self.n_hid)
+            self._decoder_from_xdec()
+            return self.reconstruction()
         self.y.zero_()
         self.y.scatter_(1, tok.view(-1, 1), 1.0)       # index plumbing: the one-hot the hard Gumbel path would produce
         self._decoder_from_y()
@@ -564,6 +620,7 @@ class DiscreteVAE:
             self._f32 = dict(x=torch.empty(B * self.Hs * self.Hs, self.img_cp, dtype=torch.float32, device=dev),
                              a=[torch.empty(mx, dtype=torch.float32, device=dev) for _ in range(3)])
         f = self._f32
+        self._logits_buffer()
         dh.space_to_depth_f32(img, f["x"], B, self.Hs, self.Hs, self.num_ch, self.stack_factor, self.img_cp)
         x, free = f["x"], list(f["a"])
 
@@ -588,8 +645,15 @@ class DiscreteVAE:
                 free.extend([h, x])
                 x = out
                 i += 2
+        if self.vq_on:
+            self.x_enc_f32 = x   # fp32 [Mg, n_hid] at the front of one of the path's scratch buffers, until its next call (read by the tests)
         dh.conv2d_f32(x, self.Mg, 1, 1, self.n_hid, 1, 1, 1, [(0, 0)], self.view(self.p, "codebook/codebook"), None, None,
                       self.logits, self.num_tokens)
+        if self.vq_on:       # s = x . C - h, both from the fp32 masters
+            if self.h32 is None:
+                self.h32 = torch.empty(self.num_tokens, dtype=torch.float32, device=dev)
+            dh.vq_half_norms(self.h32, self.num_tokens, self.n_hid, codebook_f32=self.view(self.p, "codebook/codebook"))
+            dh.vq_scores_bias(self.logits, self.h32, self.Mg, self.num_tokens)
         self._kl_fresh = False
         return self.logits.view(B, self.grid, self.grid, self.num_tokens)
 
@@ -731,7 +795,15 @@ class DiscreteVAE:
                     spare[0], d = d, nd
                 i -= 1
             ready_down_to(self.offset[lowest.name + "/kernel"])
-            if i == self.n_enc - 1:
+            if i == self.n_enc - 1 and self.vq_on:
+                # ---- VQ bottleneck: straight-through d plus the commitment gradient to the encoder, the codebook loss to the codebook
+                T, nh, Mg = self.num_tokens, self.n_hid, self.Mg
+                nd = spare[0]
+                dh.vq_bwd_x(d, nh, self.x_enc, nh, self.xdec, nh, nd, nh, Mg, nh, self.vq_beta)
+                dh.vq_codebook_grad(self.x_enc, nh, self.index, self.codebook_t, nh, self._gv("codebook/codebook"), Mg, T, nh, self.ws_vq)
+                spare[0], d = d, nd
+                ready_down_to(self.offset["codebook/codebook"])
+            elif i == self.n_enc - 1:
                 # ---- tied codebook + gumbel (between decoder and encoder); d = gradient wrt xdec [Mg, n_hid]
                 T, nh, Mg = self.num_tokens, self.n_hid, self.Mg
                 dh.gemm_tn(d, nh, self.y, T, self.gc2, Mg, nh, T, self.ws)                               # dC from x_dec = y C^T
@@ -793,7 +865,9 @@ class DiscreteVAE:
         if self._img_static is None:
             self._img_static = torch.empty(self.B, self.H, self.W, self.num_ch, dtype=torch.float32, device=self.dev)
         self._img_static.copy_(img.to(dtype=torch.float32), non_blocking=True)
-        if noise is None:
+        if self.vq_on:
+            hard_gumbel = True       # accepted and ignored: one graph
+        elif noise is None:
             self.u.uniform_(1e-9, 1.0)
         else:
             self.u.copy_(noise.to(self.dev).reshape(self.Mg, self.num_tokens))
@@ -841,6 +915,14 @@ class DiscreteVAE:
         num_tokens.  dmi_codebook_kl_fwd (unless the forward ran it) and dmi_codebook_usage; the two entropies over [num_tokens]
         are taken on the host in float64.  One device-to-host copy."""
         T, Mg = self.num_tokens, self.Mg
+        if self.vq_on:       # the picks alone: there is no posterior, so no kl and no perplexity_soft
+            if self._usage is None:
+                self._usage = dict(counts=torch.empty(T, dtype=torch.int32, device=self.dev))
+                self.ws_kl = torch.empty(int(dh.codebook_kl_workspace_bytes(Mg, T)) + 1024, dtype=torch.uint8, device=self.dev)
+            dh.codebook_usage(None, None, self.index, None, self._usage["counts"], Mg, T, self.ws_kl)
+            counts = self._usage["counts"].cpu().numpy()
+            used = int((counts > 0).sum())
+            return dict(perplexity_hard=_perplexity(counts), codes_used=used, codes_used_frac=used / T)
         self._kl_buffers()
         if self._usage is None:
             self._usage = dict(qsum=torch.empty(T, dtype=torch.float32, device=self.dev),
@@ -856,10 +938,14 @@ class DiscreteVAE:
 
     def state_dict(self):
         # reference-named variables as plain tensors in a plain dict: loadable with torch.load(weights_only=True)
-        return {"vae_variables": {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in self.export_reference().items()},
-                "m": self.m.detach().cpu(), "v": self.v.detach().cpu(), "global_step": self.global_step}
+        sd = {"vae_variables": {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in self.export_reference().items()},
+              "m": self.m.detach().cpu(), "v": self.v.detach().cpu(), "global_step": self.global_step}
+        if self.vq_on:       # only when on: a checkpoint without the key is a Gumbel one
+            sd["quantizer"] = "vq"
+        return sd
 
     def load_state_dict(self, sd):
+        check_checkpoint(self.quantizer, sd)
         self.load_reference_params({k: (v.numpy() if torch.is_tensor(v) else np.asarray(v))
                                     for k, v in sd["vae_variables"].items()})
         if "m" in sd:

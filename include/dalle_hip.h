@@ -679,6 +679,40 @@ int dmi_gumbel_softmax_bwd_kl(const uint16_t* dy, const uint16_t* y_soft, const 
 int dmi_elbo_loss(const float* recon, const float* kl, float kl_weight, const float* kl_weight_dev, float* loss, void* stream);
 int dmi_codebook_usage(const float* logits, const float* rowstat, const int32_t* index, float* qsum, int32_t* counts,
                        int64_t M, int T, void* workspace, void* stream);
+/* Vector-quantised bottleneck (project extension; DESIGN.md §4 "VAE: vector quantisation").  X bf16 [M, ldx] (D channels),
+ * codebook_t bf16 [T, ldc] (code k = row k: the transpose of the [D, T] codebook), h fp32 [T] the half-norms:
+ *   s[m,k] = sum_j X[m,j] codebook_t[k,j] - h[k] (fp32)   idx[m] = lowest k among the maxima of s[m,:]   xq[m,:] = codebook_t[idx[m],:]
+ * All: stream-ordered, no allocation, no float atomics (fixed summation orders: two runs give equal bits), rows indexed in 64 bits,
+ * rows >= M never written, operands 16-byte aligned, every ld a multiple of 8 and >= D.  DMI_ERR_INVALID with a message naming
+ * the argument, before any launch; DMI_ERR_UNSUPPORTED for a shape outside a kernel's range.
+ *   dmi_vq_half_norms     h[k] = 1/2 sum_j c[j,k]^2 in fp32, from exactly one of codebook_t (bf16 [T, ldc], D % 8 == 0, D <= 512) and
+ *                         codebook_f32 (the fp32 masters [D, T], for the exact-fp32 tokenising path).
+ *   dmi_vq_assign         the scores product on v_mfma_f32_16x16x32_bf16 with the arg-max in its epilogue: idx int32 [M], xq bf16
+ *                         [M, ldq] (nullable), score fp32 [M] = the winning s (nullable); nothing of size [M, T] is written.  The fp32
+ *                         score of (m, k) depends on row m and column k alone, so equal columns tie and the lower index wins.
+ *                         Supported: D % 64 == 0, 64 <= D <= 512, T % 64 == 0, T <= 4096, any M >= 1.
+ *   dmi_vq_scores_bias    scores[m,k] -= h[k] on fp32 [M, T] (T % 4 == 0): turns the logits product into s when DALL-E tokenises.
+ *   dmi_vq_loss           loss[0] = Lq = (1/(M D)) sum_m ||X[m] - xq[m]||^2; workspace: dmi_vq_loss_workspace_bytes() bytes.
+ *   dmi_vq_bwd_x          dx = bf16(d + (2 beta/(M D)) (X - xq)) (difference, product and sum in fp32, one bf16 rounding); beta by
+ *                         value, finite and >= 0; beta = 0 gives d's bits.
+ *   dmi_vq_codebook_grad  dC fp32 [D, T]: dC[:,k] = (2/(M D)) sum_{m: idx[m]=k} (codebook_t[k,:] - X[m,:]); a code nobody picked gets
+ *                         exactly 0; an idx outside [0, T) contributes nothing.  D % 8 == 0, D <= 512, T % 8 == 0, T <= 4096.
+ *                         workspace: dmi_vq_codebook_grad_workspace_bytes(M, T, D) bytes (0 today: workspace may then be null).
+ *   dmi_vq_gather         out[m,:] = codebook_t[idx[m],:]; an idx outside [0, T) gives a zero row and reads nothing. */
+int dmi_vq_half_norms(const uint16_t* codebook_t, int ldc, const float* codebook_f32, float* h, int T, int D, void* stream);
+int dmi_vq_assign(const uint16_t* x, int ldx, const uint16_t* codebook_t, int ldc, const float* h, int32_t* idx, uint16_t* xq,
+                  int ldq, float* score, int64_t M, int T, int D, void* stream);
+int dmi_vq_scores_bias(float* scores, const float* h, int64_t M, int T, void* stream);
+int64_t dmi_vq_loss_workspace_bytes(void);
+int dmi_vq_loss(const uint16_t* x, int ldx, const uint16_t* xq, int ldq, float* loss, int64_t M, int D, void* workspace,
+                void* stream);
+int dmi_vq_bwd_x(const uint16_t* d, int ldd, const uint16_t* x, int ldx, const uint16_t* xq, int ldq, uint16_t* dx, int lddx,
+                 int64_t M, int D, float beta, void* stream);
+int64_t dmi_vq_codebook_grad_workspace_bytes(int64_t M, int T, int D);
+int dmi_vq_codebook_grad(const uint16_t* x, int ldx, const int32_t* idx, const uint16_t* codebook_t, int ldc, float* dC,
+                         int64_t M, int T, int D, void* workspace, void* stream);
+int dmi_vq_gather(const uint16_t* codebook_t, int ldc, const int32_t* idx, uint16_t* out, int ldo, int64_t M, int T, int D,
+                  void* stream);
 
 
 /* ---- input format (host only): CRC-32C (Castagnoli) of a TFRecord length header / payload, as tf.data.TFRecordDataset
