@@ -1222,3 +1222,272 @@ extern "C" int dmi_vq_codebook_grad(const uint16_t* x, int ldx, const int32_t* i
   DMI_CHECK_LAUNCH("vq_codebook_grad");
   return DMI_OK;
 }
+
+// ------------------------------------------------------------------ EMA codebook (DESIGN.md §4 "VAE: EMA codebook and restarts")
+// Cluster sums s[k] = sum_{idx[m]=k} X[m] and counts n[k].  The ballot walk of vq_codebook_grad_kernel, cut into row chunks of
+// VQ_CS_CHUNK: block (x, y) owns eight codes (one per wave) and the rows [y CHUNK, (y+1) CHUNK); a wave ballots its code's rows in
+// row order and adds them in that order, up to four row loads in flight, lane p holding the eight channels of piece p.  The next
+// round's idx is loaded before this round's rows.  One chunk: sums / counts are written at once, [T, D] row-major, a row per wave.
+// More chunks: partial sums go to the workspace ([chunk][T][D], a code the chunk does not hold is not written) and
+// cluster_sums_combine_kernel adds them in chunk order, skipping the chunks whose count is 0.  Fixed order, no float atomics.
+#define VQ_CS_CHUNK 4096
+#define VQ_CS_MAX_CHUNKS 8
+__device__ __forceinline__ void cluster_load_idx(const int* __restrict__ idx, int64_t base, int64_t end, int lane, int* v) {
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int64_t m4 = base + q * 256 + lane * 4;
+    if (m4 + 3 < end) {
+      const u32x4 t = *(const u32x4*)(idx + m4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[q * 4 + e] = (int)t[e];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[q * 4 + e] = (m4 + e < end) ? idx[m4 + e] : -1;
+    }
+  }
+}
+__global__ __launch_bounds__(512) void cluster_sums_walk_kernel(const bf16_t* __restrict__ x, int ldx, const int* __restrict__ idx,
+                                                              float* __restrict__ out, int* __restrict__ cnt, int64_t M, int T, int D,
+                                                              int64_t rows_per_chunk, int skip_empty) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int k = blockIdx.x * 8 + wid;           // T % 8 == 0
+  const bool active = lane < D / 8;
+  const int64_t begin = (int64_t)blockIdx.y * rows_per_chunk;       // a multiple of 512: the 16-byte idx loads stay aligned
+  const int64_t end = begin + rows_per_chunk < M ? begin + rows_per_chunk : M;
+  float acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+  int n = 0;
+  int v[8], nv[8];
+  cluster_load_idx(idx, begin, end, lane, v);
+  for (int64_t base = begin; base < end; base += 512) {
+    if (base + 512 < end) cluster_load_idx(idx, base + 512, end, lane, nv);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      unsigned long long mask = __ballot(v[s] == k);
+      n += __popcll(mask);
+      const int64_t row0 = base + (s >> 2) * 256 + (s & 3);
+      while (mask) {
+        int b[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          b[j] = -1;
+          if (mask) {
+            b[j] = __ffsll(mask) - 1;
+            mask &= mask - 1;
+          }
+        }
+        if (active) {
+          u32x4 r[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            r[j] = u32x4{0, 0, 0, 0};
+            if (b[j] >= 0) r[j] = *(const u32x4*)(x + (row0 + 4 * b[j]) * ldx + lane * 8);
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (b[j] >= 0) {
+              float f[8];
+              unpack8(r[j], f);
+#pragma unroll
+              for (int e = 0; e < 8; ++e) acc[e] += f[e];
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 8; ++s) v[s] = nv[s];
+  }
+  if (lane == 0) cnt[(int64_t)blockIdx.y * T + k] = n;
+  if (active && !(skip_empty && n == 0)) {
+    float* dst = out + ((int64_t)blockIdx.y * T + k) * D + lane * 8;
+    *(f32x4*)dst = f32x4{acc[0], acc[1], acc[2], acc[3]};
+    *(f32x4*)(dst + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+  }
+}
+// one wave per code: sums[k] = partial[0][k] + partial[1][k] + ... over the chunks that hold the code, counts[k] = their total
+__global__ __launch_bounds__(256) void cluster_sums_combine_kernel(const float* __restrict__ part, const int* __restrict__ pcnt,
+                                                                 float* __restrict__ sums, int* __restrict__ counts, int T, int D, int P) {
+  const int lane = threadIdx.x & 63, k = blockIdx.x * 4 + (threadIdx.x >> 6);      // T % 8 == 0
+  const bool active = lane < D / 8;
+  float acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+  int n = 0;
+  for (int p = 0; p < P; ++p) {
+    const int c = pcnt[(int64_t)p * T + k];
+    n += c;
+    if (c > 0 && active) {
+      const float* src = part + ((int64_t)p * T + k) * D + lane * 8;
+      const f32x4 a = *(const f32x4*)src, b = *(const f32x4*)(src + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc[e] += a[e];
+        acc[4 + e] += b[e];
+      }
+    }
+  }
+  if (lane == 0) counts[k] = n;
+  if (active) {
+    float* dst = sums + (int64_t)k * D + lane * 8;
+    *(f32x4*)dst = f32x4{acc[0], acc[1], acc[2], acc[3]};
+    *(f32x4*)(dst + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+  }
+}
+static inline int cluster_chunks(int64_t M) {
+  const int64_t p = cdiv64(M, VQ_CS_CHUNK);
+  return (int)(p < VQ_CS_MAX_CHUNKS ? p : VQ_CS_MAX_CHUNKS);
+}
+extern "C" int64_t dmi_vq_cluster_sums_workspace_bytes(int64_t M, int T, int D) {
+  if (M <= 0 || T <= 0 || D <= 0) return 0;
+  const int P = cluster_chunks(M);
+  return P == 1 ? 0 : (int64_t)P * T * ((int64_t)D + 1) * 4;       // [P][T][D] partial sums, then [P][T] partial counts
+}
+extern "C" int dmi_vq_cluster_sums(const uint16_t* x, int ldx, const int32_t* idx, float* sums, int32_t* counts, int64_t M, int T, int D,
+                                   void* workspace, void* stream) {
+  DMI_REQUIRE(x && idx && sums && counts, "vq_cluster_sums: null pointer (x, idx, sums or counts)");
+  DMI_REQUIRE(M > 0, "vq_cluster_sums: M must be positive (M=%lld)", (long long)M);
+  DMI_REQUIRE(T > 0 && D > 0, "vq_cluster_sums: T and D must be positive (T=%d D=%d)", T, D);
+  DMI_REQUIRE(ldx >= D && ldx % 8 == 0, "vq_cluster_sums: ldx must be a multiple of 8 and at least D (ldx=%d D=%d)", ldx, D);
+  DMI_REQUIRE(((((uintptr_t)x) | ((uintptr_t)idx) | ((uintptr_t)sums) | ((uintptr_t)counts) | ((uintptr_t)workspace)) & 15) == 0,
+              "vq_cluster_sums: x, idx, sums, counts and workspace must be 16-byte aligned");
+  if (D % 8 != 0 || D > VQ_MAX_D || T % 8 != 0 || T > VQ_MAX_T) {
+    dmi_set_error("vq_cluster_sums: needs D %% 8 == 0, D <= %d, T %% 8 == 0, T <= %d (D=%d T=%d)", VQ_MAX_D, VQ_MAX_T, D, T);
+    return DMI_ERR_UNSUPPORTED;
+  }
+  const int P = cluster_chunks(M);
+  hipStream_t st = (hipStream_t)stream;
+  if (P == 1) {
+    cluster_sums_walk_kernel<<<dim3((unsigned)(T / 8), 1), dim3(512), 0, st>>>(x, ldx, idx, sums, counts, M, T, D, M, 0);
+    DMI_CHECK_LAUNCH("vq_cluster_sums");
+    return DMI_OK;
+  }
+  DMI_REQUIRE(workspace, "vq_cluster_sums: null pointer (workspace: dmi_vq_cluster_sums_workspace_bytes(M, T, D) bytes at M=%lld)", (long long)M);
+  const int64_t rows = cdiv64(cdiv64(M, P), 512) * 512;       // P chunks of whole 512-row rounds cover M; the last may be short
+  float* part = (float*)workspace;
+  int* pcnt = (int*)(part + (int64_t)P * T * D);
+  cluster_sums_walk_kernel<<<dim3((unsigned)(T / 8), (unsigned)P), dim3(512), 0, st>>>(x, ldx, idx, part, pcnt, M, T, D, rows, 1);
+  DMI_CHECK_LAUNCH("vq_cluster_sums");
+  cluster_sums_combine_kernel<<<dim3((unsigned)(T / 4)), dim3(256), 0, st>>>(part, pcnt, sums, counts, T, D, P);
+  DMI_CHECK_LAUNCH("vq_cluster_sums");
+  return DMI_OK;
+}
+
+// EMA update and dead-code restart of eight codes per block.  Wave w owns code k = 8 blockIdx.x + w: N, idle and the [T, D] row of S
+// (lane p the eight channels of piece p); the new code goes through LDS so that thread c rewrites C[c, k0 .. k0 + 8) of the [D, T]
+// master (32 bytes) and of its bf16 copy (16 bytes), taking the old bits for the codes that did not change.  Every product is
+// rounded on its own (contraction off): a numpy float32 restatement gives the same N and S.
+__global__ __launch_bounds__(512) void ema_codebook_step_kernel(float* __restrict__ C, bf16_t* __restrict__ Cb, float* __restrict__ N,
+                                                          float* __restrict__ S, int* __restrict__ idle, int* __restrict__ restarts,
+                                                          const float* __restrict__ sums, const int* __restrict__ counts,
+                                                          const bf16_t* __restrict__ x, int ldx, float g, float w, int restart_after,
+                                                          uint64_t seed, int64_t step, const int64_t* __restrict__ step_dev, int64_t M,
+                                                          int T, int D) {
+#pragma clang fp contract(off)
+  __shared__ float sm[8][VQ_MAX_D];
+  __shared__ int changed[8];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int k = blockIdx.x * 8 + wid;           // T % 8 == 0
+  const bool active = lane < D / 8;
+  const int n = counts[k];
+  float Nk = N[k] * g;
+  int id = idle[k];
+  if (n > 0) {
+    Nk = Nk + w * (float)n;
+    id = 0;
+  } else {
+    id += 1;
+  }
+  const bool restart = restart_after > 0 && id >= restart_after;
+  float c[8], s[8];
+  if (active) {
+    float* Sk = S + (int64_t)k * D + lane * 8;
+    if (restart) {
+      if (step_dev) step = *step_dev;
+      const uint64_t r = splitmix64(splitmix64(seed) ^ (uint64_t)step);
+      const uint64_t m = splitmix64(r + (uint64_t)k) % (uint64_t)M;
+      unpack8(*(const u32x4*)(x + (int64_t)m * ldx + lane * 8), c);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[e] = c[e];
+    } else {
+      const f32x4 a = *(const f32x4*)Sk, b = *(const f32x4*)(Sk + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        s[e] = a[e] * g;
+        s[4 + e] = b[e] * g;
+      }
+      if (n > 0) {
+        const float* sk = sums + (int64_t)k * D + lane * 8;
+        const f32x4 u = *(const f32x4*)sk, t = *(const f32x4*)(sk + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          s[e] = s[e] + w * u[e];
+          s[4 + e] = s[4 + e] + w * t[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) c[e] = s[e] / Nk;
+      }
+    }
+    *(f32x4*)Sk = f32x4{s[0], s[1], s[2], s[3]};
+    *(f32x4*)(Sk + 4) = f32x4{s[4], s[5], s[6], s[7]};
+    if (restart || n > 0) {
+      *(f32x4*)&sm[wid][lane * 8] = f32x4{c[0], c[1], c[2], c[3]};
+      *(f32x4*)&sm[wid][lane * 8 + 4] = f32x4{c[4], c[5], c[6], c[7]};
+    }
+  }
+  if (lane == 0) {
+    N[k] = restart ? 1.f : Nk;
+    idle[k] = restart ? 0 : id;
+    changed[wid] = (restart || n > 0) ? 1 : 0;
+    if (restart) atomicAdd(restarts, 1);       // an integer count: the order of the adds does not show
+  }
+  __syncthreads();
+  if (tid < D) {
+    float* dst = C + (int64_t)tid * T + blockIdx.x * 8;
+    bf16_t* dstb = Cb + (int64_t)tid * T + blockIdx.x * 8;
+    const f32x4 a = *(const f32x4*)dst, b = *(const f32x4*)(dst + 4);
+    float o[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+    const u32x4 ob = *(const u32x4*)dstb;
+    bf16_t q[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      q[j] = (bf16_t)((j & 1) ? (ob[j >> 1] >> 16) : (ob[j >> 1] & 0xffffu));
+      if (changed[j]) {
+        o[j] = sm[j][tid];
+        q[j] = f2bf(o[j]);
+      }
+    }
+    *(f32x4*)dst = f32x4{o[0], o[1], o[2], o[3]};
+    *(f32x4*)(dst + 4) = f32x4{o[4], o[5], o[6], o[7]};
+    u32x4 nb;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) nb[j] = (unsigned)q[2 * j] | ((unsigned)q[2 * j + 1] << 16);
+    *(u32x4*)dstb = nb;
+  }
+}
+extern "C" int dmi_vq_ema_step(float* codebook_f32, uint16_t* codebook_bf16, float* N, float* S, int32_t* idle, int32_t* restarts,
+                               const float* sums, const int32_t* counts, const uint16_t* x, int ldx, double gamma, int restart_after,
+                               uint64_t seed, int64_t step, const int64_t* step_dev, int64_t M, int T, int D, void* stream) {
+  DMI_REQUIRE(codebook_f32 && codebook_bf16 && N && S && idle && restarts && sums && counts && x,
+              "vq_ema_step: null pointer (codebook_f32, codebook_bf16, N, S, idle, restarts, sums, counts or x)");
+  DMI_REQUIRE(M > 0, "vq_ema_step: M must be positive (M=%lld)", (long long)M);
+  DMI_REQUIRE(T > 0 && D > 0, "vq_ema_step: T and D must be positive (T=%d D=%d)", T, D);
+  DMI_REQUIRE(gamma > 0.0 && gamma < 1.0, "vq_ema_step: gamma must lie strictly between 0 and 1 (gamma=%g)", gamma);
+  DMI_REQUIRE(restart_after >= 0, "vq_ema_step: restart_after must be >= 0 (restart_after=%d)", restart_after);
+  DMI_REQUIRE(step >= 0, "vq_ema_step: step must be >= 0 (step=%lld)", (long long)step);
+  DMI_REQUIRE(ldx >= D && ldx % 8 == 0, "vq_ema_step: ldx must be a multiple of 8 and at least D (ldx=%d D=%d)", ldx, D);
+  DMI_REQUIRE(((((uintptr_t)codebook_f32) | ((uintptr_t)codebook_bf16) | ((uintptr_t)S) | ((uintptr_t)sums) | ((uintptr_t)x)) & 15) == 0,
+              "vq_ema_step: codebook_f32, codebook_bf16, S, sums and x must be 16-byte aligned");
+  DMI_REQUIRE(((((uintptr_t)N) | ((uintptr_t)idle) | ((uintptr_t)restarts) | ((uintptr_t)counts)) & 3) == 0 && (((uintptr_t)step_dev) & 7) == 0,
+              "vq_ema_step: N, idle, restarts and counts must be 4-byte aligned, step_dev 8-byte aligned");
+  if (D % 8 != 0 || D > VQ_MAX_D || T % 8 != 0 || T > VQ_MAX_T) {
+    dmi_set_error("vq_ema_step: needs D %% 8 == 0, D <= %d, T %% 8 == 0, T <= %d (D=%d T=%d)", VQ_MAX_D, VQ_MAX_T, D, T);
+    return DMI_ERR_UNSUPPORTED;
+  }
+  const float g = (float)gamma, w = (float)(1.0 - gamma);
+  ema_codebook_step_kernel<<<dim3((unsigned)(T / 8)), dim3(512), 0, (hipStream_t)stream>>>(codebook_f32, codebook_bf16, N, S, idle, restarts, sums, counts,
+                                                                                     x, ldx, g, w, restart_after, seed, step, step_dev, M, T, D);
+  DMI_CHECK_LAUNCH("vq_ema_step");
+  return DMI_OK;
+}

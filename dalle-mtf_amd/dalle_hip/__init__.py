@@ -172,6 +172,9 @@ def _declare(L):
         "dmi_vq_codebook_grad_workspace_bytes": (L64, [L64, I, I]),
         "dmi_vq_codebook_grad": (I, [P, I, P, P, I, P, L64, I, I, P, P]),
         "dmi_vq_gather": (I, [P, I, P, P, I, L64, I, I, P]),
+        "dmi_vq_cluster_sums_workspace_bytes": (L64, [L64, I, I]),
+        "dmi_vq_cluster_sums": (I, [P, I, P, P, P, L64, I, I, P, P]),
+        "dmi_vq_ema_step": (I, [P, P, P, P, P, P, P, P, P, I, ctypes.c_double, I, U64, L64, P, L64, I, I, P]),
         "dmi_comm_load": (I, [c_char_p]),
         "dmi_comm_unique_id_bytes": (I, []),
         "dmi_comm_unique_id": (I, [P]),
@@ -1088,6 +1091,25 @@ def vq_codebook_grad(x, ldx, idx, codebook_t, ldc, dC, M, T, D, ws=None):
 def vq_gather(codebook_t, ldc, idx, out, ldo, M, T, D):
     _dev(codebook_t, idx, out)
     _check(lib().dmi_vq_gather(_p(codebook_t), ldc, _p(idx), _p(out), ldo, M, T, D, _stream()), "vq_gather")
+
+
+def vq_cluster_sums_workspace_bytes(M, T, D):
+    return int(lib().dmi_vq_cluster_sums_workspace_bytes(M, T, D))
+
+
+def vq_cluster_sums(x, ldx, idx, sums, counts, M, T, D, ws=None):
+    """counts[k] = #{m : idx[m] = k}; sums[k, :] = the fp32 sum of the rows x[m, :] with idx[m] = k, in a fixed order ([T, D])"""
+    _dev(x, idx, sums, counts, ws)
+    _check(lib().dmi_vq_cluster_sums(_p(x), ldx, _p(idx), _p(sums), _p(counts), M, T, D, _p(ws), _stream()), "vq_cluster_sums")
+
+
+def vq_ema_step(codebook_f32, codebook_bf16, N, S, idle, restarts, sums, counts, x, ldx, gamma, restart_after, seed, step, M, T, D,
+                step_dev=None):
+    """EMA update of N, S and the codebook from this step's cluster sums, then the dead-code restarts (include/dalle_hip.h)"""
+    _dev(codebook_f32, codebook_bf16, N, S, idle, restarts, sums, counts, x, step_dev)
+    _check(lib().dmi_vq_ema_step(_p(codebook_f32), _p(codebook_bf16), _p(N), _p(S), _p(idle), _p(restarts), _p(sums), _p(counts), _p(x), ldx,
+                                 float(gamma), int(restart_after), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), _p(step_dev), M, T, D, _stream()),
+           "vq_ema_step")
 
 
 def mse_workspace_bytes():

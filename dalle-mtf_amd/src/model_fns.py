@@ -50,7 +50,9 @@ def load_vae_model(params, mode_str):
         stack_factor=vae_params.get("stack_factor") or 1,
         dimensions=D,
         batch_size=params.get("_tokenizer_batch") or params[f"{mode_str}_batch_size"] // max(_dist_info()[0], 1),
-        mode="eval", quantizer=vae_params.get("quantizer"), vq_commitment=vae_params.get("vq_commitment"))
+        mode="eval", quantizer=vae_params.get("quantizer"), vq_commitment=vae_params.get("vq_commitment"),
+        vq_ema_decay=vae_params.get("vq_ema_decay"), vq_restart_after=vae_params.get("vq_restart_after"),
+        vq_restart_seed=vae_params.get("vq_restart_seed"))
     # the reference does not forward use_bf16 here, so its tokenising encoder is fp32: same here unless switched off
     vae_model.fp32_tokens = bool(params.get("vae_tokens_fp32", True))
     return vae_model, vae_checkpoint_path
@@ -71,6 +73,8 @@ def initialize_vae_weights(vae, checkpoint_path):
     sd = torch.load(checkpoint_path, map_location="cpu")
     from .vae_tf.vq import check_checkpoint
     check_checkpoint(vae.quantizer, sd)        # a .pt checkpoint of the other quantiser: ValueError
+    from .vae_tf.vq_ema import check_checkpoint as check_ema_checkpoint
+    check_ema_checkpoint(getattr(vae, "vq_ema_decay", None), sd)     # ... or of the other codebook update
     vae.load_reference_params({k: (v.numpy() if torch.is_tensor(v) else v) for k, v in sd["vae_variables"].items()})
 
 

@@ -11,6 +11,7 @@ from .utils import ModeKeys, SummaryWriter, mode_to_str
 from .vae_tf import DiscreteVAE
 from .vae_tf.kl import kl_log_lines, resolve_kl_options
 from .vae_tf.vq import resolve_vq_options, vq_log_lines
+from .vae_tf.vq_ema import resolve_vq_ema_options, vq_ema_log_lines
 
 
 def _dist_info():
@@ -32,8 +33,11 @@ def _stat_scalars(model, loss):
     summaries and eval_metrics carry with "codebook_stats" on or kl_loss_weight > 0 (one DiscreteVAE.codebook_stats() call)"""
     st = model.codebook_stats()
     if model.vq_on:      # vae_tf/vq.py STAT_SCALARS: no posterior, so no kl and no perplexity_soft
-        return dict(loss_recon=float(model.loss_recon[0]), loss_vq=float(model.loss_vq[0]), perplexity_hard=st["perplexity_hard"],
-                    codes_used_frac=st["codes_used_frac"])
+        out = dict(loss_recon=float(model.loss_recon[0]), loss_vq=float(model.loss_vq[0]), perplexity_hard=st["perplexity_hard"],
+                   codes_used_frac=st["codes_used_frac"])
+        if "vq_restarts" in st:      # vae_tf/vq_ema.py EMA_STAT_SCALARS: only with the EMA codebook
+            out.update(vq_restarts=float(st["vq_restarts"]), codes_idle=float(st["codes_idle"]))
+        return out
     on = model.kl_weight > 0
     return dict(loss_recon=float(model.loss_recon[0]) if on else float(loss), loss_kl=st["kl"],
                 kl_weight=float(model.kl_weight_t) if on else 0.0, perplexity_soft=st["perplexity_soft"],
@@ -44,6 +48,7 @@ def _build(params, mode_str):
     kl = resolve_kl_options(params)       # ValueError naming the key, before any device work
     vq = resolve_vq_options(params)
     world, rank, pg, comm = _dist_info()
+    ema = resolve_vq_ema_options(params, world=world)
     H = params["dataset"]["image_size"]
     gbs = params[f"{mode_str}_batch_size"]
     assert gbs % world == 0
@@ -58,8 +63,11 @@ def _build(params, mode_str):
         use_bf16=params.get("use_bf16") or False,
         stack_factor=params.get("stack_factor") or 1,
         dimensions=H, batch_size=gbs // world, mode=mode_str, process_group=pg, world_size=world, comm=comm,
-        kl_loss_weight=kl.kl_loss_weight, kl_anneal_steps=kl.kl_anneal_steps, quantizer=vq.quantizer, vq_commitment=vq.vq_commitment)
-    for line in vq_log_lines(vq, model.num_tokens, model.grid, model.n_hid) or kl_log_lines(kl, model.num_tokens, model.grid):
+        kl_loss_weight=kl.kl_loss_weight, kl_anneal_steps=kl.kl_anneal_steps, quantizer=vq.quantizer, vq_commitment=vq.vq_commitment,
+        vq_ema_decay=ema.vq_ema_decay, vq_restart_after=ema.vq_restart_after or None,
+        vq_restart_seed=ema.vq_restart_seed if ema.vq_restart_after else None)
+    for line in (vq_log_lines(vq, model.num_tokens, model.grid, model.n_hid) or kl_log_lines(kl, model.num_tokens, model.grid)) + \
+            vq_ema_log_lines(ema, model.num_tokens):
         logging.getLogger("dalle_mtf_amd").info("%s %s", mode_str, line)
     ck = latest_checkpoint(params["model_path"]) if params.get("model_path") else None
     if ck is not None:

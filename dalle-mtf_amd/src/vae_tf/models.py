@@ -27,6 +27,7 @@ import dalle_hip as dh
 from ..dp import GradReducer
 from .kl import _perplexity, kl_weight_at, resolve_kl_options, usage_stats
 from .vq import check_checkpoint, resolve_vq_options
+from .vq_ema import STATE_KEYS as VQ_EMA_STATE_KEYS, check_checkpoint as check_ema_checkpoint, resolve_vq_ema_options
 
 IMG_CP = 8     # padded image channels
 OUT_CP = 64    # padded reconstruction channels
@@ -72,10 +73,13 @@ class _Conv:
 class DiscreteVAE:
     def __init__(self, num_tokens, dimensions, convblocks, dim=512, hidden_dim=64, input_channels=3, recompute_grad=False,
                  use_bf16=False, stack_factor=1, batch_size=32, mode="train", device="cuda", process_group=None, world_size=1,
-                 comm=None, kl_loss_weight=0.0, kl_anneal_steps=None, quantizer=None, vq_commitment=None):
+                 comm=None, kl_loss_weight=0.0, kl_anneal_steps=None, quantizer=None, vq_commitment=None, vq_ema_decay=None, vq_restart_after=None,
+                 vq_restart_seed=None):
         kl = resolve_kl_options(dict(kl_loss_weight=kl_loss_weight, kl_anneal_steps=kl_anneal_steps))   # ValueError before any device work
         vq = resolve_vq_options(dict(quantizer=quantizer, vq_commitment=vq_commitment, kl_loss_weight=kl_loss_weight,
                                      kl_anneal_steps=kl_anneal_steps))
+        ema = resolve_vq_ema_options(dict(quantizer=quantizer, vq_ema_decay=vq_ema_decay, vq_restart_after=vq_restart_after,
+                                          vq_restart_seed=vq_restart_seed), world=world_size)
         if num_tokens > GUMBEL_MAX_TOKENS:
             raise ValueError(f"num_tokens = {num_tokens}: the Gumbel-softmax kernel (dmi_gumbel_softmax_fwd, one wave per row) "
                              f"handles codebooks of at most {GUMBEL_MAX_TOKENS} tokens")
@@ -119,6 +123,9 @@ class DiscreteVAE:
         self.rowstat = self.loss_recon = self.loss_kl = self.ws_kl = self._usage = None
         # "vq": nearest-code bottleneck, loss = recon + (1 + beta) Lq (vae_tf/vq.py); "gumbel" = the reference's, unchanged
         self.quantizer, self.vq_on, self.vq_beta = vq.quantizer, vq.quantizer == "vq", vq.vq_commitment
+        # "vq_ema_decay": the codebook follows its clusters' moving averages instead of a gradient, loss = recon + beta Lq (vae_tf/vq_ema.py)
+        self.vq_ema_decay, self.vq_restart_after, self.vq_restart_seed = ema
+        self.vq_ema = None           # N, S, idle, restarts (_alloc) when vq_ema_decay is set
         self._kl_fresh = False       # rowstat / loss_kl describe the logits buffer as it stands
         self._graphs, self._graph_warm, self._dyn_on, self._img_static = {}, False, False, None
         self._build_graph()
@@ -258,6 +265,13 @@ class DiscreteVAE:
             self.u = torch.empty(Mg, self.num_tokens, **f32)
             self.y = torch.empty(Mg, self.num_tokens, **b16)
             self.y_soft = torch.empty(Mg, self.num_tokens, **b16)
+        if self.vq_ema_decay is not None:       # cluster state, this step's cluster sums, and the step the restart hash reads in a replay
+            T, nh = self.num_tokens, self.n_hid
+            self.vq_ema = dict(N=torch.ones(T, **f32), S=torch.zeros(T, nh, **f32), idle=torch.zeros(T, dtype=torch.int32, device=dev),
+                               restarts=torch.zeros(1, dtype=torch.int32, device=dev))
+            self._ema_sums, self._ema_counts = torch.zeros(T, nh, **f32), torch.zeros(T, dtype=torch.int32, device=dev)
+            self._ema_ws = torch.empty(int(dh.vq_cluster_sums_workspace_bytes(Mg, T, nh)) + 1024, dtype=torch.uint8, device=dev)
+            self._step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.index = torch.empty(Mg, dtype=torch.int32, device=dev)
         self.xdec = torch.empty(Mg, self.n_hid, **b16)
         self.loss = torch.zeros(1, **f32)
@@ -346,6 +360,9 @@ class DiscreteVAE:
                 bsrc = torch.from_numpy(np.ascontiguousarray(P[c.name + "/bias"])).float()
                 self.view(self.p, c.name + "/bias")[:bsrc.shape[0]] = bsrc
             self.view(self.p, "codebook/codebook").copy_(torch.from_numpy(np.ascontiguousarray(P["codebook/codebook"])))
+            if self.vq_ema is not None:      # parameters without cluster state: N = 1, S[k] = C[:,k], nothing idle, no restarts yet
+                e = self.vq_ema
+                e["N"].fill_(1.0); e["S"].copy_(self.view(self.p, "codebook/codebook").t()); e["idle"].zero_(); e["restarts"].zero_()
         self.refresh_compute_copies(cast=True)
 
     def export_reference(self, buf=None) -> "OrderedDict[str, np.ndarray]":
@@ -549,7 +566,8 @@ class DiscreteVAE:
         need_grad = (self.mode == "train") if need_grad is None else need_grad
         dh.mse_loss(self.img_net, x, self.ga if need_grad else None, self.loss_recon, B * self.Hs * self.Hs, self.c_st, OUT_CP, 1.0, self.ws)
         dh.vq_loss(self.x_enc, nh, self.xdec, nh, self.loss_vq, Mg, nh, self.ws_vq)
-        dh.elbo_loss(self.loss_recon, self.loss_vq, self.loss, 1.0 + self.vq_beta)
+        # the EMA codebook has no codebook loss: commitment only
+        dh.elbo_loss(self.loss_recon, self.loss_vq, self.loss, self.vq_beta if self.vq_ema is not None else 1.0 + self.vq_beta)
         return self.loss[0], self.reconstruction()
 
     def _logits_buffer(self):
@@ -800,7 +818,8 @@ class DiscreteVAE:
                 T, nh, Mg = self.num_tokens, self.n_hid, self.Mg
                 nd = spare[0]
                 dh.vq_bwd_x(d, nh, self.x_enc, nh, self.xdec, nh, nd, nh, Mg, nh, self.vq_beta)
-                dh.vq_codebook_grad(self.x_enc, nh, self.index, self.codebook_t, nh, self._gv("codebook/codebook"), Mg, T, nh, self.ws_vq)
+                if self.vq_ema is None:      # (EMA codebook: no gradient; its slice of g keeps the zeros it was allocated with)
+                    dh.vq_codebook_grad(self.x_enc, nh, self.index, self.codebook_t, nh, self._gv("codebook/codebook"), Mg, T, nh, self.ws_vq)
                 spare[0], d = d, nd
                 ready_down_to(self.offset["codebook/codebook"])
             elif i == self.n_enc - 1:
@@ -830,8 +849,19 @@ class DiscreteVAE:
         lr_t = self.lr_t(lr, beta1, beta2)
         dh.adam_step(self.p, self.g, self.m, self.v, self.pb, self.total, None, 0.0, lr_t, beta1, beta2, eps, 0.0, 1.0 / self.world,
                      lr_dev=self._dyn[0:1] if self._dyn_on else None)
+        if self.vq_ema is not None:
+            self._ema_codebook_step()
         self.refresh_compute_copies(cast=False)
         self.global_step += 1
+
+    def _ema_codebook_step(self):
+        """the codebook's own update (Adam left it alone: its gradient is 0): cluster sums of this step's x_enc / index, the moving
+        averages, the restarts; into the fp32 master and its bf16 copy, between dmi_adam_step and refresh_compute_copies"""
+        e, T, nh, Mg = self.vq_ema, self.num_tokens, self.n_hid, self.Mg
+        dh.vq_cluster_sums(self.x_enc, nh, self.index, self._ema_sums, self._ema_counts, Mg, T, nh, self._ema_ws)
+        dh.vq_ema_step(self.view(self.p, "codebook/codebook"), self.view(self.pb, "codebook/codebook"), e["N"], e["S"], e["idle"],
+                       e["restarts"], self._ema_sums, self._ema_counts, self.x_enc, nh, self.vq_ema_decay, self.vq_restart_after,
+                       self.vq_restart_seed, self.global_step, Mg, T, nh, step_dev=self._step_dev if self._dyn_on else None)
 
     def lr_t(self, lr, beta1=0.9, beta2=0.999):
         t = self.global_step + 1
@@ -876,6 +906,8 @@ class DiscreteVAE:
         if self.kl_weight > 0:
             self.kl_weight_t = kl_weight_at(self.global_step, self.kl_weight, self.kl_anneal_steps)
             self._dyn[2:3].fill_(self.kl_weight_t)
+        if self.vq_ema is not None:
+            self._step_dev.fill_(self.global_step)       # the restart hash's step, as lr_t is: one graph serves every step
         self.temperature = float(temperature)
         key = bool(hard_gumbel)
         g = self._graphs.get(key)
@@ -922,7 +954,10 @@ class DiscreteVAE:
             dh.codebook_usage(None, None, self.index, None, self._usage["counts"], Mg, T, self.ws_kl)
             counts = self._usage["counts"].cpu().numpy()
             used = int((counts > 0).sum())
-            return dict(perplexity_hard=_perplexity(counts), codes_used=used, codes_used_frac=used / T)
+            out = dict(perplexity_hard=_perplexity(counts), codes_used=used, codes_used_frac=used / T)
+            if self.vq_ema is not None:
+                out.update(vq_restarts=int(self.vq_ema["restarts"][0]), codes_idle=int((self.vq_ema["idle"] >= 1).sum()))
+            return out
         self._kl_buffers()
         if self._usage is None:
             self._usage = dict(qsum=torch.empty(T, dtype=torch.float32, device=self.dev),
@@ -942,12 +977,21 @@ class DiscreteVAE:
               "m": self.m.detach().cpu(), "v": self.v.detach().cpu(), "global_step": self.global_step}
         if self.vq_on:       # only when on: a checkpoint without the key is a Gumbel one
             sd["quantizer"] = "vq"
+        ema = getattr(self, "vq_ema", None)
+        if ema is not None:  # likewise: a VQ checkpoint without these was trained by the codebook gradient
+            sd["vq_codebook"] = "ema"
+            sd["vq_ema"] = {k: ema[k].detach().cpu() for k in VQ_EMA_STATE_KEYS}
         return sd
 
     def load_state_dict(self, sd):
         check_checkpoint(self.quantizer, sd)
+        ema = getattr(self, "vq_ema", None)
+        check_ema_checkpoint(getattr(self, "vq_ema_decay", None), sd)
         self.load_reference_params({k: (v.numpy() if torch.is_tensor(v) else np.asarray(v))
                                     for k, v in sd["vae_variables"].items()})
         if "m" in sd:
             self.m.copy_(sd["m"]); self.v.copy_(sd["v"])
+        if ema is not None:
+            for k in VQ_EMA_STATE_KEYS:
+                ema[k].copy_(torch.as_tensor(sd["vq_ema"][k]).reshape(ema[k].shape))
         self.global_step = int(sd.get("global_step", 0))

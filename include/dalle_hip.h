@@ -713,6 +713,31 @@ int dmi_vq_codebook_grad(const uint16_t* x, int ldx, const int32_t* idx, const u
                          int64_t M, int T, int D, void* workspace, void* stream);
 int dmi_vq_gather(const uint16_t* codebook_t, int ldc, const int32_t* idx, uint16_t* out, int ldo, int64_t M, int T, int D,
                   void* stream);
+/* EMA codebook updates and dead-code restarts (project extension; DESIGN.md §4 "VAE: EMA codebook and restarts").  State per code k:
+ * N fp32 [T], S fp32 [T, D] row-major, idle int32 [T]; one int32 counter restarts.  Initial state: N = 1, S[k] = C[:,k], idle = 0.
+ *   dmi_vq_cluster_sums   counts int32 [T]: n[k] = #{m : idx[m] = k}, exact; sums fp32 [T, D]: s[k][c] = sum_{idx[m]=k} X[m][c] in fp32,
+ *                         rows added in row order inside a chunk of rows and the chunks' partial sums in chunk order: no float atomics,
+ *                         two runs give equal bits; a code nobody picked gets exactly 0; an idx outside [0, T) contributes nothing.
+ *                         D % 8 == 0, D <= 512, T % 8 == 0, T <= 4096, 16-byte alignment (DMI_ERR_INVALID / DMI_ERR_UNSUPPORTED as for
+ *                         dmi_vq_codebook_grad).  workspace: dmi_vq_cluster_sums_workspace_bytes(M, T, D) bytes (0 for M <= 4096:
+ *                         workspace may then be null).
+ *   dmi_vq_ema_step       with g = fp32(gamma), w = fp32(1 - gamma) (the difference in double) and every product rounded on its own:
+ *                           n[k] > 0:  N' = g N + w float(n), S' = g S + w s, C[:,k] = S' / N', idle = 0
+ *                           n[k] = 0:  N' = g N, S' = g S, idle += 1, C[:,k] keeps its bits (no division by a vanishing N)
+ *                         then, when restart_after > 0, every k with idle[k] >= restart_after is re-seeded from row
+ *                           m_k = splitmix64(splitmix64(splitmix64(seed) ^ step) + k) mod M    (uint64 arithmetic)
+ *                         of X: C[:,k] = float(X[m_k]), N = 1, S[k] = C[:,k], idle = 0, restarts += 1.  Two dead codes may draw the
+ *                         same row: the arg-max's tie-break (lowest index) then leaves one idle, re-seeded again restart_after steps on.
+ *                         Every changed code is written to the fp32 master codebook_f32 [D, T] and, rounded to nearest even, to its
+ *                         bf16 copy codebook_bf16 [D, T]; the others keep their bits in both.  step_dev (nullable): the step is read
+ *                         from device memory (int64), so that a captured graph serves every step; else step by value.
+ *                         0 < gamma < 1, restart_after >= 0 (0 never restarts), step >= 0; shapes as dmi_vq_cluster_sums. */
+int64_t dmi_vq_cluster_sums_workspace_bytes(int64_t M, int T, int D);
+int dmi_vq_cluster_sums(const uint16_t* x, int ldx, const int32_t* idx, float* sums, int32_t* counts, int64_t M, int T, int D,
+                        void* workspace, void* stream);
+int dmi_vq_ema_step(float* codebook_f32, uint16_t* codebook_bf16, float* N, float* S, int32_t* idle, int32_t* restarts,
+                    const float* sums, const int32_t* counts, const uint16_t* x, int ldx, double gamma, int restart_after,
+                    uint64_t seed, int64_t step, const int64_t* step_dev, int64_t M, int T, int D, void* stream);
 
 
 /* ---- input format (host only): CRC-32C (Castagnoli) of a TFRecord length header / payload, as tf.data.TFRecordDataset
