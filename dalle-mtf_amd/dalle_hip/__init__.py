@@ -191,7 +191,6 @@ def _declare(L):
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
-    # optional (VAE) entry points are declared by dalle_hip.vae when present
 
 
 def _check(rc, what):

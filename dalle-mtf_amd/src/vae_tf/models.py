@@ -1,7 +1,8 @@
 """DiscreteVAE -- same constructor / forward surface as the reference (src/vae_tf/models.py:46-184), re-hosted on
 libdalle_hip: every convolution is a tap list feeding the MFMA GEMMs -- gathered implicitly inside the GEMM
 (dmi_conv_gemm_nt / dmi_conv_wgrad_tn) for 64-channel-aligned layers, through a materialised im2col (dmi_im2col +
-dmi_gemm_nt / dmi_gemm_tn) otherwise; Gumbel-softmax and MSE are dedicated kernels (csrc/vae.hip).  bf16 activations/weights, fp32 accumulation, fp32
+dmi_gemm_nt / dmi_gemm_tn) otherwise, as lowering.py states per layer and _tap_product / _tap_wgrad launch; Gumbel-softmax and
+MSE are dedicated kernels (csrc/vae.hip).  bf16 activations/weights, fp32 accumulation, fp32
 master weights and Adam state; the codebook logits are produced in fp32 (reference: fp32 matmul, models.py:113-118).
 
 Layer structure (reference lines): encoder 81-120: per block a 4x4 s2 SAME conv (no activation) then (stack-1) x
@@ -18,56 +19,22 @@ from __future__ import annotations
 import math
 import os
 from collections import OrderedDict
-from typing import Dict, List, Optional
+from typing import Dict
 
 import numpy as np
 import torch
 
 import dalle_hip as dh
 from ..dp import GradReducer
+from . import lowering
+from .lowering import OUT_CP, TAPS3, _Conv, _ru   # noqa: F401  (TAPS3: the tests read it from here)
 from .kl import _perplexity, kl_weight_at, resolve_kl_options, usage_stats
 from .vq import check_checkpoint, resolve_vq_options
 from .vq_ema import STATE_KEYS as VQ_EMA_STATE_KEYS, check_checkpoint as check_ema_checkpoint, resolve_vq_ema_options
 
-IMG_CP = 8     # padded image channels
-OUT_CP = 64    # padded reconstruction channels
 VQ_MAX_WIDTH = 512           # widest code of dmi_vq_assign / dmi_vq_codebook_grad
 GUMBEL_MAX_TOKENS = 4096    # largest codebook of dmi_gumbel_softmax_fwd (eight 8-column chunks per lane)
-ALIGN = 128
 WS_POOL = 7    # weight gradients in flight before their slab reduces are flushed (2 reduce items each, 16 per batched launch)
-
-
-def _ru(x, m):
-    return (x + m - 1) // m * m
-
-
-TAPS4 = [(ky - 1, kx - 1) for ky in range(4) for kx in range(4)]       # 4x4 s2 SAME: pad 1 before (Appendix A.8)
-TAPS3 = [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]       # 3x3 s1 SAME
-TAPS3_REV = [(1 - ky, 1 - kx) for ky in range(3) for kx in range(3)]   # input gradient of the 3x3 conv
-
-
-def _parity(p):
-    """output-parity class of the stride-2 adjoint: [(k index, dy, dx)] for the 2x2 contributing taps."""
-    def ax(par):
-        return [(1, 0), (3, -1)] if par == 0 else [(0, 1), (2, 0)]   # (k, source offset)
-    py, px = p >> 1, p & 1
-    return [(ky * 4 + kx, dy, dx) for (ky, dy) in ax(py) for (kx, dx) in ax(px)]
-
-
-class _Conv:
-    def __init__(self, name, kind, cin, cout, H, W, cin_ref=None, cout_ref=None):
-        self.name, self.kind, self.cin, self.cout, self.H, self.W = name, kind, cin, cout, H, W
-        self.cin_ref = cin if cin_ref is None else cin_ref     # channels of the reference variable
-        self.cout_ref = cout if cout_ref is None else cout_ref
-        self.kk = {"down": 16, "up": 16, "res": 9, "final": 1}[kind]
-        if kind == "down":
-            self.Ho, self.Wo = H // 2, W // 2
-        elif kind == "up":
-            self.Ho, self.Wo = 2 * H, 2 * W
-        else:
-            self.Ho, self.Wo = H, W
-        # kernel stored [kk][A][Bn]: conv: A=cin, Bn=cout ; conv-transpose (TF [kh,kw,Cout,Cin]): A=cout(z), Bn=cin(y)
-        self.A, self.Bn = (cout, cin) if kind == "up" else (cin, cout)
 
 
 class DiscreteVAE:
@@ -128,6 +95,8 @@ class DiscreteVAE:
         self.vq_ema = None           # N, S, idle, restarts (_alloc) when vq_ema_decay is set
         self._kl_fresh = False       # rowstat / loss_kl describe the logits buffer as it stands
         self._graphs, self._graph_warm, self._dyn_on, self._img_static = {}, False, False, None
+        self.event_hook = None       # (layer name, list): HIP event pairs around that layer's implicit forward launch (bench.py)
+        self._f32 = None             # scratch of encode_logits_fp32, at its first call
         self._build_graph()
         self._alloc()
         self._dyn = torch.zeros(3, dtype=torch.float32, device=self.dev)   # [lr_t, temperature, beta_t] read by graph-replayed kernels
@@ -136,48 +105,9 @@ class DiscreteVAE:
 
     # ------------------------------------------------------------------ structure
     def _build_graph(self):
-        convs: List[_Conv] = []
-        H, cin, cin_ref = self.Hs, self.img_cp, self.c_st
-        for b, (stack, ch) in enumerate(self.convblocks):
-            for i in range(stack):
-                p = f"encoder/block_{b}/layer_{i}/"
-                if i == 0:
-                    convs.append(_Conv(p + "conv_downsample", "down", cin, ch, H, H, cin_ref=cin_ref))
-                    H //= 2
-                else:
-                    convs.append(_Conv(p + "conv_in", "res", ch, ch, H, H))
-                    convs.append(_Conv(p + "conv_out", "res", ch, ch, H, H))
-            cin = cin_ref = ch
-        self.n_enc = len(convs)
-        for b, (stack, ch) in enumerate(reversed(self.convblocks)):
-            for i in range(stack):
-                p = f"decoder/block_{b}/layer_{i}/"
-                if i == 0:
-                    convs.append(_Conv(p + "conv_upsample", "up", cin, ch, H, H))
-                    H *= 2
-                else:
-                    convs.append(_Conv(p + "conv_in", "res", ch, ch, H, H))
-                    convs.append(_Conv(p + "conv_out", "res", ch, ch, H, H))
-            cin = ch
-        convs.append(_Conv("decoder/conv2d", "final", cin, OUT_CP, H, H, cout_ref=self.c_st))
-        self.convs = convs
-        # flat parameter layout
-        self.offset: Dict[str, int] = {}
-        self.shape: Dict[str, tuple] = {}
-        off = 0
-
-        def add(name, shp):
-            nonlocal off
-            self.offset[name], self.shape[name] = off, shp
-            off += _ru(int(np.prod(shp)), ALIGN)
-        for c in convs[:self.n_enc]:
-            add(c.name + "/kernel", (c.kk, c.A, c.Bn))
-            add(c.name + "/bias", (c.cout,))
-        add("codebook/codebook", (self.n_hid, self.num_tokens))
-        for c in convs[self.n_enc:]:
-            add(c.name + "/kernel", (c.kk, c.A, c.Bn))
-            add(c.name + "/bias", (c.cout,))
-        self.total = off
+        """the layer list with every layer's tap products and the flat parameter layout (lowering.py)"""
+        self.convs, self.n_enc, self.offset, self.shape, self.total = lowering.build_graph(
+            self.Hs, self.img_cp, self.c_st, self.convblocks, self.n_hid, self.num_tokens)
 
     def _alloc(self):
         B, dev = self.B, self.dev
@@ -192,34 +122,8 @@ class DiscreteVAE:
         # derived weight copies: views of ONE flat buffer, so that the per-step refresh is two batched launches
         # (dmi_transpose_bf16_batch + dmi_weight_gather_batch) instead of one launch per copy
         self.wf, self.wd, self.wp = {}, {}, {}
-        plan = []                                   # (dict, key, index or None, rows, cols)
-        max_col = 0
-        for c in self.convs:
-            K = c.kk * c.cin
-            Kp = _ru(K, 64)
-            M_out = B * c.Ho * c.Wo
-            if c.kind in ("down", "res", "final"):
-                plan.append(("wf", c.name, None, c.cout, Kp))                             # [co][(k,ci)] fwd
-                max_col = max(max_col, M_out * Kp)
-            if c.kind == "res":
-                plan.append(("wd", c.name, None, c.cin, _ru(9 * c.cout, 64)))             # [ci][(k,co)] dgrad
-                max_col = max(max_col, M_out * _ru(9 * c.cout, 64))
-            if c.kind == "down":
-                for q in range(4):
-                    plan.append(("wp", c.name, q, c.cin, _ru(4 * c.cout, 64)))            # dgrad parity
-                max_col = max(max_col, M_out * _ru(4 * c.cout, 64))
-            if c.kind == "up":
-                for q in range(4):
-                    plan.append(("wp", c.name, q, c.cout, _ru(4 * c.cin, 64)))            # fwd parity [cz][(a,b,cy)]
-                plan.append(("wd", c.name, None, c.cin, _ru(16 * c.cout, 64)))            # [cy][(k,cz)] for dy
-                max_col = max(max_col, B * c.H * c.W * _ru(4 * c.cin, 64), B * c.H * c.W * _ru(16 * c.cout, 64))
-        plan.append(("cb", "codebook_t", None, self.num_tokens, self.n_hid))
-        off = 0
-        self._wc_off = {}
-        for kind, name, q, rows, cols in plan:
-            self._wc_off[(kind, name, q)] = off
-            off += _ru(rows * cols, ALIGN)
-        self.wcopies = torch.zeros(off, **b16)
+        plan, self._wc_off, size = lowering.weight_copies(self.convs, self.n_hid, self.num_tokens)
+        self.wcopies = torch.zeros(size, **b16)
         for kind, name, q, rows, cols in plan:
             o = self._wc_off[(kind, name, q)]
             v = self.wcopies[o:o + rows * cols].view(rows, cols)
@@ -230,7 +134,7 @@ class DiscreteVAE:
             else:
                 getattr(self, kind)[name] = v
         self._refresh_tables = None
-        self.col = torch.empty(max_col, **b16)
+        self.col = torch.empty(lowering.max_col(self.convs, B), **b16)    # sized over the implicit products too
         # im2col matrices of the forward convolutions kept for their weight gradients (288 GB HBM: ~8 GB for vae_coco at 16
         # images) -- the backward pass then gathers only dy; allocated on first use in train mode
         self.col_keep = {}
@@ -283,12 +187,8 @@ class DiscreteVAE:
         self.gc = torch.empty(max_act, **b16)
         self.dy = None if self.vq_on else torch.empty(Mg, self.num_tokens, **b16)
         self.dlogits = None if self.vq_on else torch.empty(Mg, self.num_tokens, **b16)
-        wsz = 1 << 20
-        for c in self.convs:
-            M_out = B * c.Ho * c.Wo
-            M_in = B * c.H * c.W
-            wsz = max(wsz, dh.gemm_tn_workspace_bytes(max(M_out, M_in), c.kk * max(c.cin, c.cout), max(c.cin, c.cout)),
-                      dh.colsum_workspace_bytes(max(M_out, M_in), max(c.cout, c.cin)))
+        bounds = lowering.wgrad_bounds(self.convs, B)      # per layer (M, K, N) of its weight gradient and column sum
+        wsz = max([1 << 20] + [max(dh.gemm_tn_workspace_bytes(M, K, N), dh.colsum_workspace_bytes(M, N)) for M, K, N in bounds])
         wsz = max(wsz, dh.gemm_tn_workspace_bytes(Mg, self.n_hid, self.num_tokens), dh.mse_workspace_bytes())
         if self.kl_weight > 0:
             self._kl_buffers()
@@ -296,8 +196,8 @@ class DiscreteVAE:
         # backward(): the split-m slab reduces of the weight gradients are DEFERRED and run a few layers at a time in one launch
         # (the small configurations spent a fifth of their step in ~60 reduce launches of a few microseconds); every pending
         # weight gradient owns one workspace of this pool until the flush
-        self.ws_cs = torch.empty(int(max(dh.colsum_workspace_bytes(max(B * c.Ho * c.Wo, B * c.H * c.W), max(c.cout, c.cin))
-                                         for c in self.convs)) + 1024, dtype=torch.uint8, device=dev)   # column sums reduce at once
+        self.ws_cs = torch.empty(int(max(dh.colsum_workspace_bytes(M, N) for M, K, N in bounds)) + 1024, dtype=torch.uint8,
+                                 device=dev)                                   # column sums reduce at once
         self.ws_pool = [torch.empty_like(self.ws) for _ in range(WS_POOL)]     # (self.ws stays free for the immediate calls)
         self._ws_next = 0
         self.deferred = dh.DeferredReduces()
@@ -385,39 +285,10 @@ class DiscreteVAE:
         if cast:
             dh.cast_f32_bf16(self.p, self.pb, self.total)
         if self._refresh_tables is None:
-            tr, tile, ga, blk, padded = [], 0, [], 0, []
-            for c in self.convs:
-                src = self.offset[c.name + "/kernel"]
-                K = c.kk * c.cin
-                if c.kind in ("down", "res", "final"):
-                    if _ru(K, 64) == K:
-                        tr.append([src, self._wc_off[("wf", c.name, None)], K, c.cout, tile])
-                        tile += ((K + 63) // 64) * ((c.cout + 63) // 64)
-                    else:
-                        padded.append((c.name, "wf", K, _ru(K, 64), c.cout))
-                if c.kind == "res":
-                    ga.append((src, self._wc_off[("wd", c.name, None)], c.cin, c.cout, list(range(9)), _ru(9 * c.cout, 64)))
-                if c.kind == "down":
-                    for q in range(4):
-                        ga.append((src, self._wc_off[("wp", c.name, q)], c.cin, c.cout, [t[0] for t in _parity(q)], _ru(4 * c.cout, 64)))
-                if c.kind == "up":
-                    for q in range(4):
-                        ga.append((src, self._wc_off[("wp", c.name, q)], c.cout, c.cin, [t[0] for t in _parity(q)], _ru(4 * c.cin, 64)))
-                    Kz = 16 * c.cout
-                    if _ru(Kz, 64) == Kz:
-                        tr.append([src, self._wc_off[("wd", c.name, None)], Kz, c.cin, tile])
-                        tile += ((Kz + 63) // 64) * ((c.cin + 63) // 64)
-                    else:
-                        padded.append((c.name, "wd", Kz, _ru(Kz, 64), c.cin))
-            tr.append([self.offset["codebook/codebook"], self._wc_off[("cb", "codebook_t", None)], self.n_hid, self.num_tokens, tile])
-            tile += ((self.n_hid + 63) // 64) * ((self.num_tokens + 63) // 64)
-            rows = []
-            for src, dst, A, Bn, idx, ldo in ga:
-                rows.append([src, dst, A, Bn, len(idx), ldo, blk] + idx + [0] * (16 - len(idx)))
-                blk += (A * ldo + 2047) // 2048
-            self._refresh_tables = dict(tr=torch.tensor(tr, dtype=torch.int64, device=self.dev), tiles=tile,
-                                        ga=torch.tensor(rows, dtype=torch.int64, device=self.dev) if rows else None, blocks=blk,
-                                        padded=padded)
+            T = lowering.refresh_tables(self.convs, self.offset, self._wc_off, self.n_hid, self.num_tokens)
+            for k in ("tr", "ga"):
+                T[k] = torch.tensor(T[k], dtype=torch.int64, device=self.dev) if T[k] else None
+            self._refresh_tables = T
         T = self._refresh_tables
         dh.transpose_batch(self.pb, self.wcopies, T["tr"], T["tr"].shape[0], T["tiles"])
         if T["ga"] is not None:
@@ -431,58 +302,87 @@ class DiscreteVAE:
     def _w(self, name):
         return self.view(self.pb, name)
 
-    @staticmethod
-    def _implicit_ok(c: _Conv):
-        """layers whose im2col can stay implicit in all three GEMMs: 64-channel-aligned input, power-of-two output grid."""
-        p2 = lambda v: v > 0 and (v & (v - 1)) == 0
-        return c.cin % 64 == 0 and p2(c.Ho) and p2(c.Wo)
+    _implicit_ok = staticmethod(lowering.implicit_ok)    # (bench.py and the tests ask it of a layer)
+
+    def _gather(self, t, x, col=None):
+        """the column matrix of x through t's taps: dmi_im2col into `col` (self.col when None); a direct product reads x itself"""
+        if t.direct:
+            return x
+        col = self.col if col is None else col
+        dh.im2col(x, col, self.B, t.H, t.W, t.C, t.Ho, t.Wo, t.stride, t.taps, t.Kp)
+        return col
+
+    def _tap_product(self, t, x, w, out, flags=0, col=None, **epilogue):
+        """out [B*Ho*Wo, N] = (x through t's taps) . w^T: gathered inside dmi_conv_gemm_nt, or the plain dmi_gemm_nt on the column
+        `col` (None: gathered into self.col now)"""
+        if t.implicit:
+            dh.conv_gemm_nt(x, self.B, t.H, t.W, t.C, t.Ho, t.Wo, t.stride, t.taps, w, t.Kp, out, t.N, t.N, flags, **epilogue)
+            return
+        col = self._gather(t, x) if col is None else col
+        dh.gemm_nt(col, t.Kp, w, t.Kp, out, t.N, self.B * t.Ho * t.Wo, t.N, t.Kp, flags, **epilogue)
+
+    def _tap_wgrad(self, t, x, dy, dW, ws, dfr, dbias=None, col=None):
+        """dW [(tap, c)][N] = (x through t's taps)^T . dy, with the bias gradient when `dbias`: gathered inside dmi_conv_wgrad_tn,
+        or dmi_gemm_tn on the column `col` (None: gathered into self.col now)"""
+        if t.implicit:
+            dh.conv_wgrad_tn(x, self.B, t.H, t.W, t.C, t.Ho, t.Wo, t.stride, t.taps, dy, t.N, t.N, dW, ws, dbias=dbias, deferred=dfr)
+            return
+        col = self._gather(t, x) if col is None else col
+        dh.gemm_tn(col, t.Kp, dy, t.N, dW, self.B * t.Ho * t.Wo, t.K, t.N, ws, dbias=dbias, deferred=dfr)
 
     def _conv_fwd(self, c: _Conv, x, out, flags=0, residual=None):
         B = self.B
         bias = self._w(c.name + "/bias")
-        if c.kind == "final" and c.cin % 64 == 0:
-            dh.gemm_nt(x, c.cin, self.wf[c.name], c.cin, out, c.cout, B * c.H * c.W, c.cout, c.cin, flags | dh.GEMM_BIAS, bias=bias)
-        elif c.kind in ("down", "res", "final"):
-            K = c.kk * c.cin
-            Kp = _ru(K, 64)
-            taps, s = {"down": (TAPS4, 2), "res": (TAPS3, 1), "final": ([(0, 0)], 1)}[c.kind]
-            if c.kind != "final" and self._implicit_ok(c):
-                # implicit im2col in forward, input gradient and weight gradient: no column matrix for this layer at all
-                hook = getattr(self, "event_hook", None)   # bench.py: HIP events around one named convolution launch
-                timed = hook is not None and hook[0] == c.name
-                if timed:
-                    e0 = torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                dh.conv_gemm_nt(x, B, c.H, c.W, c.cin, c.Ho, c.Wo, s, taps, self.wf[c.name], Kp, out, c.cout, c.cout,
-                                flags | dh.GEMM_BIAS, bias=bias, residual=residual)
-                if timed:
-                    e1 = torch.cuda.Event(enable_timing=True)
-                    e1.record()
-                    hook[1].append((e0, e1))
-                return
-            col = self.col
-            if self.keep_cols and c.kind != "final":
-                col = self.col_keep.get(c.name)
-                if col is None:
-                    col = self.col_keep[c.name] = torch.empty(B * c.Ho * c.Wo * Kp, dtype=torch.bfloat16, device=self.dev)
-                self._col_valid.add(c.name)
-            dh.im2col(x, col, B, c.H, c.W, c.cin, c.Ho, c.Wo, s, taps, Kp)
-            dh.gemm_nt(col, Kp, self.wf[c.name], Kp, out, c.cout, B * c.Ho * c.Wo, c.cout, Kp, flags | dh.GEMM_BIAS,
-                       bias=bias, residual=residual)
-        else:  # up: 4 output-parity GEMMs + interleave
-            Kp = _ru(4 * c.cin, 64)
+        if c.kind == "up":      # 4 output-parity GEMMs + interleave
             Mi = B * c.H * c.W
-            for p in range(4):
-                taps = [(t[1], t[2]) for t in _parity(p)]
-                if c.cin % 64 == 0:
-                    dh.conv_gemm_nt(x, B, c.H, c.W, c.cin, c.H, c.W, 1, taps, self.wp[c.name][p], Kp, self.par[p * Mi * c.cout:],
-                                    c.cout, c.cout, dh.GEMM_BIAS, bias=bias)
-                    continue
-                dh.im2col(x, self.col, B, c.H, c.W, c.cin, c.H, c.W, 1, taps, Kp)
-                dh.gemm_nt(self.col, Kp, self.wp[c.name][p], Kp, self.par[p * Mi * c.cout:], c.cout, Mi, c.cout, Kp, dh.GEMM_BIAS, bias=bias)
+            for q, t in enumerate(c.fwd):
+                self._tap_product(t, x, self.wp[c.name][q], self.par[q * Mi * c.cout:], dh.GEMM_BIAS, bias=bias)
             dh.pixel_interleave(self.par, out, B, c.H, c.W, c.cout)
+            return
+        t, = c.fwd
+        col = None
+        if self.keep_cols and c.kind != "final" and not t.implicit:     # the weight gradient of this step reads the column again
+            col = self.col_keep.get(c.name)
+            if col is None:
+                col = self.col_keep[c.name] = torch.empty(B * t.Ho * t.Wo * t.Kp, dtype=torch.bfloat16, device=self.dev)
+            self._col_valid.add(c.name)
+            self._gather(t, x, col)
+        hook = self.event_hook          # bench.py: HIP events around one named implicit convolution launch
+        timed = hook is not None and hook[0] == c.name and t.implicit
+        if timed:
+            e0 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+        self._tap_product(t, x, self.wf[c.name], out, flags | dh.GEMM_BIAS, col=col, bias=bias, residual=residual)
+        if timed:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record()
+            hook[1].append((e0, e1))
 
     # ------------------------------------------------------------------ forward
+    def _units(self, lo, hi):
+        """convs[lo:hi] as the units every pass walks: (i, layer, None) for a down / up / final layer on its own, (i, conv_in,
+        conv_out) for the residual pair at i, i + 1"""
+        i = lo
+        while i < hi:
+            c = self.convs[i]
+            pair = c.kind == "res"
+            yield i, c, self.convs[i + 1] if pair else None
+            i += 2 if pair else 1
+
+    def _run_layers(self, lo, hi, x):
+        """forward of convs[lo:hi] from x: fills act_in / act_out and returns the last output"""
+        for i, c, c_out in self._units(lo, hi):
+            self.act_in[i] = x
+            if c_out is None:
+                self._conv_fwd(c, x, self.act_out[i])
+                x = self.act_out[i]
+            else:  # residual pair: conv_in (bias+relu), conv_out (bias + residual x)
+                self._conv_fwd(c, x, self.act_out[i], flags=dh.GEMM_RELU)
+                self.act_in[i + 1] = self.act_out[i]
+                self._conv_fwd(c_out, self.act_out[i], self.act_out[i + 1], flags=dh.GEMM_RESIDUAL, residual=x)
+                x = self.act_out[i + 1]
+        return x
+
     def forward(self, features, return_recon_loss=False, return_logits=False, hard_gumbel=True, temperature=1.0, noise=None,
                 need_grad=None):
         """features: images NHWC fp32 in [-1,1] (or {"inputs": ...}).  Mirrors vae_tf/models.py:165-184.
@@ -501,22 +401,7 @@ class DiscreteVAE:
             img = self.img_st          # the loss is permutation-invariant: computed in the stacked layout
         self.img_net = img
         dh.pad_channels(img, self.x_img, Np, self.c_st, self.img_cp)
-        x = self.x_img
-        convs = self.convs
-        i = 0
-        while i < self.n_enc:
-            c = convs[i]
-            self.act_in[i] = x
-            if c.kind == "down":
-                self._conv_fwd(c, x, self.act_out[i])
-                x = self.act_out[i]
-                i += 1
-            else:  # residual pair: conv_in (bias+relu), conv_out (bias + residual x)
-                self._conv_fwd(c, x, self.act_out[i], flags=dh.GEMM_RELU)
-                self.act_in[i + 1] = self.act_out[i]
-                self._conv_fwd(convs[i + 1], self.act_out[i], self.act_out[i + 1], flags=dh.GEMM_RESIDUAL, residual=x)
-                x = self.act_out[i + 1]
-                i += 2
+        x = self._run_layers(0, self.n_enc, self.x_img)
         self.x_enc = x
         if self.vq_on:
             return self._forward_vq(return_recon_loss, return_logits, need_grad)
@@ -577,29 +462,13 @@ class DiscreteVAE:
     def _decoder_from_y(self):
         """decoder (vae_tf/models.py:123-163) on self.y [Mg, num_tokens] (soft / hard one-hot): y @ codebook^T, then per reversed
         block a 4x4 s2 conv-transpose and the residual stacks, final 1x1 conv -> self.out_pad"""
-        convs = self.convs
         dh.gemm_nt(self.y, self.num_tokens, self._w("codebook/codebook"), self.num_tokens, self.xdec, self.n_hid, self.Mg, self.n_hid,
                    self.num_tokens)
         return self._decoder_from_xdec()
 
     def _decoder_from_xdec(self):
         """the decoder's convolutions on self.xdec [Mg, n_hid] -> self.out_pad"""
-        convs = self.convs
-        x = self.xdec
-        i = self.n_enc
-        while i < len(convs):
-            c = convs[i]
-            self.act_in[i] = x
-            if c.kind in ("up", "final"):
-                self._conv_fwd(c, x, self.act_out[i])
-                x = self.act_out[i]
-                i += 1
-            else:
-                self._conv_fwd(c, x, self.act_out[i], flags=dh.GEMM_RELU)
-                self.act_in[i + 1] = self.act_out[i]
-                self._conv_fwd(convs[i + 1], self.act_out[i], self.act_out[i + 1], flags=dh.GEMM_RESIDUAL, residual=x)
-                x = self.act_out[i + 1]
-                i += 2
+        x = self._run_layers(self.n_enc, len(self.convs), self.xdec)
         self.out_pad = x
         return x
 
@@ -633,7 +502,7 @@ class DiscreteVAE:
         takes when the VAE tokenises images for DALL-E (src/model_fns.py:43-51 builds it without use_bf16; encoder
         src/vae_tf/models.py:81-120).  Forward only.  Returns logits [B, g, g, num_tokens] fp32."""
         B, dev = self.B, self.dev
-        if getattr(self, "_f32", None) is None:
+        if self._f32 is None:
             mx = max(B * c.Ho * c.Wo * c.cout for c in self.convs[:self.n_enc])
             self._f32 = dict(x=torch.empty(B * self.Hs * self.Hs, self.img_cp, dtype=torch.float32, device=dev),
                              a=[torch.empty(mx, dtype=torch.float32, device=dev) for _ in range(3)])
@@ -643,26 +512,21 @@ class DiscreteVAE:
         x, free = f["x"], list(f["a"])
 
         def conv(c, xin, out, relu=False, residual=None):
-            taps, st = (TAPS4, 2) if c.kind == "down" else (TAPS3, 1)
-            dh.conv2d_f32(xin, B, c.H, c.W, c.cin, c.Ho, c.Wo, st, taps, self.view(self.p, c.name + "/kernel"),
+            t, = c.fwd
+            dh.conv2d_f32(xin, B, t.H, t.W, t.C, t.Ho, t.Wo, t.stride, t.taps, self.view(self.p, c.name + "/kernel"),
                           self.view(self.p, c.name + "/bias"), residual, out, c.cout, relu=relu)
-        i = 0
-        while i < self.n_enc:
-            c = self.convs[i]
-            if c.kind == "down":
+        for _, c, c_out in self._units(0, self.n_enc):
+            if c_out is None:
                 out = free.pop(0)
                 conv(c, x, out)
                 if x is not f["x"]:
                     free.append(x)
-                x = out
-                i += 1
             else:
                 h, out = free.pop(0), free.pop(0)
                 conv(c, x, h, relu=True)
-                conv(self.convs[i + 1], h, out, residual=x)
+                conv(c_out, h, out, residual=x)
                 free.extend([h, x])
-                x = out
-                i += 2
+            x = out
         if self.vq_on:
             self.x_enc_f32 = x   # fp32 [Mg, n_hid] at the front of one of the path's scratch buffers, until its next call (read by the tests)
         dh.conv2d_f32(x, self.Mg, 1, 1, self.n_hid, 1, 1, 1, [(0, 0)], self.view(self.p, "codebook/codebook"), None, None,
@@ -696,79 +560,36 @@ class DiscreteVAE:
 
     def _wgrad(self, c: _Conv, x_in, dy, defer=False):
         """dW[(k,ci)][co] = col(x)^T . dy (+ bias gradient fused) -- lands directly in the TF kernel layout."""
-        B = self.B
         ws, dfr = self._defer_ws(defer)
-        if c.kind == "final":
-            dh.gemm_tn(x_in, c.cin, dy, c.cout, self._gv(c.name + "/kernel"), B * c.H * c.W, c.cin, c.cout, ws,
-                       dbias=self._gv(c.name + "/bias"), deferred=dfr)
-            return
-        K = c.kk * c.cin
-        Kp = _ru(K, 64)
-        taps, s = (TAPS4, 2) if c.kind == "down" else (TAPS3, 1)
-        if self._implicit_ok(c):
-            dh.conv_wgrad_tn(x_in, B, c.H, c.W, c.cin, c.Ho, c.Wo, s, taps, dy, c.cout, c.cout, self._gv(c.name + "/kernel"),
-                             ws, dbias=self._gv(c.name + "/bias"), deferred=dfr)
-            return
-        col = self.col
-        if c.name in self._col_valid:        # the forward pass of this step left col(x_in) in its kept buffer
-            col = self.col_keep[c.name]
-        else:
-            dh.im2col(x_in, col, B, c.H, c.W, c.cin, c.Ho, c.Wo, s, taps, Kp)
-        dh.gemm_tn(col, Kp, dy, c.cout, self._gv(c.name + "/kernel"), B * c.Ho * c.Wo, K, c.cout, ws,
-                   dbias=self._gv(c.name + "/bias"), deferred=dfr)
+        col = self.col_keep[c.name] if c.name in self._col_valid else None    # the forward pass of this step kept col(x_in)
+        self._tap_wgrad(c.wgrad, x_in, dy, self._gv(c.name + "/kernel"), ws, dfr, dbias=self._gv(c.name + "/bias"), col=col)
 
     def _dgrad3(self, c: _Conv, dy, out, flags=0, residual=None, relu_src=None):
-        Kp = _ru(9 * c.cout, 64)
-        if c.cout % 64 == 0:   # implicit im2col: the 9x column matrix of dy never exists in HBM (bit-identical results)
-            dh.conv_gemm_nt(dy, self.B, c.H, c.W, c.cout, c.H, c.W, 1, TAPS3_REV, self.wd[c.name], Kp, out, c.cin, c.cin, flags,
-                            residual=residual, relu_src=relu_src)
-            return
-        dh.im2col(dy, self.col, self.B, c.H, c.W, c.cout, c.H, c.W, 1, TAPS3_REV, Kp)
-        dh.gemm_nt(self.col, Kp, self.wd[c.name], Kp, out, c.cin, self.B * c.H * c.W, c.cin, Kp, flags, residual=residual, relu_src=relu_src)
+        self._tap_product(c.dgrad[0], dy, self.wd[c.name], out, flags, residual=residual, relu_src=relu_src)
 
     def _up_backward(self, c: _Conv, x_in, dz, out, defer=False):
         """backward of the transposed conv z = conv2d_transpose(y) (vae_tf/models.py:133-137): a stride-2 4x4 SAME conv of dz.
-        dW[kh,kw,Cout,Cin] and dbias into g, dy [B*H*W, cin] into `out`."""
-        B = self.B
-        Mi = B * c.H * c.W
-        Kz = 16 * c.cout
-        Kzp = _ru(Kz, 64)
-        p2 = lambda v: v > 0 and (v & (v - 1)) == 0
+        dW[kh,kw,Cout,Cin] and dbias into g, dy [B*H*W, cin] into `out`.  Both products read one gather of dz."""
+        t = c.wgrad
         ws, dfr = self._defer_ws(defer)
-        if c.cout % 64 == 0 and p2(c.H) and p2(c.W):
-            # both GEMMs gather dz implicitly
-            dh.colsum(dz, c.cout, self._gv(c.name + "/bias"), B * c.Ho * c.Wo, c.cout, self.ws_cs)
-            dh.conv_wgrad_tn(dz, B, c.Ho, c.Wo, c.cout, c.H, c.W, 2, TAPS4, x_in, c.cin, c.cin,
-                             self._gv(c.name + "/kernel"), ws, deferred=dfr)
-            dh.conv_gemm_nt(dz, B, c.Ho, c.Wo, c.cout, c.H, c.W, 2, TAPS4, self.wd[c.name], Kzp, out, c.cin, c.cin)
-        else:
-            dh.im2col(dz, self.col, B, c.Ho, c.Wo, c.cout, c.H, c.W, 2, TAPS4, Kzp)     # stride-2 conv view of dz
-            dh.colsum(dz, c.cout, self._gv(c.name + "/bias"), B * c.Ho * c.Wo, c.cout, self.ws_cs)
-            dh.gemm_tn(self.col, Kzp, x_in, c.cin, self._gv(c.name + "/kernel"), Mi, Kz, c.cin, ws, deferred=dfr)
-            dh.gemm_nt(self.col, Kzp, self.wd[c.name], Kzp, out, c.cin, Mi, c.cin, Kzp)
+        col = None if t.implicit else self._gather(t, dz)       # stride-2 conv view of dz
+        dh.colsum(dz, c.cout, self._gv(c.name + "/bias"), self.B * c.Ho * c.Wo, c.cout, self.ws_cs)
+        self._tap_wgrad(t, dz, x_in, self._gv(c.name + "/kernel"), ws, dfr, col=col)
+        self._tap_product(t, dz, self.wd[c.name], out, col=col)
 
     def _dgrad_down(self, c: _Conv, dy, out):
         """input gradient of the 4x4 stride-2 SAME conv (vae_tf/models.py:90-92) = its transposed conv: 4 output-parity GEMMs
         over the 2x2 contributing taps + a pixel interleave; dy [B*Ho*Wo, cout] -> out [B*H*W, cin]."""
-        B = self.B
-        Mo = B * c.Ho * c.Wo
-        Kp = _ru(4 * c.cout, 64)
-        for p in range(4):
-            taps = [(t[1], t[2]) for t in _parity(p)]
-            if c.cout % 64 == 0:
-                dh.conv_gemm_nt(dy, B, c.Ho, c.Wo, c.cout, c.Ho, c.Wo, 1, taps, self.wp[c.name][p], Kp,
-                                self.par[p * Mo * c.cin:], c.cin, c.cin)
-                continue
-            dh.im2col(dy, self.col, B, c.Ho, c.Wo, c.cout, c.Ho, c.Wo, 1, taps, Kp)
-            dh.gemm_nt(self.col, Kp, self.wp[c.name][p], Kp, self.par[p * Mo * c.cin:], c.cin, Mo, c.cin, Kp)
-        dh.pixel_interleave(self.par, out, B, c.Ho, c.Wo, c.cin)
+        Mo = self.B * c.Ho * c.Wo
+        for q, t in enumerate(c.dgrad):
+            self._tap_product(t, dy, self.wp[c.name][q], self.par[q * Mo * c.cin:], 0)
+        dh.pixel_interleave(self.par, out, self.B, c.Ho, c.Wo, c.cin)
 
     def backward(self):
         """Gradients of the last forward(return_recon_loss=True) into the flat fp32 buffer `g`."""
-        B, convs = self.B, self.convs
+        B = self.B
         d = self.ga                       # gradient wrt the padded reconstruction [M0, 64]
         spare = [self.gb, self.gc]
-        i = len(convs) - 1
         mark = [self.total]               # g[mark, total) has been handed to the exchange
 
         def ready_down_to(off):           # the layout follows the forward order, backward finishes it from the end
@@ -777,43 +598,36 @@ class DiscreteVAE:
                     self._flush_reduces()  # the exchange takes g[off, mark): its pending slab reduces must have landed
                 self.reducer.ready(off, mark[0])
                 mark[0] = off
-        while i >= 0:
-            c = convs[i]
-            lowest = convs[i - 1] if c.kind == "res" else c     # a residual pair is processed as one unit
+        for i, c, c_out in reversed(list(self._units(0, len(self.convs)))):     # (a residual pair is processed as one unit)
             if c.kind == "final":
                 M = B * c.H * c.W
                 self._wgrad(c, self.act_in[i], d, defer=True)
                 nd = spare[0]
                 dh.gemm_nt(d, c.cout, self._w(c.name + "/kernel"), c.cout, nd, c.cin, M, c.cin, c.cout)   # K = 64 padded channels
                 spare[0], d = d, nd
-                i -= 1
-            elif c.kind == "res":           # c = conv_out of a residual pair (i-1 = conv_in)
-                cin_conv = convs[i - 1]
-                x_in, r = self.act_in[i - 1], self.act_in[i]
+            elif c_out is not None:         # residual pair: c = conv_in at i, c_out = conv_out at i + 1
+                x_in, r = self.act_in[i], self.act_in[i + 1]
                 if self.recompute_grad:      # re-run the branch's first conv into the shared buffer (bit-identical to the forward)
-                    self._conv_fwd(cin_conv, x_in, r, flags=dh.GEMM_RELU)
-                self._wgrad(c, r, d, defer=True)
+                    self._conv_fwd(c, x_in, r, flags=dh.GEMM_RELU)
+                self._wgrad(c_out, r, d, defer=True)
                 da = spare[0]
-                self._dgrad3(c, d, da, flags=dh.GEMM_RELU_MASK, relu_src=r)
-                self._wgrad(cin_conv, x_in, da, defer=True)
+                self._dgrad3(c_out, d, da, flags=dh.GEMM_RELU_MASK, relu_src=r)
+                self._wgrad(c, x_in, da, defer=True)
                 nd = spare[1]
-                self._dgrad3(cin_conv, da, nd, flags=dh.GEMM_RESIDUAL, residual=d)
+                self._dgrad3(c, da, nd, flags=dh.GEMM_RESIDUAL, residual=d)
                 spare[1], d = d, nd
-                i -= 2
             elif c.kind == "up":
                 nd = spare[0]
                 self._up_backward(c, self.act_in[i], d, nd, defer=True)
                 spare[0], d = d, nd
-                i -= 1
             else:  # down
                 self._wgrad(c, self.act_in[i], d, defer=True)
                 if i > 0:
                     nd = spare[0]
                     self._dgrad_down(c, d, nd)
                     spare[0], d = d, nd
-                i -= 1
-            ready_down_to(self.offset[lowest.name + "/kernel"])
-            if i == self.n_enc - 1 and self.vq_on:
+            ready_down_to(self.offset[c.name + "/kernel"])
+            if i == self.n_enc and self.vq_on:
                 # ---- VQ bottleneck: straight-through d plus the commitment gradient to the encoder, the codebook loss to the codebook
                 T, nh, Mg = self.num_tokens, self.n_hid, self.Mg
                 nd = spare[0]
@@ -822,7 +636,7 @@ class DiscreteVAE:
                     dh.vq_codebook_grad(self.x_enc, nh, self.index, self.codebook_t, nh, self._gv("codebook/codebook"), Mg, T, nh, self.ws_vq)
                 spare[0], d = d, nd
                 ready_down_to(self.offset["codebook/codebook"])
-            elif i == self.n_enc - 1:
+            elif i == self.n_enc:
                 # ---- tied codebook + gumbel (between decoder and encoder); d = gradient wrt xdec [Mg, n_hid]
                 T, nh, Mg = self.num_tokens, self.n_hid, self.Mg
                 dh.gemm_tn(d, nh, self.y, T, self.gc2, Mg, nh, T, self.ws)                               # dC from x_dec = y C^T
@@ -887,7 +701,7 @@ class DiscreteVAE:
         the eager step (tested).  Returns the device scalar loss."""
         want = (os.environ.get("DALLE_VAE_GRAPH", "1") != "0") if graph is None else bool(graph)
         img = features["inputs"] if isinstance(features, dict) else features
-        if not want or self.world > 1 or getattr(self, "event_hook", None) is not None:
+        if not want or self.world > 1 or self.event_hook is not None:
             self.forward(img, return_recon_loss=True, hard_gumbel=hard_gumbel, temperature=temperature, noise=noise, need_grad=True)
             self.backward()
             self.optimizer_step(lr)
@@ -977,7 +791,7 @@ class DiscreteVAE:
               "m": self.m.detach().cpu(), "v": self.v.detach().cpu(), "global_step": self.global_step}
         if self.vq_on:       # only when on: a checkpoint without the key is a Gumbel one
             sd["quantizer"] = "vq"
-        ema = getattr(self, "vq_ema", None)
+        ema = getattr(self, "vq_ema", None)     # (getattr: tests/test_vae_vq.py calls these two on a stand-in without EMA attributes)
         if ema is not None:  # likewise: a VQ checkpoint without these was trained by the codebook gradient
             sd["vq_codebook"] = "ema"
             sd["vq_ema"] = {k: ema[k].detach().cpu() for k in VQ_EMA_STATE_KEYS}

@@ -12,6 +12,7 @@ Tolerances (bf16 compute, fp32 accumulation):
     are exact in fp32, only the accumulation order differs).
 The bit-identity tests against the explicit im2col path (tests/test_kernels_gpu.py) stay as implementation checks; THESE are
 the parity tests.  The whole-model test at the end runs configs/vae_coco.json end to end (one image) against both oracles."""
+import functools
 import json
 import os
 
@@ -22,6 +23,7 @@ import torch
 import dalle_hip as dh
 from oracle import vae_oracle as vo
 from parity import save_report
+import vae_conv_parity as vcp
 import vae_kernels_ref as vkr
 
 pytestmark = pytest.mark.gpu
@@ -50,39 +52,8 @@ def _conv(vae, name):
     return c
 
 
-def _bf(t):
-    return t.to(torch.bfloat16)
-
-
-def _rnd(*shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return _bf(torch.randn(*shape, generator=g) * scale)
-
-
-def _check_bf16(name, got, ref):
-    got, ref = got.double().flatten(), ref.double().flatten()
-    rel = float((got - ref).norm() / ref.norm())
-    rms = float(ref.pow(2).mean().sqrt())
-    worst = float(((got - ref).abs() - 2.0 ** -7 * ref.abs()).max())     # 2 bf16 ulp of the value
-    REPORT[name] = dict(rel_l2=rel, worst_excess_over_2ulp=worst, rms=rms)
-    print(name, REPORT[name], flush=True)
-    assert rel <= 2.1e-3, (name, rel)
-    assert worst <= 2.0 ** -8 * rms, (name, worst, rms)
-
-
-def _check_f32(name, got, ref, tol=1e-5):
-    got, ref = got.double().flatten(), ref.double().flatten()
-    rel = float((got - ref).norm() / ref.norm())
-    REPORT[name] = dict(rel_l2=rel)
-    print(name, REPORT[name], flush=True)
-    assert rel <= tol, (name, rel)
-
-
-def _weights(vae, P, c):
-    """the bf16 kernel/bias the product computes with, as fp32 oracle tensors (TF layouts)"""
-    k = _bf(torch.tensor(P[c.name + "/kernel"])).float().requires_grad_(True)
-    b = _bf(torch.tensor(P[c.name + "/bias"])).float().requires_grad_(True)
-    return k, b
+_bf, _rnd, _weights = vcp.bf, vcp.rnd, vcp.weights
+_check_bf16, _check_f32 = functools.partial(vcp.check_bf16, REPORT), functools.partial(vcp.check_f32, REPORT)
 
 
 @pytest.mark.parametrize("layer", [

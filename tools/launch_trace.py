@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Records what DalleEngine asks of libdalle_hip, so that two versions of the host code can be compared exactly.
+"""Records what DalleEngine and DiscreteVAE ask of libdalle_hip, so that two versions of the host code can be compared exactly.
 
 After dh.lib() the loaded library is swapped for a proxy that notes every dmi_* call: the entry's name, the value of every
 argument that is not declared c_void_p, and null / non-null ("-" / "*") for every pointer (the stream is the last one: null =
@@ -14,6 +14,11 @@ keep the file small, calls are numbers into the sorted table of distinct calls t
 folded: an item is a call, or [n, [items]] for n repeats in a row (`unfold` restores it).  Two runs of the same host code on
 the same library give the same file; --pkg selects the tree whose `src` / `dalle_hip` packages are imported (the library
 itself: DALLE_HIP_LIB).
+
+The configurations under vae/ build a DiscreteVAE instead: init_params(seed=3), three train_steps on seeded images and Gumbel
+uniforms (by default the eager warm step, the graph capture and a replay), one evaluation forward, the logits with fp32_tokens off
+and on, decode_tokens of seeded ids and codebook_stats(); SHA-256 of the three losses, p, g, m, v, the evaluation loss and
+reconstruction, both logits, the decoded images and index, and the statistics themselves.
 
     python tools/launch_trace.py --out trace.jsonl [--pkg OTHER/dalle-mtf_amd] [--only NAME ...]
 """
@@ -34,6 +39,7 @@ HEADLINE = dict(n_embd=512, n_layers=2, n_heads=4, text_vocab=50258, image_vocab
                 sample=None, evaluate=False)
 SAMPLER = dict(SMALL, image_vocab=64, B=4)
 SHAPES = dict(small=SMALL, wide=WIDE, headline=HEADLINE, sample=SAMPLER)    # a configuration's name starts with its shape's
+VAE_TINY = dict(num_tokens=64, dimensions=32, convblocks=[[1, 64]], batch_size=2)
 
 
 def configurations():
@@ -72,6 +78,21 @@ def configurations():
         c["small/" + name] = dict(SMALL, P=64, hp=hp)
     for name, hp in (("token_shift", shift), ("ff_glu", glu), ("qk_norm_axial", qk_axial)):
         c["sample/" + name] = dict(SAMPLER, P=64, hp=hp, sample={})
+    # DiscreteVAE: the shipped shapes, the layers that materialise their column matrix (unaligned channels, grids that are no power
+    # of two), space_to_depth, then every option of the step on one tiny model, then the eager step
+    shipped = {}
+    for name in ("vae_example", "vae_coco"):
+        p = json.load(open(os.path.join(ROOT, "configs", name + ".json")))
+        shipped[name] = dict(num_tokens=p["num_tokens"], dimensions=p["dataset"]["image_size"], convblocks=p["convblocks"], batch_size=1)
+        c["vae/" + name] = dict(model=shipped[name])
+    c["vae/unaligned"] = dict(model=dict(num_tokens=64, dimensions=16, convblocks=[[2, 16], [2, 64]], batch_size=2))
+    c["vae/nonpow2"] = dict(model=dict(num_tokens=64, dimensions=24, convblocks=[[2, 64], [2, 128]], batch_size=2))
+    c["vae/stacked"] = dict(model=dict(num_tokens=64, dimensions=32, convblocks=[[2, 64], [2, 64]], batch_size=2, stack_factor=2))
+    for name, kw in (("recompute", dict(recompute_grad=True)), ("kl", dict(kl_loss_weight=0.5, kl_anneal_steps=4)),
+                     ("vq", dict(quantizer="vq")), ("vq_ema", dict(quantizer="vq", vq_ema_decay=0.99, vq_restart_after=2))):
+        c["vae/tiny_" + name] = dict(model=dict(VAE_TINY, **kw))
+    c["vae/vae_example_eager"] = dict(model=shipped["vae_example"], graph=False)
+    c["vae/nonpow2_recompute"] = dict(model=dict(c["vae/nonpow2"]["model"], recompute_grad=True))   # residual pairs re-run in backward()
     return c
 
 
@@ -156,7 +177,41 @@ def sha(t):
     return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
 
 
+def run_vae(name, cfg, rec):
+    import numpy as np
+    import torch
+    from oracle import vae_oracle as vo
+    from src.vae_tf import DiscreteVAE
+    rec.reset()
+    vae = DiscreteVAE(mode="train", **cfg["model"])
+    vae.init_params(seed=3)
+    B, T, grid = vae.B, vae.num_tokens, vae.grid
+    digest = {}
+    for step in range(3):
+        img = torch.from_numpy(vo.synthetic_images(B, vae.H, seed=20 + step)).cuda()
+        noise = None if vae.vq_on else torch.from_numpy(vo.synthetic_uniforms((B, grid, grid, T), seed=30 + step))
+        digest[f"loss{step}"] = sha(vae.train_step(img, 1e-3, noise=noise, graph=cfg.get("graph")))
+    digest.update(p=sha(vae.p), g=sha(vae.g), m=sha(vae.m), v=sha(vae.v))
+    loss, recon = vae.forward(img, return_recon_loss=True, noise=noise, need_grad=False)
+    digest.update(eval_loss=sha(loss), reconstruction=sha(recon))
+    for fp32 in (False, True):
+        vae.fp32_tokens = fp32
+        digest["logits_fp32" if fp32 else "logits"] = sha(vae.forward(img, return_logits=True))
+    vae.fp32_tokens = False
+    ids = torch.from_numpy(np.random.default_rng(40).integers(0, T, size=(B, grid * grid)))
+    digest["decoded"] = sha(vae.decode_tokens(ids))
+    stats = vae.codebook_stats()
+    digest["index"] = sha(vae.index)
+    torch.cuda.synchronize()
+    line = dict(name=name, config=cfg, launches=list(rec.sequence), queries=dict(rec.queries), sha256=digest, codebook_stats=stats)
+    del vae
+    torch.cuda.empty_cache()
+    return line
+
+
 def run(name, cfg, rec):
+    if name.startswith("vae/"):
+        return run_vae(name, cfg, rec)
     import numpy as np
     import torch
     from oracle import dalle_oracle as do
@@ -206,7 +261,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--out", help="the JSON-lines file to write")
     ap.add_argument("--pkg", default=os.path.join(ROOT, "dalle-mtf_amd"), help="the tree whose src / dalle_hip packages are traced")
-    ap.add_argument("--only", nargs="*", help="configuration names (default: all)")
+    ap.add_argument("--only", nargs="*", help="configuration names, or prefixes ending in / (default: all)")
     ap.add_argument("--list", action="store_true")
     a = ap.parse_args()
     cfgs = configurations()
@@ -227,13 +282,14 @@ def main():
         setattr(dh, fn, counted)
     lines = []
     for name, cfg in cfgs.items():
-        if not a.only or name in a.only:
+        if not a.only or name in a.only or any(o.endswith("/") and name.startswith(o) for o in a.only):
             lines.append(run(name, cfg, rec))
             print(f"[launch_trace] {name}: {len(lines[-1]['launches'])} launches", flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     write(a.out, rec.table, lines)
-    print("[launch_trace] dh wrappers named by engine.py that no configuration reached:",
-          sorted(n for n in named if inspect.isfunction(getattr(dh, n, None)) and n not in reached), flush=True)
+    if any(not line["name"].startswith("vae/") for line in lines):
+        print("[launch_trace] dh wrappers named by engine.py that no configuration reached:",
+              sorted(n for n in named if inspect.isfunction(getattr(dh, n, None)) and n not in reached), flush=True)
 
 
 if __name__ == "__main__":
