@@ -15,6 +15,7 @@
 // No transposed operand copies: K / V / Q / dO tiles land in LDS in their natural layout by LDS-DMA (swizzled on the
 // source side) and every transposed fragment (V^T, K^T, Q^T, dO^T) is a hardware transpose read (ds_read_b64_tr_b16).
 #include "common.h"
+#include "attn_plan.h"
 #include <type_traits>
 #include <algorithm>
 #include <string.h>
@@ -195,13 +196,18 @@ __device__ __forceinline__ void fr3_wait(Fr3& f) {
   asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(f.q), "+v"(f.d), "+v"(f.v) : "n"(N) : "memory");
 }
 
-extern int g_opt_attn_xcd;
+extern AttnOptions g_attn_opt;   // both in host.hip.  What an entry point accepts and how it launches: attn_plan.h
+extern GemmOptions g_opt;        // (reserve_cus: CUs the persistent grids leave to concurrent kernels)
 #ifdef ATTN_STAMP
 extern unsigned long long* g_dbg_buf;
 #endif
-extern int g_opt_attn_fwd;      // 0: the round-2 forward kernel, 1 (default): the software-pipelined round-6 kernel (A/B switch)
-extern int g_opt_attn_bwd;      // backward kernels: bit 0 = whole-row epilogue stores through LDS (A/B switch)
-extern int g_opt_reserve_cus;   // CUs the persistent grids leave to concurrent kernels (csrc/gemm.hip)
+#define ATTN_HEAD_DIM_CHECK(name)                                                    \
+  do {                                                                               \
+    if (!attn_head_dim_ok(head_dim)) {                                               \
+      dmi_set_error("%s: head_dim must be 64 or 128 (head_dim=%d)", name, head_dim); \
+      return DMI_ERR_UNSUPPORTED;                                                    \
+    }                                                                                \
+  } while (0)
 // Persistent-block schedule: the grid is one (dK/dV) or two (forward, dQ) blocks per CU; hardware block L (dispatched to XCD L % 8) owns
 // bin k = L / 8 of its XCD.  The XCD's work items -- (tile, batch*head) for its contiguous eighth of the (batch, head) pairs,
 // sorted heaviest tile first -- are dealt to the bins in serpentine order (round 0: bins 0..P-1, round 1: P-1..0, ...): with
@@ -268,19 +274,16 @@ __device__ __forceinline__ void store_rows_via_lds(char* strip, const f32x16 (&a
 //   column bitmap [S][W]    bit b of word w of row j = M[32 w + b][j] (partial dK/dV tiles).
 // A tile no query of a block attends to is never loaded.  Bits of keys >= S are 0, so a tile that reaches past S is partial.
 //
-// The round-2 forward, the dQ and the decode kernel are templates on MASKED: one source per operation, which differs between
-// the instances only in which key tiles an item walks, what a wave does with a tile, and the predicate.  Instances:
-//   attn_fwd_kernel<false | true>, attn_bwd_dq_kernel<0 | 1, false> and <1, true>, attn_decode_kernel<128 | 64, false> and <128, true>.
-// MASKED = false compiles to the code the causal kernels compiled to before they were templates (profiles/attn_merge_isa.txt); the
+// The round-2 forward, the dQ, the dK/dV and the decode kernels are templates on MASKED: one source per operation, which differs
+// between the instances only in which tiles an item walks, what a wave does with a tile, and the predicate.  Instances:
+//   attn_fwd_kernel<false | true>, attn_bwd_dq_kernel<0 | 1, false> and <1, true>, attn_bwd_dkv_kernel<0 | 1, false> and <1, true>,
+//   attn_decode_kernel and attn_decode_kv8_kernel<128 | 64, false> and <128, true>.
+// Every instance compiles to the code its kernel compiled to before it was a template (profiles/attn_merge_isa.txt,
+// profiles/attn_dkv_merge_isa.txt; how to repeat the comparison: tools/isa_diff.py); the
 // masked instances keep the buffer layouts, the unscaled fp32 softmax, the tile shapes and the persistent schedule.  The plan
 // pointer is a kernel argument of the masked instances only (a kernel's argument offsets are part of its code): PLAN is one
-// `const int*` there and an empty pack otherwise.  The masked dK/dV kernel is still a kernel of its own (attn_bwd_dkv_masked_kernel).
-#define AMP_MAGIC 0x504d4144
-#define AMP_HDR 32
-enum {
-  AMP_S = 1, AMP_NB, AMP_W, AMP_CAUSAL, AMP_FPTR, AMP_FLIST, AMP_KPTR, AMP_KLIST, AMP_FORDER, AMP_KORDER, AMP_ROWBITS, AMP_COLBITS,
-  AMP_WORDS, AMP_LIVE_F, AMP_CAUSAL_F, AMP_LIVE_K, AMP_CAUSAL_K
-};
+// `const int*` there and an empty pack otherwise.
+// The header words (AMP_MAGIC, AMP_HDR, AMP_S ...) and the route of a plan: attn_plan.h.
 
 // row bits of a plan entry's tile for one wave: keys 64 j + 0..31 and + 32..63 of this lane's query row `mrow` if the wave's
 // sub-tile is partial (words past the row read as 0), all ones otherwise
@@ -975,39 +978,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_kernel(const bf16_t* __restr
 #endif
 }
 
-static int attn_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) n = p.multiProcessorCount;
-    else n = 256;
-  }
-  const int m = (n - g_opt_reserve_cus) & ~7;     // persistent grids: leave the reserved CUs free, keep a multiple of 8
-  return m < 8 ? 8 : m;
-}
-
-extern "C" int dmi_attention_fwd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int H, int S, void* stream) {
-  DMI_REQUIRE(qkv && o && lse, "attention_fwd: null pointer");
-  DMI_REQUIRE(B > 0 && H > 0 && S > 0 && S % 8 == 0, "attention_fwd: S must be a multiple of 8 (S=%d)", S);
-  DMI_REQUIRE((int64_t)S * 3 * H * HD * 2 < 0x7fffffff, "attention_fwd: sequence too long for 32-bit buffer offsets");
-  raise_lds_once<attn_fwd_kernel<false>>(2 * QK_STAGE);
-  raise_lds_once<attn_fwd2_kernel>(2 * QK_STAGE);
-  {
-    const int items = ((S + 127) / 128) * B * H;
-    const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();   // two persistent blocks per CU
-    const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
-    if (g_opt_attn_fwd == 0) attn_fwd_kernel<false><<<dim3(grid), dim3(256), 2 * QK_STAGE, (hipStream_t)stream>>>(qkv, o, lse, B, H, S, perxcd);
-#ifdef ATTN_STAMP
-    else attn_fwd2_kernel<<<dim3(grid), dim3(256), 2 * QK_STAGE, (hipStream_t)stream>>>(qkv, o, lse, B, H, S, perxcd, g_dbg_buf);
-#else
-    else attn_fwd2_kernel<<<dim3(grid), dim3(256), 2 * QK_STAGE, (hipStream_t)stream>>>(qkv, o, lse, B, H, S, perxcd);
-#endif
-  }
-  DMI_CHECK_LAUNCH("attention_fwd");
-  return DMI_OK;
-}
-
 // =====================================================================================
 // backward
 // =====================================================================================
@@ -1310,17 +1280,44 @@ __device__ __forceinline__ void st8_wait(St8& f) {
                : "n"(N)
                : "memory");
 }
-template <int rowstore>
+// MASKED: the same kernel walking a key block's live 32-query tiles (instantiated with rowstore = 1 only).  Every tile applies the
+// column bitmap word of this lane's key (bit = query row within the tile) with a select; a full tile takes an all-ones word without
+// a load.  A key block no query attends to (nsteps = 0) writes zero dK / dV.
+template <int rowstore, bool MASKED, typename... PLAN>
 __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ d_o,
                                                                const float* __restrict__ stats /* [B,H,S,2] (lse * log2 e, delta) */,
-                                                               bf16_t* __restrict__ dqkv, int B, int H, int S, int perxcd) {
+                                                               bf16_t* __restrict__ dqkv, PLAN __restrict__... plan_, int B, int H, int S, int perxcd) {
+  static_assert(sizeof...(PLAN) == (MASKED ? 1 : 0), "the plan pointer is an argument of the masked instance only");
+  static_assert(rowstore || !MASKED, "the masked instance has the whole-row epilogue only");
   extern __shared__ __attribute__((aligned(16))) char sm[];  // V 32768 | 4 x DKV_STAGE
   const int d = H * HD, ld3 = 3 * d;
-  const AttnSched sched = attn_sched((S + 127) / 128, B * H, perxcd);
-  int ktile, bh;
+  int T = (S + 127) / 128, W = 0;
+  const int* __restrict__ kptr = nullptr;
+  const int* __restrict__ klist = nullptr;
+  const int* __restrict__ korder = nullptr;
+  const unsigned* __restrict__ colbits = nullptr;
+  if constexpr (MASKED) {
+    const int* __restrict__ plan = (plan_, ...);
+    T = plan[AMP_NB], W = plan[AMP_W];
+    kptr = plan + plan[AMP_KPTR];
+    klist = plan + plan[AMP_KLIST];
+    korder = plan + plan[AMP_KORDER];
+    colbits = (const unsigned*)(plan + plan[AMP_COLBITS]);
+  }
+  const AttnSched sched = attn_sched(T, B * H, perxcd);
+  int tile_, bh;
   // persistent loop over this block's work items; every step of an item ends with a barrier, so the next item may overwrite
   // the LDS straight away
-  for (int round = 0; attn_item(sched, round, ktile, bh); ++round) {
+  for (int round = 0; attn_item(sched, round, tile_, bh); ++round) {
+  // what an item is: a key block and the 32-query tiles it walks -- causal: from its diagonal to the last one (nsteps below);
+  // masked: the block's list in the plan
+  int ktile = tile_, nsteps = 0;
+  const int* __restrict__ list = nullptr;
+  if constexpr (MASKED) {
+    ktile = korder[tile_];
+    list = klist + kptr[ktile];
+    nsteps = kptr[ktile + 1] - kptr[ktile];
+  }
   const int b = bh / H, hh = bh % H;
   const int key0 = ktile * 128;
   int tid = threadIdx.x;
@@ -1340,6 +1337,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
   const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)qb, 0, (int)(((int64_t)(S - 1) * ld3 + HD) * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rdo = __builtin_amdgcn_make_buffer_rsrc((void*)dob, 0, (int)(((int64_t)(S - 1) * d + HD) * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)vb, 0, (int)(((int64_t)(S - 1) * ld3 + HD) * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rcol = __builtin_amdgcn_make_buffer_rsrc((void*)colbits, 0, S * W * 4, 0x00020000);   // (masked only)
   const __amdgpu_buffer_rsrc_t rst = __builtin_amdgcn_make_buffer_rsrc((void*)(stats + (int64_t)bh * S * 2), 0, S * 8, 0x00020000);
 
   bf16x8 kf[8];
@@ -1391,7 +1389,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
       oft[dt][w2] = row * 256 + ((chunk ^ swz(row)) << 4) + 8 * (l16 & 1);
     }
 
-  f32x16 dv[4], dk[4];
+  f32x16 dv[4], dk[4];   // (a masked key block nobody attends to, nsteps = 0, writes these zeros)
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1402,7 +1400,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
 
   const int nqi = (S + 31) / 32;
   const int qi0 = key0 / 32;
-  const int nsteps = nqi - qi0;
+  if constexpr (!MASKED) nsteps = nqi - qi0;
+  // the query tile of step T (a macro: behind a lambda the causal prologue's offsets are folded in another order)
+#define DKV_QTILE(T) (MASKED ? list[T] & 0xffff : qi0 + (T))
 
   unsigned aq[8];   // natural-fragment addresses in stage slot 0; the same offsets address this wave's rows of the resident V tile
 #pragma unroll
@@ -1431,7 +1431,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
   // packed to bf16 (pw / dw = the B operands of the dV / dK MFMAs); the stats hold (lse * log2(e), delta) pairs.
   // MASK: only the four tiles that touch the block's diagonal need the causal predicate.  Rows past S need no mask: their
   // Q / dO rows and stats read as zeros (buffer bounds), so dS = 0 and P multiplies a zero dO row.
-  auto softmax_pair = [&](auto mask_c, int i, const St8& stt, const f32x16& s, const f32x16& dp, int kd, unsigned* pw, unsigned* dw) {
+  // `pred`: kd in the causal instances, the column word mw in the masked one (see body)
+  auto softmax_pair = [&](auto mask_c, int i, const St8& stt, const f32x16& s, const f32x16& dp, auto pred, unsigned* pw, unsigned* dw) {
     constexpr bool MASK = decltype(mask_c)::value;
 #ifdef ATTN_DBG_DKV_NOSOFTMAX     // experiment: what the softmax / dS VALU chain of phase A costs (upper bound of any re-placement)
     pw[i] = pack2bf(s[2 * i], s[2 * i + 1]);
@@ -1443,9 +1444,13 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
     const f32x4 sv = stt.v[i];                  // (l2, delta) of rows 8g + 4h + 2(i&1) + {0, 1}
     float x0 = __builtin_fmaf(s[2 * i], LOG2E_F, -sv[0]);
     float x1 = __builtin_fmaf(s[2 * i + 1], LOG2E_F, -sv[2]);
-    if constexpr (MASK) {
-      x0 = (kd > 8 * g + 2 * (i & 1)) ? -INFINITY : x0;   // key > query
-      x1 = (kd > 8 * g + 2 * (i & 1) + 1) ? -INFINITY : x1;
+    if constexpr (MASK && !MASKED) {
+      x0 = (pred > 8 * g + 2 * (i & 1)) ? -INFINITY : x0;   // key > query
+      x1 = (pred > 8 * g + 2 * (i & 1) + 1) ? -INFINITY : x1;
+    } else if constexpr (MASK) {   // bit (query row in the tile) of the column word selects the score or -inf.  The word is pre-shifted
+      const int qb0 = 8 * g + 2 * (i & 1);   // by 4h: the bit positions are immediates (lane-dependent shifts were hoisted, 16 registers)
+      x0 = (pred & (1u << qb0)) ? x0 : -INFINITY;
+      x1 = (pred & (2u << qb0)) ? x1 : -INFINITY;
     }
     const float p0 = __builtin_amdgcn_exp2f(x0), p1 = __builtin_amdgcn_exp2f(x1);
     const float q0 = p0 * (dp[2 * i] - sv[1]), q1 = p1 * (dp[2 * i + 1] - sv[3]);
@@ -1465,7 +1470,17 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
     tr4_issue_off<8192>(tdo, ta);
     tr4_issue_off<0>(tq, ta);
     unsigned pw[8], dw[8];
-    const int kd = krow - 32 * qi - 4 * h;   // key - (first query row of this lane in the tile)
+    std::conditional_t<MASKED, unsigned, int> pred = 0;   // what softmax_pair's predicate tests
+    if constexpr (!MASKED) {
+      pred = krow - 32 * qi - 4 * h;   // kd = key - (first query row of this lane in the tile)
+    } else if constexpr (decltype(mask_c)::value) {
+      // mw = the column word of this lane's key for this tile (~0 for a full tile), pre-shifted by 4h, by a buffer load with the tile
+      // in the scalar offset.  Loaded here: a word prefetched a step ahead, a 64-bit address kept across the loop, or a second,
+      // unpredicated body for full tiles each pushed this 512-register kernel into spills.  The cost: hipcc waits for the word with
+      // a vmcnt(0), which on a partial tile also drains the DMA of tile t + 2 (issued a step earlier) before the softmax.
+      const int kr = key0 + wid * 32 + (tid & 31);
+      pred = ((list[t] >> 16) & 1) ? __builtin_amdgcn_raw_buffer_load_b32(rcol, (kr < S ? kr : S - 1) * (4 * W), 4 * qi, 0) >> (4 * h) : 0xffffffffu;
+    }
     if constexpr (has_next) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) sn[e] = dpn[e] = 0.f;
@@ -1479,18 +1494,19 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
         if (kk + 1 < 8) fr3_issue<0>(F[(kk + 1) & 1], aq[kk + 1] + so, aq[kk + 1] + vrel);
         sn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, c.q), kf[kk], sn, 0, 0, 0);
         dpn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, c.d), __builtin_bit_cast(bf16x8, c.v), dpn, 0, 0, 0);
-        softmax_pair(mask_c, kk, stt, s, dp, kd, pw, dw);
+        softmax_pair(mask_c, kk, stt, s, dp, pred, pw, dw);
         // one MFMA, then half of the pair's VALU chain (two independent elements interleaved: a single resident wave has
-        // nothing else to cover the VALU / transcendental latencies), twice
+        // nothing else to cover the VALU / transcendental latencies), twice.  4 + 6 VALU per MFMA pair; the masked predicate's
+        // select adds two per element: 6 + 8
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, MASKED ? 6 : 4, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, MASKED ? 8 : 6, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
     } else {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) softmax_pair(mask_c, i, stt, s, dp, kd, pw, dw);
+      for (int i = 0; i < 8; ++i) softmax_pair(mask_c, i, stt, s, dp, pred, pw, dw);
     }
     bf16x8 pb[2], dsb[2];
     pb[0] = __builtin_bit_cast(bf16x8, u32x4{pw[0], pw[1], pw[2], pw[3]});
@@ -1501,7 +1517,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
     // Fragment sets: (tdo, tq) hold the first 16 queries (in since the top of the step); t2 takes dO^T of the second 16,
     // then tdo's registers are reused for Q^T of the second 16.
     const bool do_dma = t + 3 < nsteps;
-    const int st3 = (st + 3) & 3, q3 = 32 * (qi + 3);
+    const int st3 = (st + 3) & 3;
+    int q3 = 32 * (qi + 3);   // first query of the tile three steps ahead
+    if constexpr (MASKED) q3 = do_dma ? 32 * DKV_QTILE(t + 3) : 0;
     Tr4 t2;
     {
       tr4_wait(tq);   // (tdo, tq) of the first 16 queries
@@ -1538,9 +1556,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
 
   // Ring: at the barrier that opens step t, tiles t and t+1 have landed (every wave waited for its own DMAs), tile t+2 is
   // in flight; step t issues tile t+3 into the slot of tile t-1, whose last reader (dV / dK of step t-1) is behind the barrier.
-  if (nsteps > 0) stage(0, 32 * qi0);
-  if (nsteps > 1) stage(1, 32 * (qi0 + 1));
-  if (nsteps > 2) stage(2, 32 * (qi0 + 2));
+  if (nsteps > 0) stage(0, 32 * DKV_QTILE(0));
+  if (nsteps > 1) stage(1, 32 * DKV_QTILE(1));
+  if (nsteps > 2) stage(2, 32 * DKV_QTILE(2));
   if (nsteps > 2) DKV_WAIT(5); else DKV_WAIT(0);
   DKV_BARRIER();
   if (nsteps > 0) {
@@ -1548,19 +1566,24 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
     sdp_only(0, sA, dpA);   // (its final lgkmcnt(0) covers the stats reads)
   }
   int t = 0;
+  // (masked: the plan entry of step t, tile | partial << 16, is read before the ring slot is worked out and the tile taken from it
+  // after -- the order the masked copy had; it decides ties in the instruction schedule)
 #define DKV_STEP(CS, CD, NS, ND, NEXT, MASK)                                \
   {                                                                         \
-    body(t & 3, qi0 + t, t, CS, CD, NS, ND, std::integral_constant<bool, NEXT>{}, std::integral_constant<bool, MASK>{}); \
+    const int ent = MASKED ? list[t] : t;                                   \
+    body(t & 3, MASKED ? ent & 0xffff : qi0 + ent, t, CS, CD, NS, ND, std::integral_constant<bool, NEXT>{}, std::integral_constant<bool, MASK>{}); \
     if (nsteps - 1 - t >= 3) DKV_WAIT(5); else DKV_WAIT(0);                 \
     DKV_BARRIER();                                                          \
     ++t;                                                                    \
   }
-  // tiles 0..3 of a block touch its diagonal (masked variant); pairs of steps keep the A / B accumulator roles fixed
-  while (t < 4 && t + 3 <= nsteps) {
-    DKV_STEP(sA, dpA, sB, dpB, true, true) DKV_STEP(sB, dpB, sA, dpA, true, true)
-  }
+  // causal: tiles 0..3 of a block touch its diagonal (predicated variant), the tail arms may (a block of <= 4 tiles); masked: every
+  // tile is predicated.  Pairs of steps keep the A / B accumulator roles fixed
+  if constexpr (!MASKED)
+    while (t < 4 && t + 3 <= nsteps) {
+      DKV_STEP(sA, dpA, sB, dpB, true, true) DKV_STEP(sB, dpB, sA, dpA, true, true)
+    }
   while (t + 3 <= nsteps) {   // two steps that both have a successor
-    DKV_STEP(sA, dpA, sB, dpB, true, false) DKV_STEP(sB, dpB, sA, dpA, true, false)
+    DKV_STEP(sA, dpA, sB, dpB, true, MASKED) DKV_STEP(sB, dpB, sA, dpA, true, MASKED)
   }
   if (nsteps - t == 2) {
     DKV_STEP(sA, dpA, sB, dpB, true, true) DKV_STEP(sB, dpB, sA, dpA, false, true)
@@ -1568,6 +1591,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
     DKV_STEP(sA, dpA, sB, dpB, false, true)
   }
 #undef DKV_STEP
+#undef DKV_QTILE
 
   if constexpr (rowstore) {   // [r06] whole-row stores (every step ended with a barrier: the ring and the V tile have no readers left)
     bf16_t* gk = dqkv + ((int64_t)b * S + key0 + wid * 32) * ld3 + d + hh * HD;
@@ -1596,36 +1620,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const bf16_t* __re
 // pieces stored as the accumulators hold them, 8 bytes to 32 rows per instruction, 405 us, and 905 / 1820 us with write-through
 // stores: r04ag_*).  The pair moves 0.84 GB per layer through HBM; recomputing S and dP on the matrix cores costs less than that
 // traffic.  The code is on the git branch `r04-attn-two-pass`.
-extern "C" int dmi_attention_bwd(const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, float* delta,
-                                 uint16_t* dqkv, int B, int H, int S, void* stream) {
-  DMI_REQUIRE(qkv && o && d_o && lse && delta && dqkv, "attention_bwd: null pointer");
-  DMI_REQUIRE(B > 0 && H > 0 && S > 0 && S % 8 == 0, "attention_bwd: S must be a multiple of 8 (S=%d)", S);
-  DMI_REQUIRE((int64_t)S * 3 * H * HD * 2 < 0x7fffffff, "attention_bwd: sequence too long for 32-bit buffer offsets");
-  hipStream_t st = (hipStream_t)stream;
-  float* stats = delta + (int64_t)B * H * S;  // delta scratch is [3][B,H,S]: delta | (lse, delta) pairs
-  const int shm = 32768 + DKV_NSTAGE * DKV_STAGE;
-  raise_lds_once<attn_bwd_dq_kernel<0, false>>(2 * QK_STAGE);
-  raise_lds_once<attn_bwd_dq_kernel<1, false>>(2 * QK_STAGE);
-  raise_lds_once<attn_bwd_dkv_kernel<0>>(shm);
-  raise_lds_once<attn_bwd_dkv_kernel<1>>(shm);
-  const int items = ((S + 127) / 128) * B * H;
-  {
-    const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();   // two persistent blocks per CU
-    const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
-    if (g_opt_attn_bwd & 1) attn_bwd_dq_kernel<1, false><<<dim3(grid), dim3(256), 2 * QK_STAGE, st>>>(qkv, o, d_o, lse, delta, stats, dqkv, B, H, S, perxcd);
-    else attn_bwd_dq_kernel<0, false><<<dim3(grid), dim3(256), 2 * QK_STAGE, st>>>(qkv, o, d_o, lse, delta, stats, dqkv, B, H, S, perxcd);
-  }
-  DMI_CHECK_LAUNCH("attention_bwd_dq");
-  {
-    const int grid = items < attn_num_cus() ? items : attn_num_cus();   // one persistent block per CU
-    const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
-    if (g_opt_attn_bwd & 1) attn_bwd_dkv_kernel<1><<<dim3(grid), dim3(256), shm, st>>>(qkv, d_o, stats, dqkv, B, H, S, perxcd);
-    else attn_bwd_dkv_kernel<0><<<dim3(grid), dim3(256), shm, st>>>(qkv, d_o, stats, dqkv, B, H, S, perxcd);
-  }
-  DMI_CHECK_LAUNCH("attention_bwd_dkv");
-  return DMI_OK;
-}
-
 // =====================================================================================
 // incremental decode: ONE query position against the key/value cache  
 // =====================================================================================
@@ -1805,8 +1799,9 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void attn_decode_kernel(bf16_t* qkv
 // the three decode entry points: one set of checks, one launch (plan != nullptr: the masked instance, head dim 128 only -- amp_route)
 static int attn_decode_launch(const char* name, uint16_t* qkv, const uint16_t* fresh, uint16_t* o, const int* plan, int B, int H, int S,
                               int pos, const int* pos_dev, int head_dim, void* stream) {
+  ATTN_HEAD_DIM_CHECK(name);
   DMI_REQUIRE(qkv && o, "%s: null pointer", name);
-  DMI_REQUIRE(B > 0 && H > 0 && S > 0, "%s: bad shape", name);
+  DMI_REQUIRE(attn_sizes_ok(B, H, S), "%s: bad shape", name);
   DMI_REQUIRE(pos_dev || (pos >= 0 && pos < S), "%s: need 0 <= pos < S (pos=%d, S=%d)", name, pos, S);
   const dim3 grid((unsigned)(B * H)), block(64 * DEC_WAVES);
   hipStream_t st = (hipStream_t)stream;
@@ -1820,6 +1815,10 @@ static int attn_decode_launch(const char* name, uint16_t* qkv, const uint16_t* f
 extern "C" int dmi_attention_decode(uint16_t* qkv, const uint16_t* fresh, uint16_t* o, int B, int H, int S, int pos, const int* pos_dev,
                                     void* stream) {
   return attn_decode_launch("attention_decode", qkv, fresh, o, nullptr, B, H, S, pos, pos_dev, 128, stream);
+}
+extern "C" int dmi_attention_decode_hd(uint16_t* qkv, const uint16_t* fresh, uint16_t* o, int B, int H, int S, int pos, const int* pos_dev,
+                                       int head_dim, void* stream) {
+  return attn_decode_launch("attention_decode", qkv, fresh, o, nullptr, B, H, S, pos, pos_dev, head_dim, stream);
 }
 
 // =====================================================================================
@@ -1843,9 +1842,8 @@ extern "C" int dmi_attention_decode(uint16_t* qkv, const uint16_t* fresh, uint16
 #define A64_STAGE 16384      // forward / dQ stage: K 8192 | V 8192 (64 keys x 128 B)
 #define A64_DKV_STAGE 8448   // dK/dV stage: Q 4096 | dO 4096 (32 queries x 128 B) | (lse * log2 e, delta) pairs 256
 #define A64_PITCH 144        // epilogue strip pitch: 32 rows x 128 B (+16: 16-byte aligned rows for the ds_read_b128 read-back)
-#define A64_FWD_WAVES 3      // waves per SIMD (= blocks per CU of 256 threads) the kernels are built for: 168 registers (at four, 128
-#define A64_DQ_WAVES 3       // registers, both spilled: 10 and 32 VGPRs)
-#define A64_DKV_WAVES 2
+// A64_FWD_WAVES / A64_DQ_WAVES / A64_DKV_WAVES (attn_plan.h): waves per SIMD (= blocks per CU of 256 threads) the kernels are built
+// for -- 3, 3, 2: 168 registers (at four, 128 registers, both spilled: 10 and 32 VGPRs)
 __device__ __forceinline__ int swz64(int row) { return (((row >> 1) & 1) << 2) | ((row >> 2) & 3); }
 
 // Epilogue of a wave's 32 x 64 result (two 32x32 accumulators, lane (r, h) owns row r, acc[dt][e] is column 32 dt + (e & 3) + 8 (e >> 2)
@@ -2314,332 +2312,11 @@ __global__ __launch_bounds__(256, A64_DKV_WAVES) void attn64_bwd_dkv_kernel(cons
   }   // items
 }
 
-// ---- C ABI with a head-dim argument: 128 -> the calls above, 64 -> the kernels of this section (decode: the <64, false> instance)
-#define A64_HEAD_DIM_CHECK(name)                                                                             \
-  do {                                                                                                       \
-    if (head_dim != 64 && head_dim != 128) {                                                                 \
-      dmi_set_error(name ": head_dim must be 64 or 128 (head_dim=%d)", head_dim);                             \
-      return DMI_ERR_UNSUPPORTED;                                                                            \
-    }                                                                                                        \
-  } while (0)
-static int a64_grid(int items, int blocks_per_cu) {   // persistent grid: blocks_per_cu per CU left to these kernels, at most one per item
-  const int g = blocks_per_cu * attn_num_cus();
-  return items < g ? items : g;
-}
-
-extern "C" int dmi_attention_fwd_hd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int H, int S, int head_dim, void* stream) {
-  A64_HEAD_DIM_CHECK("attention_fwd");
-  if (head_dim == 128) return dmi_attention_fwd(qkv, o, lse, B, H, S, stream);
-  DMI_REQUIRE(qkv && o && lse, "attention_fwd: null pointer");
-  DMI_REQUIRE(B > 0 && H > 0 && S > 0 && S % 8 == 0, "attention_fwd: S must be a multiple of 8 (S=%d)", S);
-  DMI_REQUIRE(((int64_t)S + 64) * 3 * H * HD64 * 2 < 0x7fffffff, "attention_fwd: sequence too long for 32-bit buffer offsets");
-  const int grid = a64_grid(((S + 127) / 128) * B * H, A64_FWD_WAVES);
-  const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
-  attn64_fwd_kernel<<<dim3(grid), dim3(256), 2 * A64_STAGE, (hipStream_t)stream>>>((const bf16_t*)qkv, (bf16_t*)o, lse, B, H, S, perxcd);
-  DMI_CHECK_LAUNCH("attention_fwd");
-  return DMI_OK;
-}
-
-extern "C" int dmi_attention_bwd_hd(const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, float* delta,
-                                    uint16_t* dqkv, int B, int H, int S, int head_dim, void* stream) {
-  A64_HEAD_DIM_CHECK("attention_bwd");
-  if (head_dim == 128) return dmi_attention_bwd(qkv, o, d_o, lse, delta, dqkv, B, H, S, stream);
-  DMI_REQUIRE(qkv && o && d_o && lse && delta && dqkv, "attention_bwd: null pointer");
-  DMI_REQUIRE(B > 0 && H > 0 && S > 0 && S % 8 == 0, "attention_bwd: S must be a multiple of 8 (S=%d)", S);
-  DMI_REQUIRE(((int64_t)S + 64) * 3 * H * HD64 * 2 < 0x7fffffff, "attention_bwd: sequence too long for 32-bit buffer offsets");
-  hipStream_t st = (hipStream_t)stream;
-  float* stats = delta + (int64_t)B * H * S;  // delta scratch is [3][B,H,S]: delta | (lse, delta) pairs
-  const int items = ((S + 127) / 128) * B * H;
-  {
-    const int grid = a64_grid(items, A64_DQ_WAVES);
-    const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
-    attn64_bwd_dq_kernel<<<dim3(grid), dim3(256), 2 * A64_STAGE, st>>>((const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o, lse, delta,
-                                                                     stats, (bf16_t*)dqkv, B, H, S, perxcd);
-  }
-  DMI_CHECK_LAUNCH("attention_bwd_dq");
-  {
-    const int grid = a64_grid(items, A64_DKV_WAVES);
-    const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
-    const int shm = 4 * 32 * A64_PITCH > 2 * A64_DKV_STAGE ? 4 * 32 * A64_PITCH : 2 * A64_DKV_STAGE;
-    attn64_bwd_dkv_kernel<<<dim3(grid), dim3(256), shm, st>>>((const bf16_t*)qkv, (const bf16_t*)d_o, stats, (bf16_t*)dqkv, B, H, S, perxcd);
-  }
-  DMI_CHECK_LAUNCH("attention_bwd_dkv");
-  return DMI_OK;
-}
-
-extern "C" int dmi_attention_decode_hd(uint16_t* qkv, const uint16_t* fresh, uint16_t* o, int B, int H, int S, int pos, const int* pos_dev,
-                                       int head_dim, void* stream) {
-  A64_HEAD_DIM_CHECK("attention_decode");
-  return attn_decode_launch("attention_decode", qkv, fresh, o, nullptr, B, H, S, pos, pos_dev, head_dim, stream);
-}
-
 // =====================================================================================
-// custom attention masks, head dim 128: the masked dK/dV kernel, the plan builder and the C ABI
+// custom attention masks: the plan builder; the C ABI of the forward and the backward at either head dim, causal or with a plan
 // =====================================================================================
-// The plan format and the masked instances of the forward, dQ and decode kernels: "attention-mask plans" at the top of this file.
+// The plan format and the masked instances of the kernels (head dim 128): "attention-mask plans" at the top of this file.
 // A causal plan is routed to the causal entry points (so to the default kernels) unless the option attn_mask_force is set.
-extern int g_opt_attn_mask_force;   // 1: a causal plan runs the masked kernels too (tests, tools/attn_mask_bench.py)
-
-// ---- dK/dV: attn_bwd_dkv_kernel<1> (the software-pipelined 4-slot ring) walking a key block's live 32-query tiles.  Every tile
-// applies the column bitmap word of this lane's key (bit = query row within the tile) with a select; a full tile takes an all-ones
-// word without a load.  A key block no query attends to writes zero dK / dV.  One wave per SIMD.
-__global__ __launch_bounds__(256, 1) void attn_bwd_dkv_masked_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ d_o,
-                                                                     const float* __restrict__ stats, bf16_t* __restrict__ dqkv,
-                                                                     const int* __restrict__ plan, int B, int H, int S, int perxcd) {
-  extern __shared__ __attribute__((aligned(16))) char sm[];  // V 32768 | 4 x DKV_STAGE
-  const int d = H * HD, ld3 = 3 * d;
-  const int W = plan[AMP_W];
-  const int* __restrict__ kptr = plan + plan[AMP_KPTR];
-  const int* __restrict__ klist = plan + plan[AMP_KLIST];
-  const int* __restrict__ korder = plan + plan[AMP_KORDER];
-  const unsigned* __restrict__ colbits = (const unsigned*)(plan + plan[AMP_COLBITS]);
-  const AttnSched sched = attn_sched(plan[AMP_NB], B * H, perxcd);
-  int tile_, bh;
-  for (int round = 0; attn_item(sched, round, tile_, bh); ++round) {
-  const int ktile = korder[tile_];
-  const int* __restrict__ list = klist + kptr[ktile];
-  const int nsteps = kptr[ktile + 1] - kptr[ktile];
-  const int b = bh / H, hh = bh % H;
-  const int key0 = ktile * 128;
-  int tid = threadIdx.x;
-  asm volatile("" : "+v"(tid));
-  const int lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, h = lane >> 5, g4 = lane >> 4, l16 = lane & 15;
-  const int krow = key0 + wid * 32 + r;
-  const int krow_c = krow < S ? krow : S - 1;
-  const bf16_t* qb = qkv + (int64_t)b * S * ld3 + hh * HD;
-  const bf16_t* kb = qb + d;
-  const bf16_t* vb = qb + 2 * d;
-  const bf16_t* dob = d_o + (int64_t)b * S * d + hh * HD;
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
-
-  const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)qb, 0, (int)(((int64_t)(S - 1) * ld3 + HD) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rdo = __builtin_amdgcn_make_buffer_rsrc((void*)dob, 0, (int)(((int64_t)(S - 1) * d + HD) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc((void*)vb, 0, (int)(((int64_t)(S - 1) * ld3 + HD) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rcol = __builtin_amdgcn_make_buffer_rsrc((void*)colbits, 0, S * W * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rst = __builtin_amdgcn_make_buffer_rsrc((void*)(stats + (int64_t)bh * S * 2), 0, S * 8, 0x00020000);
-
-  bf16x8 kf[8];
-#pragma unroll
-  for (int kk = 0; kk < 8; ++kk) kf[kk] = *(const bf16x8*)(kb + (int64_t)krow_c * ld3 + 16 * kk + 8 * h);
-
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {   // resident V tile
-    const int c = tid + 256 * i, row = c >> 4, pc = c & 15;
-    int gr = key0 + row;
-    gr = gr < S ? gr : S - 1;
-    dma16(rv, sm + (wid * 64 + 256 * i) * 16, (gr * ld3 + 8 * (pc ^ swz(row))) * 2);
-  }
-  int voq[2], vod[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int c = tid + 256 * i, row = c >> 4, pc = c & 15;
-    voq[i] = (row * ld3 + 8 * (pc ^ swz(row))) * 2;
-    vod[i] = (row * d + 8 * (pc ^ swz(row))) * 2;
-  }
-  auto stage = [&](int st, int q0) {
-    char* base = sm + 32768 + st * DKV_STAGE;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      dma16(rq, base + (wid * 64 + 256 * i) * 16, voq[i] + q0 * ld3 * 2);
-      dma16(rdo, base + 8192 + (wid * 64 + 256 * i) * 16, vod[i] + q0 * d * 2);
-    }
-    dma4(rst, base + 16384, (q0 * 2 + lane) * 4);
-  };
-  auto stage_q = [&](int st, int q0, int i) {
-    char* base = sm + 32768 + st * DKV_STAGE;
-    dma16(rq, base + (wid * 64 + 256 * i) * 16, voq[i] + q0 * ld3 * 2);
-    dma16(rdo, base + 8192 + (wid * 64 + 256 * i) * 16, vod[i] + q0 * d * 2);
-  };
-  auto stage_st = [&](int st, int q0) {
-    dma4(rst, sm + 32768 + st * DKV_STAGE + 16384, (q0 * 2 + lane) * 4);
-  };
-  int ofa[8];
-#pragma unroll
-  for (int kk = 0; kk < 8; ++kk) ofa[kk] = r * 256 + (((2 * kk + h) ^ swz(r)) << 4);
-  const int rr = l16 >> 2;
-  unsigned oft[4][2];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int w2 = 0; w2 < 2; ++w2) {
-      const int row = 4 * h + rr + 8 * w2;
-      const int chunk = dt * 4 + 2 * (g4 & 1) + ((l16 & 3) >> 1);
-      oft[dt][w2] = row * 256 + ((chunk ^ swz(row)) << 4) + 8 * (l16 & 1);
-    }
-
-  f32x16 dv[4], dk[4];   // (a key block nobody attends to, nsteps = 0, writes these zeros)
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) dv[i][e] = dk[i][e] = 0.f;
-  f32x16 sA, dpA, sB, dpB;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) sA[e] = dpA[e] = sB[e] = dpB[e] = 0.f;
-
-  unsigned aq[8];
-#pragma unroll
-  for (int kk = 0; kk < 8; ++kk) aq[kk] = lds0 + 32768 + ofa[kk];
-  const unsigned vrel = (unsigned)(wid * 8192 - 32768);
-  auto sdp_only = [&](int st, f32x16& s, f32x16& dp) {
-    const unsigned so = st * DKV_STAGE;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) s[e] = dp[e] = 0.f;
-    Fr3 F[3];
-    fr3_issue<0>(F[0], aq[0] + so, aq[0] + vrel);
-    fr3_issue<0>(F[1], aq[1] + so, aq[1] + vrel);
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-      Fr3& c = F[kk % 3];
-      if (kk == 0) fr3_wait<3>(c);
-      else if (kk < 7) fr3_wait<3>(c, F[(kk + 2) % 3]);
-      else fr3_wait<0>(c, F[(kk + 2) % 3]);
-      if (kk + 2 < 8) fr3_issue<0>(F[(kk + 2) % 3], aq[kk + 2] + so, aq[kk + 2] + vrel);
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, c.q), kf[kk], s, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, c.d), __builtin_bit_cast(bf16x8, c.v), dp, 0, 0, 0);
-    }
-  };
-  // softmax + dS of the accumulator-element pair (2i, 2i+1) = query rows 8g + 4h + 2(i&1) + {0, 1} of the tile (g = i >> 1).
-  // (The phase-A interleave takes 6 + 8 VALU per MFMA pair instead of the causal kernel's 4 + 6: the select adds two per element.)
-  // MASK: bit (query row in the tile) of the lane's column word selects the score or -inf
-  auto softmax_pair = [&](auto mask_c, int i, const St8& stt, const f32x16& s, const f32x16& dp, unsigned mw, unsigned* pw, unsigned* dw) {
-    constexpr bool MASK = decltype(mask_c)::value;
-    const int g = i >> 1;
-    const f32x4 sv = stt.v[i];
-    float x0 = __builtin_fmaf(s[2 * i], LOG2E_F, -sv[0]);
-    float x1 = __builtin_fmaf(s[2 * i + 1], LOG2E_F, -sv[2]);
-    if constexpr (MASK) {   // mw is pre-shifted by 4h: the bit positions are immediates (lane-dependent shifts were hoisted, 16 registers)
-      const int qb0 = 8 * g + 2 * (i & 1);
-      x0 = (mw & (1u << qb0)) ? x0 : -INFINITY;
-      x1 = (mw & (2u << qb0)) ? x1 : -INFINITY;
-    }
-    const float p0 = __builtin_amdgcn_exp2f(x0), p1 = __builtin_amdgcn_exp2f(x1);
-    const float q0 = p0 * (dp[2 * i] - sv[1]), q1 = p1 * (dp[2 * i + 1] - sv[3]);
-    pw[i] = pack2bf(p0, p1);
-    dw[i] = pack2bf(q0, q1);
-    asm volatile("" : "+v"(pw[i]), "+v"(dw[i]));
-  };
-  St8 stt;
-  Tr4 tdo, tq;
-  auto body = [&](int st, int t, f32x16& s, f32x16& dp, f32x16& sn, f32x16& dpn, auto has_next_c, auto mask_c, int qi) {
-    constexpr bool has_next = decltype(has_next_c)::value;
-    const unsigned lb = lds0 + 32768 + st * DKV_STAGE;
-    const unsigned so = ((st + 1) & 3) * DKV_STAGE;
-    const unsigned ta[8] = {lb + oft[0][0], lb + oft[0][1], lb + oft[1][0], lb + oft[1][1], lb + oft[2][0], lb + oft[2][1], lb + oft[3][0], lb + oft[3][1]};
-    tr4_issue_off<8192>(tdo, ta);
-    tr4_issue_off<0>(tq, ta);
-    unsigned pw[8], dw[8];
-    // the column word of this lane's key for this tile (~0 for a full tile), pre-shifted by 4h, by a buffer load with the tile in
-    // the scalar offset.  Loaded here: a word prefetched a step ahead, a 64-bit address kept across the loop, or a second,
-    // unpredicated body for full tiles each pushed this 512-register kernel into spills.  The cost: hipcc waits for the word with
-    // a vmcnt(0), which on a partial tile also drains the DMA of tile t + 2 (issued a step earlier) before the softmax.
-    unsigned mw = 0u;
-    if constexpr (decltype(mask_c)::value) {
-      const int kr = key0 + wid * 32 + (tid & 31);
-      mw = ((list[t] >> 16) & 1) ? __builtin_amdgcn_raw_buffer_load_b32(rcol, (kr < S ? kr : S - 1) * (4 * W), 4 * qi, 0) >> (4 * h) : 0xffffffffu;
-    }
-    if constexpr (has_next) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) sn[e] = dpn[e] = 0.f;
-      Fr3 F[2];
-      fr3_issue<0>(F[0], aq[0] + so, aq[0] + vrel);
-#pragma unroll
-      for (int kk = 0; kk < 8; ++kk) {
-        Fr3& c = F[kk & 1];
-        if (kk == 0) fr3_wait<0>(c); else fr3_wait<0>(c, F[(kk + 1) & 1]);
-        if (kk + 1 < 8) fr3_issue<0>(F[(kk + 1) & 1], aq[kk + 1] + so, aq[kk + 1] + vrel);
-        sn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, c.q), kf[kk], sn, 0, 0, 0);
-        dpn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, c.d), __builtin_bit_cast(bf16x8, c.v), dpn, 0, 0, 0);
-        softmax_pair(mask_c, kk, stt, s, dp, mw, pw, dw);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) softmax_pair(mask_c, i, stt, s, dp, mw, pw, dw);
-    }
-    bf16x8 pb[2], dsb[2];
-    pb[0] = __builtin_bit_cast(bf16x8, u32x4{pw[0], pw[1], pw[2], pw[3]});
-    pb[1] = __builtin_bit_cast(bf16x8, u32x4{pw[4], pw[5], pw[6], pw[7]});
-    dsb[0] = __builtin_bit_cast(bf16x8, u32x4{dw[0], dw[1], dw[2], dw[3]});
-    dsb[1] = __builtin_bit_cast(bf16x8, u32x4{dw[4], dw[5], dw[6], dw[7]});
-    const bool do_dma = t + 3 < nsteps;
-    const int st3 = (st + 3) & 3, q3 = do_dma ? 32 * (list[t + 3] & 0xffff) : 0;
-    Tr4 t2;
-    {
-      tr4_wait(tq);
-      tr4_issue_off<8192 + 4096>(t2, ta);
-      dv[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.a0, tdo.a1), pb[0], dv[0], 0, 0, 0);   // dV^T[d][key]
-      dv[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.b0, tdo.b1), pb[0], dv[1], 0, 0, 0);
-      if (do_dma) stage_q(st3, q3, 0);
-      dv[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.c0, tdo.c1), pb[0], dv[2], 0, 0, 0);
-      dv[3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.d0, tdo.d1), pb[0], dv[3], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      tr4_issue_off<4096>(tdo, ta);
-      dk[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tq.a0, tq.a1), dsb[0], dk[0], 0, 0, 0);    // dK^T[d][key]
-      dk[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tq.b0, tq.b1), dsb[0], dk[1], 0, 0, 0);
-      if (do_dma) stage_q(st3, q3, 1);
-      dk[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tq.c0, tq.c1), dsb[0], dk[2], 0, 0, 0);
-      dk[3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tq.d0, tq.d1), dsb[0], dk[3], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      tr4_wait8(t2, tq);
-      if constexpr (has_next) st8_issue(stt, lds0 + 32768 + so + 16384 + 32 * h);
-      dv[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(t2.a0, t2.a1), pb[1], dv[0], 0, 0, 0);
-      dv[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(t2.b0, t2.b1), pb[1], dv[1], 0, 0, 0);
-      if (do_dma) stage_st(st3, q3);
-      dv[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(t2.c0, t2.c1), pb[1], dv[2], 0, 0, 0);
-      dv[3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(t2.d0, t2.d1), pb[1], dv[3], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (has_next) tr4_wait8(tdo, t2); else tr4_wait(tdo);
-      dk[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.a0, tdo.a1), dsb[1], dk[0], 0, 0, 0);
-      dk[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.b0, tdo.b1), dsb[1], dk[1], 0, 0, 0);
-      dk[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.c0, tdo.c1), dsb[1], dk[2], 0, 0, 0);
-      dk[3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cat2(tdo.d0, tdo.d1), dsb[1], dk[3], 0, 0, 0);
-      if constexpr (has_next) st8_wait<0>(stt);
-    }
-  };
-
-  if (nsteps > 0) stage(0, 32 * (list[0] & 0xffff));
-  if (nsteps > 1) stage(1, 32 * (list[1] & 0xffff));
-  if (nsteps > 2) stage(2, 32 * (list[2] & 0xffff));
-  if (nsteps > 2) DKV_WAIT(5); else DKV_WAIT(0);
-  DKV_BARRIER();
-  if (nsteps > 0) {
-    st8_issue(stt, lds0 + 32768 + 16384 + 32 * h);
-    sdp_only(0, sA, dpA);
-  }
-  int t = 0;
-#define DKVM_STEP(CS, CD, NS, ND, NEXT)                                                                          \
-  {                                                                                                             \
-    const int ent = list[t];                                                                                    \
-    body(t & 3, t, CS, CD, NS, ND, std::integral_constant<bool, NEXT>{}, std::true_type{}, ent & 0xffff); \
-    if (nsteps - 1 - t >= 3) DKV_WAIT(5); else DKV_WAIT(0);                                                     \
-    DKV_BARRIER();                                                                                              \
-    ++t;                                                                                                        \
-  }
-  while (t + 3 <= nsteps) {
-    DKVM_STEP(sA, dpA, sB, dpB, true) DKVM_STEP(sB, dpB, sA, dpA, true)
-  }
-  if (nsteps - t == 2) {
-    DKVM_STEP(sA, dpA, sB, dpB, true) DKVM_STEP(sB, dpB, sA, dpA, false)
-  } else if (nsteps - t == 1) {
-    DKVM_STEP(sA, dpA, sB, dpB, false)
-  }
-#undef DKVM_STEP
-
-  bf16_t* gk = dqkv + ((int64_t)b * S + key0 + wid * 32) * ld3 + d + hh * HD;
-  char* strip = sm + wid * (2 * 32 * ROWS_PITCH);
-  store_rows_via_lds(strip, dk, 1.0f, gk, ld3, S - (key0 + wid * 32), lane);
-  store_rows_via_lds(strip + 32 * ROWS_PITCH, dv, 1.0f, gk + d, ld3, S - (key0 + wid * 32), lane);
-  __syncthreads();
-  }   // items
-}
-
-// ---- host: the plan builder and the C ABI of the masked kernels
 extern "C" int64_t dmi_attn_mask_plan(const uint8_t* mask, int S, int32_t* plan, int64_t plan_bytes) {
   DMI_REQUIRE(mask, "attn_mask_plan: null mask");
   DMI_REQUIRE(S > 0 && S % 8 == 0 && S <= 65536, "attn_mask_plan: S must be a positive multiple of 8, at most 65536 (S=%d)", S);
@@ -2748,77 +2425,122 @@ extern "C" int64_t dmi_attn_mask_plan(const uint8_t* mask, int S, int32_t* plan,
   return bytes;
 }
 
-// the host copy of the plan (its header) decides the route: a causal plan runs the causal kernels unless attn_mask_force is set
+// the route of a *_masked entry (attn_route), as a status: 0 the masked kernels, 1 the causal entry points, < 0 an error
 static int amp_route(const int32_t* plan, const int32_t* plan_host, int S, int head_dim, const char* name) {
-  if (!plan || !plan_host) {
-    dmi_set_error("%s: null plan pointer", name);
-    return DMI_ERR_INVALID;
+  switch (attn_route(plan, plan_host, S, head_dim, g_attn_opt)) {
+    case AttnRoute::MASKED: return 0;
+    case AttnRoute::CAUSAL: return 1;
+    case AttnRoute::NULL_PLAN: dmi_set_error("%s: null plan pointer", name); return DMI_ERR_INVALID;
+    case AttnRoute::NOT_A_PLAN: dmi_set_error("%s: plan_host is not a mask plan (build it with dmi_attn_mask_plan)", name); return DMI_ERR_INVALID;
+    case AttnRoute::WRONG_S: dmi_set_error("%s: the plan was built for S=%d, called with S=%d", name, plan_host[AMP_S], S); return DMI_ERR_INVALID;
+    case AttnRoute::HEAD_DIM: break;
   }
-  if (plan_host[0] != AMP_MAGIC) {
-    dmi_set_error("%s: plan_host is not a mask plan (build it with dmi_attn_mask_plan)", name);
-    return DMI_ERR_INVALID;
-  }
-  if (plan_host[AMP_S] != S) {
-    dmi_set_error("%s: the plan was built for S=%d, called with S=%d", name, plan_host[AMP_S], S);
-    return DMI_ERR_INVALID;
-  }
-  if (plan_host[AMP_CAUSAL] && !g_opt_attn_mask_force) return 1;
-  if (head_dim != 128) {
-    dmi_set_error("%s: the masked attention kernels are built for head dim 128 (head_dim=%d); head dim 64 takes the causal mask only",
-                  name, head_dim);
-    return DMI_ERR_UNSUPPORTED;
-  }
-  return 0;
+  dmi_set_error("%s: the masked attention kernels are built for head dim 128 (head_dim=%d); head dim 64 takes the causal mask only", name,
+                head_dim);
+  return DMI_ERR_UNSUPPORTED;
 }
 
+// the kernels' dynamic LDS and residency are what attn_plan.h plans with
+static_assert(ATTN_QK_LDS == 2 * QK_STAGE && ATTN_DKV_LDS == 32768 + DKV_NSTAGE * DKV_STAGE && A64_QK_LDS == 2 * A64_STAGE &&
+              A64_DKV_LDS == 4 * 32 * A64_PITCH && A64_DKV_LDS >= 2 * A64_DKV_STAGE);
+
+// ---- forward: one set of checks, one launch (plan != nullptr: the masked instance, head dim 128 only -- amp_route)
+static int attn_fwd_launch(const char* name, const uint16_t* qkv, uint16_t* o, float* lse, const int* plan, int B, int H, int S, int head_dim,
+                           void* stream) {
+  ATTN_HEAD_DIM_CHECK(name);
+  DMI_REQUIRE(qkv && o && lse, "%s: null pointer", name);
+  DMI_REQUIRE(attn_shape_ok(B, H, S), "%s: S must be a multiple of 8 (S=%d)", name, S);
+  DMI_REQUIRE(attn_offsets_fit(H, S, head_dim), "%s: sequence too long for 32-bit buffer offsets", name);
+  const AttnLaunch l = attn_launch(AttnOp::FWD, B, H, S, head_dim, g_attn_opt, g_opt, num_cus());
+  const dim3 grid(l.grid), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (head_dim == 64) {
+    attn64_fwd_kernel<<<grid, block, l.lds, st>>>(qkv, o, lse, B, H, S, l.perxcd);
+  } else if (plan) {
+    raise_lds_once<attn_fwd_kernel<true, const int*>>(l.lds);
+    attn_fwd_kernel<true, const int*><<<grid, block, l.lds, st>>>(qkv, o, lse, plan, B, H, S, l.perxcd);
+  } else {
+    raise_lds_once<attn_fwd_kernel<false>>(l.lds);
+    raise_lds_once<attn_fwd2_kernel>(l.lds);
+    if (!attn_fwd_pipelined(false, g_attn_opt)) attn_fwd_kernel<false><<<grid, block, l.lds, st>>>(qkv, o, lse, B, H, S, l.perxcd);
+#ifdef ATTN_STAMP
+    else attn_fwd2_kernel<<<grid, block, l.lds, st>>>(qkv, o, lse, B, H, S, l.perxcd, g_dbg_buf);
+#else
+    else attn_fwd2_kernel<<<grid, block, l.lds, st>>>(qkv, o, lse, B, H, S, l.perxcd);
+#endif
+  }
+  DMI_CHECK_LAUNCH(name);
+  return DMI_OK;
+}
+extern "C" int dmi_attention_fwd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int H, int S, void* stream) {
+  return attn_fwd_launch("attention_fwd", qkv, o, lse, nullptr, B, H, S, 128, stream);
+}
+extern "C" int dmi_attention_fwd_hd(const uint16_t* qkv, uint16_t* o, float* lse, int B, int H, int S, int head_dim, void* stream) {
+  return attn_fwd_launch("attention_fwd", qkv, o, lse, nullptr, B, H, S, head_dim, stream);
+}
 extern "C" int dmi_attention_fwd_masked(const uint16_t* qkv, uint16_t* o, float* lse, const int32_t* plan, const int32_t* plan_host,
                                         int B, int H, int S, int head_dim, void* stream) {
   DMI_REQUIRE(qkv && o && lse, "attention_fwd_masked: null pointer");
   const int rt = amp_route(plan, plan_host, S, head_dim, "attention_fwd_masked");
   if (rt < 0) return rt;
-  if (rt == 1) return dmi_attention_fwd_hd(qkv, o, lse, B, H, S, head_dim, stream);
-  DMI_REQUIRE(B > 0 && H > 0 && S > 0 && S % 8 == 0, "attention_fwd_masked: S must be a multiple of 8 (S=%d)", S);
-  DMI_REQUIRE((int64_t)S * 3 * H * HD * 2 < 0x7fffffff, "attention_fwd_masked: sequence too long for 32-bit buffer offsets");
-  raise_lds_once<attn_fwd_kernel<true, const int*>>(2 * QK_STAGE);
-  const int items = ((S + 127) / 128) * B * H;
-  const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();   // two persistent blocks per CU
-  const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
-  attn_fwd_kernel<true, const int*><<<dim3(grid), dim3(256), 2 * QK_STAGE, (hipStream_t)stream>>>((const bf16_t*)qkv, (bf16_t*)o, lse,
-                                                                                                 (const int*)plan, B, H, S, perxcd);
-  DMI_CHECK_LAUNCH("attention_fwd_masked");
-  return DMI_OK;
+  return attn_fwd_launch(rt ? "attention_fwd" : "attention_fwd_masked", qkv, o, lse, rt ? nullptr : plan, B, H, S, head_dim, stream);
 }
 
+// ---- backward: the dQ kernel (which also writes delta and the (lse, delta) pairs), then the dK/dV kernel
+static int attn_bwd_launch(const char* name, const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, float* delta,
+                           uint16_t* dqkv, const int* plan, int B, int H, int S, int head_dim, void* stream) {
+  ATTN_HEAD_DIM_CHECK(name);
+  DMI_REQUIRE(qkv && o && d_o && lse && delta && dqkv, "%s: null pointer", name);
+  DMI_REQUIRE(attn_shape_ok(B, H, S), "%s: S must be a multiple of 8 (S=%d)", name, S);
+  DMI_REQUIRE(attn_offsets_fit(H, S, head_dim), "%s: sequence too long for 32-bit buffer offsets", name);
+  hipStream_t st = (hipStream_t)stream;
+  float* stats = delta + (int64_t)B * H * S;  // delta scratch is [3][B,H,S]: delta | (lse, delta) pairs
+  const AttnLaunch q = attn_launch(AttnOp::DQ, B, H, S, head_dim, g_attn_opt, g_opt, num_cus());
+  const AttnLaunch k = attn_launch(AttnOp::DKV, B, H, S, head_dim, g_attn_opt, g_opt, num_cus());
+  const dim3 qgrid(q.grid), kgrid(k.grid), block(256);
+  const int rowstore = attn_bwd_rowstore(plan != nullptr, g_attn_opt);
+  if (head_dim == 64) {
+    attn64_bwd_dq_kernel<<<qgrid, block, q.lds, st>>>(qkv, o, d_o, lse, delta, stats, dqkv, B, H, S, q.perxcd);
+    DMI_CHECK_LAUNCH("attention_bwd_dq");
+    attn64_bwd_dkv_kernel<<<kgrid, block, k.lds, st>>>(qkv, d_o, stats, dqkv, B, H, S, k.perxcd);
+    DMI_CHECK_LAUNCH("attention_bwd_dkv");
+  } else if (plan) {
+    raise_lds_once<attn_bwd_dq_kernel<1, true, const int*>>(q.lds);
+    raise_lds_once<attn_bwd_dkv_kernel<1, true, const int*>>(k.lds);
+    attn_bwd_dq_kernel<1, true, const int*><<<qgrid, block, q.lds, st>>>(qkv, o, d_o, lse, delta, stats, dqkv, plan, B, H, S, q.perxcd);
+    DMI_CHECK_LAUNCH("attention_bwd_dq_masked");
+    attn_bwd_dkv_kernel<1, true, const int*><<<kgrid, block, k.lds, st>>>(qkv, d_o, stats, dqkv, plan, B, H, S, k.perxcd);
+    DMI_CHECK_LAUNCH("attention_bwd_dkv_masked");
+  } else {
+    raise_lds_once<attn_bwd_dq_kernel<0, false>>(q.lds);
+    raise_lds_once<attn_bwd_dq_kernel<1, false>>(q.lds);
+    raise_lds_once<attn_bwd_dkv_kernel<0, false>>(k.lds);
+    raise_lds_once<attn_bwd_dkv_kernel<1, false>>(k.lds);
+    if (rowstore) attn_bwd_dq_kernel<1, false><<<qgrid, block, q.lds, st>>>(qkv, o, d_o, lse, delta, stats, dqkv, B, H, S, q.perxcd);
+    else attn_bwd_dq_kernel<0, false><<<qgrid, block, q.lds, st>>>(qkv, o, d_o, lse, delta, stats, dqkv, B, H, S, q.perxcd);
+    DMI_CHECK_LAUNCH("attention_bwd_dq");
+    if (rowstore) attn_bwd_dkv_kernel<1, false><<<kgrid, block, k.lds, st>>>(qkv, d_o, stats, dqkv, B, H, S, k.perxcd);
+    else attn_bwd_dkv_kernel<0, false><<<kgrid, block, k.lds, st>>>(qkv, d_o, stats, dqkv, B, H, S, k.perxcd);
+    DMI_CHECK_LAUNCH("attention_bwd_dkv");
+  }
+  return DMI_OK;
+}
+extern "C" int dmi_attention_bwd(const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, float* delta,
+                                 uint16_t* dqkv, int B, int H, int S, void* stream) {
+  return attn_bwd_launch("attention_bwd", qkv, o, d_o, lse, delta, dqkv, nullptr, B, H, S, 128, stream);
+}
+extern "C" int dmi_attention_bwd_hd(const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, float* delta,
+                                    uint16_t* dqkv, int B, int H, int S, int head_dim, void* stream) {
+  return attn_bwd_launch("attention_bwd", qkv, o, d_o, lse, delta, dqkv, nullptr, B, H, S, head_dim, stream);
+}
 extern "C" int dmi_attention_bwd_masked(const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, float* delta,
                                         uint16_t* dqkv, const int32_t* plan, const int32_t* plan_host, int B, int H, int S, int head_dim,
                                         void* stream) {
   DMI_REQUIRE(qkv && o && d_o && lse && delta && dqkv, "attention_bwd_masked: null pointer");
   const int rt = amp_route(plan, plan_host, S, head_dim, "attention_bwd_masked");
   if (rt < 0) return rt;
-  if (rt == 1) return dmi_attention_bwd_hd(qkv, o, d_o, lse, delta, dqkv, B, H, S, head_dim, stream);
-  DMI_REQUIRE(B > 0 && H > 0 && S > 0 && S % 8 == 0, "attention_bwd_masked: S must be a multiple of 8 (S=%d)", S);
-  DMI_REQUIRE((int64_t)S * 3 * H * HD * 2 < 0x7fffffff, "attention_bwd_masked: sequence too long for 32-bit buffer offsets");
-  hipStream_t st = (hipStream_t)stream;
-  float* stats = delta + (int64_t)B * H * S;
-  const int shm = 32768 + DKV_NSTAGE * DKV_STAGE;
-  raise_lds_once<attn_bwd_dq_kernel<1, true, const int*>>(2 * QK_STAGE);
-  raise_lds_once<attn_bwd_dkv_masked_kernel>(shm);
-  const int items = ((S + 127) / 128) * B * H;
-  {
-    const int grid = items < 2 * attn_num_cus() ? items : 2 * attn_num_cus();
-    const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
-    attn_bwd_dq_kernel<1, true, const int*><<<dim3(grid), dim3(256), 2 * QK_STAGE, st>>>((const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o,
-                                                                                       lse, delta, stats, (bf16_t*)dqkv, (const int*)plan, B, H, S, perxcd);
-  }
-  DMI_CHECK_LAUNCH("attention_bwd_dq_masked");
-  {
-    const int grid = items < attn_num_cus() ? items : attn_num_cus();
-    const int perxcd = g_opt_attn_xcd && (B * H) % 8 == 0 && grid % 8 == 0;
-    attn_bwd_dkv_masked_kernel<<<dim3(grid), dim3(256), shm, st>>>((const bf16_t*)qkv, (const bf16_t*)d_o, stats, (bf16_t*)dqkv,
-                                                                   (const int*)plan, B, H, S, perxcd);
-  }
-  DMI_CHECK_LAUNCH("attention_bwd_dkv_masked");
-  return DMI_OK;
+  return attn_bwd_launch(rt ? "attention_bwd" : "attention_bwd_masked", qkv, o, d_o, lse, delta, dqkv, rt ? nullptr : plan, B, H, S, head_dim,
+                         stream);
 }
 
 extern "C" int dmi_attention_decode_masked(uint16_t* qkv, const uint16_t* fresh, uint16_t* o, const int32_t* plan, const int32_t* plan_host,
@@ -2826,8 +2548,8 @@ extern "C" int dmi_attention_decode_masked(uint16_t* qkv, const uint16_t* fresh,
   DMI_REQUIRE(qkv && o, "attention_decode_masked: null pointer");
   const int rt = amp_route(plan, plan_host, S, head_dim, "attention_decode_masked");
   if (rt < 0) return rt;
-  if (rt == 1) return dmi_attention_decode_hd(qkv, fresh, o, B, H, S, pos, pos_dev, head_dim, stream);
-  return attn_decode_launch("attention_decode_masked", qkv, fresh, o, (const int*)plan, B, H, S, pos, pos_dev, head_dim, stream);
+  return attn_decode_launch(rt ? "attention_decode" : "attention_decode_masked", qkv, fresh, o, rt ? nullptr : plan, B, H, S, pos, pos_dev,
+                            head_dim, stream);
 }
 
 // =====================================================================================
@@ -2895,7 +2617,7 @@ __global__ __launch_bounds__(256) void kv8_quantize_kernel(const bf16_t* __restr
 extern "C" int dmi_kv8_quantize(const uint16_t* qkv, int ld, uint8_t* data, float* scale, int B, int S, int H, int head_dim, int s0, int s1,
                                 void* stream) {
   DMI_REQUIRE(qkv && data && scale, "kv8_quantize: null pointer");
-  A64_HEAD_DIM_CHECK("kv8_quantize");
+  ATTN_HEAD_DIM_CHECK("kv8_quantize");
   DMI_REQUIRE(B > 0 && S > 0 && H > 0, "kv8_quantize: empty shape (B=%d S=%d H=%d)", B, S, H);
   DMI_REQUIRE(0 <= s0 && s0 < s1 && s1 <= S, "kv8_quantize: need 0 <= s0 < s1 <= S (s0=%d, s1=%d, S=%d)", s0, s1, S);
   DMI_REQUIRE(ld >= 3 * H * head_dim && ld % 8 == 0, "kv8_quantize: ld must be a multiple of 8 and at least 3 H head_dim (ld=%d)", ld);
@@ -3098,10 +2820,11 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void attn_decode_kv8_kernel(uint8_t
 // both kv8 decode entry points: one set of checks, one launch (plan != nullptr: the masked instance, head dim 128 only -- amp_route)
 static int attn_decode_kv8_launch(const char* name, uint8_t* data, float* scale, const uint16_t* fresh, uint16_t* o, const int* plan, int B,
                                   int H, int S, int pos, const int* pos_dev, int head_dim, void* stream) {
+  ATTN_HEAD_DIM_CHECK(name);
   DMI_REQUIRE(data && scale && o, "%s: null pointer", name);
   DMI_REQUIRE(fresh, "%s: fresh is required (the FP8 cache holds no queries)", name);
-  DMI_REQUIRE(B > 0 && H > 0 && S > 0, "%s: bad shape", name);
-  DMI_REQUIRE((int64_t)S * 2 * H * head_dim < 0x7fffffff, "%s: sequence too long for 32-bit row offsets", name);
+  DMI_REQUIRE(attn_sizes_ok(B, H, S), "%s: bad shape", name);
+  DMI_REQUIRE(kv8_offsets_fit(H, S, head_dim), "%s: sequence too long for 32-bit row offsets", name);
   DMI_REQUIRE(pos_dev || (pos >= 0 && pos < S), "%s: need 0 <= pos < S (pos=%d, S=%d)", name, pos, S);
   DMI_REQUIRE((((uintptr_t)data | (uintptr_t)fresh) & 15) == 0 && (((uintptr_t)scale | (uintptr_t)o) & 3) == 0,
               "%s: data and fresh must be 16-byte aligned, scale and o 4-byte aligned", name);
@@ -3116,7 +2839,6 @@ static int attn_decode_kv8_launch(const char* name, uint8_t* data, float* scale,
 
 extern "C" int dmi_attention_decode_kv8(uint8_t* data, float* scale, const uint16_t* fresh, uint16_t* o, int B, int H, int S, int pos,
                                         const int* pos_dev, int head_dim, void* stream) {
-  A64_HEAD_DIM_CHECK("attention_decode_kv8");
   return attn_decode_kv8_launch("attention_decode_kv8", data, scale, fresh, o, nullptr, B, H, S, pos, pos_dev, head_dim, stream);
 }
 
@@ -3125,7 +2847,6 @@ extern "C" int dmi_attention_decode_kv8_masked(uint8_t* data, float* scale, cons
                                                void* stream) {
   const int rt = amp_route(plan, plan_host, S, head_dim, "attention_decode_kv8_masked");
   if (rt < 0) return rt;
-  if (rt == 1) return dmi_attention_decode_kv8(data, scale, fresh, o, B, H, S, pos, pos_dev, head_dim, stream);
-  return attn_decode_kv8_launch("attention_decode_kv8_masked", data, scale, fresh, o, (const int*)plan, B, H, S, pos, pos_dev, head_dim,
-                                stream);
+  return attn_decode_kv8_launch(rt ? "attention_decode_kv8" : "attention_decode_kv8_masked", data, scale, fresh, o, rt ? nullptr : plan, B, H,
+                                S, pos, pos_dev, head_dim, stream);
 }

@@ -122,3 +122,14 @@ static inline void raise_lds_once(int bytes) {
   static const hipError_t once = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   (void)once;
 }
+// CUs of the current device as the launch plans count them (gemm_plan.h, attn_plan.h): 256, the MI355X's count, where no device
+// answers or one reports fewer than 8
+static inline int num_cus() {
+  static const int n = [] {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
+    return prop.multiProcessorCount >= 8 ? prop.multiProcessorCount : 256;
+  }();
+  return n;
+}

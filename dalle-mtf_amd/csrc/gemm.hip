@@ -24,29 +24,9 @@
 #include <atomic>
 #include <type_traits>
 
-static GemmOptions g_opt;        // every dispatch option but the attention kernels' (gemm_plan.h says what each one does)
-int g_opt_reserve_cus = 0;       // = g_opt.reserve_cus, for attention.hip's persistent grids
-int g_opt_attn_fwd = 1;          // attention forward kernel: 0 round-2 form, 1 software-pipelined (round 6)
-int g_opt_attn_bwd = 1;          // attention backward: bit 0 = whole-row epilogue stores through LDS (round 6)
-int g_opt_attn_mask_force = 0;   // 1: a causal mask plan runs the masked attention kernels too (tests, tools/attn_mask_bench.py)
-int g_opt_attn_xcd = 8;          // attention block order: 0 plain grid; G >= 1: per-XCD ranges, groups of G (batch, head) pairs tile-major
+extern GemmOptions g_opt;        // every dispatch option of this file (gemm_plan.h says what each one does); host.hip, with the option table
 unsigned long long* g_dbg_buf = nullptr;   // (also read by the ATTN_STAMP experiment build of attention.hip)
 extern "C" int dmi_set_debug_buffer(void* p) { g_dbg_buf = (unsigned long long*)p; return 0; }
-
-static const OptionSlot g_option_table[] = {
-    {"nt4", &g_opt.nt4}, {"nt8", &g_opt.nt8}, {"nt8_min_k", &g_opt.nt8_min_k}, {"nt8p", &g_opt.nt8p}, {"nt8p_max_k", &g_opt.nt8p_max_k},
-    {"ntr", &g_opt.ntr}, {"nt4_lds", &g_opt.nt4_lds, 49152, 163840}, {"skinny", &g_opt.skinny}, {"res16", &g_opt.res16},
-    {"relu_bits", &g_opt.relu_bits}, {"cstream", &g_opt.cstream}, {"cstream_min_mb", &g_opt.cstream_min_mb},
-    {"cstream_nt_min_mb", &g_opt.cstream_nt_min_mb}, {"tn8", &g_opt.tn8}, {"tn8_max_tiles", &g_opt.tn8_max_tiles},
-    {"tn_wide", &g_opt.tn_wide}, {"tn_tail", &g_opt.tn_tail}, {"reserve_cus", &g_opt.reserve_cus, 0, INT32_MAX},
-    {"attn_xcd", &g_opt_attn_xcd}, {"attn_mask_force", &g_opt_attn_mask_force, INT32_MIN, INT32_MAX, true},
-    {"attn_fwd", &g_opt_attn_fwd}, {"attn_bwd", &g_opt_attn_bwd}};
-extern "C" int dmi_get_option(const char* name) { return option_get(g_option_table, name); }
-extern "C" int dmi_set_option(const char* name, int value) {
-  const int rc = option_set(g_option_table, name, value);
-  g_opt_reserve_cus = g_opt.reserve_cus;
-  return rc;
-}
 
 #define BM 128
 #define BN 128
@@ -1770,16 +1750,6 @@ __global__ __launch_bounds__(64 * SK_WAVES) void gemm_ln_nt_skinny_kernel(const 
 
 // the tile geometry gemm_plan.h plans with is the kernels'
 static_assert(BM == NT2_TILE && BN == NT2_TILE && BK == NT_BK && BM4 == NT4_TILE_M && BM8 == NT8_TILE && BN8 == NT8_TILE && GROUP_M == TN_GROUP_ORDER);
-
-static int num_cus() {    // CUs of the current device (256, the MI355X's count, where no device answers)
-  static const int n = [] {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    return prop.multiProcessorCount >= 8 ? prop.multiProcessorCount : 256;
-  }();
-  return n;
-}
 
 // the kernels of an epilogue: which arms of nt_plan exist for FLAGS (launch_nt instantiates exactly these)
 template <int FLAGS>

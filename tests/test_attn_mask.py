@@ -199,8 +199,8 @@ def test_mask_entry_points_are_declared_exported_and_bound():
     assert dh.get_option("attn_mask_force") == 0
 
 
-# the masked instances (MASKED = true, as the symbol spells it) of the forward, dQ and decode templates, and the masked dK/dV kernel
-MASKED = {"attn_fwd_kernelILb1E": 2, "attn_bwd_dq_kernelILi1ELb1E": 2, "attn_bwd_dkv_masked_kernel": 1, "attn_decode_kernelILi128ELb1E": 4}
+# the masked instances (MASKED = true, as the symbol spells it) of the forward, dQ, dK/dV and decode templates
+MASKED = {"attn_fwd_kernelILb1E": 2, "attn_bwd_dq_kernelILi1ELb1E": 2, "attn_bwd_dkv_kernelILi1ELb1E": 1, "attn_decode_kernelILi128ELb1E": 4}
 
 
 def test_masked_kernels_use_no_scratch_and_reach_their_occupancy():
@@ -223,7 +223,7 @@ def test_masked_kernels_use_no_scratch_and_reach_their_occupancy():
 
 
 def test_plan_header_names_match_the_kernel_enum():
-    src = open(os.path.join(ROOT, "dalle-mtf_amd", "csrc", "attention.hip")).read()
+    src = open(os.path.join(ROOT, "dalle-mtf_amd", "csrc", "attn_plan.h")).read()
     enum = re.search(r"enum \{\s*(AMP_S = 1[^}]*)\}", src).group(1)
     names = [n.strip().split("=")[0].strip() for n in enum.split(",") if n.strip()]
     assert {n[4:]: i + 1 for i, n in enumerate(names)} == dh.PLAN_HDR

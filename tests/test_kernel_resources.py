@@ -69,7 +69,7 @@ def test_two_blocks_per_cu_kernels_fit_two_waves_per_simd(usage):
     for k in two:
         u = usage[k]
         assert u["occupancy"] >= 2 and u["vgpr"] + u["agpr"] <= 256, (k, u)
-    dkv = [k for k in usage if "attn_bwd_dkv_kernel" in k]
+    dkv = [k for k in usage if "attn_bwd_dkv_kernel" in k and "Lb0E" in k]   # the causal instances (MASKED = false)
     assert len(dkv) == 2      # [r06] the round-2 epilogue (A/B arm) and the whole-row one
     for k in dkv:
         assert usage[k]["occupancy"] == 1 and usage[k]["vgpr"] + usage[k]["agpr"] <= 512, (k, usage[k])
