@@ -8,20 +8,23 @@ from __future__ import annotations
 
 import ctypes
 import os
-import re
 import struct
 
 import numpy as np
-from ctypes import c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
+from ctypes import c_int, c_void_p
 
 import torch
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DALLE_HIP_LIB") or os.path.join(_HERE, "libdalle_hip.so")  # override: A/B of two builds
-HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "dalle_hip.h")
+HEADER_PATH = abi.HEADER_PATH
 
-GEMM_BIAS, GEMM_RELU, GEMM_RESIDUAL, GEMM_RELU_MASK, GEMM_OUT_F32, GEMM_ROWSCALE = 1, 2, 4, 8, 16, 32
-GEMM_GELU = 512
+# signatures, struct fields and constants all come from the header (abi.py): nothing below restates them
+_H = abi.header()
+GEMM_BIAS, GEMM_RELU, GEMM_RESIDUAL, GEMM_RELU_MASK, GEMM_OUT_F32, GEMM_ROWSCALE, GEMM_GELU = (
+    _H.constants["DMI_GEMM_" + n] for n in ("BIAS", "RELU", "RESIDUAL", "RELU_MASK", "OUT_F32", "ROWSCALE", "GELU"))
 
 _lib = None
 
@@ -32,8 +35,7 @@ class DalleHipError(RuntimeError):
 
 def declared_symbols():
     """Every dmi_* function the public header declares."""
-    txt = open(HEADER_PATH).read()
-    return sorted(set(re.findall(r"\b(dmi_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(_H.functions)
 
 
 def lib():
@@ -44,153 +46,12 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python __graft_entry__.py` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the product path.")
         _lib = ctypes.CDLL(LIB_PATH)
-        _declare(_lib)
+        abi.declare(_lib)
         for kv in os.environ.get("DALLE_HIP_OPTIONS", "").split(","):   # A/B hook: e.g. DALLE_HIP_OPTIONS=tn8=0,attn_xcd=0
             if "=" in kv:
                 if _lib.dmi_set_option(kv.split("=")[0].strip().encode(), int(kv.split("=")[1])) != 0:
                     raise DalleHipError(f"DALLE_HIP_OPTIONS: unknown option {kv!r}")
     return _lib
-
-
-def _declare(L):
-    P, I, L64, F, U64 = c_void_p, c_int, c_int64, c_float, c_uint64
-    sig = {
-        "dmi_last_error_string": (c_char_p, []),
-        "dmi_version": (I, []),
-        "dmi_get_option": (I, [c_char_p]),
-        "dmi_set_option": (I, [c_char_p, I]),
-        "dmi_set_debug_buffer": (I, [P]),
-        "dmi_embed_fwd": (I, [P, P, P, P, L64, I, I, I, P, P]),
-        "dmi_sort_tokens_workspace_bytes": (L64, [L64]),
-        "dmi_sort_tokens": (I, [P, P, P, L64, I, P, P]),
-        "dmi_embed_bwd_workspace_bytes": (L64, [I, I, I]),
-        "dmi_embed_bwd": (I, [P, P, P, P, P, I, I, I, I, P, P]),
-        "dmi_layernorm_fwd": (I, [P, P, P, P, P, P, L64, I, F, P]),
-        "dmi_embed_fwd_dropout": (I, [P, P, P, P, L64, I, I, I, U64, U64, I, P]),
-        "dmi_embed_bwd_dropout": (I, [P, P, P, P, P, I, I, I, I, P, U64, U64, I, P]),
-        "dmi_dropout_add_ln": (I, [P, P, P, P, P, P, P, P, L64, I, U64, I, F, P]),
-        "dmi_dropout_bwd": (I, [P, P, L64, I, U64, I, P]),
-        "dmi_rope_qk": (I, [P, I, P, L64, I, I, I, I, P]),
-        "dmi_rope_qk_decode": (I, [P, P, I, I, I, I, I, P, P]),
-        "dmi_qk_norm_fwd": (I, [P, I, P, P, P, P, L64, I, I, I, P]),
-        "dmi_qk_norm_bwd_workspace_bytes": (L64, [L64, I]),
-        "dmi_qk_norm_bwd": (I, [P, I, P, P, P, P, P, P, P, L64, I, I, I, P]),
-        "dmi_qk_norm_decode": (I, [P, P, P, P, I, I, I, I, I, P, P]),
-        "dmi_token_shift": (I, [P, P, P, L64, I, I, I, I, I, P]),
-        "dmi_token_shift_decode": (I, [P, P, P, I, I, I, I, I, I, P, P]),
-        "dmi_layernorm_bwd_workspace_bytes": (L64, [L64, I]),
-        "dmi_layernorm_bwd": (I, [P, P, P, P, P, P, P, P, P, P, L64, I, P]),
-        "dmi_layernorm_bwd_finish_batch": (I, [P, P, P, P, I, I, P]),
-        "dmi_gemm_nt": (I, [P, I, P, I, P, I, I, I, I, I, P, P, P, P, P]),
-        "dmi_gemm_nt_splitk_workspace_bytes": (L64, [I, I, I]),
-        "dmi_gemm_nt_splitk": (I, [P, I, P, I, P, I, I, I, I, P, P, P]),
-        "dmi_gemm_tn_workspace_bytes": (L64, [I, I, I]),
-        "dmi_gemm_tn": (I, [P, I, P, I, P, P, P, I, I, I, P, P, P, P]),
-        "dmi_gemm_tn_group": (I, [P, I, I, P, P, P]),
-        "dmi_gemm_tn_group_plan": (I, [P, P, I, I]),
-        "dmi_reduce_slabs_batch": (I, [P, I, P]),
-        "dmi_colsum_workspace_bytes": (L64, [L64, I]),
-        "dmi_colsum": (I, [P, I, P, L64, I, P, P]),
-        "dmi_transpose_bf16": (I, [P, P, I, I, I, P]),
-        "dmi_attention_fwd": (I, [P, P, P, I, I, I, P]),
-        "dmi_attention_bwd": (I, [P, P, P, P, P, P, I, I, I, P]),
-        "dmi_attention_decode": (I, [P, P, P, I, I, I, I, P, P]),
-        "dmi_attention_fwd_hd": (I, [P, P, P, I, I, I, I, P]),
-        "dmi_attention_bwd_hd": (I, [P, P, P, P, P, P, I, I, I, I, P]),
-        "dmi_attention_decode_hd": (I, [P, P, P, I, I, I, I, P, I, P]),
-        "dmi_attn_mask_plan": (L64, [P, I, P, L64]),
-        "dmi_attention_fwd_masked": (I, [P, P, P, P, P, I, I, I, I, P]),
-        "dmi_attention_bwd_masked": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P]),
-        "dmi_attention_decode_masked": (I, [P, P, P, P, P, I, I, I, I, P, I, P]),
-        "dmi_kv8_quantize": (I, [P, I, P, P, I, I, I, I, I, I, P]),
-        "dmi_attention_decode_kv8": (I, [P, P, P, P, I, I, I, I, P, I, P]),
-        "dmi_attention_decode_kv8_masked": (I, [P, P, P, P, P, P, I, I, I, I, P, I, P]),
-        "dmi_label_logit": (I, [P, I, P, I, P, P, P, P, L64, I, I, P]),
-        "dmi_gemm_nt_softmax_partials": (L64, [I]),
-        "dmi_gemm_nt_softmax": (I, [P, I, P, I, P, P, P, I, P, I, I, I, P]),
-        "dmi_softmax_finish": (I, [P, I, P, P, P, P, I, P, I, P, P, I, I, P, P, P, P, P, L64, I, I, F, P]),
-        "dmi_softmax_finish_w": (I, [P, I, P, P, P, P, I, P, I, P, P, I, I, P, P, P, P, P, L64, I, I, F, P, I, P]),
-        "dmi_loss_reduce": (I, [P, L64, P, I, I, F, P, P]),
-        "dmi_loss_mask": (I, [P, L64, I, I, I, F, F, I, P, P, P]),
-        "dmi_loss_reduce_masked": (I, [P, P, P, L64, I, I, I, P, F, P, P]),
-        "dmi_shift_labels": (I, [P, P, I, I, I, P]),
-        "dmi_cross_entropy": (I, [P, I, P, P, P, L64, I, F, P]),
-        "dmi_sum_f32": (I, [P, L64, F, P, P]),
-        "dmi_assemble_tokens": (I, [P, P, P, I, I, I, I, I, P]),
-        "dmi_sample_tokens": (I, [P, I, P, I, I, F, I, ctypes.c_uint64, P, I, P, I, I, P, P, I, I, P]),
-        "dmi_sample_tokens_p": (I, [P, I, P, I, I, F, I, ctypes.c_uint64, F, P, I, P, I, I, P, P, I, I, P, P]),
-        "dmi_sample_tokens_guided": (I, [P, I, P, I, I, F, I, ctypes.c_uint64, F, F, P, I, P, I, I, P, P, I, I, P, P]),
-        "dmi_ln_gemm_nt": (I, [P, I, P, P, F, P, I, P, I, I, I, I, I, P, P]),
-        "dmi_logits_f32": (I, [P, I, P, P, I, I, P]),
-        "dmi_gemm_nt_ln": (I, [P, I, P, I, P, I, I, I, I, P, P, P, P, F, P, I, P, P, P]),
-        "dmi_gemm_nt_lnbwd_parts": (I, [I]),
-        "dmi_gemm_nt_lnbwd": (I, [P, I, P, I, I, I, I, P, P, P, P, P, P, P, P, I, P, P]),
-        "dmi_layernorm_bwd_finish_parts": (I, [P, I, P, P, I, P]),
-        "dmi_relu_bits_bytes": (L64, [I, I]),
-        "dmi_relu_bits_auto": (I, [I, I, I]),
-        "dmi_gemm_nt_ln_auto": (I, [I, I, I]),
-        "dmi_gemm_nt_relu_bits": (I, [P, I, P, I, P, I, I, I, I, P, P, P]),
-        "dmi_gemm_nt_mask_bits": (I, [P, I, P, I, P, I, I, I, I, P, P]),
-        "dmi_gemm_nt_gelu": (I, [P, I, P, I, P, I, I, I, I, P, P, I, P]),
-        "dmi_gemm_nt_gelu_grad": (I, [P, I, P, I, P, I, I, I, I, P, I, P]),
-        "dmi_glu_fwd": (I, [P, I, P, I, L64, I, I, P]),
-        "dmi_glu_bwd": (I, [P, I, P, I, P, I, L64, I, I, P]),
-        "dmi_sumsq_workspace_bytes": (L64, [L64]),
-        "dmi_sumsq": (I, [P, L64, P, P, P]),
-        "dmi_adam_step": (I, [P, P, P, P, P, L64, P, F, F, F, F, F, F, F, P, P]),
-        "dmi_ema_step": (I, [P, P, P, L64, F, P]),
-        "dmi_adafactor_plan": (I, [P, I, P]),
-        "dmi_adafactor_step": (I, [P, I, P, P, P, P, P, P, P, F, F, P, F, F, F, F, P, L64, P]),
-        "dmi_cast_f32_bf16": (I, [P, P, L64, P]),
-        "dmi_transpose_bf16_padded": (I, [P, P, I, I, I, P]),
-        "dmi_transpose_bf16_batch": (I, [P, P, P, I, L64, P]),
-        "dmi_im2col": (I, [P, P, I, I, I, I, I, I, I, I, P, P, I, P]),
-        "dmi_conv_gemm_nt": (I, [P, I, I, I, I, I, I, I, I, P, P, P, I, P, I, I, I, P, P, P, P]),
-        "dmi_conv_wgrad_tn_workspace_bytes": (L64, [I, I, I]),
-        "dmi_conv_wgrad_tn": (I, [P, I, I, I, I, I, I, I, I, P, P, P, I, I, P, P, P, P, P, P]),
-        "dmi_weight_gather": (I, [P, P, I, I, I, P, I, P]),
-        "dmi_weight_gather_batch": (I, [P, P, P, I, L64, P]),
-        "dmi_pixel_interleave": (I, [P, P, I, I, I, I, P]),
-        "dmi_pad_channels": (I, [P, P, L64, I, I, P]),
-        "dmi_unpad_channels": (I, [P, P, L64, I, I, P]),
-        "dmi_gumbel_softmax_fwd": (I, [P, P, P, P, P, L64, I, F, I, P, P]),
-        "dmi_gumbel_softmax_bwd": (I, [P, P, P, L64, I, F, P, P]),
-        "dmi_mse_workspace_bytes": (L64, []),
-        "dmi_mse_loss": (I, [P, P, P, P, L64, I, I, F, P, P]),
-        "dmi_add_f32": (I, [P, P, L64, P]),
-        "dmi_codebook_kl_workspace_bytes": (L64, [L64, I]),
-        "dmi_codebook_kl_fwd": (I, [P, P, P, L64, I, P, P]),
-        "dmi_gumbel_softmax_bwd_kl": (I, [P, P, P, P, P, L64, I, F, P, F, P, P]),
-        "dmi_elbo_loss": (I, [P, P, F, P, P, P]),
-        "dmi_codebook_usage": (I, [P, P, P, P, P, L64, I, P, P]),
-        "dmi_vq_half_norms": (I, [P, I, P, P, I, I, P]),
-        "dmi_vq_assign": (I, [P, I, P, I, P, P, P, I, P, L64, I, I, P]),
-        "dmi_vq_scores_bias": (I, [P, P, L64, I, P]),
-        "dmi_vq_loss_workspace_bytes": (L64, []),
-        "dmi_vq_loss": (I, [P, I, P, I, P, L64, I, P, P]),
-        "dmi_vq_bwd_x": (I, [P, I, P, I, P, I, P, I, L64, I, F, P]),
-        "dmi_vq_codebook_grad_workspace_bytes": (L64, [L64, I, I]),
-        "dmi_vq_codebook_grad": (I, [P, I, P, P, I, P, L64, I, I, P, P]),
-        "dmi_vq_gather": (I, [P, I, P, P, I, L64, I, I, P]),
-        "dmi_vq_cluster_sums_workspace_bytes": (L64, [L64, I, I]),
-        "dmi_vq_cluster_sums": (I, [P, I, P, P, P, L64, I, I, P, P]),
-        "dmi_vq_ema_step": (I, [P, P, P, P, P, P, P, P, P, I, ctypes.c_double, I, U64, L64, P, L64, I, I, P]),
-        "dmi_comm_load": (I, [c_char_p]),
-        "dmi_comm_unique_id_bytes": (I, []),
-        "dmi_comm_unique_id": (I, [P]),
-        "dmi_comm_init": (I, [P, I, I, P]),
-        "dmi_comm_destroy": (I, [P]),
-        "dmi_allreduce_bucket": (I, [P, P, L64, P]),
-        "dmi_comm_broadcast_f32": (I, [P, P, L64, I, P]),
-        "dmi_conv2d_f32": (I, [P, I, I, I, I, I, I, I, I, P, P, P, P, P, P, I, I, P]),
-        "dmi_space_to_depth_f32": (I, [P, P, I, I, I, I, I, I, P]),
-        "dmi_depth_to_space_f32": (I, [P, P, I, I, I, I, I, I, P]),
-        "dmi_crc32c": (ctypes.c_uint32, [c_char_p, ctypes.c_size_t]),
-    }
-    for name, (res, args) in sig.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
 
 
 def _check(rc, what):
@@ -556,7 +417,7 @@ def gemm_tn_workspace_bytes(M, I, J):
 
 class ReduceItem(ctypes.Structure):
     """dmi_reduce_item (include/dalle_hip.h)."""
-    _fields_ = [("slabs", c_void_p), ("out", c_void_p), ("nsplit", c_int), ("n4", c_int64)]
+    _fields_ = _H.structs["dmi_reduce_item"]
 
 
 class DeferredReduces:
@@ -590,8 +451,7 @@ def gemm_tn(X, ldx, dY, ldy, dW, M, I, J, ws, dbias=None, bias_weights=None, def
 
 class TnProblem(ctypes.Structure):
     """dmi_tn_problem (include/dalle_hip.h)."""
-    _fields_ = [("X", c_void_p), ("ldx", c_int), ("dY", c_void_p), ("ldy", c_int), ("dW", c_void_p), ("dbias", c_void_p),
-                ("bias_weights", c_void_p), ("I", c_int), ("J", c_int), ("workspace", c_void_p)]
+    _fields_ = _H.structs["dmi_tn_problem"]
 
 
 def gemm_tn_group_plan(shapes, M):
@@ -637,9 +497,7 @@ def transpose(inp, out, batch, R, C):
 
 def set_debug_buffer(t):
     """tools only: u64 device tensor [blocks, 5] receiving per-block phase timestamps of the 256x128 NT kernel (None: off)."""
-    fn = lib().dmi_set_debug_buffer
-    fn.restype, fn.argtypes = c_int, [c_void_p]
-    fn(_p(t))
+    lib().dmi_set_debug_buffer(_p(t))
 
 
 def transpose_batch(in_base, out_base, table, n, total_tiles):
@@ -904,7 +762,7 @@ def ema_step(ema, p, ema_bf16, n, one_minus_decay):
     _check(lib().dmi_ema_step(_p(ema), _p(p), _p(ema_bf16), int(n), float(one_minus_decay), _stream()), "ema_step")
 
 
-AF_FIELDS = 17   # DMI_AF_FIELDS: int64 per variable in an Adafactor descriptor table
+AF_FIELDS = _H.constants["DMI_AF_FIELDS"]   # int64 per variable in an Adafactor descriptor table
 
 
 def adafactor_plan(table):

@@ -51,13 +51,10 @@ def grids():
 
 
 def load(path):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), "dalle-mtf_amd"))
+    from dalle_hip import abi
     L = ctypes.CDLL(path)
-    I, L64, P = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
-    for name, res, args in (("dmi_gemm_tn_workspace_bytes", L64, [I, I, I]), ("dmi_gemm_tn_group_plan", I, [P, P, I, I]),
-                            ("dmi_relu_bits_auto", I, [I, I, I]), ("dmi_gemm_nt_ln_auto", I, [I, I, I]), ("dmi_relu_bits_bytes", L64, [I, I]),
-                            ("dmi_gemm_nt_lnbwd_parts", I, [I]), ("dmi_gemm_nt_splitk_workspace_bytes", L64, [I, I, I]),
-                            ("dmi_get_option", I, [ctypes.c_char_p]), ("dmi_set_option", I, [ctypes.c_char_p, I])):
-        getattr(L, name).restype, getattr(L, name).argtypes = res, args
+    abi.declare(L)          # the signatures of include/dalle_hip.h
     return L
 
 
